@@ -8,12 +8,13 @@ drawn uniformly from the 81-entry action table by torch.Generator(seed=0), robot
 scenarios = test cases 1000 + (global_env_id mod 500), auto-reset on done from an HBM-resident
 pool of the same 500 scenarios, Explorer-style discounted returns accumulated in-kernel.
 A "step" is one CrowdSim.step of the whole batch.  The robot's actions are a pre-drawn sequence, so the K
-steps go to the device as ceil(K / 1000) mcn_env_rollout launches (env state in registers between the steps
+timed steps go to the device as ceil(K / 1000) mcn_env_rollout launches (env state in registers between the steps
 of a launch; --steps-per-launch 1 = one mcn_env_step launch per step, also reported as single_step_launch).
-Inputs (states, the [K, E, 2] action tensor) are resident in HBM before the timed region; the launches are
-replayed from one hipGraph.  When K steps take less than ~20 ms (the driver's --steps 20 is ~0.08 ms) the timed
-region holds R back-to-back passes of the same K steps (R chosen from an untimed probe pass, reported as
-config.replays; all R * K steps are executed on every env, none skipped) and ms_per_step = elapsed / (K * R).
+Inputs (states, the action tensor) are resident in HBM before the timed region; the launches are replayed from one
+hipGraph.  After W warm-up steps, one untimed pass of the K steps warms every launch shape (and the graph); then
+exactly K steps are timed and ms_per_step = elapsed / K.  For K above ACTION_PERIOD_CAP the action sequence repeats
+with a period of at most that many steps (a whole number of launches), which bounds the action tensor.
+--dump-outputs DIR writes what the timed path returned after its last step (see dump_outputs) as .npy files.
 (Measured and dropped: stepping the shard as P independent sub-batches on P streams of one graph does not hide the
 straggling wavefronts of a launch -- a sub-batch launch is as latency-bound as the whole one.)
 Envs shard across ranks with no per-step communication (weak scaling); at the end of the
@@ -36,6 +37,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0            # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s
+ACTION_PERIOD_CAP = 4000         # timed steps with distinct pre-drawn actions (4096 envs: 262 MB of float64 actions)
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: total size of the written arrays
 
 
 def algorithmic_bytes_per_env_step(N):
@@ -59,17 +62,18 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the SARL / SGAN configurations")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--replays", type=int, default=0,
-                    help="passes of the K steps inside the timed region (0 = as many as fill --min-timed-ms)")
-    ap.add_argument("--no-merge", action="store_true",
-                    help="keep one launch per pass of the K steps instead of merging consecutive passes of the timed "
-                         "region into launches of up to --steps-per-launch steps")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy "
+                         "(float64, at most %d MB; a seeded sample of envs beyond that)" % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--force-collective", action="store_true",
                     help="run the N > 1 branches (process group, the one all_gather of episode records, the MAX / SUM "
                          "all-reduces) with a single rank too: exercises RCCL on a one-GPU box")
-    ap.add_argument("--min-timed-ms", type=float, default=20.0,
-                    help="the one-off costs of a timed region (sync, the final gather with several ranks) stay below ~2 %% of it")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def build_env(E, N, rank_offset, device):
@@ -107,6 +111,41 @@ def make_actions(steps, E, E_total, col0, device):
     idx = torch.randint(0, 81, (steps, E_total), generator=gen, dtype=torch.int64)[:, col0:col0 + E]
     tab = action_table()
     return tab[idx].to(device).contiguous()
+
+
+def action_period(K, S):
+    """Timed steps with distinct pre-drawn actions: all K up to ACTION_PERIOD_CAP, beyond that the largest whole number
+    of S-step launches that fits the cap (at least one), so that every launch reads one contiguous slice."""
+    if K <= ACTION_PERIOD_CAP:
+        return K
+    return max(1, ACTION_PERIOD_CAP // S) * S
+
+
+def dump_outputs(out_dir, env, suffix=""):
+    """What a caller of the timed path holds after its last step, as float64 .npy files in `out_dir`: the
+    (observation, reward, done, info) that VecCrowdSim.rollout / step return, the robot's state, and the Explorer
+    episode records of env.rollout_buffers.  Integer and mask outputs are widened exactly to float64.  When the whole
+    set exceeds DUMP_LIMIT_BYTES, a fixed sample of envs (numpy seed 0) is written; env_index names the rows."""
+    rb = env.rollout_buffers
+    per_env = {  # name -> (tensor, env axis)
+        "obs_human_pos": (env.hpos, 0), "obs_human_vel": (env.hvel, 0), "obs_human_radius": (env.hrad, 0),
+        "reward": (env.reward, 0), "done": (env.done, 0), "info": (env.info, 0),
+        "robot_pos": (env.rpos, 0), "robot_vel": (env.rvel, 0),
+        "episode_return": (rb["ep_return"], 0), "episode_steps": (rb["ep_steps"], 0),
+        "finished_count": (rb["fin_count"], 0), "finished_return": (rb["fin_return"], 1),
+        "finished_time": (rb["fin_time"], 1), "finished_info": (rb["fin_info"], 1),
+    }
+    E = env.num_envs
+    row_bytes = 8 * (1 + sum(t.numel() // E for t, _ in per_env.values()))     # + env_index
+    rows = np.arange(E)
+    if row_bytes * E > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(E, DUMP_LIMIT_BYTES // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "env_index%s.npy" % suffix), rows.astype(np.float64))
+    idx = torch.from_numpy(rows).to(env.device)
+    for name, (t, axis) in per_env.items():
+        a = t.index_select(axis, idx).to(torch.float64).cpu().numpy()
+        np.save(os.path.join(out_dir, "%s%s.npy" % (name, suffix)), a)
 
 
 def time_kernel_events(env, acts, n, given_v=None, reps=3):
@@ -629,7 +668,9 @@ def main():
     E, N, K, W = args.envs, args.humans, args.steps, args.warmup
     E_total = E * world
     env, pool = build_env(E, N, rank * E, device)
-    acts = make_actions(W + K, E, E_total, rank * E, device)
+    S = max(1, min(args.steps_per_launch, K))
+    P = action_period(K, S)
+    acts = make_actions(W + P, E, E_total, rank * E, device)
 
     # code objects load at a kernel's first launch: do that on a throw-away env, outside any capture, so that a
     # run with --warmup 0 still captures cleanly
@@ -647,63 +688,19 @@ def main():
     torch.cuda.synchronize()
 
     # the robot's actions are a pre-drawn random sequence, so S consecutive steps go to the device as one
-    # mcn_env_rollout call (state stays in registers between steps); S = 1 is one mcn_env_step launch per step
-    S = max(1, min(args.steps_per_launch, K))
-    chunks = [(t, min(S, K - t)) for t in range(0, K, S)]
-
-    def one_pass():
-        """The K timed steps."""
-        if S == 1:
-            for t in range(K):
-                env.step(acts[W + t])
-        else:
-            for t, n in chunks:
-                env.rollout(acts[W + t:W + t + n])
-
-    # untimed probe pass (an extra warm-up of K steps): how many passes fill the minimum timed region?
-    ev_s, ev_e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    one_pass()
-    torch.cuda.synchronize()
-    ev_s.record()
-    one_pass()
-    ev_e.record()
-    torch.cuda.synchronize()
-    probe_ms = ev_s.elapsed_time(ev_e)
-    R = args.replays if args.replays > 0 else int(min(20000, max(1, np.ceil(args.min_timed_ms / max(probe_ms, 1e-3)))))
-
-    # The pre-drawn action sequence of the whole timed region (R passes of the K steps) is known up front, so
-    # consecutive passes go to the device as ONE mcn_env_rollout launch of up to --steps-per-launch steps (the env state
-    # stays in registers across them; results equal the separate launches bit for bit,
-    # tests/test_env_step_gpu.py::test_rollout_launch_equals_single_steps).  A launch ends with its slowest env group,
-    # so 20-step launches run at 3.7 us per step and 1000-step ones at 2.8: SURVEY 8(d) defines the metric over >= 200
-    # steady-state steps, and `short_launch` below reports the 20-step figure next to it.
-    merge = 1
-    if S > 1 and len(chunks) == 1 and R > 1 and not args.no_merge:
-        merge = int(max(1, min(R, args.steps_per_launch // K)))
-    acts_rep = acts[W:W + K].repeat(merge, 1, 1).contiguous() if merge > 1 else None
-    if merge > 1 and args.replays <= 0:
-        # size the timed region with the launches it will really use: a whole number of merged launches
-        env.rollout(acts_rep)
-        torch.cuda.synchronize()
-        ev_s.record()
-        env.rollout(acts_rep)
-        ev_e.record()
-        torch.cuda.synchronize()
-        per_pass_ms = ev_s.elapsed_time(ev_e) / merge
-        R = int(np.ceil(max(1.0, args.min_timed_ms / max(per_pass_ms, 1e-4)) / merge)) * merge
-    n_full, n_rem = (R // merge, R % merge) if merge > 1 else (R, 0)
+    # mcn_env_rollout call (state stays in registers between steps); S = 1 is one mcn_env_step launch per step.
+    # Timed step t reads the action row W + t % P (P = K up to ACTION_PERIOD_CAP steps; a multiple of S above it).
+    launches = [acts[W + t % P:W + t % P + min(S, K - t)] for t in range(0, K, S)]
 
     def run_timed_steps():
-        """R back-to-back passes of the K steps."""
-        if merge > 1:
-            for _ in range(n_full):
-                env.rollout(acts_rep)
-            if n_rem:
-                env.rollout(acts_rep[:n_rem * K])
-        else:
-            for _ in range(R):
-                one_pass()
+        """The K timed steps."""
+        for a in launches:
+            if S == 1:
+                env.step(a[0])
+            else:
+                env.rollout(a)
 
+    ev_s, ev_e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     use_graph = not args.no_graph
     if use_graph:
         # captured BEFORE the process group exists: ranks are independent until the final gather, and an
@@ -711,6 +708,12 @@ def main():
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph, capture_error_mode="thread_local"):
             run_timed_steps()
+    # one untimed pass of the K steps: every launch shape of the timed region (and the graph itself) runs once first
+    if use_graph:
+        graph.replay()
+    else:
+        run_timed_steps()
+    torch.cuda.synchronize()
 
     gathered = None
     collective = world > 1 or args.force_collective
@@ -748,32 +751,33 @@ def main():
         dist.all_gather_into_tensor(gathered, packed.to(cdev))
     barrier()
     elapsed = time.perf_counter() - t0
-    env_steps_total = float(E * K * R)
+    env_steps_total = float(E * K)
     if collective:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-        # each rank chose its own pass count R from its own probe: the job's work is the sum over ranks
+        # the job's work is the sum over ranks
         ws = torch.tensor([env_steps_total], dtype=torch.float64, device=cdev)
         dist.all_reduce(ws, op=dist.ReduceOp.SUM)
         env_steps_total = float(ws.item())
     # dominant-kernel duration: HIP events (launch stream) bracketing the back-to-back launches of the timed region
-    n_launch = (K if S == 1 else len(chunks)) * R if merge == 1 else n_full + (1 if n_rem else 0)
+    n_launch = len(launches)
     kernel_ms = ev_s.elapsed_time(ev_e) / n_launch
 
     rb = env.rollout_buffers
     episodes = int(rb["fin_count"].sum().item())
     mean_ret = float(rb["fin_return"][0][rb["fin_count"] > 0].mean().item()) if episodes else float("nan")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, "" if world == 1 else "_rank%d" % rank)
 
     roof = roofline_entry(E, N, kernel_ms, {"timing": "HIP events around the %d launches of the timed region (%s)" % (
-        n_launch, "one hipGraph" if use_graph else "eager")}, steps_per_launch=K * R / n_launch)
-    S_eff = S * merge
+        n_launch, "one hipGraph" if use_graph else "eager")}, steps_per_launch=K / n_launch)
     if S > 1:
         # state lives in registers across the steps of a launch: HBM sees the state once per launch, not per step
         roof["note"] = ("algorithmic bytes = SURVEY 8(d) per-env-step figure x env-steps per launch; a launch keeps the "
                         "env state in registers for its %d steps, so real HBM traffic (`traffic`) is a fraction of "
-                        "that and the kernel is instruction-issue / latency-bound, not HBM-bound: see roofline_valu" % S_eff)
-    valu = valu_roofline(E, N, kernel_ms, K * R / n_launch, rollout=S > 1)
+                        "that and the kernel is instruction-issue / latency-bound, not HBM-bound: see roofline_valu" % S)
+    valu = valu_roofline(E, N, kernel_ms, K / n_launch, rollout=S > 1)
 
     result = {
         "metric": "env-steps/sec (whole node), 5-human CrowdSim x batched envs",
@@ -783,9 +787,9 @@ def main():
         "data": "synthetic",
         "config": {"workload": "%d envs x %d humans per GPU, ORCA humans, random robot actions (81-entry table), "
                                "auto-reset, %s" % (E, N, "1 mcn_env_step launch per step" if S == 1 else
-                                                   "%d steps per mcn_env_rollout launch" % (S * merge)),
-                   "steps_per_launch": S * merge, "passes_per_launch": merge, "replays": R, "timed_steps": K * R,
-                   "timed_region_ms": round(elapsed * 1e3, 3), "probe_pass_ms": round(probe_ms, 4),
+                                                   "%d steps per mcn_env_rollout launch" % S),
+                   "steps_per_launch": S, "timed_steps": K, "action_period": P,
+                   "timed_region_ms": round(elapsed * 1e3, 3),
                    "envs_per_gpu": E, "humans": N, "launch": "hipGraph" if use_graph else "eager",
                    "parallelism": "env-shard x%d, no per-step collective" % world},
         "episodes_finished": episodes, "mean_discounted_return": round(mean_ret, 6),
@@ -795,23 +799,6 @@ def main():
         "roofline_valu": valu,
     }
 
-    if rank == 0 and world == 1 and merge > 1:
-        # the same K steps as ONE launch per pass (what a caller with only K actions in hand pays: the launch ends with
-        # its slowest env group)
-        s_e, e_e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        reps = 50
-        one_pass()
-        torch.cuda.synchronize()
-        s_e.record()
-        for _ in range(reps):
-            one_pass()
-        e_e.record()
-        torch.cuda.synchronize()
-        sl_ms = s_e.elapsed_time(e_e) / reps
-        result["short_launch"] = roofline_entry(E, N, sl_ms, {
-            "mode": "%d steps per mcn_env_rollout launch, %d back-to-back launches" % (K, reps),
-            "env_steps_per_sec": round(E * K / (sl_ms * 1e-3), 1), "us_per_step": round(sl_ms * 1e3 / K, 4),
-            "roofline_valu": valu_roofline(E, N, sl_ms, K, rollout=True)}, steps_per_launch=K)
     if rank == 0 and world == 1 and S > 1:
         # the same workload stepped one mcn_env_step launch at a time (policy-in-the-loop callers pay this)
         one_ms, _ = time_kernel_events(env, acts, 200)

@@ -188,3 +188,69 @@ def test_python_scalar_baseline_step_equals_the_c_oracle():
                 for k in cport.EnvState.FIELDS_H + cport.EnvState.FIELDS_R + ("gtime", "human_times"):
                     getattr(st, k)[e] = getattr(fresh, k)[e]
     assert {P.TIMEOUT, P.NOTHING} <= seen and len(seen) >= 4, seen
+
+
+def test_action_period_gives_every_launch_one_contiguous_slice():
+    """bench.py's timed step t reads action row W + t % P: P is K itself up to ACTION_PERIOD_CAP, above it a whole
+    number of launches, so no launch of the timed region wraps around the end of the drawn actions."""
+    import bench
+    cap = bench.ACTION_PERIOD_CAP
+    assert bench.action_period(20, 20) == 20 and bench.action_period(cap, 1000) == cap
+    for K, S in [(20, 20), (cap + 1, 1000), (5 * cap + 3, 1000), (3 * cap, 3 * cap // 2), (2 * cap, 3 * cap // 2),
+                 (cap + 7, 1), (cap + 7, 7), (10 * cap, cap + 1)]:
+        P = bench.action_period(K, S)
+        assert 1 <= P <= max(cap, S) and (P == K or P % S == 0), (K, S, P)
+        for t in range(0, K, S):
+            assert t % P + min(S, K - t) <= P, (K, S, t)
+
+
+def _stub_env(E, N):
+    import types
+    import torch
+    g = torch.Generator().manual_seed(1)
+    r = lambda *s: torch.rand(*s, dtype=torch.float64, generator=g)
+    state = torch.zeros(E, 4, dtype=torch.float64)
+    w = state.view(torch.int32)
+    w[:, 2] = torch.arange(E, dtype=torch.int32)
+    w[:, 3] = torch.arange(E, dtype=torch.int32) % 3
+    rb = dict(ep_return=state[:, 0], ep_steps=w[:, 2], fin_count=w[:, 3], fin_return=r(1, E), fin_time=r(1, E),
+              fin_info=(torch.arange(E) % 4).to(torch.uint8).view(1, E))
+    return types.SimpleNamespace(num_envs=E, device=torch.device("cpu"), hpos=r(E, N, 2), hvel=r(E, N, 2),
+                                 hrad=r(E, N), reward=r(E), done=(torch.arange(E) % 2).to(torch.uint8),
+                                 info=(torch.arange(E) % 5).to(torch.uint8), rpos=r(E, 2), rvel=r(E, 2),
+                                 rollout_buffers=rb)
+
+
+def test_dump_outputs_writes_float64_arrays_of_the_returned_views(tmp_path):
+    import numpy as np
+    import bench
+    E, N = 37, 5
+    env = _stub_env(E, N)
+    bench.dump_outputs(str(tmp_path), env)
+    got = {os.path.basename(f)[:-4]: np.load(f) for f in glob.glob(os.path.join(str(tmp_path), "*.npy"))}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["env_index"], np.arange(E))
+    assert np.array_equal(got["obs_human_pos"], env.hpos.numpy()) and got["obs_human_vel"].shape == (E, N, 2)
+    assert np.array_equal(got["reward"], env.reward.numpy()) and np.array_equal(got["info"], np.arange(E) % 5)
+    assert np.array_equal(got["done"], np.arange(E) % 2) and np.array_equal(got["robot_vel"], env.rvel.numpy())
+    assert np.array_equal(got["episode_steps"], np.arange(E)) and np.array_equal(got["finished_count"], np.arange(E) % 3)
+    assert got["finished_return"].shape == (1, E) and np.array_equal(got["finished_info"][0], np.arange(E) % 4)
+
+
+def test_dump_outputs_samples_a_fixed_set_of_envs_above_the_size_limit(tmp_path, monkeypatch):
+    import numpy as np
+    import bench
+    E, N = 300, 5
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 32 * 1024)
+    env = _stub_env(E, N)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), env, "_rank1")
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == sorted(os.listdir(str(tmp_path / "b"))) and all(f.endswith("_rank1.npy") for f in files)
+    assert sum(np.load(str(tmp_path / "a" / f)).nbytes for f in files) <= 32 * 1024
+    rows = np.load(str(tmp_path / "a" / "env_index_rank1.npy")).astype(np.int64)
+    assert 0 < len(rows) < E and np.all(np.diff(rows) > 0)
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))), f
+    assert np.array_equal(np.load(str(tmp_path / "a" / "obs_human_pos_rank1.npy")), env.hpos.numpy()[rows])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "finished_time_rank1.npy")), env.rollout_buffers["fin_time"].numpy()[:, rows])

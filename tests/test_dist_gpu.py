@@ -89,13 +89,37 @@ def test_bench_collective_branches_on_rccl():
     all_gather_into_tensor of episode records, MAX / SUM all-reduces, barrier) executed on RCCL with one rank."""
     port = 33100 + (os.getpid() % 2000)
     out = _run_child([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "2", "--force-collective",
-                      "--no-sweep", "--no-extra", "--no-cpu-baseline", "--min-timed-ms", "5"],
+                      "--no-sweep", "--no-extra", "--no-cpu-baseline"],
                      env_extra={"RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1",
                                 "MASTER_PORT": str(port)})
     line = json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["collective"] == "nccl"
     assert line["gathered_episode_records"] is not None and line["gathered_episode_records"] >= 0
     assert line["value"] > 1e6
+
+
+def test_bench_times_exactly_the_given_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """bench.py --steps K times K steps (here 30 as launches of 7, 7, 7, 7, 2 steps) and --dump-outputs writes what the
+    timed path returned after its last step; two runs with the same arguments write identical arrays."""
+    import numpy as np
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        out = _run_child([sys.executable, "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "3",
+                          "--steps-per-launch", "7", "--no-sweep", "--no-extra", "--no-cpu-baseline", "--dump-outputs", d])
+        lines.append(json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1]))
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
+    for line in lines:
+        assert line["steps"] == 30 and line["config"]["timed_steps"] == 30 and line["config"]["steps_per_launch"] == 7
+        assert "5 launches" in line["roofline"]["timing"]
+        assert line["ms_per_step"] > 0 and abs(line["ms_per_step"] * 30 - line["config"]["timed_region_ms"]) < 1e-2
+    a, b = dumps
+    assert sorted(a) == sorted(b) and {"reward", "done", "info", "obs_human_pos", "finished_count"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert a["obs_human_pos"].shape == (4096, 5, 2) and np.array_equal(a["env_index"], np.arange(4096))
+    assert int(a["finished_count"].sum()) == lines[0]["episodes_finished"] == lines[1]["episodes_finished"]
 
 
 def test_bench_two_ranks_through_the_drivers_launcher():
@@ -106,13 +130,13 @@ def test_bench_two_ranks_through_the_drivers_launcher():
     episode records of both shards gathered."""
     port = 35100 + (os.getpid() % 2000)
     out = _run_child([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                      "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "20",
-                      "--warmup", "5", "--no-sweep", "--no-extra", "--no-cpu-baseline", "--min-timed-ms", "5"],
+                      "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--steps", "2000",
+                      "--warmup", "5", "--no-sweep", "--no-extra", "--no-cpu-baseline"],
                      timeout=600, env_extra={"MCN_BENCH_BACKEND": "gloo"})
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out[-2000:]                      # rank 0 only
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 2 and line["steps"] == 20 and line["warmup"] == 5 and line["scaling"] == "weak"
+    assert line["n_gpus"] == 2 and line["steps"] == 2000 and line["warmup"] == 5 and line["scaling"] == "weak"
     assert line["collective"] == "gloo" and line["config"]["envs_per_gpu"] == 4096
     assert "x2" in line["config"]["parallelism"]
     assert line["gathered_episode_records"] is not None and line["gathered_episode_records"] > 0
