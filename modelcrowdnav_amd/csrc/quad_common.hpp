@@ -20,9 +20,11 @@ static __device__ unsigned int g_diag_counts[8192 * 4];
 #define DIAG_COUNT(which)
 #endif
 
-// quad broadcast of lane I (0..3) of every quad: a DPP move, no LDS traffic
+// quad broadcast of lane I (0..3) of every quad: a DPP move, no LDS traffic.  No `old` operand: a lane keeps its old
+// value only when its source lane is inactive, and every quad is active or inactive as a whole (the callers' control
+// flow is quad-uniform), so the value a zero-initialised `old` would add -- one v_mov per broadcast -- is never read.
 template <int I>
-__device__ __forceinline__ int qbi(int v) { return __builtin_amdgcn_update_dpp(0, v, I * 0x55, 0xf, 0xf, false); }
+__device__ __forceinline__ int qbi(int v) { return __builtin_amdgcn_mov_dpp(v, I * 0x55, 0xf, 0xf, false); }
 template <int I>
 __device__ __forceinline__ float qbf(float v) { return __builtin_bit_cast(float, qbi<I>(__builtin_bit_cast(int, v))); }
 template <int I>
@@ -66,7 +68,7 @@ __device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], int no, float radiu
         const float ntr = fminf(tr, t), ntl = fmaxf(tl, t);
         tr = (cut & (den >= 0.0f)) ? ntr : tr;
         tl = (cut & !(den >= 0.0f)) ? ntl : tl;
-        ok = ok & !(live & par & (num < 0.0f)) & !(cut & (tl > tr));
+        ok = ok & !(live & ((par ? 0.0f : tl) > (par ? num : tr)));      // parallel: 0 > num, else tl > tr
     }
     float t;
     if (DIR) {
@@ -87,17 +89,18 @@ __device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], int no, float radiu
 // Lines the reference drops (parallel, same direction) are not compacted away but masked: the incremental LP over
 // the kept lines in their original order is the same sequence of operations.  Same arithmetic per value as
 // lp3() in orca_device.hpp / the oracle, so the same bits.  Returns whether the candidate is valid (the inner
-// 2-D LP succeeded); the result is identical on the four lanes.
-__device__ __forceinline__ bool lp3_candidate_quad(const float4 (&L)[4], int i, int k, float radius, float &rx, float &ry)
+// 2-D LP succeeded); the result is identical on the four lanes.  `li` = line i (L[i]), `lj` = line k, i.e. the sorted
+// line this lane holds itself (the quad broadcast of lane k read on lane k): no run-time select for either.
+__device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float4 &lj, int i, int k, float radius, float &rx,
+                                                   float &ry)
 {
-    const float4 li = sel4(L, i);
-    const float4 lj = sel4(L, k);
     const float dt = det2(li.z, li.w, lj.z, lj.w);
     const bool par = fabsf(dt) <= kRvoEps;
-    const int kept = ((k < i) & !(par & (dot2(li.z, li.w, lj.z, lj.w) > 0.0f))) ? 1 : 0;
+    const bool keptb = (k < i) & !(par & (dot2(li.z, li.w, lj.z, lj.w) > 0.0f));
+    const int kept = keptb ? 1 : 0;
     const float sc = det2(lj.z, lj.w, li.x - lj.x, li.y - lj.y) / dt;
     const float ddx = lj.z - li.z, ddy = lj.w - li.w;
-    const float inv = rcp_sqrt_f32(dot2(ddx, ddy, ddx, ddy), kept != 0);   // dropped / self projections: unused
+    const float inv = rcp_sqrt_f32(dot2(ddx, ddy, ddx, ddy), keptb);       // dropped / self projections: unused
     const float4 q = make_float4(par ? 0.5f * (li.x + lj.x) : li.x + sc * li.z,
                                  par ? 0.5f * (li.y + lj.y) : li.y + sc * li.w, ddx * inv, ddy * inv);
     const float4 P0 = qb4<0>(q), P1 = qb4<1>(q), P2 = qb4<2>(q);
@@ -108,7 +111,7 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 (&L)[4], int i, 
     const float dp = dot2(q.x, q.y, q.z, q.w);
     const float disc = dp * dp + radius * radius - dot2(q.x, q.y, q.x, q.y);
     bool ok = !(disc < 0.0f);
-    const float sq = sqrt_f32(disc, ok & (kept != 0));
+    const float sq = sqrt_f32(disc, ok & keptb);
     float tl = -dp - sq;
     float tr = -dp + sq;
 #pragma unroll
@@ -123,7 +126,7 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 (&L)[4], int i, 
         const float ntr = fminf(tr, t), ntl = fmaxf(tl, t);
         tr = (cut & (den >= 0.0f)) ? ntr : tr;
         tl = (cut & !(den >= 0.0f)) ? ntl : tl;
-        ok = ok & !(live & parj & (num < 0.0f)) & !(cut & (tl > tr));
+        ok = ok & !(live & ((parj ? 0.0f : tl) > (parj ? num : tr)));      // parallel: 0 > num, else tl > tr
     }
     const float tt = (dot2(ox, oy, q.z, q.w) > 0.0f) ? tr : tl;
     const float cx = q.x + tt * q.z, cy = q.y + tt * q.w;
@@ -161,18 +164,19 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
     const float range_sq = c.orca_neighbor_dist * c.orca_neighbor_dist;
     const float ddx = fpx - o.x, ddy = fpy - o.y;
     const float d = dot2(ddx, ddy, ddx, ddy);
-    const int in = (cand_valid && (d < range_sq)) ? 1 : 0;
-    const float d0 = qbf<0>(d), d1 = qbf<1>(d), d2 = qbf<2>(d), d3 = qbf<3>(d);
-    const int i0 = qbi<0>(in), i1 = qbi<1>(in), i2 = qbi<2>(in), i3 = qbi<3>(in);
-    const int nin = i0 + i1 + i2 + i3;
-    // stable ascending order among the in-range candidates (RVO2 insertAgentNeighbor); the rest fill the
-    // remaining slots in lane order so that ranks stay a permutation
-    const int rank_in = ((i0 != 0) & ((d0 < d) | ((d0 == d) & (0 < k)))) + ((i1 != 0) & ((d1 < d) | ((d1 == d) & (1 < k)))) +
-                        ((i2 != 0) & ((d2 < d) | ((d2 == d) & (2 < k)))) + ((i3 != 0) & ((d3 < d) | ((d3 == d) & (3 < k))));
-    const int rank_out = nin + (((0 < k) & !i0) ? 1 : 0) + (((1 < k) & !i1) ? 1 : 0) + (((2 < k) & !i2) ? 1 : 0);
-    const int rank = in ? rank_in : rank_out;
-    int nl = nin < c.orca_max_neighbors ? nin : c.orca_max_neighbors;
-    const float4 mine = orca_line_select(fpx, fpy, fvx, fvy, frad, o, orad, inv_th, inv_ts, in != 0);
+    const bool in = cand_valid && (d < range_sq);
+    // stable ascending order among the in-range candidates (RVO2 insertAgentNeighbor); the rest fill the remaining
+    // slots in lane order so that ranks stay a permutation.  One integer key per lane does both: an in-range d is a
+    // finite float >= +0 (a sum of squares below range_sq), so its bits order as the value does; out-of-range slots
+    // get +inf's bits, above every in-range key.  Lane q ranks before lane k iff key_q < key_k, or key_q == key_k and
+    // q < k, i.e. key_q - key_k < (q < k) (no overflow: keys lie in [0, 0x7f800000]).
+    const int key = in ? __builtin_bit_cast(int, d) : 0x7f800000;
+    const int kd0 = qbi<0>(key) - key, kd1 = qbi<1>(key) - key, kd2 = qbi<2>(key) - key, kd3 = qbi<3>(key) - key;
+    const int rank = (kd0 < (0 < k ? 1 : 0)) + (kd1 < (1 < k ? 1 : 0)) + (kd2 < (2 < k ? 1 : 0)) + (kd3 < 0);
+    // in-range candidates of the quad: the quad's four bits of one ballot
+    const int nin = __builtin_popcount((unsigned)(__builtin_amdgcn_ballot_w64(in) >> (lane & ~3)) & 0xfu);
+    const int nl = nin < c.orca_max_neighbors ? nin : c.orca_max_neighbors;
+    const float4 mine = orca_line_select(fpx, fpy, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
     // route my half-plane to lane `rank` of the quad, then share all four
     const int dst = ((lane & ~3) | rank) << 2;
     float4 srt;
@@ -184,7 +188,8 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
 
     // speculative 1-D LPs, one per lane; then the incremental LP is four compare-and-take steps
     float cx, cy;
-    const int okm = lp1_rt<false>(L, k, ms, prefx, prefy, cx, cy) ? 1 : 0;
+    // lane k's code for the take steps below: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
+    const int fcode = lp1_rt<false>(L, k, ms, prefx, prefy, cx, cy) ? 4 : k;
     {
         const float pp = dot2(prefx, prefy, prefx, prefy);
         const bool clip = pp > ms * ms;
@@ -192,13 +197,17 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
         rx = clip ? ms * (prefx * inv) : prefx;
         ry = clip ? ms * (prefy * inv) : prefy;
     }
+    // `fail` stays nl until a violated line's 1-D LP is infeasible and then is that line, so "line I is below nl and
+    // nothing failed yet" is fail > I; a violation folds the line's code in (min: nl <= 4 keeps a feasible line's 4
+    // from changing it), and the candidate is taken where fail is still above I afterwards
     int fail = nl;
 #define MCN_LP2_TAKE(I)                                                                        \
     {                                                                                          \
-        const int ok_i = qbi<I>(okm); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy);        \
-        const bool viol = (I < nl) & (fail == nl) & (det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > 0.0f); \
-        rx = (viol & (ok_i != 0)) ? cx_i : rx; ry = (viol & (ok_i != 0)) ? cy_i : ry;           \
-        fail = (viol & (ok_i == 0)) ? I : fail;                                                 \
+        const int code_i = qbi<I>(fcode); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy);    \
+        const bool out = det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > 0.0f;                 \
+        fail = ((fail > I) & out) ? min(fail, code_i) : fail;                                   \
+        const bool take = (fail > I) & out;                                                     \
+        rx = take ? cx_i : rx; ry = take ? cy_i : ry;                                           \
     }
     MCN_LP2_TAKE(0) MCN_LP2_TAKE(1) MCN_LP2_TAKE(2) MCN_LP2_TAKE(3)
 #undef MCN_LP2_TAKE
@@ -209,18 +218,20 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
         // lanes compute its candidate together, take it if valid, update `dist`.  Measured on the benchmark
         // workload: 0.65 % of the solves get here; 93 % of those need one round, 6 % two, 1 % three.
         DIAG_COUNT(0);
+        // The next line is the first one from `i` on (below nl) that the running result violates by more than
+        // `dist`: lane k tests ITS line (L[k] = srt, the same operations on the same values as every lane testing
+        // L[k]) and the quad's four bits of a ballot name the first.
         float dist = 0.0f;
         int i = fail;
         for (;;) {
-            int nxt = 4;
-#define MCN_LP3_NEXT(I) nxt = ((I >= i) & (I < nl) & (det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > dist)) ? I : nxt;
-            MCN_LP3_NEXT(3) MCN_LP3_NEXT(2) MCN_LP3_NEXT(1) MCN_LP3_NEXT(0)
-#undef MCN_LP3_NEXT
-            if (nxt >= 4) break;
-            float cx3, cy3;
-            const bool ok3 = lp3_candidate_quad(L, nxt, k, ms, cx3, cy3);
-            rx = ok3 ? cx3 : rx; ry = ok3 ? cy3 : ry;
+            const bool over = ((unsigned)(k - i) < (unsigned)(nl - i)) & (det2(srt.z, srt.w, srt.x - rx, srt.y - ry) > dist);
+            const unsigned m = (unsigned)(__builtin_amdgcn_ballot_w64(over) >> (lane & ~3)) & 0xfu;
+            if (m == 0) break;
+            const int nxt = __builtin_ctz(m);
             const float4 ln = sel4(L, nxt);
+            float cx3, cy3;
+            const bool ok3 = lp3_candidate_quad(ln, srt, nxt, k, ms, cx3, cy3);
+            rx = ok3 ? cx3 : rx; ry = ok3 ? cy3 : ry;
             dist = det2(ln.z, ln.w, ln.x - rx, ln.y - ry);
             i = nxt + 1;
         }
