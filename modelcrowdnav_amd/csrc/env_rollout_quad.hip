@@ -204,10 +204,13 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_q
         if (do_pair && has_state) ep_disc = disc_table[rs.ep_steps < disc_last ? rs.ep_steps : disc_last];
 
         // ---- candidate neighbour: from the quad that owns it instead of from memory ----
+        // All eight exchanges are issued before the first wait: one LDS round trip per step.  The float velocities
+        // are only read by the ORCA wavefront; the float64 wavefront's two extra exchanges cost it nothing it waits for.
         double2 cpos;
         cpos.x = bperm_d(src, pos.x);
         cpos.y = bperm_d(src, pos.y);
         double crd = bperm_d(src, rad);
+        float cvx = bperm_f(src, (float)vel.x), cvy = bperm_f(src, (float)vel.y);
         if (cand_r) { cpos = rpos; crd = rrad; }
 
         int dn = 0, case_g = 0;
@@ -215,7 +218,6 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_q
 
         // ---- K1: ORCA ----
         if (do_orca) {
-            float cvx = bperm_f(src, (float)vel.x), cvy = bperm_f(src, (float)vel.y);
             if (cand_r) { cvx = (float)rvel.x; cvy = (float)rvel.y; }
             float rx, ry;
             quad_orca_velocity(c, lane, k, cand_h || cand_r, pos, vel, goal, rad, vpref,

@@ -42,24 +42,33 @@ __device__ __forceinline__ float sqrt5(float x)
     return __builtin_fmaf(d, h, g);
 }
 
-// v_cmp_class_f32 masks
-constexpr int kClsPosNormal = 1 << 8, kClsNormal = (1 << 3) | (1 << 8);
-
-// x in [2^-102, 2^128): x * 2^-24 is a positive normal number exactly then (a smaller x lands in the denormals, inf / NaN
-// stay what they are) -- one multiply + one class test for the whole two-sided condition
-__device__ __forceinline__ bool sqrt5_ok(float x) { return __builtin_amdgcn_classf(x * 0x1p-24f, kClsPosNormal); }
-// x normal and |x| < 2^126
-__device__ __forceinline__ bool rcp3_ok(float x) { return __builtin_amdgcn_classf(x, kClsNormal) & (__builtin_fabsf(x) < 0x1p126f); }
-
-// no active lane that uses its result holds an operand outside the fast range
-// (two ballots and a scalar and-not: `used & !ok` as booleans goes through vector registers)
-__device__ __forceinline__ bool wave_fast(bool used, bool ok)
+// The guards are integer range tests on the bit pattern: one subtract and one unsigned compare, which a ballot reads
+// straight from the compare's lane mask.  (v_cmp_class_f32 would be one instruction, but its result reaches a ballot
+// only through a v_cndmask 0/1 and a v_cmp_ne, two more instructions and a hazard nop on the step's critical path.)
+// x positive with biased exponent 25 .. 254 (x in [2^-102, 2^128)): exactly sqrt5's verified range
+__device__ __forceinline__ bool sqrt5_ok(float x)
 {
-    return (__builtin_amdgcn_ballot_w64(used) & ~__builtin_amdgcn_ballot_w64(ok)) == 0;
+    return (unsigned)__builtin_bit_cast(int, x) - (25u << 23) < (230u << 23);
+}
+// x of either sign with biased exponent 1 .. 252 (normal and |x| < 2^126): exactly rcp3's verified range
+__device__ __forceinline__ bool rcp3_ok(float x)
+{
+    return ((unsigned)__builtin_bit_cast(int, x) & 0x7fffffffu) - (1u << 23) < (252u << 23);
 }
 
+// lane mask of a predicate (a compare's own result when `b` is one compare: no vector bool is formed)
+__device__ __forceinline__ unsigned long long lanes(bool b) { return __builtin_amdgcn_ballot_w64(b); }
+
+// no active lane that uses its result holds an operand outside the fast range
+// (two ballots and a scalar and-not: `used & !ok` as booleans goes through vector registers).  `used` may be given
+// as a lane mask when it is a combination of predicates: combined on the scalar unit, the combination is never
+// materialised in a vector register.
+__device__ __forceinline__ bool wave_fast(unsigned long long used, bool ok) { return (used & ~lanes(ok)) == 0; }
+__device__ __forceinline__ bool wave_fast(bool used, bool ok) { return wave_fast(lanes(used), ok); }
+
 // == sqrtf(x), bit for bit
-__device__ __forceinline__ float sqrt_f32(float x, bool used = true)
+template <class U = bool>
+__device__ __forceinline__ float sqrt_f32(float x, U used = true)
 {
 #if MCN_FAST_F32
     if (wave_fast(used, sqrt5_ok(x))) return sqrt5(x);
@@ -68,7 +77,8 @@ __device__ __forceinline__ float sqrt_f32(float x, bool used = true)
 }
 
 // == 1.0f / x, bit for bit
-__device__ __forceinline__ float rcp_f32(float x, bool used = true)
+template <class U = bool>
+__device__ __forceinline__ float rcp_f32(float x, U used = true)
 {
 #if MCN_FAST_F32
     if (wave_fast(used, rcp3_ok(x))) return rcp3(x);
@@ -78,7 +88,8 @@ __device__ __forceinline__ float rcp_f32(float x, bool used = true)
 
 // == 1.0f / sqrtf(x), bit for bit (two roundings, as written); the root of an x in sqrt5's range lies in [2^-51, 2^64):
 // inside rcp3's range, so one guard covers both
-__device__ __forceinline__ float rcp_sqrt_f32(float x, bool used = true)
+template <class U = bool>
+__device__ __forceinline__ float rcp_sqrt_f32(float x, U used = true)
 {
 #if MCN_FAST_F32
     if (wave_fast(used, sqrt5_ok(x))) return rcp3(sqrt5(x));

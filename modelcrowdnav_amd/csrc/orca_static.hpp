@@ -91,7 +91,10 @@ __device__ __forceinline__ float4 orca_u_dir(float px, float py, float vx, float
     // (a lane that takes the cut-off circle -- every colliding pair does -- only needs |w|, one that takes a leg only
     //  the leg and dist^2: a negative squared leg of an overlapping pair must not send the wavefront down the slow path)
     // (lane masks combined on the scalar unit: as booleans the compiler materialises them in vector registers)
-    const unsigned long long m_circle = __builtin_amdgcn_ballot_w64(circle), m_used = __builtin_amdgcn_ballot_w64(used);
+    // (m_circle is `circle` built from the masks of its three compares; bits of inactive lanes are set by the `~`
+    //  but m_used has none)
+    const unsigned long long m_circle = ~lanes(apart) | (lanes(dp1 < 0.0f) & lanes(dp1 * dp1 > cr_sq * wl_sq));
+    const unsigned long long m_used = lanes(used);
     const unsigned long long m_w = __builtin_amdgcn_ballot_w64(sqrt5_ok(wl_sq));
     const unsigned long long m_l = __builtin_amdgcn_ballot_w64(sqrt5_ok(leg_sq)) & __builtin_amdgcn_ballot_w64(dist_sq < 0x1p126f);
     if ((m_used & ~((m_circle & m_w) | (~m_circle & m_l))) == 0) {

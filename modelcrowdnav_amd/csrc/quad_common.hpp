@@ -86,38 +86,45 @@ __device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], int no, float radiu
 // projects line k on line i (RVO2 linearProgram3's inner loop, one projection per lane instead of three in a row),
 // then solves the direction-optimising 1-D LP of ITS projected line against the earlier kept ones speculatively
 // (as the 2-D LP of quad_orca_velocity does), and the incremental LP collapses into three compare-and-take steps.
-// Lines the reference drops (parallel, same direction) are not compacted away but masked: the incremental LP over
+// Lines the reference drops (parallel, same direction) are not compacted away but neutralised: the incremental LP over
 // the kept lines in their original order is the same sequence of operations.  Same arithmetic per value as
 // lp3() in orca_device.hpp / the oracle, so the same bits.  Returns whether the candidate is valid (the inner
 // 2-D LP succeeded); the result is identical on the four lanes.  `li` = line i (L[i]), `lj` = line k, i.e. the sorted
 // line this lane holds itself (the quad broadcast of lane k read on lane k): no run-time select for either.
+//
+// A line that is not kept (dropped, self, or not before i) gets the projected direction (+-0, +-0) -- its 1 / |dd|
+// is replaced by 0 -- or NaN when its operands are not finite.  Either way every test that reads it is false without
+// a mask: its violation test det2(0, 0, ., .) > 0, and in a kept lane's 1-D LP it is "parallel" with num = +-0 (0 > num
+// false) or, with a NaN den, fminf / fmaxf keep tr / tl and tl > tr repeats the previous step's answer.  So no kept
+// flag is broadcast, and the take steps are the 2-D LP's `fail > I` form (quad_orca_velocity).
 __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float4 &lj, int i, int k, float radius, float &rx,
                                                    float &ry)
 {
     const float dt = det2(li.z, li.w, lj.z, lj.w);
     const bool par = fabsf(dt) <= kRvoEps;
-    const bool keptb = (k < i) & !(par & (dot2(li.z, li.w, lj.z, lj.w) > 0.0f));
-    const int kept = keptb ? 1 : 0;
+    const bool same = dot2(li.z, li.w, lj.z, lj.w) > 0.0f;
+    const bool keptb = (k < i) & !(par & same);
+    // the same predicate as a lane mask, combined from the compares' own masks (the guards below read it)
+    const unsigned long long m_kept = lanes(k < i) & ~(lanes(par) & lanes(same));
     const float sc = det2(lj.z, lj.w, li.x - lj.x, li.y - lj.y) / dt;
     const float ddx = lj.z - li.z, ddy = lj.w - li.w;
-    const float inv = rcp_sqrt_f32(dot2(ddx, ddy, ddx, ddy), keptb);       // dropped / self projections: unused
+    const float inv = keptb ? rcp_sqrt_f32(dot2(ddx, ddy, ddx, ddy), m_kept) : 0.0f;
     const float4 q = make_float4(par ? 0.5f * (li.x + lj.x) : li.x + sc * li.z,
                                  par ? 0.5f * (li.y + lj.y) : li.y + sc * li.w, ddx * inv, ddy * inv);
     const float4 P0 = qb4<0>(q), P1 = qb4<1>(q), P2 = qb4<2>(q);
-    const int k0 = qbi<0>(kept), k1 = qbi<1>(kept), k2 = qbi<2>(kept);
     const float ox = -li.w, oy = li.z;
 
-    // speculative 1-D LP of projected line k against the kept projected lines 0 .. min(k, 2) - 1
+    // speculative 1-D LP of projected line k against the projected lines 0 .. min(k, 2) - 1 (dropped ones are no-ops)
     const float dp = dot2(q.x, q.y, q.z, q.w);
     const float disc = dp * dp + radius * radius - dot2(q.x, q.y, q.x, q.y);
     bool ok = !(disc < 0.0f);
-    const float sq = sqrt_f32(disc, ok & keptb);
+    const float sq = sqrt_f32(disc, lanes(!(disc < 0.0f)) & m_kept);
     float tl = -dp - sq;
     float tr = -dp + sq;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const float4 pj = j == 0 ? P0 : P1;
-        const bool live = (j < k) & ((j == 0 ? k0 : k1) != 0);
+        const bool live = j < k;
         const float den = det2(q.z, q.w, pj.z, pj.w);
         const float num = det2(pj.z, pj.w, q.x - pj.x, q.y - pj.y);
         const float t = num / den;
@@ -130,20 +137,23 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float
     }
     const float tt = (dot2(ox, oy, q.z, q.w) > 0.0f) ? tr : tl;
     const float cx = q.x + tt * q.z, cy = q.y + tt * q.w;
-    const int okm = ok ? 1 : 0;
+    // lane k's code for the take steps: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
+    const int fcode = ok ? 4 : k;
 
     rx = radius * ox; ry = radius * oy;
-    bool failed = false;
-#define MCN_LP3_INNER_TAKE(I, PI, KI)                                                          \
+    // as MCN_LP2_TAKE over the lines 0 .. 2: `fail` stays 3 until a violated line's 1-D LP is infeasible
+    int fail = 3;
+#define MCN_LP3_INNER_TAKE(I, PI)                                                              \
     {                                                                                          \
-        const int ok_i = qbi<I>(okm); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy);        \
-        const bool viol = (KI != 0) & !failed & (det2(PI.z, PI.w, PI.x - rx, PI.y - ry) > 0.0f); \
-        rx = (viol & (ok_i != 0)) ? cx_i : rx; ry = (viol & (ok_i != 0)) ? cy_i : ry;           \
-        failed = failed | (viol & (ok_i == 0));                                                 \
+        const int code_i = qbi<I>(fcode); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy);    \
+        const bool out = det2(PI.z, PI.w, PI.x - rx, PI.y - ry) > 0.0f;                         \
+        fail = ((fail > I) & out) ? min(fail, code_i) : fail;                                   \
+        const bool take = (fail > I) & out;                                                     \
+        rx = take ? cx_i : rx; ry = take ? cy_i : ry;                                           \
     }
-    MCN_LP3_INNER_TAKE(0, P0, k0) MCN_LP3_INNER_TAKE(1, P1, k1) MCN_LP3_INNER_TAKE(2, P2, k2)
+    MCN_LP3_INNER_TAKE(0, P0) MCN_LP3_INNER_TAKE(1, P1) MCN_LP3_INNER_TAKE(2, P2)
 #undef MCN_LP3_INNER_TAKE
-    return !failed;
+    return fail == 3;
 }
 
 // ORCA velocity of the human owning this quad.  Lane k holds candidate neighbour k: `o` = its (px, py, vx, vy) in
@@ -224,8 +234,10 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
         float dist = 0.0f;
         int i = fail;
         for (;;) {
-            const bool over = ((unsigned)(k - i) < (unsigned)(nl - i)) & (det2(srt.z, srt.w, srt.x - rx, srt.y - ry) > dist);
-            const unsigned m = (unsigned)(__builtin_amdgcn_ballot_w64(over) >> (lane & ~3)) & 0xfu;
+            // (the two tests' masks are combined on the scalar unit: as one bool it would be materialised first)
+            const unsigned long long over = lanes((unsigned)(k - i) < (unsigned)(nl - i)) &
+                                            lanes(det2(srt.z, srt.w, srt.x - rx, srt.y - ry) > dist);
+            const unsigned m = (unsigned)(over >> (lane & ~3)) & 0xfu;
             if (m == 0) break;
             const int nxt = __builtin_ctz(m);
             const float4 ln = sel4(L, nxt);
