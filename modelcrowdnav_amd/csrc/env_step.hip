@@ -210,9 +210,14 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
                     const int sb = NT - sf;                       // ring distance from j to me
                     const int owner = mine ? tid : gbase + j;
                     const int slot = (mine ? sf : sb) - 1;
-                    const float4 ud = sL[slot * BLOCK + owner];
-                    const float sg = mine ? 0.5f : -0.5f;
-                    Lnat[cidx] = make_float4(fvx + sg * ud.x, fvy + sg * ud.y, mine ? ud.z : -ud.z, mine ? ud.w : -ud.w);
+                    float4 ud = sL[slot * BLOCK + owner];
+                    // (-u, -dir) is the other human's own half-plane up to the sign of an exact zero (a difference
+                    // x - x is +0 from both sides, its negation -0): such a line is rebuilt from this side
+                    const bool rebuild = !mine & ((ud.x == 0.0f) | (ud.y == 0.0f) | (ud.z == 0.0f) | (ud.w == 0.0f));
+                    if (rebuild) ud = orca_u_dir(fpx, fpy, fvx, fvy, frad, sAgF[gbase + j], sRadF[gbase + j], inv_th, inv_ts);
+                    const bool fwd = mine | rebuild;
+                    const float sg = fwd ? 0.5f : -0.5f;
+                    Lnat[cidx] = make_float4(fvx + sg * ud.x, fvy + sg * ud.y, fwd ? ud.z : -ud.z, fwd ? ud.w : -ud.w);
                     const float4 q = sAgF[gbase + j];
                     const float ddx = fpx - q.x, ddy = fpy - q.y;
                     dd[cidx] = dot2(ddx, ddy, ddx, ddy);
@@ -334,6 +339,9 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
                 else if (gap < 1e-3f) borderline = true;
             }
         }
+        // the float32 positions decide the pre-filter only while their rounding (<= 2^-14 per coordinate below 2^10,
+        // neighbours within reach below 2^10 + 2) stays far inside the 1e-3 margin; beyond, the exact test decides
+        if (active && !(fmaxf(fabsf(fpx), fabsf(fpy)) < 1024.0f)) borderline = true;
         if (__any(borderline)) {
             hh = 0;
             if (active) {

@@ -74,6 +74,22 @@ def lp3_entries(reset=True):
     return int(f(C.c_int(1 if reset else 0)))
 
 
+EDGE_NAMES = ("disc_zero_lp2", "disc_zero_lp3", "w_zero_collision", "nonfinite_line", "nonfinite_line_in_lp3",
+              "parallel_lp1", "parallel_same_lp3", "parallel_opposite_lp3", "dist_tie", "range_edge", "tie_at_cut",
+              "leg_det_zero", "pref_on_disc", "outside_fast_range")
+
+
+def edge_counts(reset=True):
+    """Edge events the ORCA solver met since the last reset (mcn_oracle.c, EDGE_*): exact ties, exact zeros, non-finite
+    half-planes, operands outside the fast float32 ranges.  {name: count}."""
+    out = (C.c_long * len(EDGE_NAMES))()
+    f = lib().mcn_oracle_edge_counts
+    f.restype = C.c_int
+    n = f(C.c_int(1 if reset else 0), out, C.c_int(len(EDGE_NAMES)))
+    assert n == len(EDGE_NAMES), "libmcn_oracle.so has %d edge counters, cport knows %d" % (n, len(EDGE_NAMES))
+    return dict(zip(EDGE_NAMES, (int(v) for v in out)))
+
+
 def point_to_segment_dist(x1, y1, x2, y2, x3, y3):
     return lib().mcn_oracle_point_to_segment_dist(x1, y1, x2, y2, x3, y3)
 

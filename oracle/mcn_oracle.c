@@ -65,8 +65,60 @@ static inline float vdet(v2 a, v2 b) { return a.x * b.y - a.y * b.x; }
 static inline float vabssq(v2 a) { return vdot(a, a); }
 /* RVO2's Vector2::operator/(float) multiplies by the reciprocal. */
 static inline v2 vdiv(v2 a, float s) { const float inv = 1.0f / s; return V(a.x * inv, a.y * inv); }
-static inline v2 vnormalize(v2 a) { return vdiv(a, sqrtf(vabssq(a))); }
 static inline float sqrf(float a) { return a * a; }
+
+/* ------------------------------------------------------------------ */
+/* Test hook: edge-event counters                                      */
+/* ------------------------------------------------------------------ */
+/* How often the solver meets the inputs where a fast or reorganised kernel path could part from the plain one (exact
+   ties, exact zeros, non-finite half-planes, operands outside the fast float32 ranges).  Counting only: no value and no
+   evaluation order depends on them (tests/test_oracle_edges.py compares against a build with -DMCN_ORACLE_NO_EDGE_COUNTS).
+   Not thread-safe, like g_lp3_entries. */
+enum {
+    EDGE_DISC_ZERO_LP2,        /* lp1 entered from the top-level 2-D LP with disc == 0 (line tangent to the speed disc) */
+    EDGE_DISC_ZERO_LP3,        /* the same inside lp3's direction-optimising 2-D LP */
+    EDGE_W_ZERO_COLLISION,     /* |w|^2 == 0 in the collision branch */
+    EDGE_NONFINITE_LINE,       /* a half-plane with a non-finite component */
+    EDGE_NONFINITE_LINE_IN_LP3,/* a non-finite line projected (as line j) in lp3 */
+    EDGE_PARALLEL_LP1,         /* |den| <= eps in lp1 */
+    EDGE_PARALLEL_SAME_LP3,    /* |dt| <= eps in lp3, same direction (line dropped) */
+    EDGE_PARALLEL_OPPOSITE_LP3,/* |dt| <= eps in lp3, opposite direction (midpoint line) */
+    EDGE_DIST_TIE,             /* two candidates inside neighborDist with equal squared distance */
+    EDGE_RANGE_EDGE,           /* a candidate with squared distance == neighborDist^2 (excluded: strict <) */
+    EDGE_TIE_AT_CUT,           /* a full neighbour list drops a candidate whose distance ties with a kept one */
+    EDGE_LEG_DET_ZERO,         /* det(rp, w) == 0 in the leg branch (right leg taken) */
+    EDGE_PREF_ON_DISC,         /* |pref|^2 == maxSpeed^2 (not clipped: strict >) */
+    EDGE_OUTSIDE_FAST_RANGE,   /* a consumed sqrtf / 1.0f/x operand outside fast_f32.hpp's verified ranges */
+    EDGE_COUNT
+};
+static long g_edge[EDGE_COUNT];
+#ifdef MCN_ORACLE_NO_EDGE_COUNTS
+#define EDGE(k, cond) ((void)0)
+#else
+#define EDGE(k, cond) ((void)((cond) ? ++g_edge[k] : 0))
+#endif
+/* fast_f32.hpp: sqrt5 is exact for positive x with biased exponent 25..254, rcp3 for either sign with 1..252 */
+static inline uint32_t fbits(float x) { union { float f; uint32_t u; } c; c.f = x; return c.u; }
+static inline int sqrt_fast_ok(float x) { return fbits(x) - (25u << 23) < (230u << 23); }
+static inline int rcp_fast_ok(float x) { return (fbits(x) & 0x7fffffffu) - (1u << 23) < (252u << 23); }
+#define EDGE_SQRT(x) EDGE(EDGE_OUTSIDE_FAST_RANGE, !sqrt_fast_ok(x))
+#define EDGE_RCP(x) EDGE(EDGE_OUTSIDE_FAST_RANGE, !rcp_fast_ok(x))
+static inline int line_finite(hline l) { return isfinite(l.p.x) && isfinite(l.p.y) && isfinite(l.d.x) && isfinite(l.d.y); }
+
+/* Returns the counters (out[0 .. min(n, EDGE_COUNT))) and the number of counters there are; reset != 0 zeroes them. */
+int mcn_oracle_edge_counts(int reset, long *out, int n)
+{
+    for (int k = 0; k < n && k < EDGE_COUNT; ++k) out[k] = g_edge[k];
+    if (reset) for (int k = 0; k < EDGE_COUNT; ++k) g_edge[k] = 0;
+    return EDGE_COUNT;
+}
+
+static inline v2 vnormalize(v2 a)
+{
+    EDGE_SQRT(vabssq(a));
+    EDGE_RCP(sqrtf(vabssq(a)));
+    return vdiv(a, sqrtf(vabssq(a)));
+}
 
 /* 1-D LP along line `no`, constrained by lines [0,no) and the speed disc. */
 static int lp1(const hline *L, int no, float radius, v2 opt, int dir_opt, v2 *res)
@@ -74,6 +126,8 @@ static int lp1(const hline *L, int no, float radius, v2 opt, int dir_opt, v2 *re
     const float dp = vdot(L[no].p, L[no].d);
     const float disc = sqrf(dp) + sqrf(radius) - vabssq(L[no].p);
     if (disc < 0.0f) return 0;
+    EDGE(dir_opt ? EDGE_DISC_ZERO_LP3 : EDGE_DISC_ZERO_LP2, disc == 0.0f);
+    EDGE_SQRT(disc);
     const float sq = sqrtf(disc);
     float tl = -dp - sq;
     float tr = -dp + sq;
@@ -81,6 +135,7 @@ static int lp1(const hline *L, int no, float radius, v2 opt, int dir_opt, v2 *re
         const float den = vdet(L[no].d, L[i].d);
         const float num = vdet(L[i].d, vsub(L[no].p, L[i].p));
         if (fabsf(den) <= RVO_EPS) {
+            EDGE(EDGE_PARALLEL_LP1, 1);
             if (num < 0.0f) return 0;
             continue;
         }
@@ -104,6 +159,7 @@ static int lp1(const hline *L, int no, float radius, v2 opt, int dir_opt, v2 *re
 /* Incremental 2-D LP.  Returns the index of the first failing line, or n. */
 static int lp2(const hline *L, int n, float radius, v2 opt, int dir_opt, v2 *res)
 {
+    EDGE(EDGE_PREF_ON_DISC, !dir_opt && vabssq(opt) == sqrf(radius));
     if (dir_opt)                           *res = vscale(radius, opt);   /* opt * radius */
     else if (vabssq(opt) > sqrf(radius))   *res = vscale(radius, vnormalize(opt));
     else                                   *res = opt;
@@ -132,8 +188,11 @@ static void lp3(const hline *L, int n, int begin, float radius, v2 *res)
             int m = 0;
             for (int j = 0; j < i; ++j) {
                 hline q;
+                EDGE(EDGE_NONFINITE_LINE_IN_LP3, !line_finite(L[j]));
                 const float dt = vdet(L[i].d, L[j].d);
                 if (fabsf(dt) <= RVO_EPS) {
+                    EDGE(EDGE_PARALLEL_SAME_LP3, vdot(L[i].d, L[j].d) > 0.0f);
+                    EDGE(EDGE_PARALLEL_OPPOSITE_LP3, !(vdot(L[i].d, L[j].d) > 0.0f));
                     if (vdot(L[i].d, L[j].d) > 0.0f) continue;
                     q.p = vscale(0.5f, vadd(L[i].p, L[j].p));
                 } else {
@@ -171,8 +230,19 @@ static int orca_build_lines(v2 pos, v2 vel, float radius, int n_other,
     float range_sq = sqrf(neighbor_dist);
     if (max_neighbors > MCN_MAX_NEIGH) max_neighbors = MCN_MAX_NEIGH;
     if (max_neighbors > 0) {
+#ifndef MCN_ORACLE_NO_EDGE_COUNTS
         for (int j = 0; j < n_other; ++j) {
             const float d = vabssq(vsub(pos, V(opx[j], opy[j])));
+            EDGE(EDGE_RANGE_EDGE, d == range_sq);
+            for (int k = j + 1; k < n_other; ++k)
+                EDGE(EDGE_DIST_TIE, d < range_sq && d == vabssq(vsub(pos, V(opx[k], opy[k]))));
+        }
+#endif
+        for (int j = 0; j < n_other; ++j) {
+            const float d = vabssq(vsub(pos, V(opx[j], opy[j])));
+            /* full list: a candidate at the cut distance is dropped, or the last of two tied entries is */
+            EDGE(EDGE_TIE_AT_CUT, cnt == max_neighbors &&
+                                  (d == range_sq || (d < range_sq && cnt >= 2 && dsq[cnt - 2] == dsq[cnt - 1])));
             if (d < range_sq) {
                 if (cnt < max_neighbors) ++cnt;
                 int i = cnt - 1;
@@ -197,11 +267,16 @@ static int orca_build_lines(v2 pos, v2 vel, float radius, int n_other,
             const float wl_sq = vabssq(w);
             const float dp1 = vdot(w, rp);
             if (dp1 < 0.0f && sqrf(dp1) > cr_sq * wl_sq) {
+                EDGE_SQRT(wl_sq);
+                EDGE_RCP(sqrtf(wl_sq));
                 const float wl = sqrtf(wl_sq);
                 const v2 uw = vdiv(w, wl);
                 ln.d = V(uw.y, -uw.x);
                 u = vscale(cr * inv_th - wl, uw);
             } else {
+                EDGE_SQRT(dist_sq - cr_sq);
+                EDGE_RCP(dist_sq);
+                EDGE(EDGE_LEG_DET_ZERO, vdet(rp, w) == 0.0f);
                 const float leg = sqrtf(dist_sq - cr_sq);
                 if (vdet(rp, w) > 0.0f) {
                     ln.d = vdiv(V(rp.x * leg - rp.y * cr, rp.x * cr + rp.y * leg), dist_sq);
@@ -215,12 +290,16 @@ static int orca_build_lines(v2 pos, v2 vel, float radius, int n_other,
         } else {
             const float inv_ts = 1.0f / time_step;
             const v2 w = vsub(rv, vscale(inv_ts, rp));
+            EDGE(EDGE_W_ZERO_COLLISION, vabssq(w) == 0.0f);
+            EDGE_SQRT(vabssq(w));
+            EDGE_RCP(sqrtf(vabssq(w)));
             const float wl = sqrtf(vabssq(w));
             const v2 uw = vdiv(w, wl);
             ln.d = V(uw.y, -uw.x);
             u = vscale(cr * inv_ts - wl, uw);
         }
         ln.p = vadd(vel, vscale(0.5f, u));
+        EDGE(EDGE_NONFINITE_LINE, !line_finite(ln));
         L[k] = ln;
     }
     return cnt;

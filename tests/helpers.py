@@ -83,13 +83,35 @@ def download(env):
 STATE_FIELDS = cport.EnvState.FIELDS_H + cport.EnvState.FIELDS_R + ("gtime", "human_times")
 
 
+def bit_mismatch(x, y):
+    """Indices at which x and y differ bit for bit.  Floats compare as float64 bit patterns, so -0.0 != +0.0; any NaN
+    equals any NaN (the default NaN of x86 has its sign bit set, the GPU's does not).  Other dtypes compare by value."""
+    x, y = np.asarray(x), np.asarray(y)
+    if x.shape != y.shape:
+        raise AssertionError("shapes differ: %s vs %s" % (x.shape, y.shape))
+    if x.dtype.kind == "f" or y.dtype.kind == "f":
+        x, y = x.astype(np.float64), y.astype(np.float64)
+        diff = (x.view(np.uint64) != y.view(np.uint64)) & ~(np.isnan(x) & np.isnan(y))
+    else:
+        diff = x != y
+    return np.argwhere(diff)
+
+
+def bits_equal(x, y):
+    return len(bit_mismatch(x, y)) == 0
+
+
+def assert_bits_equal(x, y, what=""):
+    bad = bit_mismatch(x, y)
+    if len(bad):
+        x, y = np.asarray(x), np.asarray(y)
+        i = tuple(bad[0])
+        raise AssertionError("%s differs (bitwise) at %d places, first %s: %r vs %r" % (what, len(bad), bad[0], x[i], y[i]))
+
+
 def assert_state_equal(a, b, fields=STATE_FIELDS, what=""):
     for k in fields:
-        x, y = getattr(a, k), getattr(b, k)
-        if not np.array_equal(x, y):
-            bad = np.argwhere(x != y)
-            raise AssertionError("%s field %s differs at %d places, first %s: %r vs %r" % (
-                what, k, len(bad), bad[0], x[tuple(bad[0])], y[tuple(bad[0])]))
+        assert_bits_equal(getattr(a, k), getattr(b, k), "%s field %s" % (what, k))
 
 
 def oracle_cfg_for(env, human_policy=cport.HUMANS_ORCA):
@@ -99,4 +121,8 @@ def oracle_cfg_for(env, human_policy=cport.HUMANS_ORCA):
                              discomfort_penalty_factor=env.discomfort_penalty_factor,
                              robot_visible=1 if env.robot.visible else 0, human_policy=human_policy,
                              count_hh=1 if env.count_hh else 0, track_human_times=1 if env.track_human_times else 0,
-                             robot_unicycle=1 if getattr(env.robot, "kinematics", "") == "unicycle" else 0)
+                             robot_unicycle=1 if getattr(env.robot, "kinematics", "") == "unicycle" else 0,
+                             orca_safety_space=float(env._orca.safety_space),
+                             orca_neighbor_dist=float(env._orca.neighbor_dist),
+                             orca_max_neighbors=int(env._orca.max_neighbors),
+                             orca_time_horizon=float(env._orca.time_horizon))

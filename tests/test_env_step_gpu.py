@@ -85,9 +85,9 @@ def test_step_matches_oracle_bitexact(N, visible, randomize, update, kernel, tun
         assert cport.lp3_entries() > 20
         assert int(ref["hh_count"].sum()) > 20
     for k in ("done", "info", "hh_count"):
-        assert np.array_equal(got[k], ref[k]), k
+        H.assert_bits_equal(got[k], ref[k], k)
     for k in [k for k in ref if k not in ("done", "info", "hh_count")]:
-        assert np.array_equal(got[k], ref[k]), k
+        H.assert_bits_equal(got[k], ref[k], k)
     if update:
         H.assert_state_equal(H.download(env), ref_st, what="N=%d" % N)
     else:
@@ -121,13 +121,13 @@ def test_full_lp3_queue_turns_lanes_back_to_solving_in_place(N, visible, block, 
     assert int(_hip.lib.mcn_env_lp3_queue_bytes(E, N)) < 256 * subcap * (28 + 16 * N) + (1 << 17)
     assert cport.lp3_entries() > 1.2 * 256 * subcap, (cport.lp3_entries(), 256 * subcap)
     for k in ref:
-        assert np.array_equal(got[k], ref[k]), k
+        H.assert_bits_equal(got[k], ref[k], k)
     if update:
         H.assert_state_equal(H.download(env), ref_st, what="N=%d" % N)
     # the queue's counters were reset by the finish kernel: a second step from the same state gives the same bits
     got2, _, _ = _step_both(env, st, sp * np.cos(aa), sp * np.sin(aa), update)
     for k in ref:
-        assert np.array_equal(got2[k], ref[k]), k
+        H.assert_bits_equal(got2[k], ref[k], k)
 
 
 @pytest.mark.parametrize("E,N,mode", [(1 << 20, 5, "orca"), (1 << 22, 5, "orca"), (1 << 22, 5, "given"),
@@ -158,7 +158,7 @@ def test_roofline_sweep_sizes_every_env_against_the_oracle(E, N, mode):
     for k in ref:
         if k == "human_act" and mode == "given":
             continue
-        assert np.array_equal(got[k], ref[k]), k
+        H.assert_bits_equal(got[k], ref[k], k)
     fields = [f for f in H.STATE_FIELDS if not (mode == "given" and f == "human_times")]
     H.assert_state_equal(H.download(env), ref_st, fields=fields, what="E=%d N=%d %s" % (E, N, mode))
     del env
@@ -175,7 +175,7 @@ def test_given_velocity_and_linear_modes():
     ax, ay = rng.uniform(-1, 1, E), rng.uniform(-1, 1, E)
     got, ref, ref_st = _step_both(env, st, ax, ay, True, cport.HUMANS_GIVEN, gv)
     for k in ref:
-        assert np.array_equal(got[k], ref[k]), k
+        H.assert_bits_equal(got[k], ref[k], k)
     H.assert_state_equal(H.download(env), ref_st)
     env2 = H.make_vec_env(E, N)
     got, ref, ref_st = _step_both(env2, st, ax, ay, True, cport.HUMANS_LINEAR)
@@ -220,8 +220,10 @@ def test_streaming_pair_kernel_equals_lane_per_human(N, book, stream, tuning):
         if t == 0:
             ref = cport.env_step(H.oracle_cfg_for(a, cport.HUMANS_GIVEN), st0, acts[0, :, 0].cpu().numpy().copy(),
                                  acts[0, :, 1].cpu().numpy().copy(), update=True, given_v=gv[0].cpu().numpy())
-            assert np.array_equal(a.done.cpu().numpy(), ref["done"]) and np.array_equal(a.reward.cpu().numpy(), ref["reward"])
-            assert np.array_equal(a.dmin.cpu().numpy(), ref["dmin"]) and np.array_equal(a.info.cpu().numpy(), ref["info"])
+            H.assert_bits_equal(a.done.cpu().numpy(), ref["done"], "done")
+            H.assert_bits_equal(a.reward.cpu().numpy(), ref["reward"], "reward")
+            H.assert_bits_equal(a.dmin.cpu().numpy(), ref["dmin"], "dmin")
+            H.assert_bits_equal(a.info.cpu().numpy(), ref["info"], "info")
             if book != "pool":
                 H.assert_state_equal(H.download(a), st0, what="streaming pair kernel vs oracle")
         if t % 13 == 0 or t == T - 1:
@@ -309,7 +311,7 @@ def _rollout_4096x5():
         ref = cport.env_step(cfg, st, ax, ay, update=True)
         assert np.array_equal(done.cpu().numpy(), ref["done"]), t
         assert np.array_equal(info.cpu().numpy(), ref["info"]), t
-        assert np.array_equal(reward.cpu().numpy(), ref["reward"]), t
+        H.assert_bits_equal(reward.cpu().numpy(), ref["reward"], t)
         assert np.array_equal(env.hh_count.cpu().numpy(), ref["hh_count"]), t
         done_total += int(ref["done"].sum())
     H.assert_state_equal(H.download(env), st, what="after %d steps" % T)
@@ -419,8 +421,9 @@ def test_looped_rollout_launch_matches_oracle_trajectory(N, visible, tuning):
     for t in range(T):
         ref = cport.env_step(cfg, st, ax[t], ay[t], update=True)
     H.assert_state_equal(H.download(env), st, what="after one %d-step launch" % T)
-    assert np.array_equal(env.reward.cpu().numpy(), ref["reward"]) and np.array_equal(env.done.cpu().numpy(), ref["done"])
-    assert np.array_equal(env.human_act.cpu().numpy(), ref["human_act"])          # outputs of the last step
+    H.assert_bits_equal(env.reward.cpu().numpy(), ref["reward"], "reward")
+    H.assert_bits_equal(env.done.cpu().numpy(), ref["done"], "done")
+    H.assert_bits_equal(env.human_act.cpu().numpy(), ref["human_act"], "human_act")          # outputs of the last step
     assert cport.lp3_entries() > 100, "the crossing should drive humans into the 3-D LP"
 
 
@@ -453,9 +456,9 @@ def test_larger_crowd_trajectories_match_oracle(N, block, tuning):
         ob, reward, done, info = env.step(torch.from_numpy(np.stack([ax, ay], -1)).to(env.device))
         ref = cport.env_step(cfg, st, ax, ay, update=True)
         assert np.array_equal(done.cpu().numpy(), ref["done"]), t
-        assert np.array_equal(reward.cpu().numpy(), ref["reward"]), t
+        H.assert_bits_equal(reward.cpu().numpy(), ref["reward"], t)
         assert np.array_equal(env.hh_count.cpu().numpy(), ref["hh_count"]), t
-        assert np.array_equal(env.human_act.cpu().numpy(), ref["human_act"]), t
+        H.assert_bits_equal(env.human_act.cpu().numpy(), ref["human_act"], t)
     H.assert_state_equal(H.download(env), st, what="after %d steps" % T)
     assert cport.lp3_entries() > (100 if N > 5 else 20) * T // 10, "the crossing should drive humans into the 3-D LP"
 
@@ -567,13 +570,13 @@ def test_bench_timed_launch_shapes_against_single_steps_and_oracle(N, T):
     st, ref, episodes = _oracle_with_pool_restarts(ids, pool, N, acts.cpu().numpy(), T, a)
     assert episodes > 4 * 64
     got = {k: getattr(a, k).cpu().numpy()[ids] for k in ("hpos", "hvel", "hgoal", "hrad", "rpos", "rvel", "gtime")}
-    assert np.array_equal(got["hpos"][..., 0], st.hpx) and np.array_equal(got["hpos"][..., 1], st.hpy)
-    assert np.array_equal(got["hvel"][..., 0], st.hvx) and np.array_equal(got["hvel"][..., 1], st.hvy)
-    assert np.array_equal(got["hgoal"][..., 0], st.hgx) and np.array_equal(got["hrad"], st.hr)
-    assert np.array_equal(got["rpos"][:, 0], st.rpx) and np.array_equal(got["rpos"][:, 1], st.rpy)
-    assert np.array_equal(got["rvel"][:, 0], st.rvx) and np.array_equal(got["gtime"], st.gtime)
-    assert np.array_equal(a.reward.cpu().numpy()[ids], ref["reward"]) and np.array_equal(a.done.cpu().numpy()[ids], ref["done"])
-    assert np.array_equal(a.info.cpu().numpy()[ids], ref["info"]) and np.array_equal(a.dmin.cpu().numpy()[ids], ref["dmin"])
+    assert H.bits_equal(got["hpos"][..., 0], st.hpx) and H.bits_equal(got["hpos"][..., 1], st.hpy)
+    assert H.bits_equal(got["hvel"][..., 0], st.hvx) and H.bits_equal(got["hvel"][..., 1], st.hvy)
+    assert H.bits_equal(got["hgoal"][..., 0], st.hgx) and H.bits_equal(got["hrad"], st.hr)
+    assert H.bits_equal(got["rpos"][:, 0], st.rpx) and H.bits_equal(got["rpos"][:, 1], st.rpy)
+    assert H.bits_equal(got["rvel"][:, 0], st.rvx) and H.bits_equal(got["gtime"], st.gtime)
+    assert H.bits_equal(a.reward.cpu().numpy()[ids], ref["reward"]) and H.bits_equal(a.done.cpu().numpy()[ids], ref["done"])
+    assert H.bits_equal(a.info.cpu().numpy()[ids], ref["info"]) and H.bits_equal(a.dmin.cpu().numpy()[ids], ref["dmin"])
 
 
 def test_rollout_launch_matches_oracle_trajectory():
@@ -594,10 +597,12 @@ def test_rollout_launch_matches_oracle_trajectory():
     for t in range(T):
         ref = cport.env_step(cfg, st, ax[t], ay[t], update=True)
     H.assert_state_equal(H.download(env), st, what="after a %d-step launch" % T)
-    assert np.array_equal(env.reward.cpu().numpy(), ref["reward"]) and np.array_equal(env.done.cpu().numpy(), ref["done"])
-    assert np.array_equal(env.info.cpu().numpy(), ref["info"]) and np.array_equal(env.dmin.cpu().numpy(), ref["dmin"])
+    H.assert_bits_equal(env.reward.cpu().numpy(), ref["reward"], "reward")
+    H.assert_bits_equal(env.done.cpu().numpy(), ref["done"], "done")
+    H.assert_bits_equal(env.info.cpu().numpy(), ref["info"], "info")
+    H.assert_bits_equal(env.dmin.cpu().numpy(), ref["dmin"], "dmin")
     assert np.array_equal(env.hh_count.cpu().numpy(), ref["hh_count"])
-    np.testing.assert_array_equal(env.human_act.cpu().numpy(), ref["human_act"])
+    H.assert_bits_equal(env.human_act.cpu().numpy(), ref["human_act"], "human_act")
 
 
 def test_rollout_rejects_bad_arguments():
@@ -684,11 +689,11 @@ def test_degenerate_configurations_match_oracle(kernel, tuning):
     for update in (True, False):
         got, ref, ref_st = _step_both(env, st, ax, ay, update)
         for key in ref:
-            assert np.array_equal(got[key], ref[key], equal_nan=True), (key, update)
+            H.assert_bits_equal(got[key], ref[key], (key, update))
         if update:
             dl = H.download(env)
             for f in H.STATE_FIELDS:
-                assert np.array_equal(getattr(dl, f), getattr(ref_st, f), equal_nan=True), f
+                H.assert_bits_equal(getattr(dl, f), getattr(ref_st, f), f)
     # (coincident agents make a NaN half-plane; every comparison with it is false, so the LP skips it and the
     # outputs stay finite -- in the oracle and on the device alike)
     assert np.isfinite(ref["human_act"]).all()
@@ -707,7 +712,7 @@ def test_single_env_and_tiny_batches():
             ax, ay = rng.uniform(-1, 1, E), rng.uniform(-1, 1, E)
             got, ref, ref_st = _step_both(env, st, ax, ay, True)
             for key in ref:
-                assert np.array_equal(got[key], ref[key]), (E, N, key)
+                H.assert_bits_equal(got[key], ref[key], (E, N, key))
             H.assert_state_equal(H.download(env), ref_st)
 
 
@@ -738,7 +743,7 @@ def test_config5_shape_32768x10_exact_and_shard_invariant():
         ob, reward, done, info = env.step(torch.from_numpy(acts[t]).to(env.device))
         ref = cport.env_step(cfg, st, acts[t, :, 0].copy(), acts[t, :, 1].copy(), update=True)
         assert np.array_equal(done.cpu().numpy(), ref["done"]) and np.array_equal(info.cpu().numpy(), ref["info"]), t
-        assert np.array_equal(reward.cpu().numpy(), ref["reward"]), t
+        H.assert_bits_equal(reward.cpu().numpy(), ref["reward"], t)
         for r, sub in enumerate(shards):
             sub.step(torch.from_numpy(acts[t, r * 4096:(r + 1) * 4096]).to(sub.device))
     H.assert_state_equal(H.download(env), st, fields=[f for f in H.STATE_FIELDS if f != "human_times"])
