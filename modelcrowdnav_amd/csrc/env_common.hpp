@@ -34,12 +34,13 @@ __device__ __forceinline__ void store_step_rec(mcn_step_rec *dst, double reward,
     reinterpret_cast<unsigned long long *>(d)[2] = tail;
 }
 
-// Python's float % for a positive divisor
+// Python's float % for a positive divisor: a negative remainder moves up by m, a zero one is +0.0 (copysign(0, m)),
+// also when fmod returns -0.0 (a == -0.0 or a negative multiple of m)
 __device__ __forceinline__ double pymod(double a, double m)
 {
     double r = fmod(a, m);
-    if (r != 0 && r < 0) r += m;
-    return r;
+    if (r < 0) r += m;
+    return r == 0 ? 0.0 : r;
 }
 
 }  // namespace mcn

@@ -90,6 +90,24 @@ def edge_counts(reset=True):
     return dict(zip(EDGE_NAMES, (int(v) for v in out)))
 
 
+LADDER_NAMES = ("swept_touch", "swept_point", "swept_u_zero", "swept_u_one", "dmin_tie", "danger_edge", "reach_edge",
+                "reach_band", "collision_and_reach", "timeout_and_collision", "timeout_edge", "timeout_below",
+                "hh_touch", "hh_band6", "hh_band3", "human_time_edge", "theta_zero_rem", "theta_neg_rem", "la_touch",
+                "la_danger_edge", "la_reach_edge", "la_collision_after_min")
+
+
+def ladder_counts(reset=True):
+    """Boundary events the float64 half of the step and the look-ahead reward met since the last reset (mcn_oracle.c,
+    LAD_*): exact ties and near misses of the swept test, the overlap count, the goal test, the reward ladder, the
+    first-arrival test and the heading.  {name: count}."""
+    out = (C.c_long * len(LADDER_NAMES))()
+    f = lib().mcn_oracle_ladder_counts
+    f.restype = C.c_int
+    n = f(C.c_int(1 if reset else 0), out, C.c_int(len(LADDER_NAMES)))
+    assert n == len(LADDER_NAMES), "libmcn_oracle.so has %d ladder counters, cport knows %d" % (n, len(LADDER_NAMES))
+    return dict(zip(LADDER_NAMES, (int(v) for v in out)))
+
+
 def point_to_segment_dist(x1, y1, x2, y2, x3, y3):
     return lib().mcn_oracle_point_to_segment_dist(x1, y1, x2, y2, x3, y3)
 

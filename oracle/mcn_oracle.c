@@ -113,6 +113,50 @@ int mcn_oracle_edge_counts(int reset, long *out, int n)
     return EDGE_COUNT;
 }
 
+/* The same for the float64 half of a step (swept test, human-human overlaps, goal test, reward ladder, first-arrival
+   times, heading, look-ahead reward): exact ties and near misses where a kernel's screen, pre-filter, reduction or
+   branch-free form could part from the plain ladder below.  Separate from EDGE_* so the ORCA coverage assertions do not
+   change; compiled out by the same switch (tests/test_oracle_ladder.py). */
+enum {
+    LAD_SWEPT_TOUCH,           /* closest distance - radii == 0 (touching is no collision) */
+    LAD_SWEPT_POINT,           /* point_to_segment_dist on a point: relative velocity exactly zero */
+    LAD_SWEPT_U_ZERO,          /* unclamped u == 0 */
+    LAD_SWEPT_U_ONE,           /* unclamped u == 1 */
+    LAD_DMIN_TIE,              /* two humans of one env with equal closest distance */
+    LAD_DANGER_EDGE,           /* dmin == discomfort_dist (NOTHING, not DANGER) */
+    LAD_REACH_EDGE,            /* |end - goal| == robot radius (not reaching) */
+    LAD_REACH_BAND,            /* 0 < | |end - goal| - robot radius | <= 1e-6 */
+    LAD_COLLISION_AND_REACH,   /* both in one step: collision wins */
+    LAD_TIMEOUT_AND_COLLISION, /* both in one step: timeout wins */
+    LAD_TIMEOUT_EDGE,          /* global time == time_limit - 1 */
+    LAD_TIMEOUT_BELOW,         /* global time one ulp below time_limit - 1 */
+    LAD_HH_TOUCH,              /* human-human gap exactly 0 (not counted) */
+    LAD_HH_BAND6,              /* 0 < |gap| <= 1e-6 */
+    LAD_HH_BAND3,              /* 1e-6 < |gap| < 1e-3 */
+    LAD_HUMAN_TIME_EDGE,       /* |human - goal| == human radius at the first-arrival test */
+    LAD_THETA_ZERO_REM,        /* fmod remainder of the new heading is zero (either sign) */
+    LAD_THETA_NEG_REM,         /* fmod remainder of the new heading is negative */
+    LAD_LA_TOUCH,              /* look-ahead: d == 0 */
+    LAD_LA_DANGER_EDGE,        /* look-ahead: dmin == 0.2 */
+    LAD_LA_REACH_EDGE,         /* look-ahead: |next - goal| == robot radius */
+    LAD_LA_COLLISION_AFTER_MIN,/* look-ahead: the colliding human follows one with a finite d, and the loop breaks early */
+    LAD_COUNT
+};
+static long g_lad[LAD_COUNT];
+#ifdef MCN_ORACLE_NO_EDGE_COUNTS
+#define LAD(k, cond) ((void)0)
+#else
+#define LAD(k, cond) ((void)((cond) ? ++g_lad[k] : 0))
+#endif
+
+/* As mcn_oracle_edge_counts, for the LAD_* counters. */
+int mcn_oracle_ladder_counts(int reset, long *out, int n)
+{
+    for (int k = 0; k < n && k < LAD_COUNT; ++k) out[k] = g_lad[k];
+    if (reset) for (int k = 0; k < LAD_COUNT; ++k) g_lad[k] = 0;
+    return LAD_COUNT;
+}
+
 static inline v2 vnormalize(v2 a)
 {
     EDGE_SQRT(vabssq(a));
@@ -347,8 +391,11 @@ static inline double norm2(double x0, double x1) { return sqrt(fma(x1, x1, x0 * 
 double mcn_oracle_point_to_segment_dist(double x1, double y1, double x2, double y2, double x3, double y3)
 {
     const double px = x2 - x1, py = y2 - y1;
+    LAD(LAD_SWEPT_POINT, px == 0 && py == 0);
     if (px == 0 && py == 0) return norm2(x3 - x1, y3 - y1);
     double u = ((x3 - x1) * px + (y3 - y1) * py) / (px * px + py * py);
+    LAD(LAD_SWEPT_U_ZERO, u == 0);
+    LAD(LAD_SWEPT_U_ONE, u == 1);
     if (u > 1) u = 1; else if (u < 0) u = 0;
     const double x = x1 + u * px, y = y1 + u * py;
     return norm2(x - x3, y - y3);
@@ -431,6 +478,7 @@ void mcn_oracle_env_step(const mcn_oracle_cfg *c, int E, int N, int update,
 
         /* ---- robot-human swept test (crowd_sim.py:345-365) ---- */
         double dmin = INFINITY; int collision = 0;
+        double cds[MCN_MAX_NEIGH];
         double eax = ax[e], eay = ay[e];        /* robot velocity seen by the swept test */
         if (c->robot_unicycle) {
             eax = ax[e] * cos(ay[e] + rtheta[e]);
@@ -443,6 +491,11 @@ void mcn_oracle_env_step(const mcn_oracle_cfg *c, int E, int N, int update,
             const double cd = mcn_oracle_point_to_segment_dist(px, py, ex, ey, 0, 0) - hr[b + i] - rr[e];
             if (cd < 0) collision = 1;
             if (cd < dmin) dmin = cd;
+            cds[i] = cd;
+            LAD(LAD_SWEPT_TOUCH, cd == 0);
+#ifndef MCN_ORACLE_NO_EDGE_COUNTS
+            for (int k = 0; k < i; ++k) LAD(LAD_DMIN_TIE, cds[k] == cd);
+#endif
         }
 
         /* ---- human-human overlaps (crowd_sim.py:368-376) ---- */
@@ -457,6 +510,9 @@ void mcn_oracle_env_step(const mcn_oracle_cfg *c, int E, int N, int update,
                        the sign of `d` only for pairs within one ulp of touching
                        (tests/test_oracle_golden.py::test_pow_half_vs_sqrt_never_flips_the_overlap_test) */
                     const double d = pow(dx * dx + dy * dy, 0.5) - hr[b + i] - hr[b + j];
+                    LAD(LAD_HH_TOUCH, d == 0);
+                    LAD(LAD_HH_BAND6, d != 0 && fabs(d) <= 1e-6);
+                    LAD(LAD_HH_BAND3, fabs(d) > 1e-6 && fabs(d) < 1e-3);
                     if (d < 0) ++hh;
                 }
         }
@@ -467,12 +523,23 @@ void mcn_oracle_env_step(const mcn_oracle_cfg *c, int E, int N, int update,
             const double th = rtheta[e] + ay[e];                       /* agent.py:115-118 */
             endx = rpx[e] + cos(th) * ax[e] * dt; endy = rpy[e] + sin(th) * ax[e] * dt;
             nth = fmod(rtheta[e] + ay[e], 2 * M_PI);                   /* agent.py:133, Python % */
-            if (nth != 0 && nth < 0) nth += 2 * M_PI;
+            LAD(LAD_THETA_ZERO_REM, nth == 0);
+            LAD(LAD_THETA_NEG_REM, nth < 0);
+            if (nth < 0) nth += 2 * M_PI;
+            else if (nth == 0) nth = 0.0;                              /* Python: a zero remainder is +0.0 */
             nrvx = ax[e] * cos(nth); nrvy = ax[e] * sin(nth);
         } else {
             endx = rpx[e] + ax[e] * dt; endy = rpy[e] + ay[e] * dt;
         }
-        const int reaching = norm2(endx - rgx[e], endy - rgy[e]) < rr[e];
+        const double gdist = norm2(endx - rgx[e], endy - rgy[e]);
+        const int reaching = gdist < rr[e];
+        LAD(LAD_REACH_EDGE, gdist == rr[e]);
+        LAD(LAD_REACH_BAND, gdist != rr[e] && fabs(gdist - rr[e]) <= 1e-6);
+        LAD(LAD_COLLISION_AND_REACH, collision && reaching);
+        LAD(LAD_TIMEOUT_AND_COLLISION, gtime[e] >= c->time_limit - 1 && collision);
+        LAD(LAD_TIMEOUT_EDGE, gtime[e] == c->time_limit - 1);
+        LAD(LAD_TIMEOUT_BELOW, gtime[e] == nextafter(c->time_limit - 1, -INFINITY));
+        LAD(LAD_DANGER_EDGE, dmin == c->discomfort_dist);
         double rew; uint8_t dn, inf;
         if (gtime[e] >= c->time_limit - 1)   { rew = 0; dn = 1; inf = MCN_INFO_TIMEOUT; }
         else if (collision)                  { rew = c->collision_penalty; dn = 1; inf = MCN_INFO_COLLISION; }
@@ -491,10 +558,12 @@ void mcn_oracle_env_step(const mcn_oracle_cfg *c, int E, int N, int update,
             }
             gtime[e] += dt;
             if (c->track_human_times && human_times) {
-                for (int i = 0; i < N; ++i)
-                    if (human_times[b + i] == 0 &&
-                        norm2(hpx[b + i] - hgx[b + i], hpy[b + i] - hgy[b + i]) < hr[b + i])
-                        human_times[b + i] = gtime[e];
+                for (int i = 0; i < N; ++i) {
+                    if (human_times[b + i] != 0) continue;
+                    const double hd = norm2(hpx[b + i] - hgx[b + i], hpy[b + i] - hgy[b + i]);
+                    LAD(LAD_HUMAN_TIME_EDGE, hd == hr[b + i]);
+                    if (hd < hr[b + i]) human_times[b + i] = gtime[e];
+                }
             }
         } else {
             for (int i = 0; i < N; ++i) {
@@ -523,10 +592,15 @@ void mcn_oracle_lookahead_reward(int E, int N, int A, double dt,
                 const int k = e * N + i;
                 const double qx = hpx[k] + hvx[k] * dt, qy = hpy[k] + hvy[k] * dt;
                 const double d = norm2(nx - qx, ny - qy) - rr[e] - hr[k];
+                LAD(LAD_LA_TOUCH, d == 0);
+                LAD(LAD_LA_COLLISION_AFTER_MIN, d < 0 && dmin < INFINITY && i + 1 < N);
                 if (d < 0) { coll = 1; break; }
                 if (d < dmin) dmin = d;
             }
-            const int reach = norm2(nx - rgx[e], ny - rgy[e]) < rr[e];
+            const double gdist = norm2(nx - rgx[e], ny - rgy[e]);
+            const int reach = gdist < rr[e];
+            LAD(LAD_LA_REACH_EDGE, gdist == rr[e]);
+            LAD(LAD_LA_DANGER_EDGE, !coll && dmin == 0.2);
             double r;
             if (coll) r = -0.25; else if (reach) r = 1; else if (dmin < 0.2) r = (dmin - 0.2) * 0.5 * dt; else r = 0;
             out[e * A + a] = r;

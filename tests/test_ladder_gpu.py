@@ -1,0 +1,329 @@
+"""The float64 half of every step kernel on exact boundaries (tests/ladder_states.py), bit for bit against the C oracle:
+the swept test (touching, a point segment, u exactly 0 or 1, tied humans), the overlap count at and within 1e-6 / 1e-3 of
+touching (float32-rounded positions on the other side of touching included), the goal test at and within 1e-6 of the
+radius, the timeout rung at and one ulp below time_limit - 1, the rung precedences, first arrivals at exactly one radius,
+headings with a zero fmod remainder, and the look-ahead reward of mcn_sarl_predict.
+
+Each test replays its own inputs through the oracle and asserts that they reached the ladder events it claims
+(cport.ladder_counts); failures name the block of the first differing envs."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from oracle import cport  # noqa: E402
+from tests import helpers as H  # noqa: E402
+from tests import ladder_states as LS  # noqa: E402
+from tests.test_orca_edges_gpu import ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel, _snapshot  # noqa: E402
+
+STEP_EVENTS = ("swept_touch", "swept_point", "swept_u_zero", "swept_u_one", "dmin_tie", "danger_edge", "reach_edge",
+               "reach_band", "collision_and_reach", "timeout_and_collision", "timeout_edge", "timeout_below",
+               "hh_touch", "hh_band6", "hh_band3", "human_time_edge")
+UNICYCLE_EVENTS = STEP_EVENTS + ("theta_zero_rem", "theta_neg_rem")
+LA_EVENTS = ("la_touch", "la_danger_edge", "la_reach_edge", "la_collision_after_min")
+GENERIC_NS = (13, 32)          # only the run-time-N kernels (and the dispatcher) take more than 10 humans
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch
+
+
+def _configs(Ns, quad):
+    """(N, visible, dd, count_hh); the quad kernels take at most 4 candidate neighbours."""
+    for N in Ns:
+        for visible in (False, True):
+            if quad and N - 1 + visible > 4:
+                continue
+            for dd in LS.DISCOMFORT:
+                yield N, visible, dd, (N + visible) % 2 == 0 or dd == 0.25
+
+
+def _env(N, visible, dd, count_hh, E, unicycle=False):
+    env = H.make_vec_env(E, N, robot_visible=visible, kinematics="unicycle" if unicycle else "holonomic")
+    env.discomfort_dist = dd
+    env.count_hh = count_hh
+    return env
+
+
+def _where(names, bad):
+    return sorted({names[int(i[0])] for i in bad})[:6]
+
+
+def _assert_reached(total, events, what):
+    missing = [k for k in events if total.get(k, 0) == 0]
+    assert not missing, "%s: the inputs never reached %s (%s)" % (what, missing, total)
+
+
+def _add(total):
+    for k, v in cport.ladder_counts(reset=True).items():
+        total[k] = total.get(k, 0) + v
+
+
+def _step_and_compare(env, st, ax, ay, names, update, what, policy=cport.HUMANS_ORCA, given=None, total=None,
+                      fields=H.STATE_FIELDS):
+    torch = _torch()
+    H.upload(env, st)
+    gv = None if given is None else torch.from_numpy(np.ascontiguousarray(given)).to(env.device)
+    ob, reward, done, info = env.step(torch.from_numpy(np.stack([ax, ay], -1)).to(env.device), update=bool(update),
+                                      given_v=gv)
+    torch.cuda.synchronize()
+    got = dict(reward=reward.cpu().numpy(), done=done.cpu().numpy(), info=info.cpu().numpy(),
+               dmin=env.dmin.cpu().numpy(), hh_count=env.hh_count.cpu().numpy())
+    if env.export_human_actions:
+        got["human_act"] = env.human_act.cpu().numpy()
+    if not update:
+        got.update(nobs_px=ob.pos[..., 0].cpu().numpy(), nobs_py=ob.pos[..., 1].cpu().numpy(),
+                   nobs_vx=ob.vel[..., 0].cpu().numpy(), nobs_vy=ob.vel[..., 1].cpu().numpy())
+    ref_st = st.copy()
+    cport.ladder_counts(reset=True)
+    ref = cport.env_step(H.oracle_cfg_for(env, policy), ref_st, ax, ay, update=bool(update), given_v=given)
+    if total is not None:
+        _add(total)
+    for k in got:
+        bad = H.bit_mismatch(got[k], ref[k])
+        assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+    if fields:
+        H.assert_state_equal(H.download(env), ref_st if update else st, fields=fields, what=what)
+    return got, ref, ref_st
+
+
+@pytest.mark.parametrize("update", [1, 0])
+@pytest.mark.parametrize("kernel", STEP_KERNELS)
+def test_step_on_ladder_batches_matches_oracle_bitwise(kernel, update, tuning):
+    """Reward, done, info, dmin, hh_count, human actions, the next observation or the state, first-arrival times."""
+    quad = kernel.startswith("quad")
+    _select_step_kernel(kernel, tuning)
+    total = {}
+    Ns = list(range(1, 6)) if quad else list(range(1, 11))
+    if kernel in ("auto", "run-time-N"):
+        Ns += list(GENERIC_NS)
+    for N, visible, dd, count_hh in _configs(Ns, quad):
+        st, ax, ay, _, names = LS.ladder_batch(N, visible, dd)
+        env = _env(N, visible, dd, count_hh, st.E)
+        _step_and_compare(env, st, ax, ay, names, update, "%s N=%d visible=%d dd=%g count_hh=%d" % (
+            kernel, N, visible, dd, count_hh), total=total)
+    _assert_reached(total, STEP_EVENTS if update else [k for k in STEP_EVENTS if k != "human_time_edge"], kernel)
+
+
+@pytest.mark.parametrize("kernel", ["auto", "lane-per-human", "run-time-N", "quad"])
+def test_unicycle_step_on_ladder_batches(kernel, tuning):
+    """(v, r) robots: headings whose remainder is zero (either sign) or negative; rtheta and the ladder bitwise.  Where
+    rtheta + r is +-0 cos and sin are exact, so everything is bitwise; elsewhere the robot's position and velocity come
+    from device trig and are held to 1e-12 (as tests/test_env_step_gpu.py::test_unicycle_robot_matches_oracle_...)."""
+    torch = _torch()
+    quad = kernel.startswith("quad")
+    _select_step_kernel(kernel, tuning)
+    total = {}
+    for N, visible, dd, count_hh in _configs(range(1, 6) if quad else (1, 3, 5, 8, 10), quad):
+        st, ax, ay, _, names = LS.ladder_batch(N, visible, dd, unicycle=True)
+        env = _env(N, visible, dd, count_hh, st.E, unicycle=True)
+        what = "%s unicycle N=%d visible=%d dd=%g" % (kernel, N, visible, dd)
+        trig = ["rpx", "rpy", "rvx", "rvy"]
+        _, _, ref_st = _step_and_compare(env, st, ax, ay, names, 1, what, total=total,
+                                         fields=[f for f in H.STATE_FIELDS if f not in trig] + ["rtheta"])
+        got = H.download(env)
+        exact = np.array([(st.rtheta[e] + ay[e]) == 0 for e in range(st.E)])
+        assert exact.sum() > st.E // 2
+        for k in trig:
+            H.assert_bits_equal(getattr(got, k)[exact], getattr(ref_st, k)[exact], what + " " + k)
+            np.testing.assert_allclose(getattr(got, k), getattr(ref_st, k), rtol=0, atol=1e-12, err_msg=what + k)
+        # Python's % gives +0.0 for a zero remainder: the new heading and the velocity's y component are +0.0
+        z = np.array([(st.rtheta[e] + ay[e]) % (2 * np.pi) == 0 for e in range(st.E)])
+        assert z.any() and not np.signbit(got.rtheta[z]).any() and not np.signbit(got.rvy[z & exact]).any()
+        del env
+        torch.cuda.empty_cache()
+    _assert_reached(total, UNICYCLE_EVENTS, kernel + " unicycle")
+
+
+@pytest.mark.parametrize("stream", [0, 1, 2])
+def test_given_velocity_paths_on_ladder_batches(stream, tuning):
+    """ModelCrowdSim.step's given-velocity step: the streaming kernel (env_pair.hip, pair_stream 1 / 2: N in {5, 10},
+    no overlap count, no first arrivals, no exported actions) and env_step_kernel<GIVEN> (pair_stream 0, and the
+    configurations the streaming kernel does not take); the ladder fields and the state bitwise."""
+    from modelcrowdnav_amd import _hip
+    total = {}
+    for N in (1, 2, 5, 10):
+        for visible in (False, True):
+            for dd in LS.DISCOMFORT:
+                st, ax, ay, gv, names = LS.ladder_batch(N, visible, dd)
+                lean = N in (5, 10)
+                env = _env(N, visible, dd, not lean, st.E)
+                if lean:
+                    env.track_human_times = False
+                    env.export_human_actions = False
+                tuning(pair_stream=stream)
+                what = "given pair_stream=%d N=%d visible=%d dd=%g" % (stream, N, visible, dd)
+                _step_and_compare(env, st, ax, ay, names, 1, what, cport.HUMANS_GIVEN, gv, total,
+                                  fields=[f for f in H.STATE_FIELDS if not (lean and f == "human_times")])
+                if lean and stream:
+                    assert "pair" in _hip.last_dispatch(), (what, _hip.last_dispatch())
+    _assert_reached(total, [k for k in STEP_EVENTS if not k.startswith("hh")], "given pair_stream=%d" % stream)
+
+
+def test_linear_humans_on_ladder_batches():
+    """Linear humans (device atan2 / cos / sin): the ladder fields bitwise (they do not depend on the humans' new
+    velocities), the new positions within 1e-12."""
+    torch = _torch()
+    total = {}
+    for N in (1, 4, 7, 10):
+        for visible in (False, True):
+            st, ax, ay, _, names = LS.ladder_batch(N, visible, 0.2)
+            env = _env(N, visible, 0.2, True, st.E)
+            env.human_policy_name = "linear"
+            H.upload(env, st)
+            ob, reward, done, info = env.step(torch.from_numpy(np.stack([ax, ay], -1)).to(env.device))
+            torch.cuda.synchronize()
+            ref_st = st.copy()
+            cport.ladder_counts(reset=True)
+            ref = cport.env_step(H.oracle_cfg_for(env, cport.HUMANS_LINEAR), ref_st, ax, ay, update=True)
+            _add(total)
+            what = "linear N=%d visible=%d" % (N, visible)
+            for k, v in (("reward", reward), ("done", done), ("info", info), ("dmin", env.dmin),
+                         ("hh_count", env.hh_count)):
+                bad = H.bit_mismatch(v.cpu().numpy(), ref[k])
+                assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+            got = H.download(env)
+            np.testing.assert_allclose(got.hpx, ref_st.hpx, rtol=0, atol=1e-12, err_msg=what)
+            np.testing.assert_allclose(got.hpy, ref_st.hpy, rtol=0, atol=1e-12, err_msg=what)
+            H.assert_state_equal(got, ref_st, fields=("rpx", "rpy", "rvx", "rvy", "gtime"), what=what)
+    _assert_reached(total, [k for k in STEP_EVENTS if k != "human_time_edge"], "linear")
+
+
+@pytest.mark.parametrize("unicycle", [False, True])
+@pytest.mark.parametrize("path", sorted(ROLLOUT_PATHS))
+def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle, tuning):
+    """mcn_env_rollout over 8 steps (3 + 5) == 8 mcn_env_step calls, every byte, with and without a scenario pool
+    (Explorer records: danger count and distance sum, fin_info / fin_time / fin_return); without a pool also == the
+    oracle's trajectory (holonomic: bitwise; unicycle: the heading bitwise); a one-step launch == the oracle's boundary
+    step, bitwise (unicycle: the ladder, the heading and the clock)."""
+    torch = _torch()
+    from modelcrowdnav_amd.envs import scenarios as S
+    Ns, quad, tu = ROLLOUT_PATHS[path]
+    tuning(**tu)
+    T = 8
+    total = {}
+    for N, visible, dd, count_hh in _configs(Ns, quad):
+        st, ax0, ay0, _, names = LS.ladder_batch(N, visible, dd, unicycle)
+        E = st.E
+        rng = np.random.RandomState(N * 2 + visible)
+        ax = np.concatenate([ax0[None], rng.randint(0, 17, (T - 1, E)) / 16.0])
+        ay = np.concatenate([ay0[None], (rng.randint(-4, 5, (T - 1, E)) / 16.0) if not unicycle else
+                             np.zeros((T - 1, E))])
+        acts = torch.from_numpy(np.stack([ax, ay], -1))
+        what = "%s N=%d visible=%d dd=%g unicycle=%d" % (path, N, visible, dd, unicycle)
+        for with_pool in (False, True):
+            a, b = (_env(N, visible, dd, count_hh, E, unicycle) for _ in range(2))
+            for env in (a, b):
+                H.upload(env, st)
+                if with_pool:
+                    pool = S.scenario_pool(env.spec(), "test", range(16), N, "circle_crossing")
+                    env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=np.arange(E) % 16, fin_slots=2)
+            acts_d = acts.to(a.device)
+            a.rollout(acts_d[:3]); a.rollout(acts_d[3:])
+            for t in range(T):
+                b.step(acts_d[t])
+            torch.cuda.synchronize()
+            sa, sb = _snapshot(a), _snapshot(b)
+            for k in sa:
+                assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), (what, with_pool, k)
+            if with_pool:
+                assert int(a.rollout_buffers["fin_count"].sum().item()) > 0
+                continue
+            ref_st = st.copy()
+            cfg = H.oracle_cfg_for(a)
+            cport.ladder_counts(reset=True)
+            for t in range(T):
+                ref = cport.env_step(cfg, ref_st, ax[t], ay[t], update=True)
+                if t == 0:
+                    _add(total)
+            cport.ladder_counts(reset=True)
+            fields = H.STATE_FIELDS + ("rtheta",)
+            if unicycle:
+                fields = tuple(f for f in fields if f not in ("rpx", "rpy", "rvx", "rvy", "hpx", "hpy", "hvx", "hvy",
+                                                              "human_times"))
+            H.assert_state_equal(H.download(a), ref_st, fields=fields, what=what)
+            if unicycle:
+                continue        # later steps see device-trig robot positions: the first step is compared below
+            for k, v in (("reward", a.reward), ("done", a.done), ("info", a.info), ("dmin", a.dmin),
+                         ("hh_count", a.hh_count), ("human_act", a.human_act)):
+                bad = H.bit_mismatch(v.cpu().numpy(), ref[k])
+                assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+        # a one-step launch alone, bitwise against the oracle: the rungs of the boundary step itself (the
+        # trajectories above only show the last step's record and what the Explorer accumulates)
+        c = _env(N, visible, dd, count_hh, E, unicycle)
+        H.upload(c, st)
+        c.rollout(acts.to(c.device)[:1])
+        torch.cuda.synchronize()
+        ref_st = st.copy()
+        ref = cport.env_step(H.oracle_cfg_for(c), ref_st, ax[0], ay[0], update=True)
+        for k, v in (("reward", c.reward), ("done", c.done), ("info", c.info), ("dmin", c.dmin),
+                     ("hh_count", c.hh_count)):
+            bad = H.bit_mismatch(v.cpu().numpy(), ref[k])
+            assert len(bad) == 0, (what, "first step", k, len(bad), _where(names, bad))
+        H.assert_state_equal(H.download(c), ref_st, fields=("rtheta", "gtime") if unicycle else H.STATE_FIELDS,
+                             what=what + " first step")
+    events = UNICYCLE_EVENTS if unicycle else STEP_EVENTS
+    _assert_reached(total, events, path)
+
+
+def _sarl(seed=0, zero=True):
+    import torch
+    from tests.test_sarl_gpu import _policy
+    pol = _policy(seed=seed)
+    if zero:
+        with torch.no_grad():
+            for p_ in pol.model.parameters():
+                p_.zero_()
+    pol.build_action_space(1.0)
+    return pol
+
+
+def test_sarl_lookahead_rewards_on_ladder_batches():
+    """mcn_sarl_predict with a zeroed network (V == 0): values are exactly the look-ahead reward, bitwise against
+    cport.lookahead_reward on the look-ahead blocks, N = 1..10, 13 and 32; the argmax goes on at |robot - goal| == rr and
+    returns -1 inside."""
+    pol = _sarl()
+    table = pol._action_table
+    total = {}
+    for N in list(range(1, 11)) + list(GENERIC_NS):
+        st, names = LS.lookahead_batch(N, table)
+        env = H.make_vec_env(st.E, N)
+        H.upload(env, st)
+        actions, best, values = pol.predict_batch(env, want_values=True)
+        cport.ladder_counts(reset=True)
+        ref = cport.lookahead_reward(st, table, 0.25)
+        _add(total)
+        bad = H.bit_mismatch(values.cpu().numpy(), ref)
+        assert len(bad) == 0, (N, len(bad), _where(names, bad))
+        best = best.cpu().numpy()
+        for e, name in enumerate(names):
+            if name == "la-at-goal":
+                assert best[e] == -1, (N, e)
+            elif name == "la-at-goal-edge":
+                assert best[e] == int(np.argmax(ref[e])), (N, e, best[e])
+    _assert_reached(total, LA_EVENTS, "mcn_sarl_predict")
+
+
+@pytest.mark.parametrize("N", GENERIC_NS)
+def test_sarl_predict_above_ten_humans_against_torch_reference(N):
+    """N = 13 and 32 (mcn_sarl_predict takes N <= MCN_MAX_HUMANS = 32): a trained-size random network against
+    pyref.sarl_predict at the suite's 1e-5 bar, on a few envs of the look-ahead batch."""
+    from oracle import pyref
+    from tests.test_sarl_gpu import TOL
+    pol = _sarl(seed=3, zero=False)
+    table = pol._action_table
+    st, names = LS.lookahead_batch(N, table)
+    env = H.make_vec_env(st.E, N)
+    H.upload(env, st)
+    actions, best, values = pol.predict_batch(env, want_values=True)
+    values = values.cpu().numpy()
+    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
+    for e in range(0, st.E, 19):
+        if names[e] == "la-at-goal":
+            continue
+        row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
+        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
+        ref, idx = pyref.sarl_predict(w, row, hum, table)
+        np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="N=%d env %d (%s)" % (N, e, names[e]))
