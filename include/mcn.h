@@ -316,6 +316,63 @@ int mcn_sarl_predict(const mcn_sarl_net *net, const mcn_env_state *st, const dou
                      double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * LSTM-RL and CADRL value networks: the same 81-action one-step look-ahead (crowd_nav/policy/lstm_rl.py:9-33,90-103,
+ * cadrl.py:21-29,131-178, multi_human_rl.py:11-63).  float32 MFMA layers only (no x3 fragments).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Device pointers to the packed fragments of one LSTM-RL ValueNetwork1 (with_interaction_module = false). */
+typedef struct mcn_lstm_rl_net {
+    const float *w_gate, *b_gate; /* lstm: [weight_ih_l0 | weight_hh_l0] (13 + 50) -> 200, bias_ih_l0 + bias_hh_l0;
+                                   * input tiles x, h x4; output tile 4G + t slot s = unit u of gate G (i, f, g, o)
+                                   * where (t, s) is the slot of unit u of h */
+    const float *w_m0, *b_m0;     /* mlp.0  56 -> 150 (input tiles: self x1, h x4) */
+    const float *w_m1, *b_m1;     /* mlp.2 150 -> 100 */
+    const float *w_m2, *b_m2;     /* mlp.4 100 -> 100 */
+    const float *w_m3, *b_m3;     /* mlp.6 100 -> 1   */
+} mcn_lstm_rl_net;
+
+/* Device pointers to the packed fragments of one CADRL ValueNetwork (state_dict value_network.{0,2,4,6}). */
+typedef struct mcn_cadrl_net {
+    const float *w_l0, *b_l0;     /* value_network.0  13 -> 150 */
+    const float *w_l1, *b_l1;     /* value_network.2 150 -> 100 */
+    const float *w_l2, *b_l2;     /* value_network.4 100 -> 100 */
+    const float *w_l3, *b_l3;     /* value_network.6 100 -> 1   */
+} mcn_cadrl_net;
+
+/*
+ * mcn_lstm_rl_predict -- mcn_sarl_predict for LstmRL (lstm_rl.py:90-103): per env the humans are taken in the order
+ * LstmRL.predict sorts them, by decreasing float64 distance of their CURRENT position to the robot's current position
+ * (np.linalg.norm, lstm_rl.py:99-101), equal distances in index order (sorted(reverse=True) is stable), over the first
+ * hcount[e] humans only; the LSTM starts from h = c = 0 and humans at index >= hcount[e] do not touch it.  With
+ * next_hpos / next_hvel / rewards set (`query_env`, multi_human_rl.py:37-38) the env's next states are taken in the
+ * env's order, as the reference does.  order: [E][N] int32 device out or NULL: the human index at each LSTM step (slots
+ * >= hcount[e] hold their own index).  No workspace.  Everything else as mcn_sarl_predict.
+ */
+int mcn_lstm_rl_predict(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
+                        double time_step, double gamma_pow, int32_t kinematics,
+                        double *values, int32_t *best, double *best_val, int32_t *order,
+                        const double *next_hpos, const double *next_hvel, const double *rewards,
+                        double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream);
+
+/*
+ * mcn_lstm_rl_order -- the human order of mcn_lstm_rl_predict (without query_env) on its own, for the rows
+ * LstmRL.transform stores (multi_human_rl.py:60-61 on the sorted state).  Reads st->hpos, st->rpos and st->hcount
+ * (may be NULL); order: [E][N] int32 device out.
+ */
+int mcn_lstm_rl_order(const mcn_env_state *st, int32_t *order, int32_t E, int32_t N, void *stream);
+
+/*
+ * mcn_cadrl_predict -- mcn_sarl_predict for CADRL (cadrl.py:131-178): the value network on every (robot, human) row,
+ * V = min over the env's first hcount[e] humans (torch.min: one NaN makes V NaN), value = reward + gamma_pow * V.
+ * No workspace.  Everything else as mcn_sarl_predict.
+ */
+int mcn_cadrl_predict(const mcn_cadrl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
+                      double time_step, double gamma_pow, int32_t kinematics,
+                      double *values, int32_t *best, double *best_val,
+                      const double *next_hpos, const double *next_hvel, const double *rewards,
+                      double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Social-GAN one-step world model (crowd_nav/policy/world_model.py:134-268, sgan/models.py:501-553).
  * ---------------------------------------------------------------------------------------------- */
 
@@ -451,7 +508,7 @@ int32_t mcn_abi_version(void);
 enum { MCN_SIZEOF_ENV_CFG = 0, MCN_SIZEOF_ENV_STATE = 1, MCN_SIZEOF_ENV_OUT = 2, MCN_SIZEOF_ROLLOUT = 3,
        MCN_SIZEOF_TUNING = 4, MCN_SIZEOF_STEP_REC = 5, MCN_SIZEOF_ROLL_REC = 6, MCN_SIZEOF_SARL_NET = 7,
        MCN_SIZEOF_SGAN_NET = 8, MCN_SIZEOF_SCENARIO_CFG = 9, MCN_SIZEOF_MLP_WORLD_NET = 10, MCN_SIZEOF_ATTN_WORLD_NET = 11,
-       MCN_SIZEOF_SARL_X3 = 12 };
+       MCN_SIZEOF_SARL_X3 = 12, MCN_SIZEOF_LSTM_RL_NET = 13, MCN_SIZEOF_CADRL_NET = 14 };
 int64_t mcn_sizeof(int32_t which);                 /* sizeof the struct named by MCN_SIZEOF_*; -1 for an unknown id */
 
 /*

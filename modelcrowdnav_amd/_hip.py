@@ -19,6 +19,7 @@ MAX_HUMANS, MAX_LINES = 32, 10
 INFO_NOTHING, INFO_DANGER, INFO_REACHGOAL, INFO_COLLISION, INFO_TIMEOUT = range(5)
 HUMANS_ORCA, HUMANS_LINEAR, HUMANS_GIVEN = range(3)
 KIN_HOLONOMIC, KIN_UNICYCLE = 0, 1
+SIZEOF_LSTM_RL_NET, SIZEOF_CADRL_NET = 13, 14        # include/mcn.h: MCN_SIZEOF_*
 
 _vp, _d, _f, _i = C.c_void_p, C.c_double, C.c_float, C.c_int32
 
@@ -95,6 +96,16 @@ class Tuning(C.Structure):
                                   "step_block", "diag_noop", "pair_stream", "lp3_defer", "sarl_x3")]
 
 
+class LstmRLNet(C.Structure):
+    """mcn_lstm_rl_net: device pointers to the packed fragments of one LSTM-RL ValueNetwork1."""
+    _fields_ = [(n, _vp) for n in ("w_gate", "b_gate", "w_m0", "b_m0", "w_m1", "b_m1", "w_m2", "b_m2", "w_m3", "b_m3")]
+
+
+class CadrlNet(C.Structure):
+    """mcn_cadrl_net: device pointers to the packed fragments of one CADRL ValueNetwork."""
+    _fields_ = [(n, _vp) for n in ("w_l0", "b_l0", "w_l1", "b_l1", "w_l2", "b_l2", "w_l3", "b_l3")]
+
+
 class McnError(RuntimeError):
     pass
 
@@ -136,6 +147,13 @@ def _load():
     lib.mcn_sarl_predict.argtypes = [_vp, C.POINTER(EnvState), _vp, _i, _d, _d, _i, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _d, C.c_uint64, _i, _i, _vp]
     lib.mcn_sarl_predict.restype = C.c_int
+    lib.mcn_lstm_rl_predict.argtypes = [C.POINTER(LstmRLNet), C.POINTER(EnvState), _vp, _i, _d, _d, _i, _vp, _vp, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _d, C.c_uint64, _i, _i, _vp]
+    lib.mcn_lstm_rl_predict.restype = C.c_int
+    lib.mcn_lstm_rl_order.argtypes, lib.mcn_lstm_rl_order.restype = [C.POINTER(EnvState), _vp, _i, _i, _vp], C.c_int
+    lib.mcn_cadrl_predict.argtypes = [C.POINTER(CadrlNet), C.POINTER(EnvState), _vp, _i, _d, _d, _i, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _d, C.c_uint64, _i, _i, _vp]
+    lib.mcn_cadrl_predict.restype = C.c_int
     lib.mcn_mlp_world_step.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _vp]
     lib.mcn_mlp_world_step.restype = C.c_int
     lib.mcn_attn_world_workspace_bytes.argtypes = [_i, _i]
@@ -164,7 +182,8 @@ def _check_abi(lib):
     if got != ABI_VERSION:
         raise ImportError("modelcrowdnav_amd: %s has ABI %d, this binding was written for ABI %d -- rebuild the library "
                           "(make -C modelcrowdnav_amd/csrc)" % (LIB_PATH, got, ABI_VERSION))
-    mirrors = {0: EnvCfg, 1: EnvState, 2: EnvOut, 3: Rollout, 4: Tuning, 5: StepRec, 6: RollRec, 9: ScenarioCfg}
+    mirrors = {0: EnvCfg, 1: EnvState, 2: EnvOut, 3: Rollout, 4: Tuning, 5: StepRec, 6: RollRec, 9: ScenarioCfg,
+               SIZEOF_LSTM_RL_NET: LstmRLNet, SIZEOF_CADRL_NET: CadrlNet}
     for which, cls in mirrors.items():
         if int(lib.mcn_sizeof(which)) != C.sizeof(cls):
             raise ImportError("modelcrowdnav_amd: struct %s is %d bytes here, %d in %s" %
@@ -181,7 +200,7 @@ lib = _load()
 # every symbol include/mcn.h declares; tests/test_abi.py checks the .so exports each one
 EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
-            "mcn_attn_world_step"]
+            "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict"]
 
 
 def check(rc, what):

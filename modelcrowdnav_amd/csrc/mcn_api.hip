@@ -27,6 +27,16 @@ int launch_sarl_c(const mcn_sarl_net *net, const mcn_env_state *st, const double
                   double gamma_pow, int kinematics, void *workspace, double *values, int32_t *best, double *best_val,
                   float *attention, const double *next_hpos, const double *next_hvel, const double *reward_in,
                   double *action_out, double epsilon, unsigned long long seed, int E, int N, hipStream_t stream);
+int launch_lstm_rl(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
+                   double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val, int32_t *order,
+                   const double *next_hpos, const double *next_hvel, const double *reward_in, double *action_out,
+                   double epsilon, unsigned long long seed, int E, int N, hipStream_t stream);
+int launch_cadrl(const mcn_cadrl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
+                 double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val,
+                 const double *next_hpos, const double *next_hvel, const double *reward_in, double *action_out,
+                 double epsilon, unsigned long long seed, int E, int N, hipStream_t stream);
+int launch_lstm_rl_order(const double *hpos, const double *rpos, const int32_t *hcount, int32_t *order, int E, int N,
+                         hipStream_t stream);
 #ifdef MCN_DIAG
 int read_pool_clock(void *dst, size_t bytes);
 int read_sarl_phases(void *dst, size_t bytes, int reset);
@@ -138,6 +148,8 @@ int64_t mcn_sizeof(int32_t which)
         case MCN_SIZEOF_MLP_WORLD_NET: return sizeof(mcn_mlp_world_net);
         case MCN_SIZEOF_ATTN_WORLD_NET: return sizeof(mcn_attn_world_net);
         case MCN_SIZEOF_SARL_X3: return sizeof(mcn_sarl_x3);
+        case MCN_SIZEOF_LSTM_RL_NET: return sizeof(mcn_lstm_rl_net);
+        case MCN_SIZEOF_CADRL_NET: return sizeof(mcn_cadrl_net);
         default: return -1;
     }
 }
@@ -392,6 +404,58 @@ int mcn_sarl_predict(const mcn_sarl_net *net, const mcn_env_state *st, const dou
     if ((next_hpos == nullptr) != (rewards == nullptr)) return MCN_EINVAL;
     return sarl_lookahead_impl(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best, best_val,
                                attention, next_hpos, next_hvel, rewards, action_out, epsilon, seed, E, N, stream);
+}
+
+// shared validation of mcn_lstm_rl_predict / mcn_cadrl_predict (as sarl_lookahead_impl + mcn_sarl_predict)
+static int lookahead_args_ok(const void *net, size_t net_bytes, const mcn_env_state *st, const double *actions, int32_t A,
+                             double time_step, int32_t kinematics, const double *values, const int32_t *best,
+                             const double *best_val, const double *next_hpos, const double *next_hvel,
+                             const double *rewards, const double *action_out, double epsilon, int32_t E, int32_t N)
+{
+    if (!net || !st || !actions || !values || !best || !best_val || !action_out) return 0;
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return 0;
+    if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS || A <= 0) return 0;
+    if (!st->hpos || !st->hvel || !st->hrad || !st->rpos || !st->rgoal || !st->rrad || !st->rvpref) return 0;
+    if (kinematics != MCN_KIN_HOLONOMIC && kinematics != MCN_KIN_UNICYCLE) return 0;
+    if (kinematics == MCN_KIN_UNICYCLE && !st->rtheta) return 0;
+    if ((next_hpos == nullptr) != (next_hvel == nullptr) || (next_hpos == nullptr) != (rewards == nullptr)) return 0;
+    const float *const *fp = reinterpret_cast<const float *const *>(net);
+    for (size_t k = 0; k < net_bytes / sizeof(float *); ++k)
+        if (!fp[k]) return 0;
+    return time_step > 0;
+}
+
+int mcn_lstm_rl_predict(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
+                        double time_step, double gamma_pow, int32_t kinematics,
+                        double *values, int32_t *best, double *best_val, int32_t *order,
+                        const double *next_hpos, const double *next_hvel, const double *rewards,
+                        double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream)
+{
+    if (!lookahead_args_ok(net, sizeof(*net), st, actions, A, time_step, kinematics, values, best, best_val, next_hpos,
+                           next_hvel, rewards, action_out, epsilon, E, N))
+        return MCN_EINVAL;
+    return mcn::launch_lstm_rl(net, st, actions, A, time_step, gamma_pow, kinematics, values, best, best_val, order,
+                               next_hpos, next_hvel, rewards, action_out, epsilon, (unsigned long long)seed, E, N,
+                               (hipStream_t)stream);
+}
+
+int mcn_lstm_rl_order(const mcn_env_state *st, int32_t *order, int32_t E, int32_t N, void *stream)
+{
+    if (!st || !order || !st->hpos || !st->rpos || E <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
+    return mcn::launch_lstm_rl_order(st->hpos, st->rpos, st->hcount, order, E, N, (hipStream_t)stream);
+}
+
+int mcn_cadrl_predict(const mcn_cadrl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
+                      double time_step, double gamma_pow, int32_t kinematics,
+                      double *values, int32_t *best, double *best_val,
+                      const double *next_hpos, const double *next_hvel, const double *rewards,
+                      double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream)
+{
+    if (!lookahead_args_ok(net, sizeof(*net), st, actions, A, time_step, kinematics, values, best, best_val, next_hpos,
+                           next_hvel, rewards, action_out, epsilon, E, N))
+        return MCN_EINVAL;
+    return mcn::launch_cadrl(net, st, actions, A, time_step, gamma_pow, kinematics, values, best, best_val, next_hpos,
+                             next_hvel, rewards, action_out, epsilon, (unsigned long long)seed, E, N, (hipStream_t)stream);
 }
 
 int mcn_mlp_world_step(const mcn_mlp_world_net *net, const double *hpos, const double *hvel, double *out_vel,

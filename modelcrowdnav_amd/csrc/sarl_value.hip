@@ -593,6 +593,16 @@ int launch_sarl(SarlParams &p, int32_t *best, double *best_val, double *action_o
     return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
 }
 
+// the argmax / epsilon-greedy kernel above for the other look-ahead kernels (lstm_rl_value.hip)
+int launch_sarl_argmax(const double *values, const double *rpos, const double *rgoal, const double *rrad, int E, int A,
+                       int32_t *best, double *best_val, const double *actions, double *action_out, double epsilon,
+                       unsigned long long seed, hipStream_t stream)
+{
+    hipLaunchKernelGGL(sarl_argmax_kernel, dim3(E), dim3(64), 0, stream, values, rpos, rgoal, rrad, E, A, best, best_val,
+                       actions, action_out, epsilon, seed);
+    return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
+}
+
 int launch_sarl_c(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                   double gamma_pow, int kinematics, void *workspace, double *values, int32_t *best, double *best_val,
                   float *attention, const double *next_hpos, const double *next_hvel, const double *reward_in,

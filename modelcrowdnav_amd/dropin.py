@@ -4,7 +4,7 @@
     # from here on:
     #   import gym; env = gym.make('CrowdSim-v0')           -> modelcrowdnav_amd.envs.CrowdSim
     #   from crowd_sim.envs.utils.robot import Robot         -> modelcrowdnav_amd.envs.utils.robot
-    #   from crowd_nav.policy.policy_factory import policy_factory   (has 'sarl', 'orca', 'linear', 'none')
+    #   from crowd_nav.policy.policy_factory import policy_factory   (has 'sarl', 'lstm_rl', 'cadrl', 'orca', 'linear', 'none')
     #   from crowd_nav.policy.world_model import SGANWorld, get_generator
     #   from sgan.models import TrajectoryGenerator
 
@@ -38,6 +38,7 @@ _MAP = {
     "crowd_nav.policy.cadrl": "modelcrowdnav_amd.policy.cadrl",
     "crowd_nav.policy.multi_human_rl": "modelcrowdnav_amd.policy.multi_human_rl",
     "crowd_nav.policy.sarl": "modelcrowdnav_amd.policy.sarl",
+    "crowd_nav.policy.lstm_rl": "modelcrowdnav_amd.policy.lstm_rl",
     "crowd_nav.policy.policy_factory": "modelcrowdnav_amd.policy.policy_factory",
     "crowd_nav.policy.world_model": "modelcrowdnav_amd.policy.world_model",
     "crowd_nav.utils": "modelcrowdnav_amd.utils",

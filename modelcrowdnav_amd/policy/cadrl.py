@@ -5,8 +5,12 @@
 
 The per-step arithmetic that the reference does in Python for each of the 81 candidate
 actions (propagate :104-129, rotate :217-252, compute_reward multi_human_rl.py:65-88) runs on
-the GPU in sarl_*.hip; see policy/sarl.py.
+the GPU in one look-ahead launch per step: sarl_value.hip (policy/sarl.py), lstm_rl_value.hip
+(policy/lstm_rl.py and CADRL's own single-human network below).  The launch plumbing shared by
+all of them (`_lookahead`, `_query_env`, `predict_batch`) lives in CADRL; each policy supplies
+`_pack` (weights -> MFMA fragments) and the `_launch` hook.
 """
+import ctypes as C
 import itertools
 
 import numpy as np
@@ -47,6 +51,7 @@ import logging
 
 import torch
 
+from .. import _hip
 from ..envs.policy.policy import Policy
 from ..envs.utils.action import ActionRot, ActionXY
 from ..envs.utils.state import FullState, ObservableState
@@ -71,10 +76,80 @@ def rotate(state, kinematics):
                         hvx * c + hvy * s, hvy * c - hvx * s, hr, da, r + hr], 1)
 
 
+class ValueNetwork(nn.Module):
+    """cadrl.py:21-29: state_dict keys value_network.{0,2,4,6}.weight/.bias."""
+
+    def __init__(self, input_dim, mlp_dims):
+        super().__init__()
+        self.value_network = mlp(input_dim, mlp_dims)
+
+    def forward(self, state):
+        return self.value_network(state)
+
+
+def _ident(kin, tiles, offset=0):
+    """Slot -> feature map of a `kin`-wide activation held in `tiles` tiles of 16: full tiles in natural order, the
+    ragged last tile "q first" (feature j at slot 4(j%4) + j/4), see mcn_pack_linear in include/mcn.h."""
+    m = np.full(tiles * 16, -1, np.int32)
+    full = (kin // 16) * 16 if kin % 16 else kin
+    m[:full] = np.arange(full)
+    for j in range(kin - full):
+        m[full + 4 * (j % 4) + j // 4] = full + j
+    m[m >= 0] += offset
+    return m
+
+
+def _natural(kin, tiles):
+    m = np.full(tiles * 16, -1, np.int32)
+    m[:kin] = np.arange(kin)
+    return m
+
+
+def pack_linear(W, b, kmap, omap, dev):
+    """One layer (weight [nout, kin], bias [nout] float32 numpy) -> (device weight fragments, device bias fragments)
+    through mcn_pack_linear; kmap / omap: input / output slot maps (NT = len(omap) / 16, KT = len(kmap) / 16)."""
+    W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
+    nout, kin = W.shape
+    KT, NT = len(kmap) // 16, len(omap) // 16
+    wf = np.zeros((NT, KT, 64, 4), np.float32)
+    bf = np.zeros((NT, 64, 4), np.float32)
+    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    kmap, omap = np.ascontiguousarray(kmap, np.int32), np.ascontiguousarray(omap, np.int32)
+    _hip.check(_hip.lib.mcn_pack_linear(W.ctypes.data_as(fp), b.ctypes.data_as(fp), nout, kin, kmap.ctypes.data_as(ip),
+                                        KT, omap.ctypes.data_as(ip), NT, wf.ctypes.data_as(fp), bf.ctypes.data_as(fp)),
+               "mcn_pack_linear")
+    return torch.from_numpy(wf).to(dev), torch.from_numpy(bf).to(dev)
+
+
+def _state_arrays(model):
+    return {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in model.state_dict().items()}
+
+
+def pack_cadrl_network(model, dev):
+    """CADRL ValueNetwork -> (ctypes mcn_cadrl_net, [device tensors kept alive])."""
+    sd = _state_arrays(model)
+    expect = {"value_network.0": (150, 13), "value_network.2": (100, 150), "value_network.4": (100, 100),
+              "value_network.6": (1, 100)}
+    for k, shp in expect.items():
+        if k + ".weight" not in sd or tuple(sd[k + ".weight"].shape) != shp:
+            raise ValueError("lstm_rl_value.hip is built for the shipped CADRL dimensions (policy.config [cadrl] "
+                             "mlp_dims = 150, 100, 100, 1); %s.weight is %s" % (k, sd.get(k + ".weight", np.zeros(0)).shape))
+    plan = [("l0", "value_network.0", _natural(13, 1), _ident(150, 10)),
+            ("l1", "value_network.2", _ident(150, 10), _ident(100, 7)),
+            ("l2", "value_network.4", _ident(100, 7), _ident(100, 7)),
+            ("l3", "value_network.6", _ident(100, 7), _ident(1, 1))]
+    net, keep = _hip.CadrlNet(), []
+    for name, key, kmap, omap in plan:
+        dw, db = pack_linear(sd[key + ".weight"], sd[key + ".bias"], kmap, omap, dev)
+        keep += [dw, db]
+        setattr(net, "w_" + name, dw.data_ptr())
+        setattr(net, "b_" + name, db.data_ptr())
+    return net, keep
+
+
 class CADRL(Policy):
-    """Configuration / action-space / propagate surface shared by the value-based policies
-    (cadrl.py:31-129).  CADRL's own single-human network is not on the path BASELINE.json names;
-    SARL (policy/sarl.py) is, and inherits everything it needs from here."""
+    """CADRL (cadrl.py:31-252), and the configuration / action-space / propagate / look-ahead surface shared by the
+    value-based policies (SARL, LSTM-RL inherit it through MultiHumanRL)."""
 
     def __init__(self):
         super().__init__()
@@ -100,6 +175,9 @@ class CADRL(Policy):
         self.human_state_dim = 7
         self.joint_state_dim = self.self_state_dim + self.human_state_dim
         self._action_table = None
+        self._frags = None        # packed MFMA operand fragments (device) + the version they were packed at
+        self._ws = None
+        self._bufs = {}
 
     def set_common_parameters(self, config):
         self.gamma = config.getfloat("rl", "gamma")
@@ -112,7 +190,11 @@ class CADRL(Policy):
         self.om_channel_size = config.getint("om", "om_channel_size")
 
     def configure(self, config):
-        raise NotImplementedError("CADRL's single-human value network is outside this build's scope; use 'sarl'")
+        self.set_common_parameters(config)
+        mlp_dims = [int(x) for x in config.get("cadrl", "mlp_dims").split(", ")]
+        self.model = ValueNetwork(self.joint_state_dim, mlp_dims)
+        self.multiagent_training = config.getboolean("cadrl", "multiagent_training")
+        logging.info("Policy: CADRL without occupancy map")
 
     def set_device(self, device):
         self.device = device
@@ -153,3 +235,201 @@ class CADRL(Policy):
         assert len(state.human_states) == 1
         row = torch.Tensor(state.self_state + state.human_states[0]).to(self.device)
         return self.rotate(row.unsqueeze(0)).squeeze(dim=0)
+
+    def transform_batch(self, env):
+        """`transform` for every env of a VecCrowdSim: [E,13] float32 rotated rows.  Like `transform` (its one-human
+        assertion, cadrl.py:260) it refuses envs with more than one human instead of storing what the reference cannot."""
+        if env._alloc_N != 1:
+            raise AssertionError("CADRL.transform_batch: the reference's transform takes one human (N = %d)" % env._alloc_N)
+        f = torch.float32
+        rows = torch.cat([env.rpos, env.rvel, env.rrad.unsqueeze(1), env.rgoal, env.rvpref.unsqueeze(1),
+                          env.rtheta.unsqueeze(1), env.hpos[:, 0], env.hvel[:, 0], env.hrad[:, :1]], 1).to(f)
+        return self.rotate(rows)
+
+    # ------------------------------------------------------------------ reference surface (E = 1)
+    def predict(self, state):
+        """cadrl.py:131-178: the minimum over the humans of the value network, maximised over the action table; one
+        mcn_cadrl_predict launch.  Returns None when every value is NaN (the reference's `max_action = None`)."""
+        if self.phase is None or self.device is None:
+            raise AttributeError("Phase, device attributes have to be set!")
+        if self.phase == "train" and self.epsilon is None:
+            raise AttributeError("Epsilon attribute has to be set in training phase")
+        if self.reach_destination(state):
+            return ActionXY(0, 0) if self.kinematics == "holonomic" else ActionRot(0, 0)
+        if self.action_space is None:
+            self.build_action_space(state.self_state.v_pref)
+        probability = np.random.random()
+        if self.phase == "train" and probability < self.epsilon:
+            max_action = self.action_space[np.random.choice(len(self.action_space))]
+        else:
+            values = self._predict_one(state)
+            self.action_values = values.tolist()
+            idx = -1
+            for i, v in enumerate(self.action_values):            # strict '>' from -inf: NaN never wins
+                if v > (self.action_values[idx] if idx >= 0 else float("-inf")):
+                    idx = i
+            max_action = self.action_space[idx] if idx >= 0 else None
+        if self.phase == "train":
+            self.last_state = self.transform(state)
+        return max_action
+
+    def _predict_one(self, state, order_out=None):
+        """The E = 1 look-ahead of `state` (host JointState): values [A] (numpy float64)."""
+        me, humans = state.self_state, state.human_states
+        dev = self._gpu_device()
+        N = len(humans)
+        # one host row, one host-to-device copy; the state arrays are views of it (16-byte aligned: pairs first)
+        row = [c for h in humans for c in (h.px, h.py)] + [c for h in humans for c in (h.vx, h.vy)] + \
+              [me.px, me.py, me.vx, me.vy, me.gx, me.gy] + [h.radius for h in humans] + [me.radius, me.v_pref, me.theta]
+        stage = torch.tensor(row, dtype=torch.float64).to(dev)
+        names = ("hpos", "hvel", "rpos", "rvel", "rgoal", "hrad", "rrad", "rvpref", "rtheta")
+        sizes = (2 * N, 2 * N, 2, 2, 2, N, 1, 1, 1)
+        shapes = ((N, 2), (N, 2), (1, 2), (1, 2), (1, 2), (N,), (1,), (1,), (1,))
+        bufs = {k: piece.view(shp) for k, piece, shp in zip(names, torch.split(stage, sizes), shapes)}
+        st = _hip.EnvState()
+        for k, v in bufs.items():
+            setattr(st, k, _hip.ptr(v))
+        self._v_pref = me.v_pref
+        env_next = None
+        if self.query_env:
+            venv = self.env.__dict__.get("_vec") if hasattr(self.env, "__dict__") else None
+            if venv is None:
+                raise AttributeError("query_env needs set_env(CrowdSim)")
+            self.env._push_host_state()
+            env_next = self._query_env(venv)
+        values, _, _, _ = self._lookahead(st, 1, N, dev, env_next=env_next)
+        return values[0].cpu().numpy()
+
+    def _pack(self, dev):
+        return pack_cadrl_network(self.model, dev)
+
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
+        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
+        rc = _hip.lib.mcn_cadrl_predict(C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin,
+                                        _hip.ptr(b["values"]), _hip.ptr(b["best"]), _hip.ptr(b["best_val"]),
+                                        _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew), _hip.ptr(b["action"]),
+                                        float(epsilon), seed, E, N, _hip.stream_ptr(dev))
+        _hip.check(rc, "mcn_cadrl_predict")
+
+    # ------------------------------------------------------------------ device plumbing (every look-ahead policy)
+    def _gpu_device(self):
+        d = self.device if isinstance(self.device, torch.device) else torch.device(self.device or "cuda")
+        if d.type != "cuda":
+            # the reference accepts --device cpu; this build's look-ahead only exists as HIP kernels
+            d = torch.device("cuda", torch.cuda.current_device())
+        return d
+
+    def _packed(self, dev):
+        """ctypes net struct of device fragments, re-packed when a parameter's version or the device changes."""
+        version = tuple(p._version for p in self.model.parameters()) + (str(dev),)
+        if self._frags is None or self._frags[0] != version:
+            net, keep = self._pack(dev)
+            self._frags = (version, net, keep)
+        return self._frags[1]
+
+    def _workspace_bytes(self, E, N, A):
+        return 0
+
+    def _lookahead(self, st, E, N, dev, want_attention=False, env_next=None, epsilon=0.0):
+        """Launch the policy's look-ahead (`_launch`: mcn_sarl_predict, mcn_lstm_rl_predict, mcn_cadrl_predict) on an
+        EnvState struct; returns (values[E,A], best[E], best_val[E], att); the chosen
+        actions [E,2] (table row of `best`, zero where the robot stands on its goal) are left in self._bufs["action"].
+        env_next = (next_hpos [E,N,2], next_hvel [E,N,2], rewards [E,A]): the `query_env` form -- the env's
+        look-ahead states and rewards instead of propagate + compute_reward."""
+        if self.action_space is None:
+            raise RuntimeError("action space not built")
+        A = len(self.action_space)
+        key = (E, N, A, dev)
+        if self._bufs.get("key") != key:
+            nbytes = self._workspace_bytes(E, N, A)
+            self._bufs = {
+                "key": key,
+                "ws": torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None,
+                "values": torch.empty(E, A, dtype=torch.float64, device=dev),
+                "best": torch.empty(E, dtype=torch.int32, device=dev),
+                "best_val": torch.empty(E, dtype=torch.float64, device=dev),
+                "action": torch.empty(E, 2, dtype=torch.float64, device=dev),
+                "table": torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev),
+                "att": None,
+            }
+        b = self._bufs
+        if want_attention and b["att"] is None:
+            b["att"] = torch.empty(E, A, N, dtype=torch.float32, device=dev)
+        net = self._packed(dev)
+        kin = _hip.KIN_UNICYCLE if self.kinematics == "unicycle" else _hip.KIN_HOLONOMIC
+        gamma_pow = pow(self.gamma, self.time_step * self._v_pref)       # multi_human_rl.py:52
+        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
+        # a fresh 63-bit seed per call from torch's host generator (no device launch): torch.manual_seed() makes
+        # training rollouts reproducible
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if epsilon > 0 else 0
+        self._launch(net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention)
+        return b["values"], b["best"], b["best_val"], b["att"]
+
+    def _query_env(self, venv):
+        """`query_env = true` (multi_human_rl.py:37-38): what `env.onestep_lookahead(action)` returns for every action
+        of the table, for all E envs of the batched env `venv`.  The humans react to the robot's CURRENT state
+        (crowd_sim.py:336-342), so their next states do not depend on the candidate action: ONE mcn_env_step(update = 0)
+        gives them; the reward (swept-circle test against the candidate action, goal test, time limit) does, and comes
+        from one given-velocity mcn_env_step over the E x A (env, action) pairs on a scratch copy of the state.
+        Returns (next_hpos [E,N,2], next_hvel [E,N,2], rewards [E,A])."""
+        E, N, dev = venv.num_envs, venv._alloc_N, venv.device
+        A = len(self.action_space)
+        table = self._bufs["table"] if self._bufs.get("table") is not None else \
+            torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev)
+        ob, _, _, _ = venv.onestep_lookahead(torch.zeros(E, 2, dtype=torch.float64, device=dev))
+        npos, nvel = ob.pos.clone(), ob.vel.clone()
+        rep = lambda t: t.repeat_interleave(A, 0).contiguous()
+        x = dict(hpos=rep(venv.hpos), hvel=rep(venv.hvel), hrad=rep(venv.hrad), rpos=rep(venv.rpos), rvel=rep(venv.rvel),
+                 rgoal=rep(venv.rgoal), rrad=rep(venv.rrad), rvpref=rep(venv.rvpref), rtheta=rep(venv.rtheta),
+                 gtime=rep(venv.gtime))
+        st = _hip.EnvState()
+        for k, v in x.items():
+            setattr(st, k, _hip.ptr(v))
+        st.hgoal, st.hvpref = _hip.ptr(x["hpos"]), _hip.ptr(x["hrad"])      # not read with given velocities
+        acts = table.repeat(E, 1).contiguous()
+        given = rep(nvel)
+        rec = torch.zeros(E * A, 3, dtype=torch.float64, device=dev)
+        out = _hip.EnvOut(_hip.ptr(rec), None, None, None)
+        cfg = venv._cfg_struct("given")
+        cfg.count_hh = 0
+        cfg.track_human_times = 0
+        _hip.check(_hip.lib.mcn_env_step(cfg, st, _hip.ptr(acts), _hip.ptr(given), out, None, E * A, N, 1,
+                                         _hip.stream_ptr(dev)), "mcn_env_step")
+        return npos, nvel, rec[:, 0].reshape(E, A).contiguous()
+
+    # ------------------------------------------------------------------ batched surface
+    def predict_batch(self, env, want_values=False, hcount=None):
+        """Look-ahead for all E environments of a VecCrowdSim: greedy in phase 'test' / 'val'; in phase 'train' each
+        env independently takes a uniformly random table action with probability `epsilon` (multi_human_rl.py:27-29,
+        one draw per env per step from torch's device generator) -- `best` is -2 for those envs.
+
+        Returns (actions [E,2] float64 device tensor, best [E] int32; -1 where the robot already
+        stands on its goal and the zero action is returned, multi_human_rl.py:22-23).  Both (and `values`) are the
+        policy's own output buffers, written by the look-ahead launch: valid until the next predict_batch call.
+        hcount ([E] int32 device tensor, optional): env e shows only its first hcount[e] pedestrians to the policy
+        (the reference simply hands `predict` a shorter list, e.g. datagen.py:347-363)."""
+        if self.action_space is None:
+            self.build_action_space(float(env.robot.v_pref))
+        dev = env.device
+        self._v_pref = float(env.robot.v_pref)
+        st = env._st
+        if hcount is not None:
+            if hcount.dtype != torch.int32 or not hcount.is_contiguous() or hcount.numel() != env.num_envs:
+                raise ValueError("hcount must be a contiguous int32 tensor with one entry per env")
+            st = _hip.EnvState.from_buffer_copy(env._st)
+            st.hcount = _hip.ptr(hcount)
+        env_next = None
+        if self.query_env:
+            if hcount is not None:
+                raise NotImplementedError("query_env with per-env pedestrian counts")
+            if self._bufs.get("table") is None:
+                self._bufs["table"] = torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev)
+            env_next = self._query_env(env)
+        eps = float(getattr(self, "epsilon", 0) or 0) if self.phase == "train" else 0.0
+        # epsilon-greedy happens inside the look-ahead's argmax kernel (one draw per env per step from a counter-based
+        # stream seeded from torch's generator): best == -2 marks the envs that explored
+        values, best, best_val, _ = self._lookahead(st, env.num_envs, env._alloc_N, dev, env_next=env_next, epsilon=eps)
+        actions = self._bufs["action"]              # written by the argmax kernel: no torch launches
+        if want_values:
+            return actions, best, values
+        return actions, best

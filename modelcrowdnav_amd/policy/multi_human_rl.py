@@ -4,12 +4,10 @@
 `predict(JointState)` keeps the reference's contract -- including the draw from numpy's global
 stream before the epsilon test, the reach-destination short cut, `action_values`, `last_state`
 and the ValueError on an all-NaN network -- but the 81-iteration Python loop (propagate,
-compute_reward, 5 tiny tensors, rotate, forward, .item()) is ONE mcn_sarl_lookahead launch.
-`predict_batch(env)` is the same launch over all E environments of a VecCrowdSim, reading the
-env's HBM-resident state in place.
+compute_reward, 5 tiny tensors, rotate, forward, .item()) is ONE look-ahead launch (the policy's `_launch` hook:
+mcn_sarl_predict, mcn_lstm_rl_predict).  `predict_batch(env)` (policy/cadrl.py) is the same launch over all E
+environments of a VecCrowdSim, reading the env's HBM-resident state in place.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -19,94 +17,16 @@ from ..envs.utils.action import ActionRot, ActionXY
 
 
 class MultiHumanRL(CADRL):
-    def __init__(self):
-        super().__init__()
-        self._frags = None        # packed MFMA operand fragments (device) + the version they were packed at
-        self._ws = None
-        self._bufs = {}
+    """The [N,13]-rows policies (SARL, LSTM-RL).  The look-ahead plumbing (_lookahead, _query_env, predict_batch) is
+    CADRL's; a subclass supplies `_packed` and the launch hook `_launch`."""
 
-    # ------------------------------------------------------------------ device plumbing
-    def _gpu_device(self):
-        d = self.device if isinstance(self.device, torch.device) else torch.device(self.device or "cuda")
-        if d.type != "cuda":
-            # the reference accepts --device cpu; this build's look-ahead only exists as HIP kernels
-            d = torch.device("cuda", torch.cuda.current_device())
-        return d
+    _attention = False          # the network has per-human attention weights (SARL)
 
-    def _packed(self, dev):
+    def _pack(self, dev):
         raise NotImplementedError
 
-    def _lookahead(self, st, E, N, dev, want_attention=False, env_next=None, epsilon=0.0):
-        """Launch mcn_sarl_predict on an EnvState struct; returns (values[E,A], best[E], best_val[E], att); the chosen
-        actions [E,2] (table row of `best`, zero where the robot stands on its goal) are left in self._bufs["action"].
-        env_next = (next_hpos [E,N,2], next_hvel [E,N,2], rewards [E,A]): the `query_env` form -- the env's
-        look-ahead states and rewards instead of propagate + compute_reward."""
-        if self.action_space is None:
-            raise RuntimeError("action space not built")
-        A = len(self.action_space)
-        key = (E, N, A, dev)
-        if self._bufs.get("key") != key:
-            nbytes = _hip.lib.mcn_sarl_workspace_bytes(E, N, A)
-            self._bufs = {
-                "key": key,
-                "ws": torch.empty(nbytes // 4, dtype=torch.float32, device=dev),
-                "values": torch.empty(E, A, dtype=torch.float64, device=dev),
-                "best": torch.empty(E, dtype=torch.int32, device=dev),
-                "best_val": torch.empty(E, dtype=torch.float64, device=dev),
-                "action": torch.empty(E, 2, dtype=torch.float64, device=dev),
-                "table": torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev),
-                "att": None,
-            }
-        b = self._bufs
-        if want_attention and b["att"] is None:
-            b["att"] = torch.empty(E, A, N, dtype=torch.float32, device=dev)
-        net = self._packed(dev)
-        kin = _hip.KIN_UNICYCLE if self.kinematics == "unicycle" else _hip.KIN_HOLONOMIC
-        gamma_pow = pow(self.gamma, self.time_step * self._v_pref)       # multi_human_rl.py:52
-        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
-        rc = _hip.lib.mcn_sarl_predict(C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin,
-                                       _hip.ptr(b["ws"]), _hip.ptr(b["values"]), _hip.ptr(b["best"]),
-                                       _hip.ptr(b["best_val"]), _hip.ptr(b["att"]) if want_attention else None,
-                                       _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew), _hip.ptr(b["action"]),
-                                       float(epsilon),
-                                       # a fresh 63-bit seed per call from torch's host generator (no device launch):
-                                       # torch.manual_seed() makes training rollouts reproducible
-                                       int(torch.randint(0, 2 ** 62, (1,)).item()) if epsilon > 0 else 0,
-                                       E, N, _hip.stream_ptr(dev))
-        _hip.check(rc, "mcn_sarl_predict")
-        return b["values"], b["best"], b["best_val"], b["att"]
-
-    def _query_env(self, venv):
-        """`query_env = true` (multi_human_rl.py:37-38): what `env.onestep_lookahead(action)` returns for every action
-        of the table, for all E envs of the batched env `venv`.  The humans react to the robot's CURRENT state
-        (crowd_sim.py:336-342), so their next states do not depend on the candidate action: ONE mcn_env_step(update = 0)
-        gives them; the reward (swept-circle test against the candidate action, goal test, time limit) does, and comes
-        from one given-velocity mcn_env_step over the E x A (env, action) pairs on a scratch copy of the state.
-        Returns (next_hpos [E,N,2], next_hvel [E,N,2], rewards [E,A])."""
-        E, N, dev = venv.num_envs, venv._alloc_N, venv.device
-        A = len(self.action_space)
-        table = self._bufs["table"] if self._bufs.get("table") is not None else \
-            torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev)
-        ob, _, _, _ = venv.onestep_lookahead(torch.zeros(E, 2, dtype=torch.float64, device=dev))
-        npos, nvel = ob.pos.clone(), ob.vel.clone()
-        rep = lambda t: t.repeat_interleave(A, 0).contiguous()
-        x = dict(hpos=rep(venv.hpos), hvel=rep(venv.hvel), hrad=rep(venv.hrad), rpos=rep(venv.rpos), rvel=rep(venv.rvel),
-                 rgoal=rep(venv.rgoal), rrad=rep(venv.rrad), rvpref=rep(venv.rvpref), rtheta=rep(venv.rtheta),
-                 gtime=rep(venv.gtime))
-        st = _hip.EnvState()
-        for k, v in x.items():
-            setattr(st, k, _hip.ptr(v))
-        st.hgoal, st.hvpref = _hip.ptr(x["hpos"]), _hip.ptr(x["hrad"])      # not read with given velocities
-        acts = table.repeat(E, 1).contiguous()
-        given = rep(nvel)
-        rec = torch.zeros(E * A, 3, dtype=torch.float64, device=dev)
-        out = _hip.EnvOut(_hip.ptr(rec), None, None, None)
-        cfg = venv._cfg_struct("given")
-        cfg.count_hh = 0
-        cfg.track_human_times = 0
-        _hip.check(_hip.lib.mcn_env_step(cfg, st, _hip.ptr(acts), _hip.ptr(given), out, None, E * A, N, 1,
-                                         _hip.stream_ptr(dev)), "mcn_env_step")
-        return npos, nvel, rec[:, 0].reshape(E, A).contiguous()
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
+        raise NotImplementedError
 
     # ------------------------------------------------------------------ reference surface (E = 1)
     def predict(self, state):
@@ -149,15 +69,16 @@ class MultiHumanRL(CADRL):
                     raise AttributeError("query_env needs set_env(CrowdSim)")
                 self.env._push_host_state()
                 env_next = self._query_env(venv)
-            values, best, _, att = self._lookahead(st, 1, N, dev, want_attention=True, env_next=env_next)
+            values, best, _, att = self._lookahead(st, 1, N, dev, want_attention=self._attention, env_next=env_next)
             vals = values[0].cpu().numpy()
             self.action_values = vals.tolist()
             idx = int(best.item())
-            # the reference's model keeps the weights of its LAST forward, i.e. of the last candidate action
-            # (sarl.py:56,88-89), and that is what env.step stores per step; the chosen action's are kept beside them
-            a_host = att[0].cpu().numpy()
-            self._last_attention = a_host[-1].copy()
-            self.chosen_attention_weights = a_host[max(idx, 0)].copy()
+            if self._attention:
+                # the reference's model keeps the weights of its LAST forward, i.e. of the last candidate action
+                # (sarl.py:56,88-89), and that is what env.step stores per step; the chosen action's are kept beside them
+                a_host = att[0].cpu().numpy()
+                self._last_attention = a_host[-1].copy()
+                self.chosen_attention_weights = a_host[max(idx, 0)].copy()
             if idx < 0 or not np.isfinite(vals[idx]):
                 # every value NaN <=> `value > max_value` never fired in the reference loop
                 raise ValueError("Value network is not well trained. ")
@@ -186,40 +107,3 @@ class MultiHumanRL(CADRL):
 
     def input_dim(self):
         return self.joint_state_dim + (self.cell_num ** 2 * self.om_channel_size if self.with_om else 0)
-
-    # ------------------------------------------------------------------ batched surface
-    def predict_batch(self, env, want_values=False, hcount=None):
-        """Look-ahead for all E environments of a VecCrowdSim: greedy in phase 'test' / 'val'; in phase 'train' each
-        env independently takes a uniformly random table action with probability `epsilon` (multi_human_rl.py:27-29,
-        one draw per env per step from torch's device generator) -- `best` is -2 for those envs.
-
-        Returns (actions [E,2] float64 device tensor, best [E] int32; -1 where the robot already
-        stands on its goal and the zero action is returned, multi_human_rl.py:22-23).  Both (and `values`) are the
-        policy's own output buffers, written by the look-ahead launch: valid until the next predict_batch call.
-        hcount ([E] int32 device tensor, optional): env e shows only its first hcount[e] pedestrians to the policy
-        (the reference simply hands `predict` a shorter list, e.g. datagen.py:347-363)."""
-        if self.action_space is None:
-            self.build_action_space(float(env.robot.v_pref))
-        dev = env.device
-        self._v_pref = float(env.robot.v_pref)
-        st = env._st
-        if hcount is not None:
-            if hcount.dtype != torch.int32 or not hcount.is_contiguous() or hcount.numel() != env.num_envs:
-                raise ValueError("hcount must be a contiguous int32 tensor with one entry per env")
-            st = _hip.EnvState.from_buffer_copy(env._st)
-            st.hcount = _hip.ptr(hcount)
-        env_next = None
-        if self.query_env:
-            if hcount is not None:
-                raise NotImplementedError("query_env with per-env pedestrian counts")
-            if self._bufs.get("table") is None:
-                self._bufs["table"] = torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev)
-            env_next = self._query_env(env)
-        eps = float(getattr(self, "epsilon", 0) or 0) if self.phase == "train" else 0.0
-        # epsilon-greedy happens inside the look-ahead's argmax kernel (one draw per env per step from a counter-based
-        # stream seeded from torch's generator): best == -2 marks the envs that explored
-        values, best, best_val, _ = self._lookahead(st, env.num_envs, env._alloc_N, dev, env_next=env_next, epsilon=eps)
-        actions = self._bufs["action"]              # written by the argmax kernel: no torch launches
-        if want_values:
-            return actions, best, values
-        return actions, best

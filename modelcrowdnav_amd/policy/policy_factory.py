@@ -1,6 +1,9 @@
-"""Robot policy table (reference: crowd_nav/policy/policy_factory.py:1-8).  'cadrl' and 'lstm_rl' are
-outside the path this build covers."""
+"""Robot policy table (reference: crowd_nav/policy/policy_factory.py:1-8)."""
 from ..envs.policy.policy_factory import policy_factory
+from .cadrl import CADRL
+from .lstm_rl import LstmRL
 from .sarl import SARL
 
+policy_factory["cadrl"] = CADRL
+policy_factory["lstm_rl"] = LstmRL
 policy_factory["sarl"] = SARL

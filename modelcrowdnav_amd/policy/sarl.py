@@ -174,6 +174,20 @@ class SARL(MultiHumanRL):
             self._frags = (version, net, keep)
         return self._frags[1]
 
+    _attention = True
+
+    def _workspace_bytes(self, E, N, A):
+        return _hip.lib.mcn_sarl_workspace_bytes(E, N, A)
+
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
+        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
+        rc = _hip.lib.mcn_sarl_predict(C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin,
+                                       _hip.ptr(b["ws"]), _hip.ptr(b["values"]), _hip.ptr(b["best"]),
+                                       _hip.ptr(b["best_val"]), _hip.ptr(b["att"]) if want_attention else None,
+                                       _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew), _hip.ptr(b["action"]),
+                                       float(epsilon), seed, E, N, _hip.stream_ptr(dev))
+        _hip.check(rc, "mcn_sarl_predict")
+
     def get_attention_weights(self):
         """sarl.py:88-89: the attention weights of the model's last forward -- after predict() those of the LAST
         candidate action of the table, as in the reference (stale after a call that returned without a look-ahead).

@@ -1,0 +1,60 @@
+"""Torch-float32 restatement of the LSTM-RL / CADRL look-ahead (lstm_rl.py:90-103, cadrl.py:131-178,
+multi_human_rl.py:35-55) for the GPU tests: propagate and compute_reward in float64 numpy, rotate + the policy's own
+torch module in float32 on the CPU, value = reward + gamma^(dt v_pref) * V in float64."""
+import numpy as np
+import torch
+
+from modelcrowdnav_amd.policy.cadrl import rotate
+
+
+def stable_desc_order(self_row, hum, count=None):
+    """lstm_rl.py:99-103 on arrays: np.linalg.norm distances to the robot's current position, stable descending;
+    slots >= count keep their index."""
+    n = hum.shape[0] if count is None else count
+    d = np.array([np.linalg.norm(np.array([hum[i, 0], hum[i, 1]]) - np.array([self_row[0], self_row[1]]))
+                  for i in range(n)])
+    return np.concatenate([np.argsort(-d, kind="stable"), np.arange(n, hum.shape[0])]).astype(np.int64)
+
+
+def policy_values(model, kind, self_row, hum, table, kinematics, time_step=0.25, gamma=0.9, nexts=None,
+                  rewards=None):
+    """values [A] for one env.  hum: [N,5] (px,py,vx,vy,r) of the humans the policy sees, in the order the network
+    takes them (LSTM-RL) / any order (CADRL).  nexts: [N,4] next (px,py,vx,vy) from the env (query_env) with rewards
+    [A], instead of constant-velocity propagation and compute_reward."""
+    px, py, vx, vy, r, gx, gy, vpref, theta = [float(v) for v in self_row]
+    N = hum.shape[0]
+    if nexts is None:
+        hx, hy = hum[:, 0] + hum[:, 2] * time_step, hum[:, 1] + hum[:, 3] * time_step
+        hvx, hvy = hum[:, 2], hum[:, 3]
+    else:
+        hx, hy, hvx, hvy = nexts[:, 0], nexts[:, 1], nexts[:, 2], nexts[:, 3]
+    rows, rew = [], []
+    for ai, a in enumerate(table):
+        if kinematics == "holonomic":
+            nvx, nvy, nth = a[0], a[1], theta
+        else:
+            nth = theta + a[1]
+            nvx, nvy = a[0] * np.cos(nth), a[0] * np.sin(nth)
+        npx, npy = px + nvx * time_step, py + nvy * time_step
+        dmin, coll = float("inf"), False
+        for i in range(N):
+            d = np.linalg.norm((npx - hx[i], npy - hy[i])) - r - hum[i, 4]
+            if d < 0:
+                coll = True
+                break
+            dmin = min(dmin, d)
+        reach = np.linalg.norm((npx - gx, npy - gy)) < r
+        rw = -0.25 if coll else (1 if reach else ((dmin - 0.2) * 0.5 * time_step if dmin < 0.2 else 0))
+        rew.append(rw if rewards is None else rewards[ai])
+        rows.append([[npx, npy, nvx, nvy, r, gx, gy, vpref, nth, hx[i], hy[i], hvx[i], hvy[i], hum[i, 4]]
+                     for i in range(N)])
+    x = torch.tensor(np.array(rows), dtype=torch.float32)                       # [A, N, 14]
+    A = x.shape[0]
+    xr = rotate(x.reshape(A * N, 14), kinematics).reshape(A, N, 13)
+    with torch.no_grad():
+        if kind == "cadrl":
+            V = model(xr.reshape(A * N, 13)).reshape(A, N).min(1).values
+        else:
+            V = model(xr).reshape(A)
+    g = pow(gamma, time_step * vpref)
+    return np.array([rew[a] + g * float(V[a]) for a in range(A)])

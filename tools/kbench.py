@@ -2,6 +2,7 @@
 """Kernel micro-benchmark (GPU box): per-launch time of mcn_env_step at several batch sizes and
 human-policy modes, measured with HIP events around a hipGraph of back-to-back launches.
     python tools/kbench.py [--humans 5] [--sizes 4096,65536,1048576] [--modes orca,given]
+    python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
 """
 import argparse
 import os
@@ -54,7 +55,13 @@ def main():
     ap.add_argument("--sarl", action="store_true")
     ap.add_argument("--rollout", type=int, default=0, help="time mcn_env_rollout with this many steps per launch")
     ap.add_argument("--sgan", action="store_true", help="time mcn_sgan_step (shipped pool-net weights) at --sizes x --humans")
+    ap.add_argument("--lstm-rl", action="store_true", help="time mcn_lstm_rl_predict at 4096 envs x --humans")
+    ap.add_argument("--cadrl", action="store_true", help="time mcn_cadrl_predict at 4096 envs x --humans")
     a = ap.parse_args()
+    if a.lstm_rl or a.cadrl:
+        for N in [int(x) for x in str(a.humans).split(",")]:
+            policy_bench("lstm_rl" if a.lstm_rl else "cadrl", 4096, N)
+        return
     if a.sgan:
         for N in [int(x) for x in str(a.humans).split(",")]:
             for E in [int(x) for x in a.sizes.split(",")]:
@@ -169,6 +176,46 @@ def sarl_bench(E=4096, N=5, iters=5):
     e.record(); torch.cuda.synchronize()
     ms = s.elapsed_time(e) / iters
     print("SARL-driven env step N=%d E=%d: %.3f ms/step  %.3f M env-steps/s" % (N, E, ms, E / ms / 1e3))
+
+
+def policy_bench(kind, E=4096, N=5, iters=20):
+    """One LSTM-RL / CADRL look-ahead launch (mcn_*_predict + the argmax kernel) over E envs x 81 actions, and a torch
+    float32 batched forward of the same module on the same-sized [E*A, N, 13] input (what it replaces), both timed
+    with device events after warm-up.  Useful FLOP per (env, action): LSTM-RL N*2*200*63 + 2*33 500, CADRL N*54 100."""
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.policy.policy_factory import policy_factory
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    pol = policy_factory[kind](); pol.configure(configs.policy_config()); pol.kinematics = "holonomic"
+    pol.set_device(dev); pol.set_phase("test"); pol.time_step = 0.25
+    env, _ = bench.build_env(E, N, 0, dev)
+    pol.predict_batch(env)
+    A = len(pol.action_space)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(iters):
+            fn()
+        e.record(); torch.cuda.synchronize()
+        return s.elapsed_time(e) / iters
+
+    ms = timed(lambda: pol.predict_batch(env))
+    x = torch.rand(E * A, N, 13, device=dev)
+    with torch.no_grad():
+        if kind == "cadrl":
+            ms_t = timed(lambda: pol.model(x.view(-1, 13)).view(E * A, N).min(1))
+        else:
+            ms_t = timed(lambda: pol.model(x))
+    flop = (N * 2 * 200 * 63 + 2 * 33500) if kind == "lstm_rl" else N * 54100
+    tf = flop * E * A / ms / 1e9
+    print("%s lookahead N=%d E=%d: %.3f ms/launch  %.1f TFLOP/s useful = %.3f of the fp32 MFMA peak %.1f "
+          "(peak bound %.3f ms); torch fp32 forward of the same module on [%d, %d, 13]: %.3f ms (%.2fx)" % (
+              kind, N, E, ms, tf, tf / bench.MFMA_F32_PEAK_TFLOPS, bench.MFMA_F32_PEAK_TFLOPS,
+              flop * E * A / bench.MFMA_F32_PEAK_TFLOPS / 1e9, E * A, N, ms_t, ms_t / ms), flush=True)
 
 
 if __name__ == "__main__":
