@@ -342,8 +342,8 @@ typedef struct mcn_cadrl_net {
 /*
  * mcn_lstm_rl_predict -- mcn_sarl_predict for LstmRL (lstm_rl.py:90-103): per env the humans are taken in the order
  * LstmRL.predict sorts them, by decreasing float64 distance of their CURRENT position to the robot's current position
- * (np.linalg.norm, lstm_rl.py:99-101), equal distances in index order (sorted(reverse=True) is stable), over the first
- * hcount[e] humans only; the LSTM starts from h = c = 0 and humans at index >= hcount[e] do not touch it.  With
+ * (np.linalg.norm, lstm_rl.py:99-101), equal distances in index order (sorted(reverse=True) is stable), NaN distances
+ * last in index order, over the first hcount[e] humans only; the LSTM starts from h = c = 0 and humans at index >= hcount[e] do not touch it.  With
  * next_hpos / next_hvel / rewards set (`query_env`, multi_human_rl.py:37-38) the env's next states are taken in the
  * env's order, as the reference does.  order: [E][N] int32 device out or NULL: the human index at each LSTM step (slots
  * >= hcount[e] hold their own index).  No workspace.  Everything else as mcn_sarl_predict.

@@ -65,9 +65,11 @@ __device__ __forceinline__ float tanh_f(float x)
 }
 
 // Human order of LstmRL.predict (lstm_rl.py:99-103): sorted(humans, key=distance to the robot's CURRENT position,
-// reverse=True).  Python's sort is stable, so equal distances keep their index order: selection of the first strict
-// maximum among the humans not yet taken is the same permutation.  Only the env's first `ne` humans take part; the
-// result is always a permutation of 0 .. ne-1 (a NaN distance is never a maximum and is taken last).
+// reverse=True).  Python's sort is stable, so for non-NaN distances (+inf included) equal distances keep their index
+// order: selection of the first strict maximum among the humans not yet taken is the same permutation.  Only the
+// env's first `ne` humans take part; the result is always a permutation of 0 .. ne-1.  Where CPython's order of NaN
+// keys depends on its sort's internals, this path defines one: NaN distances come last, in index order -- init() holds
+// them as -1, below every distance (a norm is >= 0 or +inf), so they never win a strict '>' against a real one.
 template <int MAXN>
 struct HumanOrder {
     double d[MAXN];
@@ -79,7 +81,8 @@ struct HumanOrder {
             d[i] = 0.0;
             if (i < ne) {
                 const double2 h = reinterpret_cast<const double2 *>(hpos)[base + i];
-                d[i] = norm2d(h.x - rx, h.y - ry);        // np.linalg.norm(human.position - self.position)
+                const double di = norm2d(h.x - rx, h.y - ry);        // np.linalg.norm(human.position - self.position)
+                d[i] = di == di ? di : -1.0;
             }
         }
         used = 0;

@@ -21,6 +21,23 @@ def policy_values(model, kind, self_row, hum, table, kinematics, time_step=0.25,
     """values [A] for one env.  hum: [N,5] (px,py,vx,vy,r) of the humans the policy sees, in the order the network
     takes them (LSTM-RL) / any order (CADRL).  nexts: [N,4] next (px,py,vx,vy) from the env (query_env) with rewards
     [A], instead of constant-velocity propagation and compute_reward."""
+    xr, rew = rotated_rows(self_row, hum, table, kinematics, time_step, nexts, rewards)
+    V = network_value(model, kind, xr)
+    g = pow(gamma, time_step * float(self_row[7]))
+    return np.array([rew[a] + g * float(V[a]) for a in range(len(rew))])
+
+
+def network_value(model, kind, xr):
+    """V [A] of the rotated rows xr [A,N,13] in the module's own dtype (CADRL: min over the humans)."""
+    A, N = xr.shape[0], xr.shape[1]
+    with torch.no_grad():
+        if kind == "cadrl":
+            return model(xr.reshape(A * N, 13)).reshape(A, N).min(1).values
+        return model(xr).reshape(A)
+
+
+def rotated_rows(self_row, hum, table, kinematics, time_step=0.25, nexts=None, rewards=None):
+    """(the float32 rotated rows [A,N,13] of every candidate action, the rewards [A]) of policy_values."""
     px, py, vx, vy, r, gx, gy, vpref, theta = [float(v) for v in self_row]
     N = hum.shape[0]
     if nexts is None:
@@ -50,11 +67,4 @@ def policy_values(model, kind, self_row, hum, table, kinematics, time_step=0.25,
                      for i in range(N)])
     x = torch.tensor(np.array(rows), dtype=torch.float32)                       # [A, N, 14]
     A = x.shape[0]
-    xr = rotate(x.reshape(A * N, 14), kinematics).reshape(A, N, 13)
-    with torch.no_grad():
-        if kind == "cadrl":
-            V = model(xr.reshape(A * N, 13)).reshape(A, N).min(1).values
-        else:
-            V = model(xr).reshape(A)
-    g = pow(gamma, time_step * vpref)
-    return np.array([rew[a] + g * float(V[a]) for a in range(A)])
+    return rotate(x.reshape(A * N, 14), kinematics).reshape(A, N, 13), rew

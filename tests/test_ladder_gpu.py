@@ -2,7 +2,8 @@
 the swept test (touching, a point segment, u exactly 0 or 1, tied humans), the overlap count at and within 1e-6 / 1e-3 of
 touching (float32-rounded positions on the other side of touching included), the goal test at and within 1e-6 of the
 radius, the timeout rung at and one ulp below time_limit - 1, the rung precedences, first arrivals at exactly one radius,
-headings with a zero fmod remainder, and the look-ahead reward of mcn_sarl_predict.
+headings with a zero fmod remainder, and the look-ahead reward of mcn_sarl_predict, mcn_lstm_rl_predict and
+mcn_cadrl_predict.
 
 Each test replays its own inputs through the oracle and asserts that they reached the ladder events it claims
 (cport.ladder_counts); failures name the block of the first differing envs."""
@@ -327,3 +328,39 @@ def test_sarl_predict_above_ten_humans_against_torch_reference(N):
         hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
         ref, idx = pyref.sarl_predict(w, row, hum, table)
         np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="N=%d env %d (%s)" % (N, e, names[e]))
+
+
+@pytest.mark.parametrize("body", ["lstm_rl", "cadrl"])
+def test_lstm_rl_and_cadrl_lookahead_rewards_on_ladder_batches(body):
+    """lstm_rl_value.hip's reward ladder, as test_sarl_lookahead_rewards_on_ladder_batches: with a zeroed network V is
+    exactly 0 (LSTM-RL: every gate 1/2, the cell state and h stay 0), so every value is the look-ahead reward bit for
+    bit, N = 1..10, 13 and 32 (all three MAXN variants of the order)."""
+    import torch
+    if body == "lstm_rl":
+        from tests.test_lstm_rl_gpu import _policy
+    else:
+        from tests.test_cadrl_gpu import _policy
+    pol = _policy(seed=0)
+    with torch.no_grad():
+        for p_ in pol.model.parameters():
+            p_.zero_()
+    pol.build_action_space(1.0)
+    table = pol._action_table
+    total = {}
+    for N in list(range(1, 11)) + list(GENERIC_NS):
+        st, names = LS.lookahead_batch(N, table)
+        env = H.make_vec_env(st.E, N)
+        H.upload(env, st)
+        actions, best, values = pol.predict_batch(env, want_values=True)
+        cport.ladder_counts(reset=True)
+        ref = cport.lookahead_reward(st, table, 0.25)
+        _add(total)
+        bad = H.bit_mismatch(values.cpu().numpy(), ref)
+        assert len(bad) == 0, (body, N, len(bad), _where(names, bad))
+        best = best.cpu().numpy()
+        for e, name in enumerate(names):
+            if name == "la-at-goal":
+                assert best[e] == -1, (N, e)
+            elif name == "la-at-goal-edge":
+                assert best[e] == int(np.argmax(ref[e])), (N, e, best[e])
+    _assert_reached(total, LA_EVENTS, "mcn_%s_predict" % body)
