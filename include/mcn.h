@@ -460,7 +460,8 @@ int64_t mcn_attn_world_workspace_bytes(int32_t E, int32_t N);
  * mcn_attn_world_step -- AttentionWorld.forward for E scenes of N pedestrians: input = each pedestrian's
  * [px, py, vx, vy] as float32 (model_crowd_sim.py:401-405), output = its predicted velocity (mlp3's two outputs, no
  * output non-linearity, world_model.py:104-105) as float64 [E*N][2].  hcount ([E] int32 or NULL): scene e has only
- * its first hcount[e] pedestrians (the rest of the N slots is ignored and not written).
+ * its first hcount[e] pedestrians (the rest of the N slots is ignored and not written).  A scene whose present
+ * pedestrians all score exactly 0 (the softmax exp(s) (s != 0) / sum is 0 / 0) gets NaN velocities, as the module does.
  */
 int mcn_attn_world_step(const mcn_attn_world_net *net, const double *hpos, const double *hvel, const int32_t *hcount,
                         void *workspace, double *out_vel, int32_t E, int32_t N, void *stream);

@@ -19,7 +19,9 @@ MAX_HUMANS, MAX_LINES = 32, 10
 INFO_NOTHING, INFO_DANGER, INFO_REACHGOAL, INFO_COLLISION, INFO_TIMEOUT = range(5)
 HUMANS_ORCA, HUMANS_LINEAR, HUMANS_GIVEN = range(3)
 KIN_HOLONOMIC, KIN_UNICYCLE = 0, 1
-SIZEOF_LSTM_RL_NET, SIZEOF_CADRL_NET = 13, 14        # include/mcn.h: MCN_SIZEOF_*
+# include/mcn.h: MCN_SIZEOF_* ids of the network structs
+SIZEOF_SARL_NET, SIZEOF_SGAN_NET, SIZEOF_MLP_WORLD_NET, SIZEOF_ATTN_WORLD_NET = 7, 8, 10, 11
+SIZEOF_SARL_X3, SIZEOF_LSTM_RL_NET, SIZEOF_CADRL_NET = 12, 13, 14
 
 _vp, _d, _f, _i = C.c_void_p, C.c_double, C.c_float, C.c_int32
 
@@ -182,12 +184,27 @@ def _check_abi(lib):
     if got != ABI_VERSION:
         raise ImportError("modelcrowdnav_amd: %s has ABI %d, this binding was written for ABI %d -- rebuild the library "
                           "(make -C modelcrowdnav_amd/csrc)" % (LIB_PATH, got, ABI_VERSION))
-    mirrors = {0: EnvCfg, 1: EnvState, 2: EnvOut, 3: Rollout, 4: Tuning, 5: StepRec, 6: RollRec, 9: ScenarioCfg,
-               SIZEOF_LSTM_RL_NET: LstmRLNet, SIZEOF_CADRL_NET: CadrlNet}
+    check_mirrors({0: EnvCfg, 1: EnvState, 2: EnvOut, 3: Rollout, 4: Tuning, 5: StepRec, 6: RollRec, 9: ScenarioCfg,
+                   SIZEOF_LSTM_RL_NET: LstmRLNet, SIZEOF_CADRL_NET: CadrlNet}, lib)
+
+
+def check_mirrors(mirrors, lib_=None):
+    """{MCN_SIZEOF_* id: ctypes mirror}: each mirror must have the size of its C struct.  The policy modules check
+    their own net mirrors with this when they are imported (this module does not import them)."""
+    lib_ = lib if lib_ is None else lib_
     for which, cls in mirrors.items():
-        if int(lib.mcn_sizeof(which)) != C.sizeof(cls):
+        if int(lib_.mcn_sizeof(which)) != C.sizeof(cls):
             raise ImportError("modelcrowdnav_amd: struct %s is %d bytes here, %d in %s" %
-                              (cls.__name__, C.sizeof(cls), int(lib.mcn_sizeof(which)), LIB_PATH))
+                              (cls.__name__, C.sizeof(cls), int(lib_.mcn_sizeof(which)), LIB_PATH))
+
+
+def weights_stamp(params, dev):
+    """What packed HIP weight fragments were made from: every parameter's identity, storage and version counter, and
+    the target device.  It changes on in-place writes through the parameter itself (optimizer steps, load_state_dict,
+    `p.add_` / `p.copy_` under no_grad), on `p.data = t` (new storage) and on a device move.  Writes through `p.data`
+    (`p.data.copy_`, `p.data.mul_`) bypass the version counter and keep the storage: the adapters cannot see them, so
+    call their `refresh()` afterwards."""
+    return tuple((id(p), p.data_ptr(), p._version) for p in params) + (str(dev),)
 
 
 def last_dispatch():

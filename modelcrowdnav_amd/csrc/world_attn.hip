@@ -113,6 +113,10 @@ __global__ __launch_bounds__(kStageThreads, MCN_STAGE_WAVES >= 8 ? 1 : 2) void a
 #pragma unroll
             for (int r = 0; r < 4; ++r) racc[t][r] = i < ne ? racc[t][r] + es * m1[t][r] : racc[t][r];
     }
+    // every present score exactly 0 (or every exp underflowing): the reference's softmax is 0 / 0 and all of the
+    // scene's outputs are NaN.  The integer-max ReLU of the layers below maps a negative-signed NaN to 0, so the NaN
+    // of the division does not reliably reach the output: the store below writes it explicitly.
+    const bool no_weight = denom == 0.0f;
 #pragma unroll
     for (int t = 0; t < W100; ++t)
 #pragma unroll
@@ -138,8 +142,11 @@ __global__ __launch_bounds__(kStageThreads, MCN_STAGE_WAVES >= 8 ? 1 : 2) void a
         f32x4 o[W2];
         dense_staged<W100, W2, false, false, 1>(v3, nullptr, o, p.w_m3d, p.b_m3d, S, lane);
         // natural output order: (vx, vy) are rows 0 and 1 = registers 0 and 1 of lane group 0
-        if (valid && q == 0 && i < ne)
-            reinterpret_cast<double2 *>(p.out_vel)[e * N + i] = make_double2((double)o[0][0], (double)o[0][1]);
+        if (valid && q == 0 && i < ne) {
+            const double nan = __builtin_nan("");
+            reinterpret_cast<double2 *>(p.out_vel)[e * N + i] =
+                no_weight ? make_double2(nan, nan) : make_double2((double)o[0][0], (double)o[0][1]);
+        }
     }
 }
 

@@ -175,7 +175,7 @@ class CADRL(Policy):
         self.human_state_dim = 7
         self.joint_state_dim = self.self_state_dim + self.human_state_dim
         self._action_table = None
-        self._frags = None        # packed MFMA operand fragments (device) + the version they were packed at
+        self._frags = None        # packed MFMA operand fragments (device) + the weight stamp they were packed at
         self._ws = None
         self._bufs = {}
 
@@ -320,12 +320,18 @@ class CADRL(Policy):
         return d
 
     def _packed(self, dev):
-        """ctypes net struct of device fragments, re-packed when a parameter's version or the device changes."""
-        version = tuple(p._version for p in self.model.parameters()) + (str(dev),)
-        if self._frags is None or self._frags[0] != version:
+        """ctypes net struct of device fragments, re-packed when a parameter changed since they were made or the device
+        changed (_hip.weights_stamp).  Writes through `p.data` (`p.data.copy_`) are invisible: call refresh() after
+        them."""
+        stamp = _hip.weights_stamp(self.model.parameters(), dev)
+        if self._frags is None or self._frags[0] != stamp:
             net, keep = self._pack(dev)
-            self._frags = (version, net, keep)
+            self._frags = (stamp, net, keep)
         return self._frags[1]
+
+    def refresh(self):
+        """Re-pack the network at the next look-ahead (after a write the weight stamp cannot see)."""
+        self._frags = None
 
     def _workspace_bytes(self, E, N, A):
         return 0

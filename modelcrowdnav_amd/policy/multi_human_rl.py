@@ -18,7 +18,7 @@ from ..envs.utils.action import ActionRot, ActionXY
 
 class MultiHumanRL(CADRL):
     """The [N,13]-rows policies (SARL, LSTM-RL).  The look-ahead plumbing (_lookahead, _query_env, predict_batch) is
-    CADRL's; a subclass supplies `_packed` and the launch hook `_launch`."""
+    CADRL's; a subclass supplies `_pack` and the launch hook `_launch`."""
 
     _attention = False          # the network has per-human attention weights (SARL)
 

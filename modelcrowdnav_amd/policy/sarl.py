@@ -102,6 +102,9 @@ class _SarlNet(C.Structure):
                                           "x3")]
 
 
+_hip.check_mirrors({_hip.SIZEOF_SARL_NET: _SarlNet, _hip.SIZEOF_SARL_X3: _SarlX3})
+
+
 def pack_value_network(model, dev):
     """state_dict -> (ctypes mcn_sarl_net, [device tensors kept alive])."""
     sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in model.state_dict().items()}
@@ -167,12 +170,8 @@ class SARL(MultiHumanRL):
             self.name = "OM-SARL"
         logging.info("Policy: %s %s global state", self.name, "w/" if with_global_state else "w/o")
 
-    def _packed(self, dev):
-        version = tuple(p._version for p in self.model.parameters()) + (str(dev),)
-        if self._frags is None or self._frags[0] != version:
-            net, keep = pack_value_network(self.model, dev)
-            self._frags = (version, net, keep)
-        return self._frags[1]
+    def _pack(self, dev):
+        return pack_value_network(self.model, dev)
 
     _attention = True
 

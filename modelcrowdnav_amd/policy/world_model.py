@@ -15,6 +15,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from .. import _hip
 from ..sgan.models import TrajectoryGenerator, sgan_step
 
 
@@ -253,10 +254,13 @@ class _MlpWorldNet(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")]
 
 
-def _weights_stamp(module):
-    """Changes whenever a parameter of `module` is written in place (optimizer steps, load_state_dict, .copy_) or
-    replaced (another tensor object / device move): what the packed HIP fragments were made from."""
-    return tuple((id(p), p.data_ptr(), p._version) for p in module.parameters())
+class _AttnWorldNet(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in (
+        "w_m1a", "b_m1a", "w_m1b", "b_m1b", "w_m2a", "b_m2a", "w_m2b", "b_m2b", "w_ata", "b_ata", "w_atg", "w_atb", "b_atb",
+        "w_atc", "b_atc", "w_m3p", "b_m3p", "w_m3s", "w_m3b", "b_m3b", "w_m3c", "b_m3c", "w_m3d", "b_m3d")]
+
+
+_hip.check_mirrors({_hip.SIZEOF_MLP_WORLD_NET: _MlpWorldNet, _hip.SIZEOF_ATTN_WORLD_NET: _AttnWorldNet})
 
 
 def _dropout_active(module):
@@ -266,7 +270,6 @@ def _dropout_active(module):
 
 def pack_mlp_world(module, num_human, dev):
     """MlpWorld.state_dict -> (ctypes mcn_mlp_world_net, [device tensors kept alive]); layouts in include/mcn.h."""
-    from .. import _hip
     from .sarl import _ident, _natural
     sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in module.state_dict().items()}
     N = int(num_human)
@@ -298,8 +301,9 @@ def pack_mlp_world(module, num_human, dev):
 class VecMlpWorld(object):
     """MlpWorld as a VecModelCrowdSim `sim_world`: one mcn_mlp_world_step launch for all E scenes (eval mode: the
     reference calls the model under `model_sim.eval()` when it imagines, train_model_based_sgan.py).  The packed weight
-    fragments follow the module: they are re-packed whenever a parameter changed since they were made (training rounds
-    alternate with imagination on the same module, train_model_based.py) -- `refresh()` is never needed.  A module left
+    fragments follow the module: they are re-packed whenever a parameter was written or replaced since they were made
+    (training rounds alternate with imagination on the same module, train_model_based.py; _hip.weights_stamp).  Writes
+    through `p.data` (`p.data.copy_`) bypass the version counter: call `refresh()` after them.  A module left
     in train() mode with active Dropout is NOT an eval-mode forward: that call goes through the torch module instead
     (same masks / random stream as the E = 1 path)."""
 
@@ -313,14 +317,13 @@ class VecMlpWorld(object):
         self._net = None
 
     def __call__(self, hpos, noise=None):
-        from .. import _hip
         env = self.env
         E, N, dev = env.num_envs, env._alloc_N, env.device
         if _dropout_active(self.module):
             if self._torch is None:
                 self._torch = VecTorchWorld(self.module, env)
             return self._torch(hpos, noise)
-        stamp = _weights_stamp(self.module)
+        stamp = _hip.weights_stamp(self.module.parameters(), dev)
         if self._net is None or self._net[2] != (E, N) or self._net[3] != stamp:
             net, keep = pack_mlp_world(self.module, N, dev)
             self._net = (net, keep, (E, N), stamp)
@@ -331,15 +334,8 @@ class VecMlpWorld(object):
         return self.out_vel
 
 
-class _AttnWorldNet(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in (
-        "w_m1a", "b_m1a", "w_m1b", "b_m1b", "w_m2a", "b_m2a", "w_m2b", "b_m2b", "w_ata", "b_ata", "w_atg", "w_atb", "b_atb",
-        "w_atc", "b_atc", "w_m3p", "b_m3p", "w_m3s", "w_m3b", "b_m3b", "w_m3c", "b_m3c", "w_m3d", "b_m3d")]
-
-
 def pack_attn_world(module, dev):
     """AttentionWorld.state_dict -> (ctypes mcn_attn_world_net, [device tensors kept alive]); layouts in include/mcn.h."""
-    from .. import _hip
     from .sarl import _ident, _natural
     if not module.with_global_state or module.input_dim != 4:
         raise NotImplementedError("world_attn.hip is built for input_dim 4 with the global state (the reference's defaults)")
@@ -383,8 +379,10 @@ def pack_attn_world(module, dev):
 
 class VecAttnWorld(object):
     """AttentionWorld as a VecModelCrowdSim `sim_world`: one mcn_attn_world_step launch for all E scenes.  The packed
-    weight fragments follow the module (re-packed whenever a parameter changed since they were made; `refresh()` is never
-    needed).  `hcount` ([E] int32 device tensor): scene e has only its first hcount[e] pedestrians."""
+    weight fragments follow the module (re-packed whenever a parameter was written or replaced since they were made;
+    _hip.weights_stamp).  Writes through `p.data` (`p.data.copy_`) bypass the version counter: call `refresh()` after
+    them.  `hcount` ([E] int32 device tensor): scene e has only its first hcount[e] pedestrians (clamped to 1 .. N);
+    the output slots of the others are not written."""
 
     def __init__(self, module, env):
         self.module, self.env = module, env
@@ -395,12 +393,11 @@ class VecAttnWorld(object):
         self._net = None
 
     def __call__(self, hpos, noise=None, hcount=None):
-        from .. import _hip
         env = self.env
         E, N, dev = env.num_envs, env._alloc_N, env.device
         if _dropout_active(self.module):
             raise RuntimeError("AttentionWorld in train() mode with active Dropout: the HIP kernel is an eval-mode forward")
-        stamp = _weights_stamp(self.module)
+        stamp = _hip.weights_stamp(self.module.parameters(), dev)
         if self._net is None or self._net[2] != (E, N) or self._net[4] != stamp:
             net, keep = pack_attn_world(self.module, dev)
             ws = torch.empty(_hip.lib.mcn_attn_world_workspace_bytes(E, N) // 4, dtype=torch.float32, device=dev)

@@ -54,6 +54,9 @@ class _SganNet(C.Structure):
                                           "w_c2", "b_c2", "w_dlstm", "b_dlstm", "w_h2p", "b_h2p")] + [("pooling", C.c_int32)]
 
 
+_hip.check_mirrors({_hip.SIZEOF_SGAN_NET: _SganNet})
+
+
 def _fold_embedding(W, b, W_se, b_se):
     """A layer W [nout, 16 + h] applied to [spatial_embedding(d), h] equals [W_e W_se | W_h] applied to [d, h] with
     bias b + W_e b_se (the embedding is a plain Linear(2, 16): sgan/models.py:47,66 / 120,142 / 186,221-223).
@@ -107,7 +110,10 @@ class TrajectoryGenerator(nn.Module):
 
     # ------------------------------------------------------------------ packing
     def pack(self, dev):
-        version = tuple(p._version for p in self.parameters()) + (str(dev),)
+        """(ctypes mcn_sgan_net, [device tensors kept alive]), re-packed when a parameter changed since they were made
+        or the device changed (_hip.weights_stamp).  Writes through `p.data` (`p.data.copy_`) are invisible: call
+        refresh() after them."""
+        version = _hip.weights_stamp(self.parameters(), dev)
         if self._packed is not None and self._packed[0] == version:
             return self._packed[1]
         sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in self.state_dict().items()}
@@ -148,6 +154,10 @@ class TrajectoryGenerator(nn.Module):
         net.pooling = 1 if self.pooling_type else 0
         self._packed = (version, (net, keep))
         return self._packed[1]
+
+    def refresh(self):
+        """Re-pack the weights at the next step (after a write the weight stamp cannot see)."""
+        self._packed = None
 
     # ------------------------------------------------------------------ reference call signature
     def forward(self, obs_traj, obs_traj_rel, seq_start_end, user_noise=None):

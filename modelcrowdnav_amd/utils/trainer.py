@@ -57,9 +57,15 @@ class Trainer(object):
             fn(t)
 
     def sync_weights(self, src=0):
+        """Every rank takes rank `src`'s parameters.  A collective's in-place write does not bump a tensor's version
+        counter, so each parameter is broadcast into a buffer and copied in under no_grad: the copy bumps it, and packed
+        HIP weights of the model (_hip.weights_stamp) are re-made at their next use."""
         if self._world() > 1:
-            for p in self.model.parameters():
-                self._collective(lambda t: dist.broadcast(t, src), p.data)
+            with torch.no_grad():
+                for p in self.model.parameters():
+                    buf = p.detach().clone()
+                    self._collective(lambda t: dist.broadcast(t, src), buf)
+                    p.copy_(buf)
 
     def _allreduce_grads(self):
         # a process group of ONE rank still runs the collective (the world-size-1 RCCL test exercises exactly the

@@ -109,12 +109,13 @@ def _lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh):
 
 
 def sgan_generator(w, obs_traj, obs_rel, n_per_scene, noise, pooling):
-    """One-step generator.  obs_*: [8, S*N, 2] float32, noise [S, noise_dim] -> pred_rel [S*N, 2]."""
+    """One-step generator.  obs_*: [8, S*N, 2] float32, noise [S, noise_dim] -> pred_rel [S*N, 2].  Runs in the dtype
+    of obs_rel (float32, or float64 with float64 weights w: the error yardstick of tests/test_sgan_edges_gpu.py)."""
     T, B, _ = obs_rel.shape
     emb = F.linear(obs_rel.reshape(-1, 2), w["encoder.spatial_embedding.weight"], w["encoder.spatial_embedding.bias"])
     emb = emb.view(T, B, -1)
     H = w["encoder.encoder.weight_hh_l0"].shape[1]
-    h = torch.zeros(B, H); c = torch.zeros(B, H)
+    h = torch.zeros(B, H, dtype=obs_rel.dtype); c = torch.zeros(B, H, dtype=obs_rel.dtype)
     for t in range(T):
         h, c = _lstm_cell(emb[t], h, c, w["encoder.encoder.weight_ih_l0"], w["encoder.encoder.weight_hh_l0"],
                           w["encoder.encoder.bias_ih_l0"], w["encoder.encoder.bias_hh_l0"])
@@ -135,7 +136,7 @@ def sgan_generator(w, obs_traj, obs_rel, n_per_scene, noise, pooling):
         ctx_in = torch.cat([h, torch.cat(pools, 0)], 1)
     x = torch.relu(F.linear(ctx_in, w["mlp_decoder_context.0.weight"], w["mlp_decoder_context.0.bias"]))
     x = torch.relu(F.linear(x, w["mlp_decoder_context.2.weight"], w["mlp_decoder_context.2.bias"]))
-    z = noise.repeat_interleave(n_per_scene, 0)
+    z = noise.to(x.dtype).repeat_interleave(n_per_scene, 0)
     dh = torch.cat([x, z], 1)
     dc = torch.zeros_like(dh)
     din = F.linear(obs_rel[-1], w["decoder.spatial_embedding.weight"], w["decoder.spatial_embedding.bias"])

@@ -97,10 +97,23 @@ def test_abi_version_and_struct_sizes_are_checked_against_the_library():
     hdr = open(os.path.join(ROOT, "include", "mcn.h")).read()
     want = int(re.search(r"#define\s+MCN_ABI_VERSION\s+(\d+)", hdr).group(1))
     assert _hip.lib.mcn_abi_version() == want == _hip.ABI_VERSION
-    for which, cls in {0: _hip.EnvCfg, 1: _hip.EnvState, 2: _hip.EnvOut, 3: _hip.Rollout, 4: _hip.Tuning, 5: _hip.StepRec,
-                       6: _hip.RollRec, 9: _hip.ScenarioCfg}.items():
+    from modelcrowdnav_amd.policy.sarl import _SarlNet, _SarlX3
+    from modelcrowdnav_amd.policy.world_model import _AttnWorldNet, _MlpWorldNet
+    from modelcrowdnav_amd.sgan.models import _SganNet
+    mirrors = {0: _hip.EnvCfg, 1: _hip.EnvState, 2: _hip.EnvOut, 3: _hip.Rollout, 4: _hip.Tuning, 5: _hip.StepRec,
+               6: _hip.RollRec, 7: _SarlNet, 8: _SganNet, 9: _hip.ScenarioCfg, 10: _MlpWorldNet, 11: _AttnWorldNet,
+               12: _SarlX3, 13: _hip.LstmRLNet, 14: _hip.CadrlNet}
+    ids = sorted(int(v) for v in re.findall(r"MCN_SIZEOF_[A-Z0-9_]+\s*=\s*(\d+)", hdr))
+    assert ids == list(range(15)) == sorted(mirrors)            # every id of the header has its mirror here
+    for which, cls in mirrors.items():
         assert _hip.lib.mcn_sizeof(which) == ctypes.sizeof(cls), cls.__name__
-    assert _hip.lib.mcn_sizeof(7) > 0 and _hip.lib.mcn_sizeof(8) > 0 and _hip.lib.mcn_sizeof(99) == -1
+    assert _hip.lib.mcn_sizeof(15) == -1 and _hip.lib.mcn_sizeof(99) == -1 and _hip.lib.mcn_sizeof(-1) == -1
+
+    class Shrunk(object):                                # a library whose struct differs from a module's mirror
+        def mcn_sizeof(self, which):
+            return ctypes.sizeof(_SganNet) + 8
+    with pytest.raises(ImportError):
+        _hip.check_mirrors({_hip.SIZEOF_SGAN_NET: _SganNet}, Shrunk())
 
     class Old(object):                                   # a library built from an older header
         def mcn_abi_version(self):

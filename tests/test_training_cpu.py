@@ -195,7 +195,12 @@ def _dp_worker(rank, ws, port, out_dir):
     mem = ReplayMemory(32)
     mem.push_batch(states[rank * 32:(rank + 1) * 32], values[rank * 32:(rank + 1) * 32])
     tr = Trainer(model, mem, torch.device("cpu"), 32)
+    from modelcrowdnav_amd import _hip
+    before = [_hip.weights_stamp([p], "cpu") for p in model.parameters()]
     tr.sync_weights()
+    after = [_hip.weights_stamp([p], "cpu") for p in model.parameters()]
+    # every rank (src included) must see every parameter as written: packed HIP weights follow the sync
+    assert all(a != b for a, b in zip(after, before)), "sync_weights left a weight stamp unchanged"
     tr.set_learning_rate(0.05)
     tr.optimize_epoch(2)                        # batch == whole shard, so the order inside it is irrelevant
     torch.save({k: v.clone() for k, v in model.state_dict().items()}, os.path.join(out_dir, "w%d.pt" % rank))

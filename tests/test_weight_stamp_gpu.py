@@ -1,0 +1,120 @@
+"""GPU: every HIP adapter's packed weights follow the module's parameters (modelcrowdnav_amd._hip.weights_stamp).
+
+For VecMlpWorld, VecAttnWorld, TrajectoryGenerator (the SGAN step), SARL, CADRL and LSTM-RL, after each of
+  * an in-place write under no_grad (`p.add_`), as an optimizer step makes;
+  * a replacement of the storage (`p.data = p.data + d`);
+  * a write through `.data` (`p.data.copy_`), which bypasses the version counter, followed by `refresh()`;
+the HIP output must be that of the current weights: the torch module's (world models, 1e-5) or pyref's (SGAN, 1e-5),
+and for the look-ahead policies bit for bit that of a new policy built with the current state_dict."""
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-5
+ADAPTERS = ("mlp_world", "attn_world", "sgan", "sarl", "cadrl", "lstm_rl")
+
+
+def _world_case(kind):
+    import torch
+    from modelcrowdnav_amd.policy.world_model import AttentionWorld, MlpWorld, VecAttnWorld, VecMlpWorld
+    dev = torch.device("cuda", 0)
+    E, N = 37, 5
+    rng = np.random.RandomState(1)
+    t = lambda a: torch.from_numpy(a).to(dev)
+    env = SimpleNamespace(num_envs=E, _alloc_N=N, human_num=N, device=dev, hpos=t(rng.uniform(-4, 4, (E, N, 2))),
+                          hvel=t(rng.uniform(-1, 1, (E, N, 2))))
+    torch.manual_seed(2)
+    module = (MlpWorld(N) if kind == "mlp_world" else AttentionWorld()).to(dev).eval()
+    fast = (VecMlpWorld if kind == "mlp_world" else VecAttnWorld)(module, env)
+    x = torch.cat([env.hpos, env.hvel], 2).reshape(E, -1).float()
+
+    def run():
+        with torch.no_grad():
+            want = module(x).view(E, N, 2).double()
+        return fast(env.hpos).clone(), want
+    return module, fast.refresh, run
+
+
+def _sgan_case():
+    import torch
+    from modelcrowdnav_amd.sgan.models import TrajectoryGenerator, sgan_step
+    from tests import sgan_states as S
+    dev = torch.device("cuda", 0)
+    gen = S.load(TrajectoryGenerator(pooling_type="pool_net"), S.weights("p"))
+    E, N = 9, 6
+    rng = np.random.RandomState(3)
+    hist = S.histories(rng, E, N)
+    noise = rng.normal(0, 1, (E, 8)).astype(np.float32)
+    h, z = torch.from_numpy(hist).to(dev), torch.from_numpy(noise).to(dev)
+
+    def run():
+        _, rel = sgan_step(gen, h, 0, 0, None, z, 0.25, want_rel=True)
+        w = {k: v.detach().cpu().float() for k, v in gen.state_dict().items()}
+        pr, _ = S.reference(w, S.window(hist, 0), N, noise, True)
+        return rel.cpu(), torch.from_numpy(pr)
+    return gen, gen.refresh, run
+
+
+def _policy_case(kind):
+    import torch
+    from tests import helpers as H
+    make = {"sarl": "tests.test_sarl_gpu", "cadrl": "tests.test_cadrl_gpu", "lstm_rl": "tests.test_lstm_rl_gpu"}[kind]
+    make = __import__(make, fromlist=["_policy"])._policy
+    pol = make(seed=4)
+    E, N = 23, 5
+    env = H.make_vec_env(E, N)
+    H.upload(env, H.random_state(np.random.RandomState(5), E, N))
+
+    def run():
+        _, _, got = pol.predict_batch(env, want_values=True)
+        got = got.clone()
+        fresh = make(weights={k: v.detach().clone() for k, v in pol.model.state_dict().items()})
+        _, _, want = fresh.predict_batch(env, want_values=True)
+        torch.cuda.synchronize()
+        return got, want.clone()
+    return pol.model, pol.refresh, run
+
+
+def _case(kind):
+    if kind in ("mlp_world", "attn_world"):
+        return _world_case(kind)
+    if kind == "sgan":
+        return _sgan_case()
+    return _policy_case(kind)
+
+
+def _agree(kind, got, want):
+    if kind in ("sarl", "cadrl", "lstm_rl"):
+        return bool((got == want).all())
+    return float((got.double() - want.double()).abs().max()) <= TOL * max(1.0, float(want.abs().max()))
+
+
+@pytest.mark.parametrize("kind", ADAPTERS)
+def test_packed_weights_follow_every_write(kind):
+    import torch
+    module, refresh, run = _case(kind)
+    got, want = run()
+    assert _agree(kind, got, want), "fresh pack"
+    gen = torch.Generator().manual_seed(7)
+
+    def delta(p):
+        return (torch.randn(p.shape, generator=gen) * 0.05).to(p.device, p.dtype)
+
+    for write in ("no_grad add_", "p.data = p.data + d", "p.data.copy_ + refresh()"):
+        before = got
+        with torch.no_grad():
+            for p in module.parameters():
+                if write == "no_grad add_":
+                    p.add_(delta(p))
+                elif write == "p.data = p.data + d":
+                    p.data = p.data + delta(p)
+                else:
+                    p.data.copy_(p.data + delta(p))
+        if write.endswith("refresh()"):
+            refresh()
+        got, want = run()
+        assert _agree(kind, got, want), "stale packed weights after %s" % write
+        assert float((got.double() - before.double()).abs().max()) > 1e-4, "the write must change the output"
