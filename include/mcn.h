@@ -279,6 +279,12 @@ int64_t mcn_sarl_workspace_bytes(int32_t E, int32_t N, int32_t A);
  * actions: [A][2] device; values: [E][A] device out; best: [E] int32 out (-1 = robot already at its goal,
  * multi_human_rl.py:22; may be NULL); best_val: [E]; attention: [E][A][N] float out or NULL.
  * gamma_pow = pow(gamma, time_step * v_pref) computed by the caller (multi_human_rl.py:52).
+ * Values are NaN where the reference's are (its masked softmax, exp(s) (s != 0) / sum, is not stabilised): for an env
+ * with a NaN or infinite feature in a pedestrian it sees or in the robot, for an action row that holds one, where every
+ * score of the env's pedestrians is exactly 0 or every exp(score) underflows (0 / 0) and where an exp(score)
+ * overflows (inf / inf); `attention` is NaN there too, for the pedestrians the env sees, and exactly 0 for the slots
+ * beyond hcount.  NaN values never win the argmax: an env whose values are all NaN reports best = -1, best_val = -inf.
+ * Sums of exp(score) down to the smallest float32 subnormal give finite values, as the reference's division does.
  */
 int mcn_sarl_lookahead(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
                        double time_step, double gamma_pow, int32_t kinematics, void *workspace,
@@ -485,7 +491,12 @@ typedef struct mcn_tuning {
                               * 2 / 3: wherever it applies, with non-temporal per-human streams forced on / off */
     int32_t lp3_defer;       /* lane-per-human ORCA kernels with mcn_env_out.lp3_queue set: park the 3-D LPs for a second,
                               * dense launch (1) or solve them in the step kernel (0); -1: defer from 8 ORCA neighbours and 16 384 wavefronts */
-    int32_t sarl_x3;         /* SARL look-ahead with mcn_sarl_net.x3 set: bf16x3 layers (1 / -1) or the float32 MFMA layers (0) */
+    int32_t sarl_x3;         /* SARL look-ahead with mcn_sarl_net.x3 set: bf16x3 layers (1 / -1) or the float32 MFMA layers (0).
+                              * Input range of the bf16x3 layers: features and activations below 2^128 - 2^119 (3.3962e38)
+                              * in size.  From there on a float32 rounds to an infinite first bfloat16 piece and has no
+                              * three-piece split: what that variant returns for such an env is not specified, while the
+                              * float32 MFMA layers, like the reference, carry every finite float32.  (+-inf and NaN
+                              * features give NaN in both variants, as in the reference.) */
 } mcn_tuning;
 
 /* NULL restores the initial values.  Returns MCN_EINVAL for out-of-range fields.  The settings are one process-wide

@@ -245,6 +245,17 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
 #pragma unroll
     for (int t = 0; t < T100; ++t) gsum[t] = (f32x4){0, 0, 0, 0};
     double dmin = INFINITY;
+    // NaN where the reference is NaN: its masked softmax makes NaN a specified result and torch.relu keeps NaN, while
+    // the layers' ReLU here (relu_f32, an integer max: one vector instruction) turns a NaN with the sign bit set into 0
+    // -- and both signs occur: hosts hand over either, the matrix pipe makes its own.  A ReLU that keeps NaN (compare +
+    // select, one instruction more per activation) was measured in every layer: +0.7 % (4096 x 5) and +1.8 % (4096 x 10)
+    // of the look-ahead, the latter outside the run-to-run spread.  So the layers keep the integer max and
+    // this per-pair flag forces the stored value to NaN instead.  It is set by
+    //   * a non-finite float32 feature of a present human (the robot's six are among every human's thirteen): in the
+    //     reference it reaches every unit of mlp1, the mean and with it every score of the pair (NaN whatever the
+    //     weights are; +-inf unless every weight it meets has one sign);
+    //   * the normalised sum of the tail being NaN: 0 / 0 or inf / inf in the softmax.
+    bool poisoned = false;
     SARL_PHASE(0);                      // tile set-up: robot state, self features
     for (int i = 0; i < N; ++i) {
         // per-pass opaque copy of the thread id: the staging addresses of this pass's layers are re-derived here
@@ -278,6 +289,12 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
         { const float ax_ = spx - hx, ay_ = spy - hy; feat[11] = sqrt_f32(ax_ * ax_ + ay_ * ay_); }   // == sqrtf (fast_f32.hpp)
         feat[12] = srad + hrad;
         feat[13] = feat[14] = feat[15] = 0.0f;
+        {
+            float z = 0.0f;                     // +-0 while every feature is finite, NaN otherwise (0 * inf, 0 * NaN)
+#pragma unroll
+            for (int k = 0; k < 13; ++k) z = z + feat[k] * 0.0f;
+            poisoned = poisoned || (i < ne && z != z);
+        }
         f32x4 x[T13];
 #pragma unroll
         for (int r = 0; r < 4; ++r)      // register r of lane group q carries feature 4q + r
@@ -453,12 +470,27 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
     // ---- tail: mlp3 on [self(6), pooled(50)] ----
     f32x4 jin[T56];
     {
-        // weights = exp(s) (s != 0) / sum (sarl.py:52-53): normalise the accumulated hidden activations, then mlp2.2
-        const float inv_d = 1.0f / denom;            // 0 / 0 stays NaN (0 * inf), as in the reference's softmax
+        // weights = exp(s) (s != 0) / sum (sarl.py:52-53): normalise the accumulated hidden activations, then mlp2.2.
+        // One reciprocal and 28 multiplies, as for the mean -- but 1 / denom overflows below 2^-128 where the reference,
+        // which divides, is finite (scores near -92: each exp ~1e-40), so a tiny sum is first scaled, with the
+        // accumulators, by 2^64: exact, subnormals included (a branch no ordinary pair takes; no barrier inside).
+        float dsum = denom;                     // (the attention output below divides by the sum itself)
+        if (dsum < 0x1p-100f) {
+            dsum *= 0x1p+64f;
+#pragma unroll
+            for (int t = 0; t < T100; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) racc[t][r] *= 0x1p+64f;
+        }
+        const float inv_d = 1.0f / dsum;
 #pragma unroll
         for (int t = 0; t < T100; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) racc[t][r] = racc[t][r] * inv_d;
+        // The softmax is the reference's, un-stabilised, and NaN where the reference's is: every present score exactly 0
+        // or every exp underflowing is 0 / 0 (here 0 * inf), an exp that overflows is inf / inf (here inf * 0, or a NaN
+        // accumulator).  Either makes EVERY accumulator of the pair NaN, so one is tested.
+        poisoned = poisoned || racc[0][0] != racc[0][0];
         f32x4 pooled[T50];
         if constexpr (USE_X3) {
             X3 rp3[B100];
@@ -503,10 +535,11 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
     }
     if (valid && q == 0) {
         // value = reward + gamma^(dt * v_pref) * V   (multi_human_rl.py:52, Python float arithmetic)
-        p.values[pair] = reward + p.gamma_pow * (double)vo[0][0];
+        p.values[pair] = poisoned ? __builtin_nan("") : reward + p.gamma_pow * (double)vo[0][0];
     }
     if (p.attention && valid && q == 0) {
-        for (int i = 0; i < N; ++i) p.attention[pair * N + i] /= denom;
+        // absent slots hold exactly 0 whatever the sum is; present ones are NaN where the reference's weights are
+        for (int i = 0; i < ne; ++i) p.attention[pair * N + i] = poisoned ? __builtin_nanf("") : p.attention[pair * N + i] / denom;
     }
     SARL_PHASE(14);                     // mlp3, value store
   }

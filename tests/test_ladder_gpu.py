@@ -274,15 +274,19 @@ def _sarl(seed=0, zero=True):
     from tests.test_sarl_gpu import _policy
     pol = _policy(seed=seed)
     if zero:
+        # V == 0.0 exactly: every parameter zero except attention.4.bias = 1, so that every score is 1, the attention
+        # weights are uniform and mlp2 / mlp3 give 0.  (With that bias zero too every score is exactly 0 and the masked
+        # softmax of sarl.py:52-53 is 0 / 0: NaN in the reference and in the kernel.)
         with torch.no_grad():
             for p_ in pol.model.parameters():
                 p_.zero_()
+            pol.model.attention[4].bias.fill_(1.0)
     pol.build_action_space(1.0)
     return pol
 
 
 def test_sarl_lookahead_rewards_on_ladder_batches():
-    """mcn_sarl_predict with a zeroed network (V == 0): values are exactly the look-ahead reward, bitwise against
+    """mcn_sarl_predict with a network whose V is exactly 0 (_sarl): values are exactly the look-ahead reward, bitwise against
     cport.lookahead_reward on the look-ahead blocks, N = 1..10, 13 and 32; the argmax goes on at |robot - goal| == rr and
     returns -1 inside."""
     pol = _sarl()

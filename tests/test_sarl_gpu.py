@@ -184,7 +184,9 @@ def test_epsilon_greedy_in_train_phase():
 
 
 def test_rewards_are_float64_exact():
-    """With a zeroed network V == 0, so values are exactly MultiHumanRL.compute_reward (float64)."""
+    """With a network whose V is exactly 0, values are exactly MultiHumanRL.compute_reward (float64).  Every parameter
+    is zero except attention.4.bias = 1: uniform attention weights, mlp2 and mlp3 zero.  (All zero would make every score
+    exactly 0, which the masked softmax of sarl.py:52-53 turns into 0 / 0 = NaN, in the reference and in the kernel.)"""
     import torch
     from oracle import cport
     rng = np.random.RandomState(9)
@@ -193,6 +195,7 @@ def test_rewards_are_float64_exact():
     with torch.no_grad():
         for p_ in pol.model.parameters():
             p_.zero_()
+        pol.model.attention[4].bias.fill_(1.0)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, crowded_frac=0.6)
     H.upload(env, st)
