@@ -22,8 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mcn.h"
-#include "mfma_chain.hpp"
-#include "fast_f32.hpp"
+#include "lookahead_common.hpp"
 
 namespace mcn {
 
@@ -43,19 +42,9 @@ constexpr int kCadrlOff[5] = {0, 10 * 1 * 64, 10 * 64 + 7 * 10 * 64, 10 * 64 + 7
 
 struct LookParams {
     const float4 *w[5], *b[5];     // LSTM: gate, mlp.0, mlp.2, mlp.4, mlp.6; CADRL: value_network.{0,2,4,6}
-    const double *rpos, *rvel, *rgoal, *rrad, *rvpref, *rtheta;
-    const double *hpos, *hvel, *hrad;
-    const int32_t *hcount;
-    const double *next_hpos, *next_hvel, *reward_in;
-    const double *actions;
-    double *values;                // [E*A]
+    PairParams c;
     int32_t *order;                // [E*N] or NULL (LSTM-RL)
-    long ngroups;
-    int E, N, A, kinematics;
-    double dt, gamma_pow;
 };
-
-__device__ __forceinline__ double norm2d(double x0, double x1) { return sqrt(fma(x1, x1, x0 * x0)); }
 
 // sgan_step.hip's forms (~2e-7 absolute error)
 __device__ __forceinline__ float sigmoid_f(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
@@ -102,61 +91,6 @@ struct HumanOrder {
     }
 };
 
-// Two output tiles n0, n1 of a layer: acc = bias + sum_t in[t] x W[n][t]; FIRST / LAST = k-steps carried by input
-// tile 0 / KT-1 (ragged tiles are packed "q first", see mcn_pack_linear).  w may point to LDS or global memory.
-template <int KT, int FIRST, int LAST, bool TWO>
-__device__ __forceinline__ void tile2(const f32x4 (&in)[KT], const float4 *w, const float4 *__restrict__ bf, int n0,
-                                      int n1, int lane, f32x4 &a0, f32x4 &a1)
-{
-    { const float4 b = bf[n0 * 64 + lane]; a0 = (f32x4){b.x, b.y, b.z, b.w}; }
-    if (TWO) { const float4 b = bf[n1 * 64 + lane]; a1 = (f32x4){b.x, b.y, b.z, b.w}; }
-#pragma unroll
-    for (int t = 0; t < KT; ++t) {
-        const float4 w0 = w[(n0 * KT + t) * 64 + lane];
-        float4 w1 = make_float4(0, 0, 0, 0);
-        if (TWO) w1 = w[(n1 * KT + t) * 64 + lane];
-        int steps = 4;
-        if (t == 0 && FIRST < steps) steps = FIRST;
-        if (t == KT - 1 && LAST < steps) steps = LAST;
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, in[t][0], a0, 0, 0, 0);
-        if (TWO) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, in[t][0], a1, 0, 0, 0);
-        if (steps > 1) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, in[t][1], a0, 0, 0, 0);
-            if (TWO) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, in[t][1], a1, 0, 0, 0);
-        }
-        if (steps > 2) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, in[t][2], a0, 0, 0, 0);
-            if (TWO) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, in[t][2], a1, 0, 0, 0);
-        }
-        if (steps > 3) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, in[t][3], a0, 0, 0, 0);
-            if (TWO) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, in[t][3], a1, 0, 0, 0);
-        }
-    }
-}
-
-// ReLU that keeps NaN, as torch.relu does (mfma_chain.hpp's relu_f32 maps a NaN with the sign bit set to 0): CADRL's
-// min over the humans must see a NaN network output to propagate it (cadrl.py:164)
-__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.0f ? 0.0f : x; }
-
-template <int KT, int NT, bool RELU, int FIRST, int LAST>
-__device__ __forceinline__ void layer(const f32x4 (&in)[KT], f32x4 (&out)[NT], const float4 *w,
-                                      const float4 *__restrict__ bf, int lane)
-{
-#pragma unroll
-    for (int n = 0; n < NT; n += 2) {
-        f32x4 a0, a1 = {0, 0, 0, 0};
-        if (n + 1 < NT) tile2<KT, FIRST, LAST, true>(in, w, bf, n, n + 1, lane, a0, a1);
-        else tile2<KT, FIRST, LAST, false>(in, w, bf, n, n, lane, a0, a1);
-        if (RELU) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { a0[r] = relu_keep_nan(a0[r]); a1[r] = relu_keep_nan(a1[r]); }
-        }
-        out[n] = a0;
-        if (n + 1 < NT) out[n + 1] = a1;
-    }
-}
-
 template <int BODY, int MAXN>
 __global__ __launch_bounds__(kWaves * 64, 1) void lookahead_kernel(const LookParams p)
 {
@@ -171,11 +105,12 @@ __global__ __launch_bounds__(kWaves * 64, 1) void lookahead_kernel(const LookPar
     }
     __syncthreads();
 
-    const long npairs = (long)p.E * p.A;
-    const int N = p.N;
+    const PairParams &pp = p.c;
+    const long npairs = (long)pp.E * pp.A;
+    const int N = pp.N;
     // no barrier below: a wavefront may leave as soon as its tiles are done
 #pragma unroll 1
-    for (long grp = blockIdx.x; grp < p.ngroups; grp += gridDim.x) {
+    for (long grp = blockIdx.x; grp < pp.ngroups; grp += gridDim.x) {
         // the thread id is made opaque once per pass (as in sarl_value.hip): the per-lane addresses of every weight
         // fragment would otherwise be hoisted out of the loop as loop invariants, live -- and spill -- across it
         int tid = threadIdx.x;
@@ -187,75 +122,20 @@ __global__ __launch_bounds__(kWaves * 64, 1) void lookahead_kernel(const LookPar
         long pair = pair0 + j;
         const bool valid = pair < npairs;
         if (!valid) pair = npairs - 1;
-        const int e = (int)(pair / p.A), a = (int)(pair - (long)e * p.A);
-        int ne = N;
-        if (p.hcount) { ne = p.hcount[e]; ne = ne < 1 ? 1 : (ne > N ? N : ne); }
-        const double dt = p.dt;
-
-        // ---- robot after the candidate action (cadrl.py:104-129), float64; as sarl_value.hip ----
-        const double2 rp = reinterpret_cast<const double2 *>(p.rpos)[e];
-        const double2 rg = reinterpret_cast<const double2 *>(p.rgoal)[e];
-        const double2 ra = make_double2(p.rrad[e], p.rvpref[e]);
-        const double2 ac = reinterpret_cast<const double2 *>(p.actions)[a];
-        double npx, npy, nvx, nvy, nth;
-        if (p.kinematics == MCN_KIN_UNICYCLE) {
-            nth = p.rtheta[e] + ac.y;
-            nvx = ac.x * cos(nth); nvy = ac.x * sin(nth);
-            npx = rp.x + nvx * dt; npy = rp.y + nvy * dt;
-        } else {
-            nth = p.rtheta ? p.rtheta[e] : 0.0;
-            nvx = ac.x; nvy = ac.y;
-            npx = rp.x + ac.x * dt; npy = rp.y + ac.y * dt;
-        }
-        // ---- self part of the rotated state (cadrl.py:223-240), float32 ----
-        const float spx = (float)npx, spy = (float)npy, svx = (float)nvx, svy = (float)nvy;
-        const float srad = (float)ra.x, sgx = (float)rg.x, sgy = (float)rg.y, svpref = (float)ra.y;
-        const float gdx = sgx - spx, gdy = sgy - spy;
-        const float dg = sqrtf(gdx * gdx + gdy * gdy);
-        const float cr = dg > 0.0f ? gdx / dg : 1.0f;
-        const float sr = dg > 0.0f ? gdy / dg : 0.0f;
-        const float f_theta = (p.kinematics == MCN_KIN_UNICYCLE) ? ((float)nth - atan2f(gdy, gdx)) : 0.0f;
-        const float f_vx = svx * cr + svy * sr;
-        const float f_vy = svy * cr - svx * sr;
-
-        // the 13 features of human `hi` after propagation, as the B operand tile x (sarl_value.hip: pass 1)
+        const int e = (int)(pair / pp.A), a = (int)(pair - (long)e * pp.A);
+        const int ne = humans_seen(pp.hcount, e, N);
+        const double2 rp = reinterpret_cast<const double2 *>(pp.rpos)[e];
+        const double2 rg = reinterpret_cast<const double2 *>(pp.rgoal)[e];
+        const double2 ra = make_double2(pp.rrad[e], pp.rvpref[e]);               // radius, v_pref
+        const RobotNext rn = robot_after(pp, e, a, rp);
+        const SelfFeatures sf = self_features(rn, rg, ra, pp.kinematics);
         double dmin = INFINITY;
-        auto human_tile = [&](int hi, bool seen, f32x4 &x) {
-            const long ha = (long)e * N + hi;
-            const double2 hp = reinterpret_cast<const double2 *>(p.hpos)[ha];
-            const double2 hv = reinterpret_cast<const double2 *>(p.hvel)[ha];
-            const double hr = p.hrad[ha];
-            double qx = hp.x + hv.x * dt, qy = hp.y + hv.y * dt;
-            double nhvx = hv.x, nhvy = hv.y;
-            if (p.next_hpos) {
-                const double2 np_ = reinterpret_cast<const double2 *>(p.next_hpos)[ha];
-                const double2 nv_ = reinterpret_cast<const double2 *>(p.next_hvel)[ha];
-                qx = np_.x; qy = np_.y; nhvx = nv_.x; nhvy = nv_.y;
-            }
-            const double d = norm2d(npx - qx, npy - qy) - ra.x - hr;        // multi_human_rl.py:70
-            dmin = seen ? fmin(dmin, d) : dmin;
-            const float hx = (float)qx, hy = (float)qy, hvx = (float)nhvx, hvy = (float)nhvy, hrad = (float)hr;
-            const float ox = hx - spx, oy = hy - spy;
-            float feat[16];
-            feat[0] = dg; feat[1] = svpref; feat[2] = f_theta; feat[3] = srad; feat[4] = f_vx; feat[5] = f_vy;
-            feat[6] = ox * cr + oy * sr;
-            feat[7] = oy * cr - ox * sr;
-            feat[8] = hvx * cr + hvy * sr;
-            feat[9] = hvy * cr - hvx * sr;
-            feat[10] = hrad;
-            { const float ax_ = spx - hx, ay_ = spy - hy; feat[11] = sqrt_f32(ax_ * ax_ + ay_ * ay_); }
-            feat[12] = srad + hrad;
-            feat[13] = feat[14] = feat[15] = 0.0f;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = q == 0 ? feat[r] : (q == 1 ? feat[4 + r] : (q == 2 ? feat[8 + r] : feat[12 + r]));
-        };
-
         float V;
         if constexpr (BODY == kBodyLstm) {
             // ---- LSTM over the humans in sorted order (identity with the env's next states, multi_human_rl.py:37-38) ----
             HumanOrder<MAXN> ord;
-            const bool sort = p.next_hpos == nullptr;
-            if (sort) ord.init(p.hpos, (long)e * N, rp.x, rp.y, ne);
+            const bool sort = pp.next_hpos == nullptr;
+            if (sort) ord.init(pp.hpos, (long)e * N, rp.x, rp.y, ne);
             f32x4 in[5];                               // [x | h0 h1 h2 h3]
             f32x4 c[4];
 #pragma unroll
@@ -266,13 +146,13 @@ __global__ __launch_bounds__(kWaves * 64, 1) void lookahead_kernel(const LookPar
                 const bool seen = s < ne;
                 const int hi = (seen && sort) ? ord.next(ne) : s;
                 if (p.order && valid && q == 0 && a == 0) p.order[(long)e * N + s] = hi;
-                human_tile(hi, seen, in[0]);
+                in[0] = human_tile(pp, (long)e * N + hi, rn, ra.x, sf, q, seen, dmin).x;
                 f32x4 hn[4];
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
                     f32x4 gi, gf, gg, go;
-                    tile2<5, 4, 1, true>(in, s_w, p.b[0], t, 4 + t, lane_s, gi, gf);
-                    tile2<5, 4, 1, true>(in, s_w, p.b[0], 8 + t, 12 + t, lane_s, gg, go);
+                    dense_tiles<5, kBiasFrag, 4, 1>(in, s_w, p.b[0], t, 4 + t, true, lane_s, gi, gf);
+                    dense_tiles<5, kBiasFrag, 4, 1>(in, s_w, p.b[0], 8 + t, 12 + t, true, lane_s, gg, go);
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const float cn = sigmoid_f(gf[r]) * c[t][r] + sigmoid_f(gi[r]) * tanh_f(gg[r]);
@@ -285,13 +165,12 @@ __global__ __launch_bounds__(kWaves * 64, 1) void lookahead_kernel(const LookPar
                 for (int t = 0; t < 4; ++t) in[1 + t] = hn[t];
             }
             // ---- tail: mlp on [self(6) | h(50)] (lstm_rl.py:30-32) ----
-            in[0] = (f32x4){q == 0 ? dg : (q == 1 ? svpref : (q == 2 ? f_theta : srad)),
-                            q == 0 ? f_vx : (q == 1 ? f_vy : 0.0f), 0.0f, 0.0f};   // self features, "q first"
+            in[0] = self_tile(sf, q);
             f32x4 v1[10], v2[7], v3[7], vo[1];
-            layer<5, 10, true, 2, 1>(in, v1, p.w[1], p.b[1], lane);
-            layer<10, 7, true, 4, 2>(v1, v2, p.w[2], p.b[2], lane);
-            layer<7, 7, true, 4, 1>(v2, v3, p.w[3], p.b[3], lane);
-            layer<7, 1, false, 4, 1>(v3, vo, p.w[4], p.b[4], lane);
+            dense<5, 10, kReluKeepNan, kBiasFrag, 2, 1>(in, v1, p.w[1], p.b[1], lane);
+            dense<10, 7, kReluKeepNan, kBiasFrag, 4, 2>(v1, v2, p.w[2], p.b[2], lane);
+            dense<7, 7, kReluKeepNan, kBiasFrag, 4, 1>(v2, v3, p.w[3], p.b[3], lane);
+            dense<7, 1, kLinear, kBiasFrag, 4, 1>(v3, vo, p.w[4], p.b[4], lane);
             V = vo[0][0];
         } else {
             // ---- CADRL: value network per (robot, human) pair, min over the humans (cadrl.py:162-165) ----
@@ -301,25 +180,19 @@ __global__ __launch_bounds__(kWaves * 64, 1) void lookahead_kernel(const LookPar
                 asm volatile("" : "+v"(lane_i));
                 const bool seen = i < ne;
                 f32x4 x[1];
-                human_tile(i, seen, x[0]);
+                x[0] = human_tile(pp, (long)e * N + i, rn, ra.x, sf, q, seen, dmin).x;
                 f32x4 v1[10], v2[7], v3[7], vo[1];
-                layer<1, 10, true, 4, 4>(x, v1, s_w + kCadrlOff[0], p.b[0], lane_i);
-                layer<10, 7, true, 4, 2>(v1, v2, s_w + kCadrlOff[1], p.b[1], lane_i);
-                layer<7, 7, true, 4, 1>(v2, v3, s_w + kCadrlOff[2], p.b[2], lane_i);
-                layer<7, 1, false, 4, 1>(v3, vo, s_w + kCadrlOff[3], p.b[3], lane_i);
+                dense<1, 10, kReluKeepNan, kBiasFrag, 4, 4>(x, v1, s_w + kCadrlOff[0], p.b[0], lane_i);
+                dense<10, 7, kReluKeepNan, kBiasFrag, 4, 2>(v1, v2, s_w + kCadrlOff[1], p.b[1], lane_i);
+                dense<7, 7, kReluKeepNan, kBiasFrag, 4, 1>(v2, v3, s_w + kCadrlOff[2], p.b[2], lane_i);
+                dense<7, 1, kLinear, kBiasFrag, 4, 1>(v3, vo, s_w + kCadrlOff[3], p.b[3], lane_i);
                 const float v = vo[0][0];
                 // torch.min: the first NaN wins and stays
                 if (seen && (v < V || v != v) && V == V) V = v;
             }
         }
-        const bool reach = norm2d(npx - rg.x, npy - rg.y) < ra.x;
-        double reward;
-        if (dmin < 0) reward = -0.25;
-        else if (reach) reward = 1;
-        else if (dmin < 0.2) reward = (dmin - 0.2) * 0.5 * dt;
-        else reward = 0;
-        if (p.reward_in) reward = p.reward_in[pair];
-        if (valid && q == 0) p.values[pair] = reward + p.gamma_pow * (double)V;
+        const double reward = pair_reward(pp, rn, rg, ra.x, dmin, pair);
+        if (valid && q == 0) pp.values[pair] = pair_value(pp, reward, V);
     }
 }
 
@@ -331,8 +204,7 @@ __global__ __launch_bounds__(64) void lstm_rl_order_kernel(const double *hpos, c
 {
     const int e = blockIdx.x * 64 + threadIdx.x;
     if (e >= E) return;
-    int ne = N;
-    if (hcount) { ne = hcount[e]; ne = ne < 1 ? 1 : (ne > N ? N : ne); }
+    const int ne = humans_seen(hcount, e, N);
     const double2 rp = reinterpret_cast<const double2 *>(rpos)[e];
     HumanOrder<MAXN> ord;
     ord.init(hpos, (long)e * N, rp.x, rp.y, ne);
@@ -342,11 +214,14 @@ __global__ __launch_bounds__(64) void lstm_rl_order_kernel(const double *hpos, c
 template <int BODY>
 void launch_body(const LookParams &p, int blocks, hipStream_t stream)
 {
-    if (BODY == kBodyCadrl || p.next_hpos) {       // no sort: the order state is not used
+    // MAXN sizes the sort state: 1 where there is no sort (CADRL; the env's next states keep the env's order)
+    if constexpr (BODY == kBodyCadrl) {
         hipLaunchKernelGGL((lookahead_kernel<BODY, 1>), dim3(blocks), dim3(kWaves * 64), 0, stream, p);
-    } else if (p.N <= 8) {
+    } else if (p.c.next_hpos) {
+        hipLaunchKernelGGL((lookahead_kernel<BODY, 1>), dim3(blocks), dim3(kWaves * 64), 0, stream, p);
+    } else if (p.c.N <= 8) {
         hipLaunchKernelGGL((lookahead_kernel<BODY, 8>), dim3(blocks), dim3(kWaves * 64), 0, stream, p);
-    } else if (p.N <= 16) {
+    } else if (p.c.N <= 16) {
         hipLaunchKernelGGL((lookahead_kernel<BODY, 16>), dim3(blocks), dim3(kWaves * 64), 0, stream, p);
     } else {
         hipLaunchKernelGGL((lookahead_kernel<BODY, 32>), dim3(blocks), dim3(kWaves * 64), 0, stream, p);
@@ -363,18 +238,13 @@ int launch_lookahead(int body, const void *const *frags, int nlayers, const mcn_
         p.w[l] = l < nlayers ? reinterpret_cast<const float4 *>(frags[2 * l]) : nullptr;
         p.b[l] = l < nlayers ? reinterpret_cast<const float4 *>(frags[2 * l + 1]) : nullptr;
     }
-    p.rpos = st->rpos; p.rvel = st->rvel; p.rgoal = st->rgoal; p.rrad = st->rrad; p.rvpref = st->rvpref; p.rtheta = st->rtheta;
-    p.hpos = st->hpos; p.hvel = st->hvel; p.hrad = st->hrad; p.hcount = st->hcount;
-    p.next_hpos = next_hpos; p.next_hvel = next_hvel; p.reward_in = reward_in;
-    p.actions = actions; p.values = values; p.order = order;
-    p.E = E; p.N = N; p.A = A; p.kinematics = kinematics; p.dt = dt; p.gamma_pow = gamma_pow;
-    const long waves = ((long)E * A + 15) / 16;
-    p.ngroups = (waves + kWaves - 1) / kWaves;
-    const int blocks = (int)(p.ngroups < kMaxBlocks ? p.ngroups : kMaxBlocks);
+    p.c = pair_params(st, actions, A, dt, gamma_pow, kinematics, values, next_hpos, next_hvel, reward_in, E, N, kWaves);
+    p.order = order;
+    const int blocks = (int)(p.c.ngroups < kMaxBlocks ? p.c.ngroups : kMaxBlocks);
     if (body == kBodyLstm) launch_body<kBodyLstm>(p, blocks, stream);
     else launch_body<kBodyCadrl>(p, blocks, stream);
     if (hipGetLastError() != hipSuccess) return MCN_ELAUNCH;
-    if (best) return launch_sarl_argmax(values, p.rpos, p.rgoal, p.rrad, E, A, best, best_val, actions, action_out,
+    if (best) return launch_sarl_argmax(values, p.c.rpos, p.c.rgoal, p.c.rrad, E, A, best, best_val, actions, action_out,
                                         epsilon, seed, stream);
     return MCN_OK;
 }

@@ -351,24 +351,36 @@ int64_t mcn_sarl_workspace_bytes(int32_t E, int32_t N, int32_t A)
     return (int64_t)mcn::sarl_workspace_float4s(E, N, A) * 16;
 }
 
+// What every look-ahead entry point checks alike (SARL, LSTM-RL, CADRL); each adds its own on top: which outputs may
+// be NULL, whether `kinematics` is range-checked, how `rewards` pairs with the next states.
+static bool lookahead_common_ok(const void *net, size_t net_bytes, const mcn_env_state *st, const double *actions,
+                                int32_t A, double time_step, int32_t kinematics, const double *values,
+                                const double *next_hpos, const double *next_hvel, double epsilon, int32_t E, int32_t N)
+{
+    if (!net || !st || !actions || !values) return false;
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return false;
+    if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS || A <= 0) return false;
+    if (!st->hpos || !st->hvel || !st->hrad || !st->rpos || !st->rgoal || !st->rrad || !st->rvpref) return false;
+    if (kinematics == MCN_KIN_UNICYCLE && !st->rtheta) return false;
+    if ((next_hpos == nullptr) != (next_hvel == nullptr)) return false;
+    const float *const *fp = reinterpret_cast<const float *const *>(net);
+    for (size_t k = 0; k < net_bytes / sizeof(float *); ++k)
+        if (!fp[k]) return false;
+    return time_step > 0;
+}
+
 static int sarl_lookahead_impl(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
                                double time_step, double gamma_pow, int32_t kinematics, void *workspace,
                                double *values, int32_t *best, double *best_val, float *attention,
                                const double *next_hpos, const double *next_hvel, const double *rewards,
                                double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream)
 {
-    if (!net || !st || !actions || !workspace || !values) return MCN_EINVAL;
-    if (action_out && !best) return MCN_EINVAL;
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return MCN_EINVAL;
-    if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS || A <= 0) return MCN_EINVAL;
-    if (best && !best_val) return MCN_EINVAL;
-    if (!st->hpos || !st->hvel || !st->hrad || !st->rpos || !st->rgoal || !st->rrad || !st->rvpref) return MCN_EINVAL;
-    if (kinematics == MCN_KIN_UNICYCLE && !st->rtheta) return MCN_EINVAL;
-    if ((next_hpos == nullptr) != (next_hvel == nullptr)) return MCN_EINVAL;
-    const float *const *fp = reinterpret_cast<const float *const *>(net);
-    for (size_t k = 0; k < sizeof(mcn_sarl_net) / sizeof(float *); ++k)
-        if (!fp[k]) return MCN_EINVAL;
-    if (!(time_step > 0)) return MCN_EINVAL;
+    if (!lookahead_common_ok(net, sizeof(*net), st, actions, A, time_step, kinematics, values, next_hpos, next_hvel,
+                             epsilon, E, N))
+        return MCN_EINVAL;
+    if (!workspace) return MCN_EINVAL;
+    if (action_out && !best) return MCN_EINVAL;         // best may be NULL (values only) ...
+    if (best && !best_val) return MCN_EINVAL;           // ... but not without best_val
     return mcn::launch_sarl_c(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best,
                               best_val, attention, next_hpos, next_hvel, rewards, action_out, epsilon,
                               (unsigned long long)seed, E, N, (hipStream_t)stream);
@@ -406,23 +418,17 @@ int mcn_sarl_predict(const mcn_sarl_net *net, const mcn_env_state *st, const dou
                                attention, next_hpos, next_hvel, rewards, action_out, epsilon, seed, E, N, stream);
 }
 
-// shared validation of mcn_lstm_rl_predict / mcn_cadrl_predict (as sarl_lookahead_impl + mcn_sarl_predict)
+// validation of mcn_lstm_rl_predict / mcn_cadrl_predict: the common part, and every output required
 static int lookahead_args_ok(const void *net, size_t net_bytes, const mcn_env_state *st, const double *actions, int32_t A,
                              double time_step, int32_t kinematics, const double *values, const int32_t *best,
                              const double *best_val, const double *next_hpos, const double *next_hvel,
                              const double *rewards, const double *action_out, double epsilon, int32_t E, int32_t N)
 {
-    if (!net || !st || !actions || !values || !best || !best_val || !action_out) return 0;
-    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return 0;
-    if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS || A <= 0) return 0;
-    if (!st->hpos || !st->hvel || !st->hrad || !st->rpos || !st->rgoal || !st->rrad || !st->rvpref) return 0;
+    if (!lookahead_common_ok(net, net_bytes, st, actions, A, time_step, kinematics, values, next_hpos, next_hvel, epsilon, E, N))
+        return 0;
+    if (!best || !best_val || !action_out) return 0;
     if (kinematics != MCN_KIN_HOLONOMIC && kinematics != MCN_KIN_UNICYCLE) return 0;
-    if (kinematics == MCN_KIN_UNICYCLE && !st->rtheta) return 0;
-    if ((next_hpos == nullptr) != (next_hvel == nullptr) || (next_hpos == nullptr) != (rewards == nullptr)) return 0;
-    const float *const *fp = reinterpret_cast<const float *const *>(net);
-    for (size_t k = 0; k < net_bytes / sizeof(float *); ++k)
-        if (!fp[k]) return 0;
-    return time_step > 0;
+    return (next_hpos == nullptr) == (rewards == nullptr);
 }
 
 int mcn_lstm_rl_predict(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int32_t A,

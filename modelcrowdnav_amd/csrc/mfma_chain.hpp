@@ -24,90 +24,76 @@ __device__ __forceinline__ float relu_f32(float x)
     return __builtin_bit_cast(float, b > 0 ? b : 0);
 }
 
-// out[n] = act( bias[n] (+ init) + sum_t in[t] x W[n][t] ), two accumulators in flight per step so
-// back-to-back dependent MFMAs (40-cycle latency vs 32-cycle issue) never stall the pipe.
-// FIRST: k-steps of input tile 0 that carry anything (a 2-vector packed into slots 0 and 4 needs one).
-template <int KT, int NT, bool RELU, int FIRST = 4>
-__device__ __forceinline__ void dense(const f32x4 (&in)[KT], f32x4 (&out)[NT], const float4 *__restrict__ wf,
-                                      const float4 *__restrict__ bf, int lane)
+// ReLU that keeps NaN, as torch.relu does (relu_f32 maps a NaN with the sign bit set to 0): CADRL's min over the humans
+// must see a NaN network output to propagate it (cadrl.py:164)
+__device__ __forceinline__ float relu_keep_nan(float x) { return x < 0.0f ? 0.0f : x; }
+enum Act { kLinear, kRelu, kReluKeepNan };
+template <Act ACT>
+__device__ __forceinline__ void activate(f32x4 &a0, f32x4 &a1)      // (a tile pair's accumulators, register by register)
 {
+    if (ACT == kLinear) return;
 #pragma unroll
-    for (int n = 0; n < NT; n += 2) {
-        const bool two = (n + 1 < NT);
-        f32x4 a0, a1 = {0, 0, 0, 0};
-        { const float4 b = bf[n * 64 + lane]; a0 = (f32x4){b.x, b.y, b.z, b.w}; }
-        if (two) { const float4 b = bf[(n + 1) * 64 + lane]; a1 = (f32x4){b.x, b.y, b.z, b.w}; }
-#pragma unroll
-        for (int t = 0; t < KT; ++t) {
-            const float4 w0 = wf[(n * KT + t) * 64 + lane];
-            float4 w1 = make_float4(0, 0, 0, 0);
-            if (two) w1 = wf[((n + 1) * KT + t) * 64 + lane];
-            const int steps = t == 0 ? FIRST : 4;
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, in[t][0], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, in[t][0], a1, 0, 0, 0);
-            if (steps > 1) {
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, in[t][1], a0, 0, 0, 0);
-                if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, in[t][1], a1, 0, 0, 0);
-            }
-            if (steps > 2) {
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, in[t][2], a0, 0, 0, 0);
-                if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, in[t][2], a1, 0, 0, 0);
-            }
-            if (steps > 3) {
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, in[t][3], a0, 0, 0, 0);
-                if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, in[t][3], a1, 0, 0, 0);
-            }
-        }
-        if (RELU) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { a0[r] = relu_f32(a0[r]); a1[r] = relu_f32(a1[r]); }
-        }
-        out[n] = a0;
-        if (two) out[n + 1] = a1;
+    for (int r = 0; r < 4; ++r) {
+        a0[r] = ACT == kRelu ? relu_f32(a0[r]) : relu_keep_nan(a0[r]);
+        a1[r] = ACT == kRelu ? relu_f32(a1[r]) : relu_keep_nan(a1[r]);
     }
 }
 
-// Same layer with its fragments RESIDENT in LDS (small networks whose weights fit next to the workgroup for the whole
-// kernel): w = [NT][KT][64] float4 as packed by mcn_pack_linear, bq = biases by (output tile, lane group): the float4
-// of features 16n + 4q .. + 3 at bq[4n + q] (column 0 of the packed bias fragment).
-template <int KT, int NT, bool RELU, int FIRST = 4>
-__device__ __forceinline__ void dense_lds(const f32x4 (&in)[KT], f32x4 (&out)[NT], const float4 *w, const float4 *bq,
-                                          int lane)
+// The MFMA ladder: k-steps from .. to - 1 of one input tile x into a0 and, when `two`, a1 -- the accumulators of two
+// output tiles alternate, so back-to-back dependent MFMAs (40-cycle latency vs 32-cycle issue) never stall the pipe.
+// w0 / w1: the tiles' A fragments, one k-step per component.  from, to and two fold at every call site (the tile loops
+// around the calls are fully unrolled); skipped steps would multiply the zeros of a ragged tile.
+__device__ __forceinline__ void mfma_ksteps(int from, int to, bool two, const float4 &w0, const float4 &w1, const f32x4 &x,
+                                            f32x4 &a0, f32x4 &a1)
 {
-    const int q = lane >> 4;
+#define MCN_KSTEP(k_, c_)                                                                                     \
+    if (from <= k_ && k_ < to) {                                                                              \
+        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.c_, x[k_], a0, 0, 0, 0);                                 \
+        if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.c_, x[k_], a1, 0, 0, 0);                        \
+    }
+    MCN_KSTEP(0, x) MCN_KSTEP(1, y) MCN_KSTEP(2, z) MCN_KSTEP(3, w)
+#undef MCN_KSTEP
+}
+
+// Where a layer's accumulators start: the packed bias fragment of mcn_pack_linear (bf[n][64 lanes], any memory), or, for
+// a layer RESIDENT in LDS, the biases by (output tile, lane group) -- the float4 of features 16n + 4q .. + 3 at
+// bq[4n + q] (column 0 of the packed fragment, see lds_fill_layer).  The value is the stride between output tiles.
+// (A plain index: with the fetch passed in as a functor or lambda world_mlp.hip's kernels came out 8 registers larger.)
+enum BiasForm { kBiasFrag = 64, kBiasQuarter = 4 };
+
+// Output tiles n0 and (`two`, folding) n1 of a layer: acc = bias + sum_t in[t] x W[n][t], w = [NT][KT][64] float4 as
+// packed by mcn_pack_linear, in global memory or LDS.  FIRST / LAST: k-steps carried by input tile 0 / KT - 1 (ragged
+// tiles are packed "q first": a 2-vector in slots 0 and 4 needs one).
+template <int KT, BiasForm BIAS, int FIRST, int LAST>
+__device__ __forceinline__ void dense_tiles(const f32x4 (&in)[KT], const float4 *w, const float4 *__restrict__ b, int n0, int n1,
+                                            bool two, int lane, f32x4 &a0, f32x4 &a1)
+{
+    const int bi = BIAS == kBiasFrag ? lane : lane >> 4;
+    { const float4 v = b[n0 * BIAS + bi]; a0 = (f32x4){v.x, v.y, v.z, v.w}; }
+    if (two) { const float4 v = b[n1 * BIAS + bi]; a1 = (f32x4){v.x, v.y, v.z, v.w}; }
+#pragma unroll
+    for (int t = 0; t < KT; ++t) {
+        const float4 w0 = w[(n0 * KT + t) * 64 + lane];
+        float4 w1 = make_float4(0, 0, 0, 0);
+        if (two) w1 = w[(n1 * KT + t) * 64 + lane];
+        int steps = 4;
+        if (t == 0 && FIRST < steps) steps = FIRST;
+        if (t == KT - 1 && LAST < steps) steps = LAST;
+        mfma_ksteps(0, steps, two, w0, w1, in[t], a0, a1);
+    }
+}
+
+// out[n] = act( bias[n] + sum_t in[t] x W[n][t] ), tile pair by tile pair
+template <int KT, int NT, Act ACT, BiasForm BIAS, int FIRST = 4, int LAST = 4>
+__device__ __forceinline__ void dense(const f32x4 (&in)[KT], f32x4 (&out)[NT], const float4 *w, const float4 *__restrict__ b, int lane)
+{
 #pragma unroll
     for (int n = 0; n < NT; n += 2) {
-        const bool two = (n + 1 < NT);
         f32x4 a0, a1 = {0, 0, 0, 0};
-        { const float4 b = bq[4 * n + q]; a0 = (f32x4){b.x, b.y, b.z, b.w}; }
-        if (two) { const float4 b = bq[4 * n + 4 + q]; a1 = (f32x4){b.x, b.y, b.z, b.w}; }
-#pragma unroll
-        for (int t = 0; t < KT; ++t) {
-            const float4 w0 = w[(n * KT + t) * 64 + lane];
-            float4 w1 = make_float4(0, 0, 0, 0);
-            if (two) w1 = w[((n + 1) * KT + t) * 64 + lane];
-            const int steps = t == 0 ? FIRST : 4;
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, in[t][0], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, in[t][0], a1, 0, 0, 0);
-            if (steps > 1) {
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, in[t][1], a0, 0, 0, 0);
-                if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, in[t][1], a1, 0, 0, 0);
-            }
-            if (steps > 2) {
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, in[t][2], a0, 0, 0, 0);
-                if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, in[t][2], a1, 0, 0, 0);
-            }
-            if (steps > 3) {
-                a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, in[t][3], a0, 0, 0, 0);
-                if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, in[t][3], a1, 0, 0, 0);
-            }
-        }
-        if (RELU) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { a0[r] = relu_f32(a0[r]); a1[r] = relu_f32(a1[r]); }
-        }
+        dense_tiles<KT, BIAS, FIRST, LAST>(in, w, b, n, n + 1, n + 1 < NT, lane, a0, a1);
+        activate<ACT>(a0, a1);
         out[n] = a0;
-        if (two) out[n + 1] = a1;
+        if (n + 1 < NT) out[n + 1] = a1;
     }
 }
 
@@ -138,18 +124,15 @@ constexpr int kChunkScale = MCN_STAGE_WAVES >= 8 ? 2 : 1;
 __host__ __device__ constexpr int chunk_tiles(int KT) { return kChunkScale * (KT > 16 ? 1 : (KT > 7 ? 2 : 4)); }
 constexpr int kStageFloat4 = kChunkScale * 32 * 64;              // max over layers of chunk_tiles(KT) * KT * 64
 // bias fragments of the chunk's output tiles -- and, for the flow / x3 layers that place their biases themselves, simply
-// the tail of the stage buffer: MCN_STAGE_BIAS_ROWS = 512 makes a buffer 40 KiB (two workgroups then use all 160 KiB)
-#ifndef MCN_STAGE_BIAS_ROWS
-#define MCN_STAGE_BIAS_ROWS 256
-#endif
-constexpr int kStageBias = kChunkScale * MCN_STAGE_BIAS_ROWS;
+// the tail of the stage buffer (512 rows would make a buffer 40 KiB: two workgroups then use all 160 KiB)
+constexpr int kStageBias = kChunkScale * 256;
 
 struct WeightStage {
     float4 *buf;      // LDS, 2 * (kStageFloat4 + kStageBias) float4
     int tid;          // threadIdx.x, 0 .. kStageThreads-1
 };
 
-// MCN_DENSE_PIPE = 1 (default): the chunk loop below is software-pipelined by hand.  Left to itself the compiler
+// The chunk loop of dense_staged is software-pipelined by hand.  Left to itself the compiler
 // issues the ds_read_b128 pair of an 8-MFMA group right before that group's MFMAs (it reuses the registers of the
 // previous fragments, so the reads cannot start earlier) and the wavefront sits out an LDS round trip (~100+ cycles)
 // per 256 cycles of matrix work: a lone wavefront reaches ~75 % of the pipe and two of them still leave 10 % idle
@@ -158,9 +141,6 @@ struct WeightStage {
 // tile pairs and across staged chunks; __builtin_amdgcn_sched_barrier(0) keeps the scheduler from sinking them back.
 // The chunk barrier sits before the LAST group of a chunk (all reads of the chunk have been issued and have
 // returned by then), so the next chunk's first fragments are fetched under that group's MFMAs as well.
-#ifndef MCN_DENSE_PIPE
-#define MCN_DENSE_PIPE 1
-#endif
 
 // LAST / LAST2: k-steps actually needed in the last / second-to-last input tile (ragged tiles packed "q first",
 // see mcn_pack_linear): the skipped steps would multiply zeros.
@@ -180,8 +160,6 @@ __device__ __forceinline__ void dense_staged(const f32x4 (&in)[KT], const f32x4 
     // exactly what global_load_lds writes (wave-uniform LDS base + lane * 16 B), so the weights go L2 -> LDS
     // without passing through (and pinning) VGPRs.  Biases ride along in a small tail region so that no ordinary
     // global load sits between a DMA and the barrier that retires it.
-    const int wave_base = S.tid & ~63; (void)wave_base;
-#if MCN_DENSE_PIPE
     // straight-line staging: every thread issues every DMA (a chunk is a whole number of 256-thread rounds); the source
     // index of the ragged last chunk / of bias slots beyond the layer is clamped, the duplicates land in stage slots
     // nobody reads.  No exec-mask branches: the DMA issue can sit between the MFMAs of a group.
@@ -210,27 +188,8 @@ __device__ __forceinline__ void dense_staged(const f32x4 (&in)[KT], const f32x4 
                 16, 0, 0);
         }
     };
-#else
-    auto stage = [&](int c, int b) {
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int i = S.tid + k * kStageThreads;
-            if (i < CH && c * CH + i < TOTAL)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)(wf + c * CH + i),
-                    (__attribute__((address_space(3))) void *)(S.buf + b * (kStageFloat4 + kStageBias) + k * kStageThreads + wave_base),
-                    16, 0, 0);
-        }
-        if (!HAS_INIT && S.tid < BCH && c * BCH + S.tid < NT * 64)
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(bf + c * BCH + S.tid),
-                (__attribute__((address_space(3))) void *)(S.buf + b * (kStageFloat4 + kStageBias) + kStageFloat4 + wave_base),
-                16, 0, 0);
-    };
-#endif
     stage(0, 0);
     __syncthreads();                                      // drains vmcnt (the DMA) and orders it before the reads
-#if MCN_DENSE_PIPE
     // flattened (output tile pair, input tile) groups of the whole layer, eight MFMAs each
     constexpr int PAIRS = (kChunkTiles + 1) / 2;          // tile pairs per staged chunk
     constexpr int NP = (NT + 1) / 2;                      // tile pairs of the layer
@@ -273,86 +232,19 @@ __device__ __forceinline__ void dense_staged(const f32x4 (&in)[KT], const f32x4 
         // LDS wait is lgkmcnt(0)), so the wait for this group's fragments must not see the next group's reads yet.
         // This group's fragments were requested seven MFMAs (~230 cycles) ago: the wait is free.
         __builtin_amdgcn_sched_barrier(0);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, in[t][0], a0, 0, 0, 0);
-        if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, in[t][0], a1, 0, 0, 0);
+        mfma_ksteps(0, 1, two, w0, w1, in[t], a0, a1);
         __builtin_amdgcn_sched_barrier(0);
         if (g + 1 < NG) issue(g + 1);
         if (chunk_first && c + 1 < NCH) stage(c + 1, (c + 1) & 1);          // DMA of the next chunk, other buffer
         __builtin_amdgcn_sched_barrier(0);
-        if (steps > 1) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, in[t][1], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, in[t][1], a1, 0, 0, 0);
-        }
-        if (steps > 2) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, in[t][2], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, in[t][2], a1, 0, 0, 0);
-        }
-        if (steps > 3) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, in[t][3], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, in[t][3], a1, 0, 0, 0);
-        }
+        mfma_ksteps(1, steps, two, w0, w1, in[t], a0, a1);
         __builtin_amdgcn_sched_barrier(0);
         if (t == KT - 1) {
-            if (RELU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { a0[r] = relu_f32(a0[r]); a1[r] = relu_f32(a1[r]); }
-            }
+            activate<RELU ? kRelu : kLinear>(a0, a1);
             out[n] = a0;
             if (two) out[n + 1] = a1;
         }
     }
-#else
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        if (c + 1 < NCH) stage(c + 1, (c + 1) & 1);
-        const float4 *wc = S.buf + (c & 1) * (kStageFloat4 + kStageBias);
-        const float4 *bc = wc + kStageFloat4;
-#pragma unroll
-        for (int h2 = 0; h2 < kChunkTiles; h2 += 2) {
-            const int n = kChunkTiles * c + h2;
-            if (n < NT) {
-                const bool two = (n + 1 < NT);
-                const float4 *w = wc + h2 * KT * 64;
-                f32x4 a0, a1 = {0, 0, 0, 0};
-                if (HAS_INIT) {
-                    a0 = init[n];
-                    if (two) a1 = init[n + 1];
-                } else {
-                    { const float4 b = bc[h2 * 64 + lane]; a0 = (f32x4){b.x, b.y, b.z, b.w}; }
-                    if (two) { const float4 b = bc[(h2 + 1) * 64 + lane]; a1 = (f32x4){b.x, b.y, b.z, b.w}; }
-                }
-#pragma unroll
-                for (int t = 0; t < KT; ++t) {
-                    const float4 w0 = w[t * 64 + lane];
-                    float4 w1 = make_float4(0, 0, 0, 0);
-                    if (two) w1 = w[(KT + t) * 64 + lane];
-                    const int steps = (t == KT - 1) ? LAST : ((t == KT - 2) ? LAST2 : 4);
-                    a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, in[t][0], a0, 0, 0, 0);
-                    if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, in[t][0], a1, 0, 0, 0);
-                    if (steps > 1) {
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, in[t][1], a0, 0, 0, 0);
-                        if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, in[t][1], a1, 0, 0, 0);
-                    }
-                    if (steps > 2) {
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, in[t][2], a0, 0, 0, 0);
-                        if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, in[t][2], a1, 0, 0, 0);
-                    }
-                    if (steps > 3) {
-                        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, in[t][3], a0, 0, 0, 0);
-                        if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, in[t][3], a1, 0, 0, 0);
-                    }
-                }
-                if (RELU) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { a0[r] = relu_f32(a0[r]); a1[r] = relu_f32(a1[r]); }
-                }
-                out[n] = a0;
-                if (two) out[n + 1] = a1;
-            }
-        }
-        __syncthreads();
-    }
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -388,15 +280,6 @@ struct WeightFlow {
 };
 constexpr int kStageBuf = kStageFloat4 + kStageBias;
 
-#ifndef MCN_X3_WHATIF
-#define MCN_X3_WHATIF 0     // timing-only what-if bits (profiles/r04_sarl_x3_whatif.txt); any non-zero value computes garbage
-#endif
-#ifndef MCN_DMA_SKIP_EMPTY
-#define MCN_DMA_SKIP_EMPTY 1
-#endif
-#ifndef MCN_LEAN_DMA
-#define MCN_LEAN_DMA 1
-#endif
 // One workgroup-wide LDS-DMA of `n` float4 rows src[0 .. n) to dst[0 .. n) in rounds of kStageThreads rows (round 4).
 // The what-if builds (profiles/r04_sarl_x3_whatif.txt) showed ISSUING the weight stream -- ~750 global_load_lds per
 // wavefront and tile, each with a 64-bit vector address, a clamp, a readfirstlane and an M0 move -- to cost as much as
@@ -416,8 +299,7 @@ __device__ __forceinline__ DmaLane dma_lane(int tid)
     return {static_cast<unsigned>(t) * 16u, t & ~63};
 }
 template <int MAX_ROUNDS>
-__device__ __forceinline__ void dma_rows(const float4 *base, int first, int n, float4 *dst, const DmaLane &L,
-                                         int k0 = 0, int k1 = MAX_ROUNDS)
+__device__ __forceinline__ void dma_rows(const float4 *base, int first, int n, float4 *dst, const DmaLane &L)
 {
     // rows base[first .. first + n); the row offset goes into the VGPR offset (one v_add per instruction, wrapping
     // unsigned so that it cannot be split off again): a scalar base per round would cost an SGPR pair per round and
@@ -425,18 +307,18 @@ __device__ __forceinline__ void dma_rows(const float4 *base, int first, int n, f
 #pragma unroll
     for (int k = 0; k < MAX_ROUNDS; ++k) {
         const int left = n - k * kStageThreads;            // rows from this round's first to the end
-        if (left > 0 && k >= k0 && k < k1) {               // wave-uniform (compile-time at the call sites)
+        if (left > 0) {                                     // wave-uniform (compile-time at the call sites)
             unsigned off = L.off;
             if (left < kStageThreads) {
                 // the round that straddles the end: wavefronts wholly past it issue nothing (a piece costs its issue
                 // slot whatever it moves), the one across it clamps
-                if (MCN_DMA_SKIP_EMPTY && __builtin_amdgcn_readfirstlane(L.wave_base) >= left) continue;
+                if (__builtin_amdgcn_readfirstlane(L.wave_base) >= left) continue;
                 off = off < (left - 1) * 16u ? off : (left - 1) * 16u;
             }
             off += static_cast<unsigned>(first + k * kStageThreads) * 16u;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(reinterpret_cast<const char *>(base) + off),
-                (__attribute__((address_space(3))) void *)(dst + k * kStageThreads + L.wave_base), (MCN_X3_WHATIF & 128) ? 4 : 16, 0, 0);
+                (__attribute__((address_space(3))) void *)(dst + k * kStageThreads + L.wave_base), 16, 0, 0);
         }
     }
 }
@@ -445,35 +327,9 @@ __device__ __forceinline__ void dma_rows(const float4 *base, int first, int n, f
 __device__ __forceinline__ void flow_stage_first(const WeightFlow &F, const NextChunk &d, int b)
 {
     float4 *dst = F.buf + b * kStageBuf;
-#if MCN_LEAN_DMA
     const DmaLane L = dma_lane(F.tid);
     dma_rows<kStageFloat4 / kStageThreads>(d.w, 0, d.n_w, dst, L);
     dma_rows<3>(d.b, 0, d.n_b, dst + d.b_at, L);              // up to 12 bias tiles
-#else
-    int tid_ = F.tid;
-    asm volatile("" : "+v"(tid_));
-    const int wave_base = tid_ & ~63;
-#pragma unroll
-    for (int k = 0; k < kStageFloat4 / kStageThreads; ++k) {
-        if (k * kStageThreads < d.n_w) {                                   // wave-uniform
-            int i = tid_ + k * kStageThreads;
-            i = i < d.n_w - 1 ? i : d.n_w - 1;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(d.w + i),
-                                             (__attribute__((address_space(3))) void *)(dst + k * kStageThreads + wave_base),
-                                             16, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {                                          // up to 12 bias tiles
-        if (k * kStageThreads < d.n_b) {
-            int i = tid_ + k * kStageThreads;
-            i = i < d.n_b - 1 ? i : d.n_b - 1;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(d.b + i),
-                                             (__attribute__((address_space(3))) void *)(dst + d.b_at + k * kStageThreads + wave_base),
-                                             16, 0, 0);
-        }
-    }
-#endif
 }
 
 // Precondition: chunk 0 of this layer has been requested into buffer F.parity AND a workgroup barrier (with vmcnt(0))
@@ -557,8 +413,7 @@ __device__ __forceinline__ void dense_flow(const f32x4 (&in)[KT], const f32x4 *i
         const float4 w0 = ra[g & 1], w1 = rb[g & 1];
         const int steps = (t == KT - 1) ? LAST : ((t == KT - 2) ? LAST2 : 4);
         __builtin_amdgcn_sched_barrier(0);
-        a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.x, in[t][0], a0, 0, 0, 0);
-        if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.x, in[t][0], a1, 0, 0, 0);
+        mfma_ksteps(0, 1, two, w0, w1, in[t], a0, a1);
         __builtin_amdgcn_sched_barrier(0);
         if (g + 1 < NG) issue(g + 1);
         if (chunk_first && !chunk_last) {
@@ -566,24 +421,10 @@ __device__ __forceinline__ void dense_flow(const f32x4 (&in)[KT], const f32x4 *i
             else if (next.n_w > 0) flow_stage_first(F, next, (F.parity + NCH) & 1);   // chunk 0 of the layer that follows
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (steps > 1) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.y, in[t][1], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.y, in[t][1], a1, 0, 0, 0);
-        }
-        if (steps > 2) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.z, in[t][2], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.z, in[t][2], a1, 0, 0, 0);
-        }
-        if (steps > 3) {
-            a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(w0.w, in[t][3], a0, 0, 0, 0);
-            if (two) a1 = __builtin_amdgcn_mfma_f32_16x16x4f32(w1.w, in[t][3], a1, 0, 0, 0);
-        }
+        mfma_ksteps(1, steps, two, w0, w1, in[t], a0, a1);
         __builtin_amdgcn_sched_barrier(0);
         if (t == KT - 1) {
-            if (RELU) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) { a0[r] = relu_f32(a0[r]); a1[r] = relu_f32(a1[r]); }
-            }
+            activate<RELU ? kRelu : kLinear>(a0, a1);
             out[n] = a0;
             if (two) out[n + 1] = a1;
         }
@@ -605,23 +446,10 @@ __device__ __forceinline__ void dense_flow(const f32x4 (&in)[KT], const f32x4 *i
 // mcn_pack_x3: per (output tile, input block) three 16-byte pieces per lane.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 struct X3 { bf16x8 hi, mid, lo; };
-// a chunk's DMA rounds in one burst behind its first MFMA (1) or spread over its first groups (measured: no gain)
-#ifndef MCN_X3_DMA_SPREAD
-#define MCN_X3_DMA_SPREAD 1
-#endif
-// scheduling fences around the MFMA groups of an x3 layer: 0 = nothing moves across (the split / ReLU blocks of one
-// wavefront then run between its MFMA groups and overlap the OTHER wavefront's MFMAs), 6 = vector / scalar ALU work may
-#ifndef MCN_X3_FENCE
-#define MCN_X3_FENCE 0
-#endif
 
 __device__ __forceinline__ X3 split8(const f32x4 a, const f32x4 b)
 {
     X3 s;
-#if MCN_X3_WHATIF & 16
-    s.hi = __builtin_bit_cast(bf16x8, a); s.mid = __builtin_bit_cast(bf16x8, b); s.lo = s.hi;
-    return s;
-#endif
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const float x = i < 4 ? a[i] : b[i - 4];
@@ -657,52 +485,26 @@ __device__ __forceinline__ NextChunk first_chunk_x3(const float4 *wf, const floa
                      x3_bias_at(KB, NT)};
 }
 
-#if MCN_X3_WHATIF & 8
-#define X3_MFMA(wa, xb, acc, c0, c1, c2) (acc)
-#else
-#define X3_MFMA(wa, xb, acc, c0, c1, c2) __builtin_amdgcn_mfma_f32_16x16x32_bf16(wa, xb, acc, c0, c1, c2)
-#endif
 // One layer: in = KB input blocks of 32 features (split), out = NT output tiles of 16 features (float32 accumulators,
-// bias / init added, ReLU applied); SPLIT: also outp = the ceil(NT / 2) input blocks of the layer that follows, each
-// split as soon as its two tiles are finished, so that the splitting's vector instructions run in the shadow of the
-// next tiles' MFMAs (a bf16 MFMA holds the vector issue for 8 of its 16 cycles; the scheduling fences below let vector
-// and scalar instructions -- and nothing else -- move across them).  Weight stream and hand-over of the following
-// layer's first chunk as dense_flow; the A pieces are requested TWO groups ahead (a group is only 96 cycles here,
-// less than an LDS round trip under load) into a three-slot register ring, and the chunk barrier sits before the
-// second-to-last group of a chunk (every read of the chunk has been issued by then).
-// init: accumulator start when HAS_INIT -- a register array, or (INIT_MEM) this lane's column of a [NT][64] float4 table
-// in global memory (`init` then points at element [0][lane]; tile n + 1's row is fetched while tile n is multiplied).
-// chunk geometry of an x3 layer.  A UNIT is one (output tile, input block): three A pieces, six MFMAs, 96 pipe cycles.
-// A GROUP is up to MCN_X3_UNITS consecutive units of one chunk; the A pieces of group G + 1 are requested behind the first
-// MFMA of group G, so a group's length is the cover its successor's LDS reads get.  (While an LDS-DMA is in flight every
-// LDS wait the compiler emits is lgkmcnt(0): "request further ahead" does not lengthen the cover -- the wait of group G
-// drains the reads of G + 1 as well -- longer groups do.)  Measured at 4096 x 5 (same box, diagnostic builds): 1 unit
-// 1.62-1.63 ms per step, 2 units 1.64, 3 units 1.66-1.69: the LDS round trip is not what the layers wait for, and the
-// longer ring costs registers.  Default 1.
-#ifndef MCN_X3_UNITS
-#define MCN_X3_UNITS 1
-#endif
-// TIMING-ONLY what-if builds (wrong values; tools/ab_build.sh + kbench): bit 0 no workgroup barriers, bit 1 no weight DMA,
-// bit 2 no LDS reads of the A pieces (after the first group), bit 3 no MFMAs, bit 4 no splitting (split8 returns its input
-// bits), bit 5 no workspace traffic between the passes.  0 in every product build.
+// bias / init added, ReLU applied); the caller splits them into the next layer's input blocks (split8).  Weight stream
+// and hand-over of the following layer's first chunk as dense_flow.  The scheduling fences let nothing move across the
+// MFMA groups: the split / ReLU blocks of one wavefront run between its groups and overlap the OTHER wavefront's MFMAs.
+// init: accumulator start when HAS_INIT, a register array.
+// Chunk geometry: a GROUP is one (output tile, input block): three A pieces, six MFMAs, 96 pipe cycles.  The A pieces of
+// group G + 1 are requested behind the first MFMA of group G into a two-slot register ring, and the chunk barrier sits
+// before the last group of a chunk (every read of the chunk has been issued by then).  (While an LDS-DMA is in flight
+// every LDS wait the compiler emits is lgkmcnt(0): "request further ahead" does not lengthen the cover -- the wait of
+// group G drains the reads of G + 1 as well -- longer groups would, and were measured slower: DESIGN 9.)
 template <int KB, int NT>
 struct X3Geo {
-    static constexpr int U = MCN_X3_UNITS;
     static constexpr int CT = x3_chunk_tiles(KB, NT);
     static constexpr int NCH = x3_chunks(KB, NT);
-    static constexpr int UC = CT * KB;                                   // units of a full chunk
-    static constexpr int GPC = (UC + U - 1) / U;                         // groups of a full chunk
-    static constexpr int units_in(int c) { return ((c + 1) * CT < NT ? CT : NT - c * CT) * KB; }
-    static constexpr int groups_in(int c) { return (units_in(c) + U - 1) / U; }
-    static constexpr int NG = (NCH - 1) * GPC + groups_in(NCH - 1);
+    static constexpr int GPC = CT * KB;                                  // groups of a full chunk
+    static constexpr int groups_in(int c) { return ((c + 1) * CT < NT ? CT : NT - c * CT) * KB; }
+    static constexpr int NG = (NCH - 1) * GPC + groups_in(NCH - 1);      // = NT * KB
     static constexpr int chunk_of(int g) { return g / GPC < NCH ? g / GPC : NCH - 1; }
     static constexpr int first_of(int c) { return c * GPC; }
     static constexpr int last_of(int c) { return c * GPC + groups_in(c) - 1; }
-    static constexpr int unit0(int g) { return chunk_of(g) * UC + (g - first_of(chunk_of(g))) * U; }
-    static constexpr int count(int g)
-    {
-        return units_in(chunk_of(g)) - (g - first_of(chunk_of(g))) * U < U ? units_in(chunk_of(g)) - (g - first_of(chunk_of(g))) * U : U;
-    }
 };
 template <class Fn, int... Gs>
 __device__ __forceinline__ void static_for(Fn &&f, std::integer_sequence<int, Gs...>)
@@ -713,9 +515,8 @@ __device__ __forceinline__ void static_for(Fn &&f, std::integer_sequence<int, Gs
 // on_tile(n, a): called with every finished output tile (a consumer that needs each tile once -- a running sum -- does not
 // keep the layer's whole float32 output alive).
 struct NoTileHook { __device__ __forceinline__ void operator()(int, const f32x4 &) const {} };
-template <int KB, int NT, bool RELU, bool HAS_INIT, bool SPLIT = false, bool INIT_MEM = false, class OnTile = NoTileHook>
+template <int KB, int NT, bool RELU, bool HAS_INIT, class OnTile = NoTileHook>
 __device__ __forceinline__ void dense_flow_x3(const X3 (&in)[KB], const f32x4 *init, f32x4 (&out)[NT],
-                                              X3 (&outp)[(NT + 1) / 2],
                                               const float4 *__restrict__ wf, const float4 *__restrict__ bf,
                                               WeightFlow &F, int lane, const NextChunk &next, const OnTile &on_tile = OnTile())
 {
@@ -741,119 +542,62 @@ __device__ __forceinline__ void dense_flow_x3(const X3 (&in)[KB], const f32x4 *i
         }
     };
     using Geo = X3Geo<KB, NT>;
-    constexpr int NG = Geo::NG, U = Geo::U;
-    float4 ra[2][U][3], bias[4] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
+    constexpr int NG = Geo::NG;
+    float4 ra[2][3], bias[4] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
     // (The group loop is a compile-time expansion -- static_for over integral constants -- not an unrolled run-time loop:
     //  every array index is a constant from the start, so the register promotion of the operand arrays does not depend
     //  on when the optimiser gets round to unrolling ~50 groups; as a `for` loop the output pieces ended up in scratch.)
-    auto issue = [&](auto gc) {                           // LDS -> ring slot g & 1: the A pieces of the group's units
+    auto issue = [&](auto gc) {                           // LDS -> ring slot g & 1: the A pieces of the group
         constexpr int g = decltype(gc)::value;
         constexpr int c = Geo::chunk_of(g);
-        static_for([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            if constexpr (k < Geo::count(g)) {
-                constexpr int u = Geo::unit0(g) + k, n = u / KB, m = u - n * KB, h = n - c * CT;
-                const float4 *w = bufp[c & 1] + (h * KB + m) * 192;
-                if (MCN_X3_WHATIF & 64) {                // timing only: the same three reads at half the bytes
-                    const float2 *w2 = reinterpret_cast<const float2 *>(w);
-                    const float2 t0 = w2[lane], t1 = w2[128 + lane], t2 = w2[256 + lane];
-                    ra[g & 1][k][0] = make_float4(t0.x, t0.y, t0.x, t0.y); ra[g & 1][k][1] = make_float4(t1.x, t1.y, t1.x, t1.y);
-                    ra[g & 1][k][2] = make_float4(t2.x, t2.y, t2.x, t2.y);
-                } else {
-                    ra[g & 1][k][0] = w[lane]; ra[g & 1][k][1] = w[64 + lane]; ra[g & 1][k][2] = w[128 + lane];
-                }
-                if (m == 0 && !HAS_INIT) bias[n & 3] = bufp[c & 1][BOFF + h * 64 + lane];
-            }
-        }, std::make_integer_sequence<int, U>{});
+        constexpr int n = g / KB, m = g - n * KB, h = n - c * CT;
+        const float4 *w = bufp[c & 1] + (h * KB + m) * 192;
+        ra[g & 1][0] = w[lane]; ra[g & 1][1] = w[64 + lane]; ra[g & 1][2] = w[128 + lane];
+        if (m == 0 && !HAS_INIT) bias[n & 3] = bufp[c & 1][BOFF + h * 64 + lane];
     };
     auto request_next = [&](int c) {                      // what follows chunk c: this layer's next chunk, or the next layer's first
-        if (MCN_X3_WHATIF & 2) return;
         if (c + 1 < NCH) stage(c + 1);
         else if (next.n_w > 0) flow_stage_first(F, next, (F.parity + NCH) & 1);
     };
-    // part j of `parts` of the same request (MCN_X3_DMA_SPREAD > 1: the rounds of a chunk's DMA spread over its first
-    // groups instead of one burst behind the first MFMA)
-    auto request_part = [&](int c, int j, int parts) {
-        if (MCN_X3_WHATIF & 2) return;
-        const DmaLane L = dma_lane(F.tid);
-        if (c + 1 < NCH) {
-            float4 *dst = bufp[(c + 1) & 1];
-            const int rows = TOTAL - (c + 1) * CH < CH ? TOTAL - (c + 1) * CH : CH;
-            const int brows = HAS_INIT ? 0 : (NT * 64 - (c + 1) * BCH < BCH ? NT * 64 - (c + 1) * BCH : BCH);
-            const int rw = (rows + kStageThreads - 1) / kStageThreads, rb = (brows + kStageThreads - 1) / kStageThreads;
-            const int k0 = j * (rw + rb) / parts, k1 = (j + 1) * (rw + rb) / parts;
-            dma_rows<PER>(wf, (c + 1) * CH, rows, dst, L, k0, k1 < rw ? k1 : rw);
-            if (!HAS_INIT) dma_rows<BPER>(bf, (c + 1) * BCH, brows, dst + BOFF, L, k0 - rw, k1 - rw);
-        } else if (next.n_w > 0) {
-            float4 *dst = F.buf + ((F.parity + NCH) & 1) * kStageBuf;
-            const int rw = (next.n_w + kStageThreads - 1) / kStageThreads, rb = (next.n_b + kStageThreads - 1) / kStageThreads;
-            const int k0 = j * (rw + rb) / parts, k1 = (j + 1) * (rw + rb) / parts;
-            dma_rows<kStageFloat4 / kStageThreads>(next.w, 0, next.n_w, dst, L, k0, k1 < rw ? k1 : rw);
-            dma_rows<3>(next.b, 0, next.n_b, dst + next.b_at, L, k0 - rw, k1 - rw);
-        }
-    };
     issue(std::integral_constant<int, 0>{});
     f32x4 a = {0, 0, 0, 0};
-    float4 initv[2] = {make_float4(0, 0, 0, 0), make_float4(0, 0, 0, 0)};
-    if (HAS_INIT && INIT_MEM) initv[0] = reinterpret_cast<const float4 *>(init)[0];
     auto group = [&](auto gc) {
         constexpr int g = decltype(gc)::value;
         constexpr int c = Geo::chunk_of(g);
         constexpr bool at_first = g == Geo::first_of(c), at_last = g == Geo::last_of(c);
         if constexpr (at_last) {
             if constexpr (at_first) request_next(c);      // (the request must precede the barrier that publishes it)
-            if (!(MCN_X3_WHATIF & 1)) __syncthreads();    // every read of chunk c has been issued and is back; DMAs landed
+            __syncthreads();                              // every read of chunk c has been issued and is back; DMAs landed
         }
-        static_for([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            if constexpr (k < Geo::count(g)) {
-                constexpr int u = Geo::unit0(g) + k, n = u / KB, m = u - n * KB;
-                if constexpr (m == 0) {
-                    if constexpr (HAS_INIT && INIT_MEM) {
-                        a = (f32x4){initv[n & 1].x, initv[n & 1].y, initv[n & 1].z, initv[n & 1].w};
-                        if constexpr (n + 1 < NT) initv[(n + 1) & 1] = reinterpret_cast<const float4 *>(init)[(n + 1) * 64];
-                    } else if constexpr (HAS_INIT) a = init[n];
-                    else a = (f32x4){bias[n & 3].x, bias[n & 3].y, bias[n & 3].z, bias[n & 3].w};
-                }
-                const bf16x8 wh = __builtin_bit_cast(bf16x8, ra[g & 1][k][0]), wm = __builtin_bit_cast(bf16x8, ra[g & 1][k][1]),
-                             wl = __builtin_bit_cast(bf16x8, ra[g & 1][k][2]);
-                __builtin_amdgcn_sched_barrier(MCN_X3_FENCE);
-                a = X3_MFMA(wl, in[m].hi, a, 0, 0, 0);    // smallest terms first
-                if constexpr (k == 0) {
-                    // behind the group's FIRST MFMA (whose wait for this group's pieces must not see them yet): the next
-                    // group's reads, and at a chunk's first group the DMA of what follows the chunk
-                    __builtin_amdgcn_sched_barrier(MCN_X3_FENCE);
-                    if constexpr (g + 1 < NG) { if (!(MCN_X3_WHATIF & 4)) issue(std::integral_constant<int, g + 1>{}); }
-                    if constexpr (MCN_X3_DMA_SPREAD <= 1) {
-                        if constexpr (at_first && !at_last) request_next(c);
-                    } else if constexpr (!at_last) {
-                        constexpr int gn = Geo::groups_in(c), j = g - Geo::first_of(c);
-                        constexpr int parts = gn - 1 < MCN_X3_DMA_SPREAD ? gn - 1 : MCN_X3_DMA_SPREAD;
-                        if constexpr (j < parts) request_part(c, j, parts);
-                    }
-                    __builtin_amdgcn_sched_barrier(MCN_X3_FENCE);
-                }
-                a = X3_MFMA(wh, in[m].lo, a, 0, 0, 0);
-                a = X3_MFMA(wm, in[m].mid, a, 0, 0, 0);
-                a = X3_MFMA(wm, in[m].hi, a, 0, 0, 0);
-                a = X3_MFMA(wh, in[m].mid, a, 0, 0, 0);
-                a = X3_MFMA(wh, in[m].hi, a, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(MCN_X3_FENCE);
-                if constexpr (m == KB - 1) {
-                    if (RELU) {
+        constexpr int n = g / KB, m = g - n * KB;
+        if constexpr (m == 0) {
+            if constexpr (HAS_INIT) a = init[n];
+            else a = (f32x4){bias[n & 3].x, bias[n & 3].y, bias[n & 3].z, bias[n & 3].w};
+        }
+        const bf16x8 wh = __builtin_bit_cast(bf16x8, ra[g & 1][0]), wm = __builtin_bit_cast(bf16x8, ra[g & 1][1]),
+                     wl = __builtin_bit_cast(bf16x8, ra[g & 1][2]);
+        __builtin_amdgcn_sched_barrier(0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl, in[m].hi, a, 0, 0, 0);    // smallest terms first
+        // behind the group's FIRST MFMA (whose wait for this group's pieces must not see them yet): the next group's
+        // reads, and at a chunk's first group the DMA of what follows the chunk, in one burst
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (g + 1 < NG) issue(std::integral_constant<int, g + 1>{});
+        if constexpr (at_first && !at_last) request_next(c);
+        __builtin_amdgcn_sched_barrier(0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, in[m].lo, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, in[m].mid, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wm, in[m].hi, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, in[m].mid, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh, in[m].hi, a, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (m == KB - 1) {
+            if (RELU) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) a[r] = relu_f32(a[r]);
-                    }
-                    out[n] = a;
-                    on_tile(n, a);
-                    if constexpr (SPLIT && ((n & 1) || n == NT - 1)) {
-                        const f32x4 z = {0, 0, 0, 0};
-                        if constexpr (n & 1) outp[n >> 1] = split8(out[n - 1], out[n]);
-                        else outp[n >> 1] = split8(out[n], z);
-                    }
-                }
+                for (int r = 0; r < 4; ++r) a[r] = relu_f32(a[r]);
             }
-        }, std::make_integer_sequence<int, U>{});
+            out[n] = a;
+            on_tile(n, a);
+        }
     };
     static_for(group, std::make_integer_sequence<int, NG>{});
     F.parity = (F.parity + NCH) & 1;

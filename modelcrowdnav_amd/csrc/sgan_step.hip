@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kSganWaves * 64, MCN_ENC_MINWAVES) void sgan_encode
 #endif
         f32x4 cat[3] = {tile_xy(rx, ry, q), h[0], h[1]};
         f32x4 g[8];
-        dense_lds<3, 8, false, 1>(cat, g, s_wl, s_bl, ln);
+        dense<3, 8, kLinear, kBiasQuarter, 1>(cat, g, s_wl, s_bl, ln);
         lstm_update(g, h, c);
     }
     if (valid) {
@@ -392,12 +392,12 @@ __global__ __launch_bounds__(kSganWaves * 64) void sgan_decode_kernel(const Sgan
         if (q < 2) pool = as_tile(reinterpret_cast<const float4 *>(p.pool)[ped * 2 + q]);
         f32x4 cin[3] = {hi[0], hi[1], pool};
         f32x4 c1[4];
-        dense<3, 4, true>(cin, c1, p.f.w_c1, p.f.b_c1, lane);
-        dense<4, 2, true>(c1, ctx, p.f.w_c2, p.f.b_c2, lane);
+        dense<3, 4, kRelu, kBiasFrag>(cin, c1, p.f.w_c1, p.f.b_c1, lane);
+        dense<4, 2, kRelu, kBiasFrag>(c1, ctx, p.f.w_c2, p.f.b_c2, lane);
     } else {
         f32x4 c1[4];
-        dense<2, 4, true>(hi, c1, p.f.w_c1, p.f.b_c1, lane);
-        dense<4, 2, true>(c1, ctx, p.f.w_c2, p.f.b_c2, lane);
+        dense<2, 4, kRelu, kBiasFrag>(hi, c1, p.f.w_c1, p.f.b_c1, lane);
+        dense<4, 2, kRelu, kBiasFrag>(c1, ctx, p.f.w_c2, p.f.b_c2, lane);
     }
     // decoder_h = [context(24), noise(8)] (add_noise, 'global' mix: one vector per scene)
     f32x4 dh[2] = {ctx[0], ctx[1]}, dc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
@@ -407,10 +407,10 @@ __global__ __launch_bounds__(kSganWaves * 64) void sgan_decode_kernel(const Sgan
     }
     f32x4 cat[3] = {tile_xy(mine.z, mine.w, q), dh[0], dh[1]};
     f32x4 g[8];
-    dense<3, 8, false, 1>(cat, g, p.f.w_dlstm, p.f.b_dlstm, lane);
+    dense<3, 8, kLinear, kBiasFrag, 1>(cat, g, p.f.w_dlstm, p.f.b_dlstm, lane);
     lstm_update(g, dh, dc);
     f32x4 out[1];
-    dense<2, 1, false>(dh, out, p.f.w_h2p, p.f.b_h2p, lane);
+    dense<2, 1, kLinear, kBiasFrag>(dh, out, p.f.w_h2p, p.f.b_h2p, lane);
     if (valid && q == 0) {
         const float rx = out[0][0], ry = out[0][1];
         const float ax = rx + mine.x, ay = ry + mine.y;                 // relative_to_abs, float32

@@ -54,10 +54,10 @@ __global__ __launch_bounds__(256) void mlp_world_kernel(const MlpWorldParams p)
         x[t] = v;
     }
     f32x4 h1[T128], h2[T64], h3[T12], o[NT4];
-    dense_lds<KT1, T128, true>(x, h1, s_w1, s_b1, lane);
-    dense_lds<T128, T64, true>(h1, h2, s_w2, s_b2, lane);
-    dense_lds<T64, T12, true>(h2, h3, s_w3, s_b3, lane);
-    dense_lds<T12, NT4, false, 3>(h3, o, s_w4, s_b4, lane);       // 12 inputs packed "q first": 3 k-steps
+    dense<KT1, T128, kRelu, kBiasQuarter>(x, h1, s_w1, s_b1, lane);
+    dense<T128, T64, kRelu, kBiasQuarter>(h1, h2, s_w2, s_b2, lane);
+    dense<T64, T12, kRelu, kBiasQuarter>(h2, h3, s_w3, s_b3, lane);
+    dense<T12, NT4, kLinear, kBiasQuarter, 3>(h3, o, s_w4, s_b4, lane);       // 12 inputs packed "q first": 3 k-steps
     if (valid) {
 #pragma unroll
         for (int n = 0; n < NT4; ++n) {

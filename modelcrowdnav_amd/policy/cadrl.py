@@ -52,6 +52,7 @@ import logging
 import torch
 
 from .. import _hip
+from .._pack import ident as _ident, natural as _natural, pack_linear
 from ..envs.policy.policy import Policy
 from ..envs.utils.action import ActionRot, ActionXY
 from ..envs.utils.state import FullState, ObservableState
@@ -85,40 +86,6 @@ class ValueNetwork(nn.Module):
 
     def forward(self, state):
         return self.value_network(state)
-
-
-def _ident(kin, tiles, offset=0):
-    """Slot -> feature map of a `kin`-wide activation held in `tiles` tiles of 16: full tiles in natural order, the
-    ragged last tile "q first" (feature j at slot 4(j%4) + j/4), see mcn_pack_linear in include/mcn.h."""
-    m = np.full(tiles * 16, -1, np.int32)
-    full = (kin // 16) * 16 if kin % 16 else kin
-    m[:full] = np.arange(full)
-    for j in range(kin - full):
-        m[full + 4 * (j % 4) + j // 4] = full + j
-    m[m >= 0] += offset
-    return m
-
-
-def _natural(kin, tiles):
-    m = np.full(tiles * 16, -1, np.int32)
-    m[:kin] = np.arange(kin)
-    return m
-
-
-def pack_linear(W, b, kmap, omap, dev):
-    """One layer (weight [nout, kin], bias [nout] float32 numpy) -> (device weight fragments, device bias fragments)
-    through mcn_pack_linear; kmap / omap: input / output slot maps (NT = len(omap) / 16, KT = len(kmap) / 16)."""
-    W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
-    nout, kin = W.shape
-    KT, NT = len(kmap) // 16, len(omap) // 16
-    wf = np.zeros((NT, KT, 64, 4), np.float32)
-    bf = np.zeros((NT, 64, 4), np.float32)
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
-    kmap, omap = np.ascontiguousarray(kmap, np.int32), np.ascontiguousarray(omap, np.int32)
-    _hip.check(_hip.lib.mcn_pack_linear(W.ctypes.data_as(fp), b.ctypes.data_as(fp), nout, kin, kmap.ctypes.data_as(ip),
-                                        KT, omap.ctypes.data_as(ip), NT, wf.ctypes.data_as(fp), bf.ctypes.data_as(fp)),
-               "mcn_pack_linear")
-    return torch.from_numpy(wf).to(dev), torch.from_numpy(bf).to(dev)
 
 
 def _state_arrays(model):

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from .._pack import ident as _ident, natural as _natural, pack_linear
 from .cadrl import mlp
 from .multi_human_rl import MultiHumanRL
 
@@ -50,26 +51,7 @@ class ValueNetwork(nn.Module):
         return self.mlp3(torch.cat([state[:, 0, :self.self_state_dim], pooled], dim=1))
 
 
-# input-slot -> weight-column maps of each packed layer (see mcn_pack_linear in include/mcn.h)
-def _ident(kin, tiles, offset=0):
-    """Slot -> feature map of a `kin`-wide activation held in `tiles` tiles of 16.  Full tiles are in natural
-    order; the ragged last tile is packed "q first" (feature j at slot 4(j%4) + j/4) so that its consumers need
-    only ceil(w/4) k-steps (include/mcn.h, mcn_pack_linear)."""
-    m = np.full(tiles * 16, -1, np.int32)
-    full = (kin // 16) * 16 if kin % 16 else kin
-    m[:full] = np.arange(full)
-    for j in range(kin - full):
-        m[full + 4 * (j % 4) + j // 4] = full + j
-    m[m >= 0] += offset
-    return m
-
-
-def _natural(kin, tiles, offset=0):
-    m = np.full(tiles * 16, -1, np.int32)
-    m[:kin] = np.arange(kin) + offset
-    return m
-
-
+# input-slot -> weight-column maps of each packed layer (_pack.py; see mcn_pack_linear in include/mcn.h)
 def _pack_plan():
     m3a = np.full(5 * 16, -1, np.int32)
     m3a[:64] = _ident(50, 4, offset=6)    # pooled features occupy tiles 0..3 -> mlp3.0 columns 6..55
@@ -119,22 +101,14 @@ def pack_value_network(model, dev):
     x3 = _SarlX3()
     fp = C.POINTER(C.c_float)
     for name, key, kmap, KT, with_bias in _pack_plan():
-        W, b = sd[key + ".weight"], sd[key + ".bias"]
-        nout, kin = W.shape
-        NT = (nout + 15) // 16
-        wf = np.zeros((NT, KT, 64, 4), np.float32)
-        bf = np.zeros((NT, 64, 4), np.float32)
-        omap = _ident(nout, NT)             # outputs use the same ragged-tile packing their consumers assume
-        ip = C.POINTER(C.c_int32)
-        rc = _hip.lib.mcn_pack_linear(W.ctypes.data_as(fp), b.ctypes.data_as(fp), nout, kin,
-                                      kmap.ctypes.data_as(ip), KT, omap.ctypes.data_as(ip), NT,
-                                      wf.ctypes.data_as(fp), bf.ctypes.data_as(fp) if with_bias else None)
-        _hip.check(rc, "mcn_pack_linear(%s)" % name)
-        dw = torch.from_numpy(wf).to(dev)
+        W = sd[key + ".weight"]
+        NT = (W.shape[0] + 15) // 16
+        omap = _ident(W.shape[0], NT)       # outputs use the same ragged-tile packing their consumers assume
+        dw, db, wf = pack_linear(W, sd[key + ".bias"], kmap, omap, dev, bias=with_bias, host=True,
+                                 what="mcn_pack_linear(%s)" % name)
         keep.append(dw)
         setattr(net, "w_" + name, dw.data_ptr())
         if with_bias:
-            db = torch.from_numpy(bf).to(dev)
             keep.append(db)
             setattr(net, "b_" + name, db.data_ptr())
         # the same fragments as three bfloat16 pieces per weight, for the bf16 matrix pipe (include/mcn.h: mcn_pack_x3)

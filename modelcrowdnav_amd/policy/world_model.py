@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from .. import _hip
+from .._pack import ident as _ident, natural as _natural, pack_linear
 from ..sgan.models import TrajectoryGenerator, sgan_step
 
 
@@ -270,7 +271,6 @@ def _dropout_active(module):
 
 def pack_mlp_world(module, num_human, dev):
     """MlpWorld.state_dict -> (ctypes mcn_mlp_world_net, [device tensors kept alive]); layouts in include/mcn.h."""
-    from .sarl import _ident, _natural
     sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in module.state_dict().items()}
     N = int(num_human)
     if tuple(sd["mlp.0.weight"].shape) != (128, 4 * N) or tuple(sd["mlp.8.weight"].shape) != (2 * N, 12):
@@ -281,17 +281,10 @@ def pack_mlp_world(module, num_human, dev):
             ("3", "mlp.6", _natural(64, 4), 4, _ident(12, 1), 1),
             ("4", "mlp.8", _ident(12, 1), 1, None, nt4)]
     net, keep = _MlpWorldNet(), []
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     for tag, key, kmap, KT, omap, NT in plan:
-        W, b = sd[key + ".weight"], sd[key + ".bias"]
-        nout, kin = W.shape
-        wf = np.zeros((NT, KT, 64, 4), np.float32)
-        bf = np.zeros((NT, 64, 4), np.float32)
-        om = omap if omap is not None else _natural(nout, NT)
-        rc = _hip.lib.mcn_pack_linear(W.ctypes.data_as(fp), b.ctypes.data_as(fp), nout, kin, kmap.ctypes.data_as(ip), KT,
-                                      om.ctypes.data_as(ip), NT, wf.ctypes.data_as(fp), bf.ctypes.data_as(fp))
-        _hip.check(rc, "mcn_pack_linear(mlp_world %s)" % key)
-        dw, db = torch.from_numpy(wf).to(dev), torch.from_numpy(bf).to(dev)
+        W = sd[key + ".weight"]
+        om = omap if omap is not None else _natural(W.shape[0], NT)
+        dw, db = pack_linear(W, sd[key + ".bias"], kmap, om, dev, what="mcn_pack_linear(mlp_world %s)" % key)
         keep += [dw, db]
         setattr(net, "w" + tag, dw.data_ptr())
         setattr(net, "b" + tag, db.data_ptr())
@@ -336,7 +329,6 @@ class VecMlpWorld(object):
 
 def pack_attn_world(module, dev):
     """AttentionWorld.state_dict -> (ctypes mcn_attn_world_net, [device tensors kept alive]); layouts in include/mcn.h."""
-    from .sarl import _ident, _natural
     if not module.with_global_state or module.input_dim != 4:
         raise NotImplementedError("world_attn.hip is built for input_dim 4 with the global state (the reference's defaults)")
     sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in module.state_dict().items()}
@@ -355,23 +347,13 @@ def pack_attn_world(module, dev):
             ("m3c", "mlp3.4", _ident(100, 7), 7, True, None),
             ("m3d", "mlp3.6", _ident(100, 7), 7, True, _natural(2, 1))]
     net, keep = _AttnWorldNet(), []
-    fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     for name, key, kmap, KT, with_bias, omap in plan:
-        W, b = sd[key + ".weight"], sd[key + ".bias"]
-        nout, kin = W.shape
-        NT = (nout + 15) // 16
-        wf = np.zeros((NT, KT, 64, 4), np.float32)
-        bf = np.zeros((NT, 64, 4), np.float32)
-        om = omap if omap is not None else _ident(nout, NT)
-        rc = _hip.lib.mcn_pack_linear(W.ctypes.data_as(fp), b.ctypes.data_as(fp), nout, kin, kmap.ctypes.data_as(ip), KT,
-                                      om.ctypes.data_as(ip), NT, wf.ctypes.data_as(fp),
-                                      bf.ctypes.data_as(fp) if with_bias else None)
-        _hip.check(rc, "mcn_pack_linear(attn_world %s)" % name)
-        dw = torch.from_numpy(wf).to(dev)
+        W = sd[key + ".weight"]
+        om = omap if omap is not None else _ident(W.shape[0], (W.shape[0] + 15) // 16)
+        dw, db = pack_linear(W, sd[key + ".bias"], kmap, om, dev, bias=with_bias, what="mcn_pack_linear(attn_world %s)" % name)
         keep.append(dw)
         setattr(net, "w_" + name, dw.data_ptr())
         if with_bias:
-            db = torch.from_numpy(bf).to(dev)
             keep.append(db)
             setattr(net, "b_" + name, db.data_ptr())
     return net, keep

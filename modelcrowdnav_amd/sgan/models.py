@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from .._pack import natural as _natural, pack_linear
 
 
 def make_mlp(dim_list):
@@ -76,12 +77,6 @@ def _kmap_rel_h():
     return m
 
 
-def _ident(kin, tiles, offset=0):
-    m = np.full(tiles * 16, -1, np.int32)
-    m[:kin] = np.arange(kin) + offset
-    return m
-
-
 class TrajectoryGenerator(nn.Module):
     def __init__(self, obs_len=8, pred_len=1, embedding_dim=16, encoder_h_dim=32, decoder_h_dim=32, mlp_dim=64,
                  num_layers=1, noise_dim=(8,), noise_type="gaussian", noise_mix_type="global", pooling_type=None,
@@ -118,18 +113,9 @@ class TrajectoryGenerator(nn.Module):
             return self._packed[1]
         sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in self.state_dict().items()}
         net, keep = _SganNet(), []
-        fp = C.POINTER(C.c_float)
 
-        def put(name, W, b, kmap, KT):
-            W, b = np.ascontiguousarray(W, np.float32), np.ascontiguousarray(b, np.float32)
-            nout, kin = W.shape
-            NT = (nout + 15) // 16
-            wf, bf = np.zeros((NT, KT, 64, 4), np.float32), np.zeros((NT, 64, 4), np.float32)
-            _hip.check(_hip.lib.mcn_pack_linear(W.ctypes.data_as(fp), b.ctypes.data_as(fp), nout, kin,
-                                                kmap.ctypes.data_as(C.POINTER(C.c_int32)), KT, None, NT,
-                                                wf.ctypes.data_as(fp), bf.ctypes.data_as(fp)), "mcn_pack_linear")
-            for pre, arr in (("w_", wf), ("b_", bf)):
-                t = torch.from_numpy(arr).to(dev)
+        def put(name, W, b, kmap):
+            for pre, t in zip(("w_", "b_"), pack_linear(W, b, kmap, None, dev)):
                 keep.append(t)
                 setattr(net, pre + name, t.data_ptr())
 
@@ -138,19 +124,19 @@ class TrajectoryGenerator(nn.Module):
             return W, sd[prefix + ".bias_ih_l0"] + sd[prefix + ".bias_hh_l0"]
 
         put("elstm", *_fold_embedding(*lstm("encoder.encoder"), sd["encoder.spatial_embedding.weight"],
-                                      sd["encoder.spatial_embedding.bias"]), _kmap_rel_h(), 3)
+                                      sd["encoder.spatial_embedding.bias"]), _kmap_rel_h())
         if self.pooling_type:
             put("p1", *_fold_embedding(sd["pool_net.mlp_pre_pool.0.weight"], sd["pool_net.mlp_pre_pool.0.bias"],
                                        sd["pool_net.spatial_embedding.weight"], sd["pool_net.spatial_embedding.bias"]),
-                _kmap_rel_h(), 3)
-            put("p2", sd["pool_net.mlp_pre_pool.2.weight"], sd["pool_net.mlp_pre_pool.2.bias"], _ident(512, 32), 32)
-            put("c1", sd["mlp_decoder_context.0.weight"], sd["mlp_decoder_context.0.bias"], _ident(40, 3), 3)
+                _kmap_rel_h())
+            put("p2", sd["pool_net.mlp_pre_pool.2.weight"], sd["pool_net.mlp_pre_pool.2.bias"], _natural(512, 32))
+            put("c1", sd["mlp_decoder_context.0.weight"], sd["mlp_decoder_context.0.bias"], _natural(40, 3))
         else:
-            put("c1", sd["mlp_decoder_context.0.weight"], sd["mlp_decoder_context.0.bias"], _ident(32, 2), 2)
-        put("c2", sd["mlp_decoder_context.2.weight"], sd["mlp_decoder_context.2.bias"], _ident(64, 4), 4)
+            put("c1", sd["mlp_decoder_context.0.weight"], sd["mlp_decoder_context.0.bias"], _natural(32, 2))
+        put("c2", sd["mlp_decoder_context.2.weight"], sd["mlp_decoder_context.2.bias"], _natural(64, 4))
         put("dlstm", *_fold_embedding(*lstm("decoder.decoder"), sd["decoder.spatial_embedding.weight"],
-                                      sd["decoder.spatial_embedding.bias"]), _kmap_rel_h(), 3)
-        put("h2p", sd["decoder.hidden2pos.weight"], sd["decoder.hidden2pos.bias"], _ident(32, 2), 2)
+                                      sd["decoder.spatial_embedding.bias"]), _kmap_rel_h())
+        put("h2p", sd["decoder.hidden2pos.weight"], sd["decoder.hidden2pos.bias"], _natural(32, 2))
         net.pooling = 1 if self.pooling_type else 0
         self._packed = (version, (net, keep))
         return self._packed[1]
