@@ -321,6 +321,40 @@ int mcn_sarl_predict(const mcn_sarl_net *net, const mcn_env_state *st, const dou
                      const double *next_hpos, const double *next_hvel, const double *rewards,
                      double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream);
 
+/*
+ * OM-SARL (`[sarl] with_om = true`): mlp1.0 is 61 -> 150 on [13 rotated features | 48 occupancy-map entries].
+ *
+ * mcn_sarl_om_prepare -- once per step, for the first hcount[e] humans of every env (hcount as in the look-ahead,
+ * clamped to 1 .. N): MultiHumanRL.build_occupancy_maps (multi_human_rl.py:109-163) with cell_num = 4 and
+ * om_channel_size = 3 -- a 4 x 4 grid of `cell_size` cells centred on the human, +x along its velocity; per cell
+ * [occupied by another human of the env, mean vx, mean vy of those humans in the turned frame], entry 3 cell + channel,
+ * cell = 4 iy + ix; float64 in the reference's operation sequence, stored as float32.  The humans' states are
+ * next_hpos / next_hvel ([E*N][2], both or neither: the `query_env` form) when given, else hpos + time_step * hvel
+ * with hvel (the look-ahead's constant-velocity propagation), or the current ones for time_step = 0 (what
+ * MultiHumanRL.transform stores).  A human with a non-finite coordinate falls into no cell.  Rows the reference has
+ * no answer for are ZERO maps: humans at index >= hcount[e] (which are in nobody's map either) and the single human
+ * of an env with hcount[e] = 1 (or N = 1), where the reference's np.concatenate of an empty list raises.
+ * om: [E][N][48] float32 device out.  w_om / b_om: device fragments of mlp1.0.weight[:, 13:61] (mcn_pack_linear with
+ * three natural input tiles over columns 13 .. 60 and ten output tiles in mcn_sarl_net's ragged-tile order) and of
+ * mlp1.0.bias; init: [E][N][160] float32 device out, W[:, 13:61] om + bias in that output-slot order -- what
+ * mcn_sarl_predict_om starts mlp1.0's accumulators from.  w_om, b_om and init are given together or all NULL (maps only).
+ */
+int mcn_sarl_om_prepare(const mcn_env_state *st, double time_step, const double *next_hpos, const double *next_hvel,
+                        double cell_size, const float *w_om, const float *b_om, float *om, float *init,
+                        int32_t E, int32_t N, void *stream);
+
+/*
+ * mcn_sarl_predict_om -- mcn_sarl_predict for an OM-SARL network: net->w_m1a holds mlp1.0.weight[:, 0:13] as for SARL,
+ * net->b_m1a is not read, and `om_init` ([E][N][160], mcn_sarl_om_prepare's `init` of the same step, same stream) is
+ * where mlp1.0 starts from for all A actions of an env.  Same workspace, same MFMA work per (env, action) as SARL.
+ */
+int mcn_sarl_predict_om(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
+                        double time_step, double gamma_pow, int32_t kinematics, void *workspace,
+                        double *values, int32_t *best, double *best_val, float *attention,
+                        const double *next_hpos, const double *next_hvel, const double *rewards,
+                        double *action_out, double epsilon, uint64_t seed, const float *om_init,
+                        int32_t E, int32_t N, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LSTM-RL and CADRL value networks: the same 81-action one-step look-ahead (crowd_nav/policy/lstm_rl.py:9-33,90-103,
  * cadrl.py:21-29,131-178, multi_human_rl.py:11-63).  float32 MFMA layers only (no x3 fragments).

@@ -26,7 +26,11 @@ long attn_world_workspace_float4s(int E, int N);
 int launch_sarl_c(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                   double gamma_pow, int kinematics, void *workspace, double *values, int32_t *best, double *best_val,
                   float *attention, const double *next_hpos, const double *next_hvel, const double *reward_in,
-                  double *action_out, double epsilon, unsigned long long seed, int E, int N, hipStream_t stream);
+                  double *action_out, double epsilon, unsigned long long seed, int E, int N, const float *om_init,
+                  hipStream_t stream);
+int launch_sarl_om(const mcn_env_state *st, double dt, const double *next_hpos, const double *next_hvel,
+                   double cell_size, const float *w_om, const float *b_om, float *om, float *init, int E, int N,
+                   hipStream_t stream);
 int launch_lstm_rl(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                    double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val, int32_t *order,
                    const double *next_hpos, const double *next_hvel, const double *reward_in, double *action_out,
@@ -373,7 +377,8 @@ static int sarl_lookahead_impl(const mcn_sarl_net *net, const mcn_env_state *st,
                                double time_step, double gamma_pow, int32_t kinematics, void *workspace,
                                double *values, int32_t *best, double *best_val, float *attention,
                                const double *next_hpos, const double *next_hvel, const double *rewards,
-                               double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream)
+                               double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N,
+                               const float *om_init, void *stream)
 {
     if (!lookahead_common_ok(net, sizeof(*net), st, actions, A, time_step, kinematics, values, next_hpos, next_hvel,
                              epsilon, E, N))
@@ -383,7 +388,7 @@ static int sarl_lookahead_impl(const mcn_sarl_net *net, const mcn_env_state *st,
     if (best && !best_val) return MCN_EINVAL;           // ... but not without best_val
     return mcn::launch_sarl_c(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best,
                               best_val, attention, next_hpos, next_hvel, rewards, action_out, epsilon,
-                              (unsigned long long)seed, E, N, (hipStream_t)stream);
+                              (unsigned long long)seed, E, N, om_init, (hipStream_t)stream);
 }
 
 int mcn_sarl_lookahead(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
@@ -392,7 +397,7 @@ int mcn_sarl_lookahead(const mcn_sarl_net *net, const mcn_env_state *st, const d
                        int32_t E, int32_t N, void *stream)
 {
     return sarl_lookahead_impl(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best, best_val,
-                               attention, nullptr, nullptr, nullptr, nullptr, 0.0, 0, E, N, stream);
+                               attention, nullptr, nullptr, nullptr, nullptr, 0.0, 0, E, N, nullptr, stream);
 }
 
 int mcn_sarl_lookahead_env(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
@@ -403,7 +408,7 @@ int mcn_sarl_lookahead_env(const mcn_sarl_net *net, const mcn_env_state *st, con
 {
     if (!next_hpos || !next_hvel || !rewards) return MCN_EINVAL;
     return sarl_lookahead_impl(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best, best_val,
-                               attention, next_hpos, next_hvel, rewards, nullptr, 0.0, 0, E, N, stream);
+                               attention, next_hpos, next_hvel, rewards, nullptr, 0.0, 0, E, N, nullptr, stream);
 }
 
 int mcn_sarl_predict(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
@@ -415,7 +420,35 @@ int mcn_sarl_predict(const mcn_sarl_net *net, const mcn_env_state *st, const dou
     if (!best || !action_out) return MCN_EINVAL;
     if ((next_hpos == nullptr) != (rewards == nullptr)) return MCN_EINVAL;
     return sarl_lookahead_impl(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best, best_val,
-                               attention, next_hpos, next_hvel, rewards, action_out, epsilon, seed, E, N, stream);
+                               attention, next_hpos, next_hvel, rewards, action_out, epsilon, seed, E, N, nullptr, stream);
+}
+
+int mcn_sarl_om_prepare(const mcn_env_state *st, double time_step, const double *next_hpos, const double *next_hvel,
+                        double cell_size, const float *w_om, const float *b_om, float *om, float *init,
+                        int32_t E, int32_t N, void *stream)
+{
+    if (!st || !om) return MCN_EINVAL;
+    if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
+    if (!st->hpos || !st->hvel) return MCN_EINVAL;
+    if ((next_hpos == nullptr) != (next_hvel == nullptr)) return MCN_EINVAL;
+    if (!(time_step >= 0.0) || !(cell_size > 0.0)) return MCN_EINVAL;
+    // the layer's operands and its output go together: all three, or none (maps only)
+    if ((w_om == nullptr) != (init == nullptr) || (b_om == nullptr) != (init == nullptr)) return MCN_EINVAL;
+    return mcn::launch_sarl_om(st, time_step, next_hpos, next_hvel, cell_size, w_om, b_om, om, init, E, N,
+                               (hipStream_t)stream);
+}
+
+int mcn_sarl_predict_om(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int32_t A,
+                        double time_step, double gamma_pow, int32_t kinematics, void *workspace,
+                        double *values, int32_t *best, double *best_val, float *attention,
+                        const double *next_hpos, const double *next_hvel, const double *rewards,
+                        double *action_out, double epsilon, uint64_t seed, const float *om_init,
+                        int32_t E, int32_t N, void *stream)
+{
+    if (!best || !action_out || !om_init) return MCN_EINVAL;
+    if ((next_hpos == nullptr) != (rewards == nullptr)) return MCN_EINVAL;
+    return sarl_lookahead_impl(net, st, actions, A, time_step, gamma_pow, kinematics, workspace, values, best, best_val,
+                               attention, next_hpos, next_hvel, rewards, action_out, epsilon, seed, E, N, om_init, stream);
 }
 
 // validation of mcn_lstm_rl_predict / mcn_cadrl_predict: the common part, and every output required

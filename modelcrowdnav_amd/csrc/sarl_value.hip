@@ -87,6 +87,7 @@ struct SarlParams {
     PairParams c;                                         // ngroups: 4-tile groups (one per workgroup pass)
     float4 *workspace;                                    // [resident waves][N][12 rows][64] float4 (+ 7 rows unused)
     float *attention;                                     // [E*A*N] or NULL
+    const float4 *om_init;                                // WITH_OM: [E*N][40], mlp1.0's accumulator start (sarl_om.hip)
 };
 
 // Diagnostic build only (tools/sarl_phases.py): shader cycles each resident wavefront spends in each phase of a tile,
@@ -122,7 +123,10 @@ constexpr int kSarlWaves = kStageThreads / 64;     // 8 wavefronts share one LDS
 // layer that follows it (mfma_chain.hpp: dense_flow, dense_flow_x3).
 // USE_X3 = false: float32 MFMA layers (v_mfma_f32_16x16x4_f32); USE_X3 = true: the same layers on the bf16 matrix pipe with every
 // operand split into three bfloat16 pieces (mfma_chain.hpp: dense_flow_x3) -- float32-accurate, ~2.7 x fewer pipe cycles.
-template <bool USE_X3>
+// WITH_OM (OM-SARL, sarl.py with_om = true: mlp1.0 is 61 -> 150 on [x13 | occupancy map 48]): the map's share of mlp1.0
+// and the bias are the same for every action of an env and come precomputed per (env, human) in p.om_init, so mlp1.0
+// stays the 13-wide layer and takes that row as its accumulator start, as attention.0 takes its global half.
+template <bool USE_X3, bool WITH_OM>
 __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl_value_kernel(const SarlParams p)
 {
     __shared__ float4 s_stage[2 * (kStageFloat4 + kStageBias)];
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
     // chunk 0 of every layer, as the layer before it requests it
 #define SARL_FIRST(KT, KB, NT, INIT, name, bias)                                                              \
     (USE_X3 ? first_chunk_x3<KB, NT, INIT>(p.x.w_##name, bias) : first_chunk<KT, NT, INIT>(p.f.w_##name, bias))
-    const NextChunk d_m1a = SARL_FIRST(T13, B13, T150, false, m1a, p.f.b_m1a), d_m1b = SARL_FIRST(T150, B150, T100, false, m1b, p.f.b_m1b);
+    const NextChunk d_m1a = SARL_FIRST(T13, B13, T150, WITH_OM, m1a, WITH_OM ? nullptr : p.f.b_m1a), d_m1b = SARL_FIRST(T150, B150, T100, false, m1b, p.f.b_m1b);
     const NextChunk d_atg = SARL_FIRST(T100, B100, T100, false, atg, p.f.b_ata), d_ata = SARL_FIRST(T100, B100, T100, true, ata, nullptr);
     const NextChunk d_atb = SARL_FIRST(T100, B100, T100, false, atb, p.f.b_atb), d_atc = SARL_FIRST(T100, B100, T1, false, atc, p.f.b_atc);
     const NextChunk d_m2a = SARL_FIRST(T100, B100, T100, false, m2a, p.f.b_m2a), d_m2b = SARL_FIRST(T100, B100, T50, false, m2b, p.f.b_m2b);
@@ -197,6 +201,16 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
         // one to make in passing
         int tid_i = tid;
         asm volatile("" : "+v"(tid_i));
+        // mlp1.0's accumulator start of this human: ten 16-byte loads, by the LANE's env (a tile spans two envs whenever
+        // A is not a multiple of 16); in registers for the length of that layer (fetched tile by tile inside the layer
+        // the loads would queue on vmcnt behind the LDS-DMA weight stream: DESIGN 9)
+        f32x4 omi[WITH_OM ? T150 : 1];
+        if constexpr (WITH_OM) {
+            const float4 *src = p.om_init + ((long)e * N + i) * (T150 * 4) + q;
+#pragma unroll
+            for (int n = 0; n < T150; ++n) { const float4 v = src[4 * n]; omi[n] = (f32x4){v.x, v.y, v.z, v.w}; }
+        }
+        const f32x4 *const m1a_init = WITH_OM ? omi : nullptr;
         const HumanTile ht = human_tile(c, (long)e * N + i, rn, ra.x, sf, q, i < ne, dmin);
         poisoned = poisoned || (i < ne && ht.nonfinite);
         f32x4 x[T13] = {ht.x};
@@ -207,7 +221,7 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
         if constexpr (USE_X3) {
             const X3 xin[B13] = {split8(x[0], zero4)};
             X3 h1p[B150];
-            dense_flow_x3<B13, T150, true, false>(xin, nullptr, h1, p.x.w_m1a, reinterpret_cast<const float4 *>(p.f.b_m1a), F, lane, d_m1b);
+            dense_flow_x3<B13, T150, true, WITH_OM>(xin, m1a_init, h1, p.x.w_m1a, reinterpret_cast<const float4 *>(p.f.b_m1a), F, lane, d_m1b);
             split_after(h1, h1p);
             SARL_PHASE(2);              // mlp1.0
             X3 h2p[B100];
@@ -224,7 +238,7 @@ __global__ __launch_bounds__(kSarlWaves * 64, kSarlWaves >= 8 ? 1 : 2) void sarl
                 ws[(i * WSR + 3 * m + 2) * 64 + lane] = __builtin_bit_cast(float4, h2p[m].lo);
             }
         } else {
-        dense_flow<T13, T150, true, false, 4, 4>(x, nullptr, h1, p.f.w_m1a, p.f.b_m1a, F, lane, d_m1b);
+        dense_flow<T13, T150, true, WITH_OM, 4, 4>(x, m1a_init, h1, p.f.w_m1a, p.f.b_m1a, F, lane, d_m1b);
         SARL_PHASE(2);                  // mlp1.0
         dense_flow<T150, T100, true, false, 2, 4>(h1, nullptr, h2, p.f.w_m1b, p.f.b_m1b, F, lane, (i + 1 < N ? d_m1a : d_atg));
         SARL_PHASE(3);                  // mlp1.2
@@ -465,8 +479,14 @@ int launch_sarl(SarlParams &p, int32_t *best, double *best_val, double *action_o
                 unsigned long long seed, hipStream_t stream)
 {
     const int blocks = (int)(p.c.ngroups < kSarlMaxBlocks ? p.c.ngroups : kSarlMaxBlocks);
-    if (p.x.w_m1a) hipLaunchKernelGGL(sarl_value_kernel<true>, dim3(blocks), dim3(kSarlWaves * 64), 0, stream, p);
-    else hipLaunchKernelGGL(sarl_value_kernel<false>, dim3(blocks), dim3(kSarlWaves * 64), 0, stream, p);
+    const dim3 grid(blocks), block(kSarlWaves * 64);
+    if (p.om_init) {
+        if (p.x.w_m1a) hipLaunchKernelGGL((sarl_value_kernel<true, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((sarl_value_kernel<false, true>), grid, block, 0, stream, p);
+    } else {
+        if (p.x.w_m1a) hipLaunchKernelGGL((sarl_value_kernel<true, false>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((sarl_value_kernel<false, false>), grid, block, 0, stream, p);
+    }
     if (best) {
         hipLaunchKernelGGL(sarl_argmax_kernel, dim3(p.c.E), dim3(64), 0, stream, p.c.values, p.c.rpos, p.c.rgoal, p.c.rrad,
                            p.c.E, p.c.A, best, best_val, p.c.actions, action_out, epsilon, seed);
@@ -487,7 +507,8 @@ int launch_sarl_argmax(const double *values, const double *rpos, const double *r
 int launch_sarl_c(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                   double gamma_pow, int kinematics, void *workspace, double *values, int32_t *best, double *best_val,
                   float *attention, const double *next_hpos, const double *next_hvel, const double *reward_in,
-                  double *action_out, double epsilon, unsigned long long seed, int E, int N, hipStream_t stream)
+                  double *action_out, double epsilon, unsigned long long seed, int E, int N, const float *om_init,
+                  hipStream_t stream)
 {
     SarlParams p;
     const float4 *const *src = reinterpret_cast<const float4 *const *>(net);
@@ -499,6 +520,7 @@ int launch_sarl_c(const mcn_sarl_net *net, const mcn_env_state *st, const double
     if (net->x3 && tuning_sarl_x3()) memcpy(&p.x, net->x3, sizeof(p.x));
     p.c = pair_params(st, actions, A, dt, gamma_pow, kinematics, values, next_hpos, next_hvel, reward_in, E, N, kSarlWaves);
     p.workspace = reinterpret_cast<float4 *>(workspace); p.attention = attention;
+    p.om_init = reinterpret_cast<const float4 *>(om_init);
     return launch_sarl(p, best, best_val, action_out, epsilon, seed, stream);
 }
 

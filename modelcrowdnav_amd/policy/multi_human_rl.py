@@ -16,6 +16,10 @@ from .cadrl import CADRL
 from ..envs.utils.action import ActionRot, ActionXY
 
 
+OM_CELL_NUM, OM_CHANNELS = 4, 3           # the [om] geometry sarl_om.hip is built for (policy.config); any cell_size
+OM_WIDTH = OM_CELL_NUM ** 2 * OM_CHANNELS
+
+
 class MultiHumanRL(CADRL):
     """The [N,13]-rows policies (SARL, LSTM-RL).  The look-ahead plumbing (_lookahead, _query_env, predict_batch) is
     CADRL's; a subclass supplies `_pack` and the launch hook `_launch`."""
@@ -40,14 +44,14 @@ class MultiHumanRL(CADRL):
         me, humans = state.self_state, state.human_states
         if self.action_space is None:
             self.build_action_space(me.v_pref)
-        if self.with_om:
-            raise NotImplementedError("occupancy maps (with_om) are outside this build's scope")
         probability = np.random.random()                       # drawn unconditionally, as the reference does
         if self.phase == "train" and probability < self.epsilon:
             max_action = self.action_space[np.random.choice(len(self.action_space))]
         else:
-            dev = self._gpu_device()
             N = len(humans)
+            if self.with_om:
+                self._om_needs_others(N)
+            dev = self._gpu_device()
             # one host row, one host-to-device copy; the state arrays are views of it (16-byte aligned: pairs first)
             row = [c for h in humans for c in (h.px, h.py)] + [c for h in humans for c in (h.vx, h.vy)] + \
                   [me.px, me.py, me.vx, me.vy, me.gx, me.gy] + [h.radius for h in humans] + [me.radius, me.v_pref, me.theta]
@@ -91,7 +95,8 @@ class MultiHumanRL(CADRL):
         """multi_human_rl.py:90-104: [N,13] rotated rows (float32) for the replay memory."""
         rows = torch.cat([torch.Tensor([state.self_state + h]).to(self.device) for h in state.human_states], dim=0)
         if self.with_om:
-            raise NotImplementedError("occupancy maps (with_om) are outside this build's scope")
+            om = self.build_occupancy_maps(state.human_states)            # of the CURRENT states (:99-101)
+            return torch.cat([self.rotate(rows), om.to(self.device)], dim=1)
         return self.rotate(rows)
 
     def transform_batch(self, env):
@@ -103,7 +108,55 @@ class MultiHumanRL(CADRL):
                          env.rtheta.unsqueeze(1)], 1).to(f)                                  # [E,9]
         hum = torch.cat([env.hpos, env.hvel, env.hrad.unsqueeze(2)], 2).to(f)                 # [E,N,5]
         rows = torch.cat([rob.unsqueeze(1).expand(E, N, 9), hum], 2).reshape(E * N, 14)
-        return self.rotate(rows).view(E, N, 13)
+        rows = self.rotate(rows).view(E, N, 13)
+        if self.with_om:
+            # maps of the current states; env.hcount, when the env keeps one, masks as in the look-ahead
+            st, hcount = env._st, getattr(env, "hcount", None)
+            if hcount is not None:
+                st = _hip.EnvState.from_buffer_copy(env._st)
+                st.hcount = _hip.ptr(hcount)
+            om = torch.empty(E, N, OM_WIDTH, dtype=f, device=env.device)
+            self._om_prepare(st, 0.0, None, None, om, E, N, env.device)
+            rows = torch.cat([rows, om.to(rows.device)], 2)
+        return rows
 
     def input_dim(self):
         return self.joint_state_dim + (self.cell_num ** 2 * self.om_channel_size if self.with_om else 0)
+
+    # ------------------------------------------------------------------ occupancy maps (with_om)
+    @staticmethod
+    def _om_needs_others(n):
+        if n < 2:
+            # the reference's np.concatenate of an empty list of other humans (multi_human_rl.py:117-118)
+            raise ValueError("need at least one array to concatenate (an occupancy map needs another human)")
+
+    def _om_geometry_check(self):
+        if (self.cell_num, self.om_channel_size) != (OM_CELL_NUM, OM_CHANNELS) or not self.cell_size > 0:
+            raise ValueError("sarl_om.hip is built for the shipped occupancy-map geometry (policy.config [om]: cell_num = "
+                             "%d, om_channel_size = %d, a positive cell_size); got cell_num = %r, om_channel_size = %r, "
+                             "cell_size = %r" % (OM_CELL_NUM, OM_CHANNELS, self.cell_num, self.om_channel_size,
+                                                 self.cell_size))
+
+    def _om_prepare(self, st, dt, npos, nvel, om, E, N, dev, net=None, init=None):
+        """mcn_sarl_om_prepare: the maps of st's humans (after dt of constant velocity, or the given next states) into
+        `om` [E,N,48] and, with the packed net, their share of mlp1.0 into `init` [E,N,160]."""
+        self._om_geometry_check()
+        rc = _hip.lib.mcn_sarl_om_prepare(st, float(dt), _hip.ptr(npos), _hip.ptr(nvel), float(self.cell_size),
+                                          _hip.ptr(net.om_w) if net is not None else None,
+                                          _hip.ptr(net.om_b) if net is not None else None, _hip.ptr(om),
+                                          _hip.ptr(init), E, N, _hip.stream_ptr(dev))
+        _hip.check(rc, "mcn_sarl_om_prepare")
+
+    def build_occupancy_maps(self, human_states):
+        """multi_human_rl.py:109-163: [N, cell_num^2 * om_channel_size] float32 (CPU tensor, as the reference's), one
+        E = 1 mcn_sarl_om_prepare launch -- the maps have one definition, on the device."""
+        N = len(human_states)
+        self._om_needs_others(N)
+        dev = self._gpu_device()
+        stage = torch.tensor([c for h in human_states for c in (h.px, h.py)] +
+                             [c for h in human_states for c in (h.vx, h.vy)], dtype=torch.float64).to(dev)
+        st = _hip.EnvState()
+        st.hpos, st.hvel = _hip.ptr(stage[:2 * N]), _hip.ptr(stage[2 * N:])
+        om = torch.empty(1, N, OM_WIDTH, dtype=torch.float32, device=dev)
+        self._om_prepare(st, 0.0, None, None, om, 1, N, dev)
+        return om[0].cpu()

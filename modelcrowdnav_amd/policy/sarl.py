@@ -5,6 +5,11 @@ mlp1.{0,2} / mlp2.{0,2} / attention.{0,2,4} / mlp3.{0,2,4,6} .weight/.bias and `
 files load unchanged (train.py:57-58,147-148).  Its torch forward exists for training code that
 back-propagates through it; every inference on the rollout path (`SARL.predict`,
 `SARL.predict_batch`) runs sarl_value.hip on weights re-packed into MFMA operand order.
+
+`[sarl] with_om = true` (OM-SARL): mlp1.0 is 61 -> 150 on [13 rotated features | 48 occupancy-map entries].  The maps
+do not depend on the candidate action, so one mcn_sarl_om_prepare launch per step builds them and multiplies them
+through mlp1.0's columns 13..60 (+ bias); the look-ahead starts mlp1.0's accumulators from that row and is otherwise
+SARL's (sarl_om.hip, sarl_value.hip WITH_OM).
 """
 import ctypes as C
 import logging
@@ -16,7 +21,7 @@ import torch.nn as nn
 from .. import _hip
 from .._pack import ident as _ident, natural as _natural, pack_linear
 from .cadrl import mlp
-from .multi_human_rl import MultiHumanRL
+from .multi_human_rl import OM_WIDTH, MultiHumanRL
 
 
 class ValueNetwork(nn.Module):
@@ -87,10 +92,12 @@ class _SarlNet(C.Structure):
 _hip.check_mirrors({_hip.SIZEOF_SARL_NET: _SarlNet, _hip.SIZEOF_SARL_X3: _SarlX3})
 
 
-def pack_value_network(model, dev):
-    """state_dict -> (ctypes mcn_sarl_net, [device tensors kept alive])."""
+def pack_value_network(model, dev, with_om=False):
+    """state_dict -> (ctypes mcn_sarl_net, [device tensors kept alive]).  with_om: mlp1.0.weight is (150, 61); its
+    columns 0..12 go into `m1a` as for SARL, columns 13..60 and the bias into the fragments of mcn_sarl_om_prepare
+    (net.om_w / net.om_b, attributes of the ctypes object beside the C fields)."""
     sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in model.state_dict().items()}
-    expect = {"mlp1.0": (150, 13), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
+    expect = {"mlp1.0": (150, 13 + (OM_WIDTH if with_om else 0)), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
               "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
               "mlp3.0": (150, 56), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (1, 100)}
     for k, shp in expect.items():
@@ -119,6 +126,10 @@ def pack_value_network(model, dev):
         setattr(x3, "w_" + name, dx.data_ptr())
     keep.append(x3)                                     # the host struct mcn_sarl_net.x3 points at
     net.x3 = C.addressof(x3)
+    net.om_w = net.om_b = None
+    if with_om:
+        net.om_w, net.om_b = pack_linear(sd["mlp1.0.weight"], sd["mlp1.0.bias"], _natural(OM_WIDTH, 3, offset=13),
+                                         _ident(150, 10), dev, what="mcn_pack_linear(mlp1.0 occupancy-map columns)")
     return net, keep
 
 
@@ -133,6 +144,8 @@ class SARL(MultiHumanRL):
         self.set_common_parameters(config)
         dims = lambda key: [int(x) for x in config.get("sarl", key).split(", ")]
         self.with_om = config.getboolean("sarl", "with_om")
+        if self.with_om:
+            self._om_geometry_check()
         with_global_state = config.getboolean("sarl", "with_global_state")
         if not with_global_state:
             raise NotImplementedError("with_global_state=false is outside this build's scope (shipped config: true)")
@@ -145,7 +158,7 @@ class SARL(MultiHumanRL):
         logging.info("Policy: %s %s global state", self.name, "w/" if with_global_state else "w/o")
 
     def _pack(self, dev):
-        return pack_value_network(self.model, dev)
+        return pack_value_network(self.model, dev, bool(self.with_om))
 
     _attention = True
 
@@ -154,12 +167,21 @@ class SARL(MultiHumanRL):
 
     def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
         npos, nvel, rew = env_next if env_next is not None else (None, None, None)
-        rc = _hip.lib.mcn_sarl_predict(C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin,
-                                       _hip.ptr(b["ws"]), _hip.ptr(b["values"]), _hip.ptr(b["best"]),
-                                       _hip.ptr(b["best_val"]), _hip.ptr(b["att"]) if want_attention else None,
-                                       _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew), _hip.ptr(b["action"]),
-                                       float(epsilon), seed, E, N, _hip.stream_ptr(dev))
-        _hip.check(rc, "mcn_sarl_predict")
+        head = (C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin, _hip.ptr(b["ws"]),
+                _hip.ptr(b["values"]), _hip.ptr(b["best"]), _hip.ptr(b["best_val"]),
+                _hip.ptr(b["att"]) if want_attention else None, _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew),
+                _hip.ptr(b["action"]), float(epsilon), seed)
+        if not self.with_om:
+            _hip.check(_hip.lib.mcn_sarl_predict(*head, E, N, _hip.stream_ptr(dev)), "mcn_sarl_predict")
+            return
+        # the maps of the humans' next states (multi_human_rl.py:46-49: built once, for every action) and their share of
+        # mlp1.0, then the look-ahead that starts mlp1.0 from it
+        if b.get("om_init") is None:
+            b["om"] = torch.empty(E, N, OM_WIDTH, dtype=torch.float32, device=dev)
+            b["om_init"] = torch.empty(E, N, 160, dtype=torch.float32, device=dev)
+        self._om_prepare(st, float(self.time_step), npos, nvel, b["om"], E, N, dev, net, b["om_init"])
+        _hip.check(_hip.lib.mcn_sarl_predict_om(*head, _hip.ptr(b["om_init"]), E, N, _hip.stream_ptr(dev)),
+                   "mcn_sarl_predict_om")
 
     def get_attention_weights(self):
         """sarl.py:88-89: the attention weights of the model's last forward -- after predict() those of the LAST

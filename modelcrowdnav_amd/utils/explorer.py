@@ -70,8 +70,6 @@ class Explorer(object):
             eps = getattr(pol, "epsilon", None)
             if eps is None or eps > 0:
                 return "train phase with epsilon-greedy exploration on the shared numpy stream"
-        if getattr(pol, "with_om", False):
-            return "occupancy maps"
         if update_memory:
             src = self.target_policy if imitation_learning else pol
             if not hasattr(src, "transform_batch"):

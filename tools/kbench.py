@@ -53,6 +53,7 @@ def main():
     ap.add_argument("--step-block", type=int, default=-1, help="mcn_tuning.step_block (64 / 256)")
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--sarl", action="store_true")
+    ap.add_argument("--om", action="store_true", help="with --sarl: OM-SARL ([sarl] with_om = true: mcn_sarl_om_prepare + mcn_sarl_predict_om)")
     ap.add_argument("--rollout", type=int, default=0, help="time mcn_env_rollout with this many steps per launch")
     ap.add_argument("--sgan", action="store_true", help="time mcn_sgan_step (shipped pool-net weights) at --sizes x --humans")
     ap.add_argument("--lstm-rl", action="store_true", help="time mcn_lstm_rl_predict at 4096 envs x --humans")
@@ -74,7 +75,7 @@ def main():
         return
     if a.sarl:
         for N in [int(x) for x in str(a.humans).split(",")]:
-            sarl_bench(4096, N)
+            sarl_bench(4096, N, om=a.om)
         return
     dev = torch.device("cuda", 0)
     N = a.humans
@@ -145,13 +146,14 @@ def rollout_bench(a):
         del env
 
 
-def sarl_bench(E=4096, N=5, iters=5):
-    """mcn_sarl_lookahead alone and SARL-driven env steps (BASELINE config 3)."""
+def sarl_bench(E=4096, N=5, iters=5, om=False):
+    """mcn_sarl_lookahead alone and SARL-driven env steps (BASELINE config 3).  om: OM-SARL -- the same look-ahead with
+    mlp1.0 started from the occupancy maps' share, plus the launch that builds it."""
     from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.policy.sarl import SARL
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    pol = SARL(); pol.configure(configs.policy_config()); pol.kinematics = "holonomic"
+    pol = SARL(); pol.configure(configs.policy_config(**({"sarl.with_om": "true"} if om else {}))); pol.kinematics = "holonomic"
     pol.set_device(dev); pol.set_phase("test"); pol.time_step = 0.25
     env, _ = bench.build_env(E, N, 0, dev)
     for _ in range(2):
@@ -165,7 +167,7 @@ def sarl_bench(E=4096, N=5, iters=5):
     e.record(); torch.cuda.synchronize()
     ms = s.elapsed_time(e) / iters
     r = bench._sarl_roofline(E, N, ms)
-    print("SARL lookahead N=%d E=%d: %.3f ms/launch  %.1f TFLOP/s executed = %.3f of the %.1f peak [%s]; float32-MFMA "
+    print(("OM-" if om else "") + "SARL lookahead N=%d E=%d: %.3f ms/launch  %.1f TFLOP/s executed = %.3f of the %.1f peak [%s]; float32-MFMA "
           "equivalent %.1f TFLOP/s = %.3f of the fp32 MFMA peak 157.3 (%.1f by the reference's FLOP count)  %.3f M env-steps/s" % (
               N, E, ms, r["achieved"], r["frac"], r["peak"], "bf16x3" if bench.sarl_uses_x3() else "f32", r["f32_mfma_equivalent_rate"],
               r["f32_mfma_equivalent_rate_over_f32_peak"], r["reference_flop_rate"], E / ms / 1e3))
