@@ -89,6 +89,84 @@ def test_more_bad_arguments_are_rejected_on_host():
     assert ctypes.sizeof(_hip.ScenarioCfg) == 10 * 8 + 2 * 4
 
 
+_ROLLOUT_VALIDATION = r"""
+import ctypes as C
+from modelcrowdnav_amd import _hip
+fake = 0x1000                                 # never dereferenced: validation fails first
+cfg = _hip.EnvCfg(0.25, 25.0, 1.0, -0.25, 0.2, 0.5, 0.0, 10.0, 5.0, 10, 0, _hip.HUMANS_ORCA, _hip.KIN_HOLONOMIC, 1, 0)
+st = _hip.EnvState(*([fake] * 13))
+out = _hip.EnvOut(fake, None, fake, fake, None)
+
+
+def good(pool=True):
+    r = _hip.Rollout()
+    r.disc_table, r.disc_len, r.state, r.fin_slots = fake, 102, fake, 1
+    r.fin_return = r.fin_time = r.fin_info = fake
+    if pool:
+        r.pool_hpos = r.pool_hgoal = r.pool_hrad = r.pool_hvpref = r.pool_hvel = fake
+        r.pool_size, r.case_stride = 16, 3
+    return r
+
+
+def rejected(r):
+    a = _hip.lib.mcn_env_step(cfg, st, C.c_void_p(fake), None, out, r, 4, 5, 1, None)
+    b = _hip.lib.mcn_env_rollout(cfg, st, C.c_void_p(fake), 8, out, r, 4, 5, None)
+    assert a == b, (a, b)
+    return a == _hip.MCN_EINVAL
+
+
+# everything but the rollout struct is acceptable: the unmodified struct gets past validation (and, with no device in
+# sight, fails at the launch), so each MCN_EINVAL below comes from the one field that was changed
+# (made only once the runtime itself confirms that it sees no device: never a launch on fake addresses)
+count = C.c_int(-1)
+err = C.CDLL("libamdhip64.so").hipGetDeviceCount(C.byref(count))
+if err != 0 or count.value <= 0:
+    assert _hip.lib.mcn_env_step(cfg, st, C.c_void_p(fake), None, out, good(), 4, 5, 1, None) == _hip.MCN_ELAUNCH
+    print("POSITIVE_CONTROL_OK")
+cases = {
+    "state with a NULL table": dict(disc_table=None),
+    "state with disc_len = 0": dict(disc_len=0),
+    "state with disc_len < 0": dict(disc_len=-1),
+    "state with fin_slots = 0": dict(fin_slots=0),
+    "a pool without state": dict(state=None),
+    "a pool without pool_hgoal": dict(pool_hgoal=None),
+    "a pool without pool_hrad": dict(pool_hrad=None),
+    "a pool without pool_hvpref": dict(pool_hvpref=None),
+    "pool_size = 0": dict(pool_size=0, case_stride=0),
+    "case_stride = -1": dict(case_stride=-1),
+    "case_stride = pool_size": dict(case_stride=16),
+}
+for what, fields in cases.items():
+    r = good()
+    for k, v in fields.items():
+        setattr(r, k, v)
+    assert rejected(r), what
+# the same three rules about `state` hold without a pool
+for fields in (dict(disc_table=None), dict(disc_len=0), dict(fin_slots=0)):
+    r = good(pool=False)
+    for k, v in fields.items():
+        setattr(r, k, v)
+    assert rejected(r), fields
+print("ROLLOUT_VALIDATION_OK")
+"""
+
+
+def test_rollout_struct_is_validated_on_host():
+    """mcn_rollout's own rules (include/mcn.h), through mcn_env_step and mcn_env_rollout: everything else about the call
+    is acceptable, so MCN_EINVAL comes from the rollout struct.  The pointers are fakes, so a check that went missing
+    would launch a kernel on them: the calls are made in a fresh child process that sees NO device
+    (HIP_VISIBLE_DEVICES / ROCR_VISIBLE_DEVICES), where such a launch fails with MCN_ELAUNCH instead of faulting a GPU
+    that others share."""
+    import subprocess
+    import sys
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1",
+               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    res = subprocess.run([sys.executable, "-c", _ROLLOUT_VALIDATION], env=env, cwd=ROOT, capture_output=True, text=True,
+                         timeout=300)
+    assert res.returncode == 0 and "ROLLOUT_VALIDATION_OK" in res.stdout, (res.returncode, res.stdout[-2000:], res.stderr[-2000:])
+    assert "POSITIVE_CONTROL_OK" in res.stdout, "the child process still saw a device: %s" % res.stdout[-500:]
+
+
 def test_abi_version_and_struct_sizes_are_checked_against_the_library():
     """include/mcn.h's ABI guard: the library reports the ABI it was built with and the size of every struct of the
     header; the binding refuses a library of another ABI at import (no GPU needed for either call)."""

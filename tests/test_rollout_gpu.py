@@ -20,26 +20,7 @@ def _goal_seeking(env, t):
     return (torch.where(d > 0.2, v, z) - torch.where(d < -0.2, v, z)).contiguous()
 
 
-def _oracle_episode(scen, gamma=0.9):
-    st = cport.EnvState(1, scen.shape[0])
-    st.hpx[0], st.hpy[0], st.hgx[0], st.hgy[0] = scen[:, 0], scen[:, 1], scen[:, 2], scen[:, 3]
-    st.hr[0], st.hvpref[0] = scen[:, 7], scen[:, 8]
-    st.rpy[0], st.rgy[0], st.rr[0] = -4.0, 4.0, 0.3
-    cfg = cport.default_cfg()
-    rewards, too_close, min_dist = [], 0, 0.0
-    while True:
-        dx, dy = st.rgx[0] - st.rpx[0], st.rgy[0] - st.rpy[0]
-        ax = 0.6 if dx > 0.2 else (-0.6 if dx < -0.2 else 0.0)
-        ay = 0.6 if dy > 0.2 else (-0.6 if dy < -0.2 else 0.0)
-        out = cport.env_step(cfg, st, np.array([ax]), np.array([ay]))
-        rewards.append(float(out["reward"][0]))
-        if out["info"][0] == cport.INFO_DANGER:                      # explorer.py:88-90
-            too_close += 1
-            min_dist += float(out["dmin"][0])
-        if out["done"][0]:
-            tm = 25.0 if out["info"][0] == cport.INFO_TIMEOUT else float(st.gtime[0])
-            ret = sum([pow(gamma, t * 0.25 * 1.0) * r for t, r in enumerate(rewards)])
-            return ret, int(out["info"][0]), tm, too_close, min_dist
+from tests.rollout_ref import oracle_episode as _oracle_episode  # noqa: E402  (also held to the host replay there)
 
 
 def test_vec_explorer_equals_sequential_loop():
