@@ -220,7 +220,10 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_q
         if (do_orca) {
             if (cand_r) { cvx = (float)rvel.x; cvy = (float)rvel.y; }
             float rx, ry;
-            quad_orca_velocity(c, lane, k, cand_h || cand_r, pos, vel, goal, rad, vpref,
+            // idle lanes (g >= G, envs >= E) alias env 0 and, for g >= G, get their candidates from another env's
+            // lanes: their slots count as unpopulated, so they hold no half-plane and cannot send the wavefront into
+            // the 3-D LP (as `counted` below; they store nothing)
+            quad_orca_velocity(c, lane, k, (cand_h || cand_r) && active, pos, vel, goal, rad, vpref,
                                make_float4((float)cpos.x, (float)cpos.y, cvx, cvy), crd, inv_th, inv_ts, rx, ry);
             hax = (double)rx; hay = (double)ry;
         }

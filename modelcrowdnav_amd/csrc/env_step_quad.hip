@@ -112,7 +112,9 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
     // (opaque reciprocals: the compiler would fold `apart ? 1 / a : 1 / b` into one IEEE division after the select)
     float inv_th = 1.0f / c.orca_time_horizon, inv_ts = 1.0f / (float)dt;
     asm("" : "+v"(inv_th), "+v"(inv_ts));
-    quad_orca_velocity(c, lane, k, cand_h || cand_r, pos, vel, goal, rad, vpref,
+    // idle lanes (g >= G, envs >= E) alias env 0: their slots count as unpopulated, so they hold no half-plane and
+    // cannot send the wavefront into the 3-D LP (they store nothing)
+    quad_orca_velocity(c, lane, k, (cand_h || cand_r) && active, pos, vel, goal, rad, vpref,
                        make_float4((float)cpos.x, (float)cpos.y, (float)cvel.x, (float)cvel.y), crd, inv_th, inv_ts, rx, ry);
     hax = (double)rx; hay = (double)ry;
     }

@@ -43,11 +43,12 @@ __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
     return i >= 2 ? b : a;
 }
 
-// linearProgram1 on line `no` (run-time, 0..3) against lines [0, no): uniform code, predicated steps.
+// linearProgram1 on line `no` (run-time, 0..3) against lines [0, no): uniform code, predicated steps.  `ln` is line
+// `no` itself (L[no]), handed over by the caller, who holds it without a run-time select (lane k's own sorted line).
 template <bool DIR>
-__device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], int no, float radius, float optx, float opty, float &rx, float &ry)
+__device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], const float4 &ln, int no, float radius, float optx, float opty,
+                                       float &rx, float &ry)
 {
-    const float4 ln = sel4(L, no);
     const float dp = dot2(ln.x, ln.y, ln.z, ln.w);
     const float disc = dp * dp + radius * radius - dot2(ln.x, ln.y, ln.x, ln.y);
     bool ok = !(disc < 0.0f);
@@ -194,12 +195,8 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
     srt.y = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.y)));
     srt.z = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.z)));
     srt.w = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.w)));
-    const float4 L[4] = {qb4<0>(srt), qb4<1>(srt), qb4<2>(srt), qb4<3>(srt)};
-
-    // speculative 1-D LPs, one per lane; then the incremental LP is four compare-and-take steps
-    float cx, cy;
-    // lane k's code for the take steps below: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
-    const int fcode = lp1_rt<false>(L, k, ms, prefx, prefy, cx, cy) ? 4 : k;
+    // the starting point of the take steps, the clipped preferred velocity, first: it depends on no half-plane, so it
+    // is computed while the ds_permutes are in flight
     {
         const float pp = dot2(prefx, prefy, prefx, prefy);
         const bool clip = pp > ms * ms;
@@ -207,6 +204,13 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
         rx = clip ? ms * (prefx * inv) : prefx;
         ry = clip ? ms * (prefy * inv) : prefy;
     }
+    const float4 L[4] = {qb4<0>(srt), qb4<1>(srt), qb4<2>(srt), qb4<3>(srt)};
+
+    // speculative 1-D LPs, one per lane (lane k's line L[k] is its own `srt`); then the incremental LP is four
+    // compare-and-take steps
+    float cx, cy;
+    // lane k's code for the take steps below: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
+    const int fcode = lp1_rt<false>(L, srt, k, ms, prefx, prefy, cx, cy) ? 4 : k;
     // `fail` stays nl until a violated line's 1-D LP is infeasible and then is that line, so "line I is below nl and
     // nothing failed yet" is fail > I; a violation folds the line's code in (min: nl <= 4 keeps a feasible line's 4
     // from changing it), and the candidate is taken where fail is still above I afterwards
