@@ -457,6 +457,23 @@ int mcn_sgan_step(const mcn_sgan_net *net, double *hist, int32_t push_slot, int3
                   const float *noise, const int32_t *hcount, void *workspace, double *out_vel, float *out_rel,
                   double time_step, int32_t E, int32_t N, void *stream);
 
+/*
+ * mcn_sgan_predict -- TrajectoryGenerator.forward with decoder.seq_len = T (sgan/models.py:501-553, Decoder.forward
+ * :127-164) for K user_noise vectors per scene (the K samples of generator_step's best_k / evaluate's num_samples),
+ * from the ring as it stands: nothing is pushed, hist is only read.  `oldest`, `hcount` and `workspace`
+ * (mcn_sgan_workspace_bytes(E, N)) as in mcn_sgan_step.  The encoder, the pooling module and mlp_decoder_context do not
+ * depend on the noise or on the decoder step (pool_every_timestep = False), so they run once; the K T decoder cells
+ * follow in one kernel, each step's displacement being the next step's input (:156-158).
+ * noise: [K][E][8] float; out_rel: [K][T][E*N][2] float, pred_traj_fake_rel of sample k;
+ * out_pos: [K][T][E*N][2] float64 or NULL: the last observed position (as float32, what the decoder holds) plus the
+ * running float64 sum of those float32 displacements (relative_to_abs, sgan/utils.py:85-98, without float32 drift).
+ * K < 1, K > 65535, T < 1 or a NULL net / hist / noise / workspace / out_rel: MCN_EINVAL, nothing is launched.
+ * K = T = 1 gives out_rel of mcn_sgan_step(cur_pos = NULL) bit for bit.
+ */
+int mcn_sgan_predict(const mcn_sgan_net *net, const double *hist, int32_t oldest, const float *noise, int32_t K, int32_t T,
+                     const int32_t *hcount, void *workspace, float *out_rel, double *out_pos, int32_t E, int32_t N,
+                     void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * MlpWorld one-step world model (crowd_nav/policy/world_model.py:22-42).
  * ---------------------------------------------------------------------------------------------- */
@@ -552,7 +569,7 @@ const char *mcn_version(void);
 /*
  * ABI guard.  MCN_ABI_VERSION changes whenever a struct of this header changes size or layout or an entry point
  * changes its signature (0.3 grew mcn_tuning by lp3_defer and mcn_env_out by lp3_queue: ABI 4; 0.4 grew mcn_sarl_net by
- * x3: ABI 5).  A caller built against
+ * x3: ABI 5; an entry point that is only ADDED, like mcn_sgan_predict, leaves it as it is).  A caller built against
  * another header must not pass structs to this library: compare mcn_abi_version() with the MCN_ABI_VERSION it was
  * compiled with, and (bindings without the header: ctypes, cgo) mcn_sizeof() with the size of its own struct mirrors.
  */

@@ -171,6 +171,8 @@ def _load():
     lib.mcn_sgan_workspace_bytes.restype = C.c_int64
     lib.mcn_sgan_step.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _i, _i, _vp]
     lib.mcn_sgan_step.restype = C.c_int
+    lib.mcn_sgan_predict.argtypes = [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp]
+    lib.mcn_sgan_predict.restype = C.c_int
     lib.mcn_pack_x3_bytes.argtypes, lib.mcn_pack_x3_bytes.restype = [_i, _i], C.c_int64
     lib.mcn_pack_x3.argtypes, lib.mcn_pack_x3.restype = [C.POINTER(C.c_float), _i, _i, _vp], C.c_int
     lib.mcn_abi_version.restype = _i
@@ -221,7 +223,7 @@ lib = _load()
 
 # every symbol include/mcn.h declares; tests/test_abi.py checks the .so exports each one
 EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
-            "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
+            "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict"]
 
 

@@ -48,6 +48,9 @@ int read_sarl_phases(void *dst, size_t bytes, int reset);
 int launch_sgan(const mcn_sgan_net *net, double *hist, int push_slot, int oldest, const double *cur_pos,
                 const float *noise, const int32_t *hcount, void *workspace, double *out_vel, float *out_rel,
                 double time_step, int E, int N, hipStream_t stream);
+int launch_sgan_predict(const mcn_sgan_net *net, const double *hist, int oldest, const float *noise, int K, int T,
+                        const int32_t *hcount, void *workspace, float *out_rel, double *out_pos, int E, int N,
+                        hipStream_t stream);
 int launch_orca_batch(const float *self, const float *others, const int32_t *n_other, float *out,
                       int B, int M, float neighbor_dist, int max_neighbors, float time_horizon, float time_step,
                       hipStream_t stream);
@@ -543,6 +546,22 @@ int mcn_sgan_step(const mcn_sgan_net *net, double *hist, int32_t push_slot, int3
     }
     return mcn::launch_sgan(net, hist, push_slot, oldest, cur_pos, noise, hcount, workspace, out_vel, out_rel,
                             time_step, E, N, (hipStream_t)stream);
+}
+
+int mcn_sgan_predict(const mcn_sgan_net *net, const double *hist, int32_t oldest, const float *noise, int32_t K, int32_t T,
+                     const int32_t *hcount, void *workspace, float *out_rel, double *out_pos, int32_t E, int32_t N,
+                     void *stream)
+{
+    if (!net || !hist || !noise || !workspace || !out_rel) return MCN_EINVAL;
+    if (K < 1 || K > 65535 || T < 1) return MCN_EINVAL;          // (K is a grid dimension)
+    if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS || oldest < 0 || oldest > 7) return MCN_EINVAL;
+    const float *const *fp = reinterpret_cast<const float *const *>(net);
+    for (int k = 0; k < 14; ++k) {
+        const bool pool_only = (k >= 2 && k < 6);
+        if (!fp[k] && !(pool_only && !net->pooling)) return MCN_EINVAL;
+    }
+    return mcn::launch_sgan_predict(net, hist, oldest, noise, K, T, hcount, workspace, out_rel, out_pos, E, N,
+                                    (hipStream_t)stream);
 }
 
 #ifdef MCN_DIAG

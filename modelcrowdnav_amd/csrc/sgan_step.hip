@@ -13,6 +13,7 @@
 //   sgan_encode_kernel  one wavefront = 16 pedestrians; 8 LSTM steps chained in registers (mfma_chain.hpp)
 //   sgan_pool_kernel    one wavefront = 16 partners x 5 pedestrians of their scenes; pool-net weights LDS-resident
 //   sgan_decode_kernel  one wavefront = 16 pedestrians; context MLP, noise, decoder cell, output.
+// mcn_sgan_predict runs the first two once and sgan_predict_kernel (T decoder steps for each of K noise samples) third.
 // All network arithmetic is float32 (MFMA fmaf chains); positions / velocities are float64 like the env.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -420,6 +421,87 @@ __global__ __launch_bounds__(kSganWaves * 64) void sgan_decode_kernel(const Sgan
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Full-horizon, K-sample prediction (mcn_sgan_predict): Decoder.forward (sgan/models.py:127-164) for seq_len = T and
+// K user_noise vectors per scene.  With pool_every_timestep = False nothing before add_noise (:531) depends on the
+// noise or on the decoder step, so the encoder and pool kernels above run once for all samples.  This kernel evaluates
+// mlp_decoder_context, starts sample k at dh = [context | noise_k], dc = 0 and the last observed displacement as input,
+// and per step runs the folded gate layer, the cell and hidden2pos and feeds the displacement back (:156-158).  The decoder LSTM and hidden2pos fragments are read T times per wavefront: LDS-resident (26 KiB).
+// A wavefront owns (16 pedestrians, sample k = blockIdx.y) in the layout of sgan_decode_kernel and recomputes the
+// context MLP of its pedestrians (the MFMAs of one decoder step): K fills the machine when E x N is small, and at
+// 4096 x 10 the K x 2 560 wavefronts balance where 2 560 leave half a round of the SIMDs idle (looping K inside one
+// wavefront instead was measured 15 - 45 % slower at K = 20 and 4 - 5 x slower at E = 64 .. 256: DESIGN 9).
+// K = T = 1 is sgan_decode_kernel's arithmetic, bit for bit.
+struct SganHorizon {
+    const float *noise;       // [K][E][8]
+    float *out_rel;           // [K][T][E*N][2]
+    double *out_pos;          // [K][T][E*N][2] or NULL: last_pos + float64 running sum of the float32 displacements
+    int T;
+};
+
+__global__ __launch_bounds__(kSganWaves * 64) void sgan_predict_kernel(const SganParams p, const SganHorizon r)
+{
+    __shared__ float4 s_wl[8 * 3 * 64], s_bl[8 * 4], s_wh[2 * 64], s_bh[4];
+    lds_fill_layer<kSganWaves * 64>(s_wl, s_bl, p.f.w_dlstm, p.f.b_dlstm, 3, 8, threadIdx.x);
+    lds_fill_layer<kSganWaves * 64>(s_wh, s_bh, p.f.w_h2p, p.f.b_h2p, 2, 1, threadIdx.x);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 15, q = lane >> 4;
+    const long nped = (long)p.E * p.N;
+    const long ped0 = ((long)blockIdx.x * kSganWaves + wave) * 16;
+    if (ped0 >= nped) return;
+    long ped = ped0 + j;
+    const bool valid = ped < nped;
+    if (!valid) ped = nped - 1;
+    const int e = (int)(ped / p.N);
+    const float4 mine = reinterpret_cast<const float4 *>(p.last)[ped];       // last_pos.xy, last_rel.xy
+    f32x4 ctx[2];
+    {
+        const float4 *src = reinterpret_cast<const float4 *>(p.henc + ped * 32);
+        f32x4 hi[2] = {as_tile(src[q]), as_tile(src[4 + q])};
+        f32x4 c1[4];
+        if (p.pooling) {
+            f32x4 pool = {0, 0, 0, 0};
+            if (q < 2) pool = as_tile(reinterpret_cast<const float4 *>(p.pool)[ped * 2 + q]);
+            f32x4 cin[3] = {hi[0], hi[1], pool};
+            dense<3, 4, kRelu, kBiasFrag>(cin, c1, p.f.w_c1, p.f.b_c1, lane);
+        } else {
+            dense<2, 4, kRelu, kBiasFrag>(hi, c1, p.f.w_c1, p.f.b_c1, lane);
+        }
+        dense<4, 2, kRelu, kBiasFrag>(c1, ctx, p.f.w_c2, p.f.b_c2, lane);
+    }
+    // decoder_h = [context(24), noise_k(8)] (add_noise, 'global' mix: one vector per scene and sample)
+    const int k = blockIdx.y;
+    f32x4 dh[2] = {ctx[0], ctx[1]}, dc[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    if (q >= 2) dh[1] = as_tile(reinterpret_cast<const float4 *>(r.noise + ((size_t)k * p.E + e) * 8)[q - 2]);
+    float ix = mine.z, iy = mine.w;                      // decoder input: the last observed displacement, then its own output
+    double sx = 0.0, sy = 0.0;
+    const size_t step_stride = (size_t)nped;             // float2 / double2 elements per step
+    float2 *rel = reinterpret_cast<float2 *>(r.out_rel) + (size_t)k * r.T * step_stride + ped;
+    double2 *pos = r.out_pos ? reinterpret_cast<double2 *>(r.out_pos) + (size_t)k * r.T * step_stride + ped : nullptr;
+#pragma unroll 1
+    for (int t = 0; t < r.T; ++t) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                     // the LDS reads stay inside the loop (as in sgan_encode_kernel)
+        f32x4 cat[3] = {tile_xy(ix, iy, q), dh[0], dh[1]};
+        f32x4 g[8];
+        dense<3, 8, kLinear, kBiasQuarter, 1>(cat, g, s_wl, s_bl, ln);
+        lstm_update(g, dh, dc);
+        f32x4 out[1];
+        dense<2, 1, kLinear, kBiasQuarter>(dh, out, s_wh, s_bh, ln);
+        // rows 0 / 1 of the output tile (lane group 0) are the displacement; lane group 1 takes y for tile_xy
+        ix = out[0][0];
+        iy = __shfl(out[0][1], j);
+        if (valid && q == 0) {
+            rel[t * step_stride] = make_float2(ix, iy);
+            if (pos) {
+                sx += (double)ix; sy += (double)iy;
+                pos[t * step_stride] = make_double2((double)mine.x + sx, (double)mine.y + sy);
+            }
+        }
+    }
+}
+
 static int device_cus()
 {
     static const int cus = [] {
@@ -457,6 +539,35 @@ int launch_sgan(const mcn_sgan_net *net, double *hist, int push_slot, int oldest
         hipLaunchKernelGGL(sgan_pool_kernel, dim3(grid), dim3(kPoolWaves * 64), 0, stream, p);
     }
     hipLaunchKernelGGL(sgan_decode_kernel, dim3(blocks), dim3(kSganWaves * 64), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
+}
+
+int launch_sgan_predict(const mcn_sgan_net *net, const double *hist, int oldest, const float *noise, int K, int T,
+                        const int32_t *hcount, void *workspace, float *out_rel, double *out_pos, int E, int N,
+                        hipStream_t stream)
+{
+    SganParams p;
+    const float4 *const *src = reinterpret_cast<const float4 *const *>(net);
+    const float4 **dst = reinterpret_cast<const float4 **>(&p.f);
+    for (int k = 0; k < 14; ++k) dst[k] = src[k];
+    p.hist = const_cast<double *>(hist);          // the encoder writes the ring only when a frame is pushed
+    p.cur_pos = nullptr; p.noise = nullptr; p.hcount = hcount;
+    p.henc = reinterpret_cast<float *>(workspace);
+    p.last = p.henc + (size_t)E * N * 32;
+    p.pool = p.last + (size_t)E * N * 4;
+    p.out_vel = nullptr; p.out_rel = nullptr;
+    p.E = E; p.N = N; p.pooling = net->pooling; p.push_slot = 0; p.oldest = oldest; p.time_step = 1.0;
+    const SganHorizon r = {noise, out_rel, out_pos, T};
+    const long tiles = ((long)E * N + 15) / 16;
+    const int blocks = (int)((tiles + kSganWaves - 1) / kSganWaves);
+    hipLaunchKernelGGL(sgan_encode_kernel, dim3(blocks), dim3(kSganWaves * 64), 0, stream, p);
+    if (p.pooling) {
+        const long units = tiles * ((N + kPoolIC - 1) / kPoolIC);
+        const long want = (units + kPoolWaves - 1) / kPoolWaves;
+        const int grid = (int)(want < device_cus() ? want : device_cus());
+        hipLaunchKernelGGL(sgan_pool_kernel, dim3(grid), dim3(kPoolWaves * 64), 0, stream, p);
+    }
+    hipLaunchKernelGGL(sgan_predict_kernel, dim3(blocks, K), dim3(kSganWaves * 64), 0, stream, p, r);
     return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
 }
 

@@ -50,6 +50,7 @@ _MAP = {
     "crowd_nav.utils.misc": "modelcrowdnav_amd.utils.misc",
     "sgan.models": "modelcrowdnav_amd.sgan.models",
     "sgan.utils": "modelcrowdnav_amd.sgan.utils",
+    "sgan.losses": "modelcrowdnav_amd.sgan.losses",
 }
 
 _REGISTRY = {}

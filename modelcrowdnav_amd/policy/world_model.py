@@ -2,7 +2,8 @@
 
   get_generator   :108-131  build a TrajectoryGenerator from a checkpoint dict
   SGANWorld       :134-268  E = 1 callable with the reference's constructor and return type
-  VecSGANWorld              the same step for E scenes, history kept as a ring in HBM
+  VecSGANWorld              the same step for E scenes, history kept as a ring in HBM; predict(): K-sample,
+                            multi-step futures from that ring
 
   MlpWorld        :22-51    torch module (trained by Trainer_Sim); VecMlpWorld runs it for E scenes in one HIP launch
   AttentionWorld  :54-106   torch module; VecTorchWorld runs any [B,4N] -> [B,2N] module on a VecModelCrowdSim
@@ -17,7 +18,7 @@ from torch import nn
 
 from .. import _hip
 from .._pack import ident as _ident, natural as _natural, pack_linear
-from ..sgan.models import TrajectoryGenerator, sgan_step
+from ..sgan.models import TrajectoryGenerator, sgan_predict, sgan_step
 
 
 def get_generator(checkpoint, device):
@@ -93,6 +94,20 @@ class VecSGANWorld(object):
         sgan_step(self.generator, self.hist, push, self.oldest, cur, noise.float().contiguous(), self.time_step,
                   out_vel=self.out_vel, hcount=hcount)
         return self.out_vel
+
+    def predict(self, steps, samples=1, noise=None, hcount=None):
+        """`samples` futures of `steps` decoder steps from the ring as it stands, one encoder / pooling pass for all of
+        them (mcn_sgan_predict): (displacements [K,T,E,N,2] float32, positions [K,T,E,N,2] float64).  Nothing is pushed
+        and `oldest` does not move: the next __call__ behaves as if predict had not been called.  noise: [K,E,8]; only
+        when it is None are K vectors drawn, from this world's generator (outside draw_noise's blocks)."""
+        if noise is None:
+            noise = torch.randn(int(samples), self.E, 8, generator=self._gen)
+        noise = noise.to(self.device, torch.float32).contiguous()
+        if tuple(noise.shape) != (int(samples), self.E, 8):
+            raise ValueError("noise must be [samples, E, 8]")
+        rel, pos = sgan_predict(self.generator, self.hist, self.oldest, noise, steps, hcount=hcount)
+        shape = (int(samples), int(steps), self.E, self.N, 2)
+        return rel.view(shape), pos.view(shape)
 
 
 class SGANWorld(nn.Module):

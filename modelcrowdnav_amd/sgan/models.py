@@ -5,8 +5,8 @@ sgan/models/sgan-models/*.pt and sgan-p-models/*.pt loads with load_state_dict
 (encoder.encoder.*, encoder.spatial_embedding.*, decoder.decoder.*, decoder.spatial_embedding.*,
 decoder.hidden2pos.*, pool_net.spatial_embedding.*, pool_net.mlp_pre_pool.{0,2}.*,
 mlp_decoder_context.{0,2}.*).  Inference does not run these modules: `pack()` permutes the
-weights into MFMA operand order and sgan_step.hip evaluates the network (one-step prediction,
-models.py:501-553).  SocialPooling, the discriminator, batch-norm variants and
+weights into MFMA operand order and sgan_step.hip evaluates the network (models.py:501-553: one step per
+mcn_sgan_step for the world model, decoder.seq_len steps x K noise samples per mcn_sgan_predict).  SocialPooling, the discriminator, batch-norm variants and
 pool_every_timestep are not used by any shipped checkpoint and are not built.
 """
 import ctypes as C
@@ -147,24 +147,59 @@ class TrajectoryGenerator(nn.Module):
 
     # ------------------------------------------------------------------ reference call signature
     def forward(self, obs_traj, obs_traj_rel, seq_start_end, user_noise=None):
-        """models.py:501-553 for pred_len 1 and equally sized scenes.  obs_traj [8,B,2]; returns [1,B,2]
-        float32 on obs_traj's device.  obs_traj_rel is recomputed from obs_traj (identical values)."""
-        if self.decoder.seq_len != 1:
-            raise NotImplementedError("only one-step prediction (decoder.seq_len = 1, world_model.py:252) is built")
+        """models.py:501-553.  obs_traj [8,B,2]; returns [decoder.seq_len,B,2] float32 on obs_traj's device (seq_len is
+        1 unless the caller sets it, whatever pred_len the checkpoint carries: world_model.py:252).  Scenes may differ
+        in size.  obs_traj_rel is recomputed from obs_traj (identical values)."""
+        S = int(seq_start_end.shape[0])
+        noise = user_noise if user_noise is not None else torch.randn(S, self.noise_dim[0]).to(obs_traj.device)
+        return self.sample(obs_traj, seq_start_end, noise.view(1, S, -1), int(self.decoder.seq_len))[0]
+
+    def sample(self, obs_traj, seq_start_end, noise, steps):
+        """K futures of `steps` decoder steps from one encoder / pooling pass: noise [K,S,8] (one user_noise vector per
+        sample and scene) -> pred_traj_fake_rel [K,steps,B,2] float32, rows in obs_traj's order.  Scenes of different
+        sizes are scattered into an [S, Nmax] padded ring whose unused slots the pooling module does not look at
+        (mcn_sgan_predict's hcount)."""
         dev = obs_traj.device
         if dev.type != "cuda":
             raise RuntimeError("TrajectoryGenerator inference only exists as HIP kernels; move inputs to the GPU")
-        sizes = (seq_start_end[:, 1] - seq_start_end[:, 0]).tolist()
-        if len(set(sizes)) != 1:
-            raise NotImplementedError("scenes of different sizes in one batch are not supported")
-        N, S = int(sizes[0]), len(sizes)
-        noise = user_noise if user_noise is not None else torch.randn(S, self.noise_dim[0]).to(dev)
-        hist = obs_traj.double().view(8, S, N, 2).permute(1, 0, 2, 3).contiguous()
-        vel, rel = sgan_step(self, hist, 0, 0, None, noise.float().contiguous(), 1.0, want_rel=True)
-        return rel.view(1, S * N, 2)
+        if int(steps) < 1:
+            raise ValueError("steps must be >= 1")
+        sse = torch.as_tensor(seq_start_end).to("cpu", torch.long)
+        sizes = sse[:, 1] - sse[:, 0]
+        S, N, B = int(sse.shape[0]), int(sizes.max()), int(obs_traj.shape[1])
+        noise = noise.to(dev, torch.float32).contiguous()
+        if noise.dim() != 3 or tuple(noise.shape[1:]) != (S, self.noise_dim[0]):
+            raise ValueError("noise must be [K, %d, %d]" % (S, self.noise_dim[0]))
+        if bool((sizes == N).all()) and S * N == B and int(sse[0, 0]) == 0 and bool((sse[1:, 0] == sse[:-1, 1]).all()):
+            hist = obs_traj.double().view(8, S, N, 2).permute(1, 0, 2, 3).contiguous()
+            rel, _ = sgan_predict(self, hist, 0, noise, steps, want_pos=False)
+            return rel
+        if bool((sizes < 1).any()):
+            raise ValueError("every scene of seq_start_end needs at least one pedestrian")
+        # row b of the batch -> slot (scene, index in scene) of the padded ring
+        scene = torch.repeat_interleave(torch.arange(S), sizes)
+        rows = torch.cat([torch.arange(int(a), int(b)) for a, b in sse.tolist()])
+        slot = (scene * N + (torch.arange(len(rows)) - torch.repeat_interleave(sizes.cumsum(0) - sizes, sizes))).to(dev)
+        rows = rows.to(dev)
+        padded = torch.zeros(8, S * N, 2, dtype=torch.float64, device=dev)
+        padded[:, slot] = obs_traj.double()[:, rows]
+        hist = padded.view(8, S, N, 2).permute(1, 0, 2, 3).contiguous()
+        rel, _ = sgan_predict(self, hist, 0, noise, steps, hcount=sizes.to(dev, torch.int32), want_pos=False)
+        out = torch.zeros(rel.shape[0], rel.shape[1], B, 2, dtype=torch.float32, device=dev)
+        out[:, :, rows] = rel[:, :, slot]
+        return out
 
 
 _WS = {}
+
+
+def _workspace(E, N, dev):
+    """The step's and the prediction's scratch buffer (mcn_sgan_workspace_bytes), one kept per process."""
+    key = (E, N, str(dev))
+    if key not in _WS:
+        _WS.clear()
+        _WS[key] = torch.empty(_hip.lib.mcn_sgan_workspace_bytes(E, N) // 4, dtype=torch.float32, device=dev)
+    return _WS[key]
 
 
 def sgan_step(gen, hist, push_slot, oldest, cur_pos, noise, time_step, want_rel=False, out_vel=None, hcount=None):
@@ -172,15 +207,27 @@ def sgan_step(gen, hist, push_slot, oldest, cur_pos, noise, time_step, want_rel=
     E, T, N, _ = hist.shape
     dev = hist.device
     net, _keep = gen.pack(dev)
-    key = (E, N, str(dev))
-    if key not in _WS:
-        _WS.clear()
-        _WS[key] = torch.empty(_hip.lib.mcn_sgan_workspace_bytes(E, N) // 4, dtype=torch.float32, device=dev)
     if out_vel is None:
         out_vel = torch.empty(E, N, 2, dtype=torch.float64, device=dev)
     rel = torch.empty(E * N, 2, dtype=torch.float32, device=dev) if want_rel else None
     rc = _hip.lib.mcn_sgan_step(C.byref(net), _hip.ptr(hist), int(push_slot), int(oldest), _hip.ptr(cur_pos),
-                                _hip.ptr(noise), _hip.ptr(hcount), _hip.ptr(_WS[key]), _hip.ptr(out_vel), _hip.ptr(rel),
+                                _hip.ptr(noise), _hip.ptr(hcount), _hip.ptr(_workspace(E, N, dev)), _hip.ptr(out_vel), _hip.ptr(rel),
                                 float(time_step), E, N, _hip.stream_ptr(dev))
     _hip.check(rc, "mcn_sgan_step")
     return out_vel, rel
+
+
+def sgan_predict(gen, hist, oldest, noise, steps, hcount=None, want_pos=True):
+    """Thin wrapper over mcn_sgan_predict.  hist [E,8,N,2] f64 (read only), noise [K,E,8] f32 ->
+    (rel [K,steps,E*N,2] f32, pos [K,steps,E*N,2] f64 or None)."""
+    E, _, N, _ = hist.shape
+    K, T = int(noise.shape[0]), int(steps)
+    dev = hist.device
+    net, _keep = gen.pack(dev)
+    rel = torch.empty(K, T, E * N, 2, dtype=torch.float32, device=dev)
+    pos = torch.empty(K, T, E * N, 2, dtype=torch.float64, device=dev) if want_pos else None
+    rc = _hip.lib.mcn_sgan_predict(C.byref(net), _hip.ptr(hist), int(oldest), _hip.ptr(noise), K, T, _hip.ptr(hcount),
+                                   _hip.ptr(_workspace(E, N, dev)), _hip.ptr(rel), _hip.ptr(pos), E, N,
+                                   _hip.stream_ptr(dev))
+    _hip.check(rc, "mcn_sgan_predict")
+    return rel, pos

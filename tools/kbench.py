@@ -2,6 +2,7 @@
 """Kernel micro-benchmark (GPU box): per-launch time of mcn_env_step at several batch sizes and
 human-policy modes, measured with HIP events around a hipGraph of back-to-back launches.
     python tools/kbench.py [--humans 5] [--sizes 4096,65536,1048576] [--modes orca,given]
+    python tools/kbench.py --sgan-predict --sizes 4096 --humans 10,5 --samples 1,20 --steps 8,12
     python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
 """
 import argparse
@@ -41,6 +42,39 @@ def sgan_bench(E, N, iters):
         N, E, ms * 1e3, tf, 100 * tf / bench.MFMA_F32_PEAK_TFLOPS, bench.MFMA_F32_PEAK_TFLOPS), flush=True)
 
 
+def sgan_predict_bench(E, N, K, T, iters):
+    """One mcn_sgan_predict (encoder + pool-net once, K x T decoder cells) for E scenes of N pedestrians, beside
+    mcn_sgan_step on the same ring (no push) and K T times that: what K T one-step calls would cost."""
+    from modelcrowdnav_amd.policy.world_model import generator_from_arrays
+    from modelcrowdnav_amd.sgan.models import sgan_predict, sgan_step
+    dev = torch.device("cuda", 0)
+    gen = generator_from_arrays(np.load(os.path.join(ROOT, "tests", "golden", "g6_sgan.npz")), "p", dev)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    pos = torch.rand(E, 1, N, 2, dtype=torch.float64, generator=g) * 8 - 4
+    vel = torch.rand(E, 1, N, 2, dtype=torch.float64, generator=g) - 0.5
+    k = torch.arange(7, -1, -1, dtype=torch.float64).view(1, 8, 1, 1)
+    hist = (torch.round((pos - vel * 0.25 * k) * 1e4) / 1e4).to(dev)
+    noise = torch.randn(K, E, 8, generator=g).to(dev)
+    out_vel = torch.empty(E, N, 2, dtype=torch.float64, device=dev)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(iters):
+            fn()
+        t1.record()
+        torch.cuda.synchronize()
+        return t0.elapsed_time(t1) / iters * 1e3
+
+    us_step = timed(lambda: sgan_step(gen, hist, 0, 0, None, noise[0], 0.25, want_rel=False, out_vel=out_vel))
+    us = timed(lambda: sgan_predict(gen, hist, 0, noise, T))
+    print("SGAN predict N=%d E=%d K=%d T=%d: %.1f us/call; mcn_sgan_step %.1f us/call, x K T = %.1f us (%.1f x)" % (
+        N, E, K, T, us, us_step, us_step * K * T, us_step * K * T / us), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--humans", type=str, default="5", help="humans per env (a comma list with --sarl)")
@@ -56,12 +90,23 @@ def main():
     ap.add_argument("--om", action="store_true", help="with --sarl: OM-SARL ([sarl] with_om = true: mcn_sarl_om_prepare + mcn_sarl_predict_om)")
     ap.add_argument("--rollout", type=int, default=0, help="time mcn_env_rollout with this many steps per launch")
     ap.add_argument("--sgan", action="store_true", help="time mcn_sgan_step (shipped pool-net weights) at --sizes x --humans")
+    ap.add_argument("--sgan-predict", action="store_true",
+                    help="time mcn_sgan_predict at --sizes x --humans for --samples noise vectors and --steps decoder steps")
+    ap.add_argument("--steps", default="8", help="with --sgan-predict: decoder steps T (a comma list)")
+    ap.add_argument("--samples", default="1", help="with --sgan-predict: noise samples K per scene (a comma list)")
     ap.add_argument("--lstm-rl", action="store_true", help="time mcn_lstm_rl_predict at 4096 envs x --humans")
     ap.add_argument("--cadrl", action="store_true", help="time mcn_cadrl_predict at 4096 envs x --humans")
     a = ap.parse_args()
     if a.lstm_rl or a.cadrl:
         for N in [int(x) for x in str(a.humans).split(",")]:
             policy_bench("lstm_rl" if a.lstm_rl else "cadrl", 4096, N)
+        return
+    if a.sgan_predict:
+        for N in [int(x) for x in str(a.humans).split(",")]:
+            for E in [int(x) for x in a.sizes.split(",")]:
+                for K in [int(x) for x in a.samples.split(",")]:
+                    for T in [int(x) for x in a.steps.split(",")]:
+                        sgan_predict_bench(E, N, K, T, a.iters)
         return
     if a.sgan:
         for N in [int(x) for x in str(a.humans).split(",")]:
