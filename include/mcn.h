@@ -42,7 +42,9 @@ enum { MCN_INFO_NOTHING = 0, MCN_INFO_DANGER = 1, MCN_INFO_REACHGOAL = 2, MCN_IN
 /* how humans choose their velocity */
 enum { MCN_HUMANS_ORCA = 0,     /* crowd_sim/envs/policy/orca.py:82-132            */
        MCN_HUMANS_LINEAR = 1,   /* crowd_sim/envs/policy/linear.py:15-22           */
-       MCN_HUMANS_GIVEN = 2 };  /* model_crowd_sim.py:347 step(new_v=...) / world model output */
+       MCN_HUMANS_GIVEN = 2,    /* model_crowd_sim.py:347 step(new_v=...) / world model output */
+       MCN_HUMANS_SOCIALFORCE = 3 };  /* social-force pedestrians: mcn_env_step_sf / mcn_env_rollout_sf only (they carry
+                                       * the model's three parameters; mcn_env_step / mcn_env_rollout reject this value) */
 enum { MCN_KIN_HOLONOMIC = 0, MCN_KIN_UNICYCLE = 1 };
 
 /* Scalar configuration: env.config [env]/[reward] + orca.py:60-66 + robot flags. */
@@ -182,6 +184,34 @@ int mcn_env_step(const mcn_env_cfg *cfg, const mcn_env_state *st, const double *
  */
 int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const double *actions, int32_t T,
                     const mcn_env_out *out, const mcn_rollout *roll, int32_t E, int32_t N, void *stream);
+
+/*
+ * mcn_env_step_sf / mcn_env_rollout_sf -- mcn_env_step / mcn_env_rollout for social-force pedestrians
+ * (cfg->human_policy == MCN_HUMANS_SOCIALFORCE; the reference has no such model, it is defined here).  Circular form of
+ * Helbing, Farkas and Vicsek (2000) without body-contact or friction terms.  Human i with position p, velocity v, goal g,
+ * radius r, preferred speed s chooses, all in float64 and in this operation order (no fused multiply-add):
+ *   1  e = g - p; d = sqrt(e.x*e.x + e.y*e.y); if d > s: e = (e.x / d * s, e.y / d * s)      (orca.py:113's vector)
+ *   2  a = (k*(e.x - v.x), k*(e.y - v.y))
+ *   3  for every other human j of the env in index order, then -- if cfg->robot_visible -- the robot (current position,
+ *      plain radius): dx = p.x - q.x; dy = p.y - q.y; dist = sqrt(dx*dx + dy*dy); if dist > 0:
+ *      m = A * exp((r + r_j - dist) / B); a.x = a.x + m * (dx / dist); a.y = a.y + m * (dy / dist)
+ *      (a coincident agent contributes nothing; radii are the plain ones: no ORCA margin, no safety_space)
+ *   4  w = (v.x + a.x*dt, v.y + a.y*dt); n = sqrt(w.x*w.x + w.y*w.y)
+ *   5  if n > s: w = (w.x / n * s, w.y / n * s)
+ * and w is the human's action; everything after it (swept test, overlap count, reward ladder, integration, look-ahead
+ * observation, rollout accounting, pool restart) is mcn_env_step's.  strength = A (m/s^2, >= 0), range = B (m, > 0),
+ * relaxation_rate = k (1/s, >= 0), all finite: anything else, or another cfg->human_policy, is MCN_EINVAL before any
+ * launch.  No given_v.  `update`, out->human_act, out->nobs_*, roll: as mcn_env_step.  mcn_env_rollout_sf equals T
+ * mcn_env_step_sf(update = 1) calls bit for bit; in a latency-bound batch it is one launch (env_step.hip:
+ * env_step_loop_sf_kernel), otherwise T launches.  The cfg's orca_* fields are not read (orca_max_neighbors is still
+ * range-checked).
+ */
+int mcn_env_step_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
+                    const mcn_env_state *st, const double *actions, const mcn_env_out *out,
+                    const mcn_rollout *roll, int32_t E, int32_t N, int32_t update, void *stream);
+int mcn_env_rollout_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
+                       const mcn_env_state *st, const double *actions, int32_t T, const mcn_env_out *out,
+                       const mcn_rollout *roll, int32_t E, int32_t N, void *stream);
 
 /* Scenario rules of CrowdSim.reset (crowd_sim.py:120-163). */
 enum { MCN_RULE_CIRCLE = 0, MCN_RULE_SQUARE = 1 };
@@ -569,7 +599,8 @@ const char *mcn_version(void);
 /*
  * ABI guard.  MCN_ABI_VERSION changes whenever a struct of this header changes size or layout or an entry point
  * changes its signature (0.3 grew mcn_tuning by lp3_defer and mcn_env_out by lp3_queue: ABI 4; 0.4 grew mcn_sarl_net by
- * x3: ABI 5; an entry point that is only ADDED, like mcn_sgan_predict, leaves it as it is).  A caller built against
+ * x3: ABI 5; an entry point that is only ADDED, like mcn_sgan_predict or
+ * mcn_env_step_sf, leaves it as it is).  A caller built against
  * another header must not pass structs to this library: compare mcn_abi_version() with the MCN_ABI_VERSION it was
  * compiled with, and (bindings without the header: ctypes, cgo) mcn_sizeof() with the size of its own struct mirrors.
  */
@@ -583,8 +614,8 @@ int64_t mcn_sizeof(int32_t which);                 /* sizeof the struct named by
 
 /*
  * Diagnostic: the kernel family ("env_step_quad_kernel", "env_rollout_quad_kernel", "env_step_loop_kernel",
- * "env_pair_kernel", "env_step_kernel") that the calling thread's latest mcn_env_step / mcn_env_rollout call
- * dispatched to; "" before the first call.  bench.py attributes profiles to the kernel that really ran with it.
+ * "env_pair_kernel", "env_step_kernel", "env_step_loop_sf_kernel") that the calling thread's latest mcn_env_step /
+ * mcn_env_rollout call (or social-force twin) dispatched to; "" before the first call.  bench.py attributes profiles to the kernel that really ran with it.
  */
 const char *mcn_last_dispatch(void);
 

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("MCN_HIP_LIB") or os.path.join(_HERE, "csrc", "libmcn_
 MCN_OK, MCN_EINVAL, MCN_ELAUNCH = 0, -1, -2
 MAX_HUMANS, MAX_LINES = 32, 10
 INFO_NOTHING, INFO_DANGER, INFO_REACHGOAL, INFO_COLLISION, INFO_TIMEOUT = range(5)
-HUMANS_ORCA, HUMANS_LINEAR, HUMANS_GIVEN = range(3)
+HUMANS_ORCA, HUMANS_LINEAR, HUMANS_GIVEN, HUMANS_SOCIALFORCE = range(4)
 KIN_HOLONOMIC, KIN_UNICYCLE = 0, 1
 # include/mcn.h: MCN_SIZEOF_* ids of the network structs
 SIZEOF_SARL_NET, SIZEOF_SGAN_NET, SIZEOF_MLP_WORLD_NET, SIZEOF_ATTN_WORLD_NET = 7, 8, 10, 11
@@ -127,6 +127,13 @@ def _load():
     lib.mcn_env_rollout.argtypes = [C.POINTER(EnvCfg), C.POINTER(EnvState), _vp, _i, C.POINTER(EnvOut),
                                     C.POINTER(Rollout), _i, _i, _vp]
     lib.mcn_env_rollout.restype = C.c_int
+    # social-force humans: the model's strength / range / relaxation_rate follow cfg, no given_v
+    lib.mcn_env_step_sf.argtypes = [C.POINTER(EnvCfg), _d, _d, _d, C.POINTER(EnvState), _vp, C.POINTER(EnvOut),
+                                    C.POINTER(Rollout), _i, _i, _i, _vp]
+    lib.mcn_env_step_sf.restype = C.c_int
+    lib.mcn_env_rollout_sf.argtypes = [C.POINTER(EnvCfg), _d, _d, _d, C.POINTER(EnvState), _vp, _i, C.POINTER(EnvOut),
+                                       C.POINTER(Rollout), _i, _i, _vp]
+    lib.mcn_env_rollout_sf.restype = C.c_int
     lib.mcn_set_tuning.argtypes = [C.POINTER(Tuning)]
     lib.mcn_set_tuning.restype = C.c_int
     lib.mcn_get_tuning.argtypes = [C.POINTER(Tuning)]
@@ -222,7 +229,7 @@ def last_dispatch():
 lib = _load()
 
 # every symbol include/mcn.h declares; tests/test_abi.py checks the .so exports each one
-EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
+EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict"]
 

@@ -28,6 +28,7 @@
 #include "env_step_params.hpp"
 #include "env_common.hpp"
 #include "lp3_queue.hpp"
+#include "social_force.hpp"
 
 namespace mcn {
 void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispatch()
@@ -49,7 +50,9 @@ struct GroupCand {
 // NT > 0: humans per env known at compile time (register-resident ORCA, constant lane->(env,human)
 // split); NT == 0: run-time N (LDS-resident lines), any N <= MCN_MAX_HUMANS.  VIS: robot visible to humans.
 // MODE: MCN_HUMANS_* fixed at compile time, so the given-velocity / linear variants carry no ORCA registers,
-// no neighbour staging and no goal loads (they are pure streaming kernels and want maximum occupancy).
+// no neighbour staging and no goal loads (they are pure streaming kernels and want maximum occupancy).  The social-force
+// variant stages the humans like ORCA (it reads the float64 tiles) but has no half-planes and no line slots: run-time N, or 5 / 10 humans at
+// compile time (the loop over the others unrolled).
 // HH_T: 0 never count overlaps, 1 always, 2 decide at run time from cfg.count_hh.
 // One env step for the workgroup's env slots: everything between the state in HBM before the step and after it.  A
 // device function so that two kernels can share it: env_step_kernel (one step per launch) and env_step_loop_kernel
@@ -57,7 +60,7 @@ struct GroupCand {
 template <int BLOCK, int NT, int VIS, int MODE, int HH_T>
 __device__ __forceinline__ void env_step_body(const StepParams &p)
 {
-    constexpr bool kStageHumans = (MODE == MCN_HUMANS_ORCA) || (HH_T != 0);
+    constexpr bool kStageHumans = (MODE == MCN_HUMANS_ORCA) || (MODE == MCN_HUMANS_SOCIALFORCE) || (HH_T != 0);
 #ifdef MCN_DIAG
     if (p.debug_noop) return;      // diagnostic build only: launch-floor measurement
 #endif
@@ -294,6 +297,11 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
         } else if constexpr (MODE == MCN_HUMANS_LINEAR) {
             const double th = atan2(goal.y - pos.y, goal.x - pos.x);
             hax = cos(th) * attr.y; hay = sin(th) * attr.y;
+        } else if constexpr (MODE == MCN_HUMANS_SOCIALFORCE) {
+            const SocialForce f{p.sf_strength, p.sf_range, p.sf_relaxation_rate};
+            const double2 w = social_force_velocity<NT>(pos, vel, goal, attr.x, attr.y, sPosD, sRadD, gbase, h, N,
+                                                    c.robot_visible != 0, sRobPos[slot], sRobRad[slot], f, dt);
+            hax = w.x; hay = w.y;
         } else {
             const double2 gv = reinterpret_cast<const double2 *>(p.given_v)[a];
             hax = gv.x; hay = gv.y;
@@ -503,6 +511,20 @@ __global__ __launch_bounds__(64) void env_step_loop_kernel(StepParams p, const i
     }
 }
 
+// The same for social-force humans (mcn_env_rollout_sf): the run-time-N body, T times.  The argument above holds
+// unchanged -- a lane re-reads only its own human (the leader lane its robot, clock and rollout record); what it reads
+// of the others goes through the LDS tiles, restaged every step behind the barrier.
+template <int HH_T>
+__global__ __launch_bounds__(64) void env_step_loop_sf_kernel(StepParams p, const int T)
+{
+    const double *acts = p.actions;
+    for (int t = 0; t < T; ++t) {
+        p.actions = acts + (size_t)t * (size_t)p.E * 2;
+        env_step_body<64, 0, 0, MCN_HUMANS_SOCIALFORCE, HH_T>(p);
+        __syncthreads();                       // the next step restages the LDS tiles this one still reads
+    }
+}
+
 // The deferred 3-D LPs of one step (lp3_queue.hpp).  Finishes each parked solve exactly as the step kernel would have
 // (same sorted half-planes, same running result) and then does for that human what the step kernel skipped: the
 // exported action, and -- by the flag the step kernel left -- the integration (crowd_sim.py:416-421) or the look-ahead
@@ -650,6 +672,17 @@ static void dispatch(const StepParams &p, int blocks, hipStream_t stream)
     } else if (p.cfg.human_policy == MCN_HUMANS_GIVEN) {
         if (p.cfg.count_hh) launch_one<BLOCK, 0, 0, MCN_HUMANS_GIVEN, 1>(p, blocks, stream);
         else                launch_one<BLOCK, 0, 0, MCN_HUMANS_GIVEN, 0>(p, blocks, stream);
+    } else if (p.cfg.human_policy == MCN_HUMANS_SOCIALFORCE) {
+#define MCN_SF_CASE(NT_) if (p.cfg.count_hh) launch_one<BLOCK, NT_, 0, MCN_HUMANS_SOCIALFORCE, 1>(p, blocks, stream); \
+                                  else                launch_one<BLOCK, NT_, 0, MCN_HUMANS_SOCIALFORCE, 0>(p, blocks, stream); return;
+        // compile-time N for the reference's crowd sizes: the loop over the others is unrolled (4 - 9 % per launch)
+        switch (p.force_generic ? 0 : p.N) {
+            case 5: MCN_SF_CASE(5)
+            case 10: MCN_SF_CASE(10)
+            default: break;
+        }
+        MCN_SF_CASE(0)
+#undef MCN_SF_CASE
     } else {
         if (p.cfg.count_hh) launch_one<BLOCK, 0, 0, MCN_HUMANS_LINEAR, 1>(p, blocks, stream);
         else                launch_one<BLOCK, 0, 0, MCN_HUMANS_LINEAR, 0>(p, blocks, stream);
@@ -696,6 +729,25 @@ bool launch_env_step_loop(const StepParams &p, int T, hipStream_t stream)
     }
 #undef MCN_LOOP_CASE
     return false;
+}
+
+// mcn_env_rollout_sf in a latency-bound batch (launch_env_step's own one-wavefront rule): one env_step_loop_sf_kernel
+// launch instead of T step launches.  false = not applicable (the caller falls back to T launches).
+bool launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream)
+{
+    if (p.cfg.human_policy != MCN_HUMANS_SOCIALFORCE || !p.update) return false;
+    const int G = 64 / p.N;
+    const int waves_total = (p.E + G - 1) / G;
+    const int nc = p.N - 1 + (p.cfg.robot_visible ? 1 : 0);
+    if (!one_wave_batch(p, waves_total, nc)) return false;
+    StepParams q = p;
+    q.G = G;
+    const size_t sm = step_smem_bytes(64, 0);
+    note_dispatch("env_step_loop_sf_kernel");
+    // (run-time N only: the 5- / 10-human forms of the step kernel did not pass the adoption rule inside the loop)
+    if (p.cfg.count_hh) hipLaunchKernelGGL((env_step_loop_sf_kernel<1>), dim3(waves_total), dim3(64), sm, stream, q, T);
+    else                hipLaunchKernelGGL((env_step_loop_sf_kernel<0>), dim3(waves_total), dim3(64), sm, stream, q, T);
+    return true;
 }
 
 bool launch_env_step_quad(const StepParams &p, hipStream_t stream);      // env_step_quad.hip

@@ -21,6 +21,8 @@ struct StepParams {
     int step_block;      // mcn_tuning.step_block: 64 / 256 lanes per workgroup in the lane-per-human kernels, -1 automatic
     int lp3_defer;       // mcn_tuning.lp3_defer (-1 automatic); launch_env_step turns it into 0 / 1 for the kernel
     int pair_stream;     // given-velocity step: streaming kernel of env_pair.hip (-1 automatic, 0 never, 1 where it applies)
+    // MCN_HUMANS_SOCIALFORCE only (mcn_env_step_sf / mcn_env_rollout_sf): A (m/s^2), B (m), k (1/s) of social_force.hpp
+    double sf_strength, sf_range, sf_relaxation_rate;
 };
 
 }  // namespace mcn

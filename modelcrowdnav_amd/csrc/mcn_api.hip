@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <stdlib.h>
+#include <math.h>
 #include <mutex>
 #include "../../include/mcn.h"
 
@@ -14,6 +15,7 @@ namespace mcn {
 int launch_env_step(const StepParams &p, hipStream_t stream);
 bool launch_env_rollout_quad(const StepParams &p, int T, hipStream_t stream);
 bool launch_env_step_loop(const StepParams &p, int T, hipStream_t stream);
+bool launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream);
 int launch_scenario_pool(const mcn_scenario_cfg &c, uint64_t seed, int64_t first_case, int P, int N, double *hpos,
                          double *hgoal, double *hrad, double *hvpref, hipStream_t stream);
 struct SarlParams;
@@ -161,10 +163,11 @@ int64_t mcn_sizeof(int32_t which)
     }
 }
 
-// Validates one env-step problem and fills the kernel argument block.  Shared by mcn_env_step / mcn_env_rollout.
+// Validates one env-step problem and fills the kernel argument block.  Shared by mcn_env_step / mcn_env_rollout and
+// their social-force twins: `social_force` says which family the caller is, and the cfg's policy must belong to it.
 static int fill_step_params(mcn::StepParams &p, const mcn_env_cfg *cfg, const mcn_env_state *st, const double *actions,
                             const double *given_v, const mcn_env_out *out, const mcn_rollout *roll,
-                            int32_t E, int32_t N, int32_t update)
+                            int32_t E, int32_t N, int32_t update, bool social_force = false)
 {
     if (!cfg || !st || !out || !actions) return MCN_EINVAL;
     if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
@@ -174,7 +177,9 @@ static int fill_step_params(mcn::StepParams &p, const mcn_env_cfg *cfg, const mc
     if (!out->rec) return MCN_EINVAL;
     if (!update && (!out->nobs_pos || !out->nobs_vel)) return MCN_EINVAL;
     if (cfg->human_policy == MCN_HUMANS_GIVEN && !given_v) return MCN_EINVAL;
-    if (cfg->human_policy < MCN_HUMANS_ORCA || cfg->human_policy > MCN_HUMANS_GIVEN) return MCN_EINVAL;
+    if (social_force) {
+        if (cfg->human_policy != MCN_HUMANS_SOCIALFORCE) return MCN_EINVAL;
+    } else if (cfg->human_policy < MCN_HUMANS_ORCA || cfg->human_policy > MCN_HUMANS_GIVEN) return MCN_EINVAL;
     if (cfg->orca_max_neighbors < 0 || cfg->orca_max_neighbors > MCN_MAX_LINES) return MCN_EINVAL;
     if (!(cfg->time_step > 0)) return MCN_EINVAL;
     if (roll) {
@@ -288,6 +293,46 @@ int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const doubl
     // 6-10 ORCA humans, latency-bound batch: the one-wavefront step kernel run T times inside one launch
     // (env_step.hip: env_step_loop_kernel); rollout_fused = 0 keeps the T launches
     if (tu.rollout_fused != 0 && T > 1 && mcn::launch_env_step_loop(p, T, (hipStream_t)stream))
+        return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
+    for (int32_t t = 0; t < T; ++t) {
+        p.actions = actions + (size_t)t * E * 2;
+        const int r = mcn::launch_env_step(p, (hipStream_t)stream);
+        if (r != MCN_OK) return r;
+    }
+    return MCN_OK;
+}
+
+// the model's parameters (include/mcn.h): A >= 0, B > 0, k >= 0, all finite
+static bool sf_params_ok(double strength, double range, double relaxation_rate)
+{
+    return isfinite(strength) && isfinite(range) && isfinite(relaxation_rate) && strength >= 0 && range > 0 &&
+           relaxation_rate >= 0;
+}
+
+int mcn_env_step_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
+                    const mcn_env_state *st, const double *actions, const mcn_env_out *out,
+                    const mcn_rollout *roll, int32_t E, int32_t N, int32_t update, void *stream)
+{
+    if (!sf_params_ok(strength, range, relaxation_rate)) return MCN_EINVAL;
+    mcn::StepParams p;
+    const int rc = fill_step_params(p, cfg, st, actions, nullptr, out, roll, E, N, update, true);
+    if (rc != MCN_OK) return rc;
+    p.sf_strength = strength; p.sf_range = range; p.sf_relaxation_rate = relaxation_rate;
+    return mcn::launch_env_step(p, (hipStream_t)stream);
+}
+
+int mcn_env_rollout_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
+                       const mcn_env_state *st, const double *actions, int32_t T, const mcn_env_out *out,
+                       const mcn_rollout *roll, int32_t E, int32_t N, void *stream)
+{
+    if (T <= 0 || !sf_params_ok(strength, range, relaxation_rate)) return MCN_EINVAL;
+    mcn::StepParams p;
+    const int rc = fill_step_params(p, cfg, st, actions, nullptr, out, roll, E, N, 1, true);
+    if (rc != MCN_OK) return rc;
+    p.sf_strength = strength; p.sf_range = range; p.sf_relaxation_rate = relaxation_rate;
+    // latency-bound batch: the one-wavefront step kernel run T times inside one launch (env_step.hip:
+    // env_step_loop_sf_kernel); rollout_fused = 0 keeps the T launches
+    if (tuning().rollout_fused != 0 && T > 1 && mcn::launch_env_step_loop_sf(p, T, (hipStream_t)stream))
         return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
     for (int32_t t = 0; t < T; ++t) {
         p.actions = actions + (size_t)t * E * 2;

@@ -3,8 +3,10 @@
 Reference surface kept (crowd_sim/envs/crowd_sim.py): configure :58, set_robot :91,
 reset :261, step :331, onestep_lookahead :325, plus the attributes its callers read
 (case_size, case_counter, human_num, time_step, time_limit, global_time, humans, robot, states,
-sim_world, device, test_sim), get_human_times :219 (an all-ORCA simulation to the end: one mcn_orca_batch
-launch per simulated step).  render is host-only visual tooling and out of scope.
+sim_world, device, test_sim), `[humans] policy = socialforce` (not in the reference: social-force pedestrians,
+mcn_env_step_sf, parameters from the optional [social_force] section), get_human_times :219 (an all-ORCA simulation
+to the end: one mcn_orca_batch launch per simulated step).  render is host-only visual tooling and out of scope
+(SURVEY.md section 2, row 1).
 
   VecCrowdSim  tensors in / tensors out, E envs, SoA float64 state (layout: include/mcn.h)
   CrowdSim     the E = 1 gym-style view returning the reference's value types
@@ -62,6 +64,7 @@ class VecCrowdSim(object):
         self._sim_adapter = None
         self.human_policy_name = "orca"
         self._orca = policy_factory["orca"]()      # parameter carrier (orca.py:59-66)
+        self._sf = policy_factory["socialforce"]() # parameter carrier ([social_force] strength / range / relaxation_rate)
         self._human_radius = self._human_v_pref = None
         self._alloc_N = None
         self._roll = None
@@ -85,8 +88,13 @@ class VecCrowdSim(object):
         self.collision_penalty = config.getfloat("reward", "collision_penalty")
         self.discomfort_dist = config.getfloat("reward", "discomfort_dist")
         self.discomfort_penalty_factor = config.getfloat("reward", "discomfort_penalty_factor")
-        if config.get("humans", "policy") != "orca":
+        human_policy = config.get("humans", "policy")
+        if human_policy == "socialforce":
+            self._sf.configure(config)             # optional [social_force] section
+        elif human_policy != "orca":
             raise NotImplementedError
+        if self.human_policy_name in ("orca", "socialforce"):     # (the model env keeps its given velocities)
+            self.human_policy_name = human_policy
         self.case_capacity = {"train": _UINT32_MAX - 2000, "val": 1000, "test": 1000}
         self.case_size = self._case_sizes(config)
         self.train_val_sim = config.get("sim", "train_val_sim")
@@ -145,8 +153,8 @@ class VecCrowdSim(object):
                                                              self.lp3_queue)])
 
     def _cfg_struct(self, human_policy=None):
-        hp = {"orca": _hip.HUMANS_ORCA, "linear": _hip.HUMANS_LINEAR, "given": _hip.HUMANS_GIVEN}[
-            human_policy or self.human_policy_name]
+        hp = {"orca": _hip.HUMANS_ORCA, "linear": _hip.HUMANS_LINEAR, "given": _hip.HUMANS_GIVEN,
+              "socialforce": _hip.HUMANS_SOCIALFORCE}[human_policy or self.human_policy_name]
         kin = _hip.KIN_UNICYCLE if getattr(self.robot, "kinematics", "holonomic") == "unicycle" else _hip.KIN_HOLONOMIC
         o = self._orca
         return _hip.EnvCfg(self.time_step, float(self.time_limit), self.success_reward, self.collision_penalty,
@@ -252,7 +260,7 @@ class VecCrowdSim(object):
         return ObsBatch(self.hpos, self.hvel, self.hrad)
 
     def step(self, actions, update=True, given_v=None):
-        """crowd_sim.py:331-434 for every env: one mcn_env_step launch, no host sync.
+        """crowd_sim.py:331-434 for every env: one mcn_env_step (social-force humans: mcn_env_step_sf) launch, no host sync.
 
         actions: [E,2] float64 device tensor ((vx,vy) holonomic, (v,r) unicycle).
         Returns (ObsBatch, reward[E] f64, done[E] u8, info[E] u8 codes) -- all device views that
@@ -269,11 +277,17 @@ class VecCrowdSim(object):
             if tuple(given_v.shape) != (E, N, 2):
                 raise ValueError("given_v must be [E,N,2]")
         cfg = self._cfg_struct(policy)
-        rc = _hip.lib.mcn_env_step(cfg, self._st, _hip.ptr(actions), _hip.ptr(given_v),
-                                   self._out if self.export_human_actions else self._out_lean,
-                                   self._roll if (self._roll is not None and update) else None,
-                                   E, N, 1 if update else 0, _hip.stream_ptr(self.device))
-        _hip.check(rc, "mcn_env_step")
+        out = self._out if self.export_human_actions else self._out_lean
+        roll = self._roll if (self._roll is not None and update) else None
+        if policy is None and self.human_policy_name == "socialforce":
+            sf = self._sf
+            rc = _hip.lib.mcn_env_step_sf(cfg, sf.strength, sf.range, sf.relaxation_rate, self._st, _hip.ptr(actions),
+                                          out, roll, E, N, 1 if update else 0, _hip.stream_ptr(self.device))
+            _hip.check(rc, "mcn_env_step_sf")
+        else:
+            rc = _hip.lib.mcn_env_step(cfg, self._st, _hip.ptr(actions), _hip.ptr(given_v), out, roll,
+                                       E, N, 1 if update else 0, _hip.stream_ptr(self.device))
+            _hip.check(rc, "mcn_env_step")
         if update:
             ob = self.observation()
         else:
@@ -291,10 +305,17 @@ class VecCrowdSim(object):
             raise ValueError("actions must be [T,E,2]")
         if actions.dtype != torch.float64 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(self.device, torch.float64).contiguous()
-        rc = _hip.lib.mcn_env_rollout(self._cfg_struct(None), self._st, _hip.ptr(actions), int(actions.shape[0]),
-                                      self._out if self.export_human_actions else self._out_lean,
-                                      self._roll, E, N, _hip.stream_ptr(self.device))
-        _hip.check(rc, "mcn_env_rollout")
+        out = self._out if self.export_human_actions else self._out_lean
+        if self.human_policy_name == "socialforce":
+            sf = self._sf
+            rc = _hip.lib.mcn_env_rollout_sf(self._cfg_struct(None), sf.strength, sf.range, sf.relaxation_rate, self._st,
+                                             _hip.ptr(actions), int(actions.shape[0]), out, self._roll, E, N,
+                                             _hip.stream_ptr(self.device))
+            _hip.check(rc, "mcn_env_rollout_sf")
+        else:
+            rc = _hip.lib.mcn_env_rollout(self._cfg_struct(None), self._st, _hip.ptr(actions), int(actions.shape[0]),
+                                          out, self._roll, E, N, _hip.stream_ptr(self.device))
+            _hip.check(rc, "mcn_env_rollout")
         return self.observation(), self.reward, self.done, self.info
 
     def onestep_lookahead(self, actions):
@@ -586,6 +607,9 @@ class CrowdSim(object):
         The reference loops for ever if somebody never arrives (it only logs past t = 1000); this stops after
         `max_steps` simulated steps with the same warning."""
         v, robot = self._vec, self._vec.robot
+        if v.human_policy_name == "socialforce":
+            raise NotImplementedError("get_human_times runs the reference's all-ORCA simulation to the end: it is not "
+                                      "defined for social-force humans")
         if not robot.reached_destination():
             raise ValueError("Episode is not done yet")
         agents = [robot] + self.humans

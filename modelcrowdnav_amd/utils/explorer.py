@@ -9,7 +9,7 @@ side -- and fills `memory` / `raw_memory` / `rawob` / `cacheFile` in the referen
 reference's tuple (pinned by g15_explorer.npz = the reference's own run_k_episodes, tests/test_explorer_golden_gpu.py).
 What stays sequential (`_batched_reason` says why): k = 1 (train.py:218), the train phase of a trainable policy with
 epsilon > 0 (the reference draws exploration from numpy's shared global stream, one draw per step, so the episodes are
-not independent of their order), policies without `predict_batch`, and env classes other than CrowdSim with ORCA humans.
+not independent of their order), policies without `predict_batch`, and env classes other than CrowdSim with ORCA or social-force humans.
 
 The data-collection side channels are kept (explorer.py:60-85,112-121): `raw_memory` rows `(ob, reward, done, info)`
 for DataGen, `rawob` pairs (humans' [px,py,vx,vy], their next velocities) for the world-model trainers, and the
@@ -61,8 +61,8 @@ class Explorer(object):
             return "k = 1"
         if type(self.env) is not CrowdSim or self.env.__dict__.get("_vec") is None:
             return "env is not the drop-in CrowdSim"
-        if self.env._vec.human_policy_name != "orca" or self.env._vec.robot is not self.robot:
-            return "humans are not ORCA / robot differs from the env's"
+        if self.env._vec.human_policy_name not in ("orca", "socialforce") or self.env._vec.robot is not self.robot:
+            return "humans are neither ORCA nor social-force / robot differs from the env's"
         pol = self.robot.policy
         if not stay and not hasattr(pol, "predict_batch"):
             return "policy has no predict_batch"

@@ -1,0 +1,439 @@
+"""GPU: social-force pedestrians (mcn_env_step_sf / mcn_env_rollout_sf, MCN_HUMANS_SOCIALFORCE in env_step.hip).
+
+  1  the exported velocities against the definition's plain-Python restatement (tests/social_force_ref.py), per component
+     within 8 * 2^-52 * M, M the magnitude the restatement returns: sqrt and / are correctly rounded on both sides and the
+     order of the sum is fixed, so only exp (1-2 ulp from libm) can differ -- 8 ulp of the magnitudes involved is a
+     fourfold margin (5 and 10 humans: the compile-time-N step kernels and, with force_generic, the run-time-N ones);
+  2  everything after the velocity, bit for bit: the device's own velocities fed back as given velocities to
+     mcn_env_step(MCN_HUMANS_GIVEN) and to the C oracle must leave the same bytes;
+  3  mcn_env_rollout_sf against the same number of mcn_env_step_sf calls, every byte;
+  4  exact symmetry of a mirrored pair on the device;
+  5  the public surface: VecCrowdSim / CrowdSim / Explorer / the query_env look-ahead.
+"""
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+from oracle import cport  # noqa: E402
+from tests import helpers as H  # noqa: E402
+from tests import social_force_ref as R  # noqa: E402
+
+E = 251
+DT = 0.25
+DEFAULT = (4.0, 0.2, 2.0)
+PARAMS = {7: (2.5, 0.35, 1.5), 13: (1.0, 1.0, 0.5)}            # crowd sizes that run with other than the defaults
+NS = (1, 2, 5, 7, 10, 13, 32)
+STATE_FIELDS = H.STATE_FIELDS + ("rtheta",)
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch
+
+
+def _sf_env(E_, N, vis, kinematics="holonomic", params=DEFAULT):
+    env = H.make_vec_env(E_, N, robot_visible=bool(vis), kinematics=kinematics, **{"humans.policy": "socialforce"})
+    assert env.human_policy_name == "socialforce"
+    env._sf.strength, env._sf.range, env._sf.relaxation_rate = params
+    return env
+
+
+@functools.lru_cache(maxsize=None)
+def _state(N, seed=0):
+    """Mid-episode states with randomised radii and preferred speeds; every third env is constructed."""
+    rng = np.random.RandomState(1000 * seed + N)
+    st = H.random_state(rng, E, N, randomize=True)
+    for e in range(0, E, 3):
+        kind = (e // 3) % 6
+        if kind == 0 and N >= 2:                                 # duplicated humans
+            st.hpx[e, 1], st.hpy[e, 1] = st.hpx[e, 0], st.hpy[e, 0]
+        elif kind == 1:                                          # a human on its goal
+            st.hgx[e, 0], st.hgy[e, 0] = st.hpx[e, 0], st.hpy[e, 0]
+        elif kind == 2:                                          # a human within v_pref of its goal
+            a, d = rng.uniform(0, 2 * np.pi), rng.uniform(0.1, 0.9) * st.hvpref[e, 0]
+            st.hgx[e, 0], st.hgy[e, 0] = st.hpx[e, 0] + d * np.cos(a), st.hpy[e, 0] + d * np.sin(a)
+        elif kind == 3 and N >= 2:                               # overlapping humans
+            st.hpx[e, 1], st.hpy[e, 1] = st.hpx[e, 0] + 0.25, st.hpy[e, 0] - 0.125
+        elif kind == 4 and N >= 2:                               # a neighbour 800 m away
+            st.hpx[e, N - 1], st.hpy[e, N - 1] = st.hpx[e, 0] + 800.0, st.hpy[e, 0] + 1.0
+        elif kind == 5:
+            st.hvpref[e, 0] = 0.0
+    return st
+
+
+def _features(st):
+    pos = np.stack([st.hpx, st.hpy], -1)
+    d = np.sqrt(((pos[:, :, None] - pos[:, None]) ** 2).sum(-1))
+    iu = np.triu_indices(st.N, 1)
+    dp, rs = d[:, iu[0], iu[1]], (st.hr[:, :, None] + st.hr[:, None])[:, iu[0], iu[1]]
+    dg = np.sqrt((st.hgx - st.hpx) ** 2 + (st.hgy - st.hpy) ** 2)
+    return dict(duplicated=bool((dp == 0).any()), on_goal=bool((dg == 0).any()),
+                within_s=bool(((dg > 0) & (dg <= st.hvpref) & (st.hvpref > 0)).any()),
+                overlapping=bool(((dp > 0) & (dp < rs)).any()), far=bool((dp > 700).any()),
+                vpref_zero=bool((st.hvpref == 0).any()))
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(N, vis):
+    st = _state(N)
+    A, B, K = PARAMS.get(N, DEFAULT)
+    return R.batch_velocities(np.stack([st.hpx, st.hpy], -1), np.stack([st.hvx, st.hvy], -1),
+                              np.stack([st.hgx, st.hgy], -1), st.hr, st.hvpref, A, B, K, DT,
+                              np.stack([st.rpx, st.rpy], -1) if vis else None, st.rr if vis else None)
+
+
+def _actions(seed, n=E):
+    rng = np.random.RandomState(seed)
+    return rng.uniform(-0.7, 0.7, (n, 2))
+
+
+def _bytes_equal(x, y, what):
+    x, y = np.ascontiguousarray(x), np.ascontiguousarray(y)
+    assert x.shape == y.shape and x.dtype == y.dtype, what
+    bad = np.argwhere(x.view(np.uint8).reshape(x.shape[0], -1) != y.view(np.uint8).reshape(y.shape[0], -1))
+    assert len(bad) == 0, "%s: %d bytes differ, first in row %d" % (what, len(bad), bad[0][0])
+
+
+# ------------------------------------------------------------------------------------------ 1 the velocities
+@pytest.mark.parametrize("N", NS)
+def test_velocities_match_the_definition(N, tuning):
+    torch = _torch()
+    from modelcrowdnav_amd import _hip
+    st = _state(N)
+    feats = _features(st)
+    for k, v in feats.items():
+        assert v or (N == 1 and k in ("duplicated", "overlapping", "far")), "no env with %s at N = %d" % (k, N)
+    act = torch.from_numpy(_actions(N)).cuda()
+    pos0 = np.stack([st.hpx, st.hpy], -1)
+    worst = 0.0
+    for vis in (0, 1):
+        want, mag = _reference(N, vis)
+        tol = 8 * 2.0 ** -52 * mag[..., None]
+        env = _sf_env(E, N, vis, params=PARAMS.get(N, DEFAULT))
+        # 5 and 10 humans have compile-time-N kernels: both those and the run-time-N ones (force_generic)
+        for block, generic in [(b, g) for b in (64, 256) for g in ((0, 1) if N in (5, 10) else (0,))]:
+            tuning(step_block=block, force_generic=generic)
+            for update in (0, 1):
+                H.upload(env, st)
+                env.human_act.fill_(float("nan"))
+                env.step(act, update=bool(update))
+                torch.cuda.synchronize()
+                assert _hip.last_dispatch() == "env_step_kernel"
+                got = env.human_act.cpu().numpy()
+                err = np.abs(got - want)
+                assert not np.isnan(got).any()
+                ratio = float(np.max(np.where(tol > 0, err / np.where(tol > 0, tol, 1), 0)))
+                worst = max(worst, ratio)
+                print("N=%d vis=%d block=%d generic=%d update=%d: largest error / tolerance %.4f" % (
+                    N, vis, block, generic, update, ratio))
+                assert (err <= tol).all(), (N, vis, block, generic, update, ratio, np.argwhere(err > tol)[:4].tolist())
+                speed = np.sqrt((got ** 2).sum(-1))
+                assert (speed <= st.hvpref * (1 + 1e-15)).all()          # the clip
+                nxt = pos0 + got * DT                                      # two roundings, as the kernel's
+                if update:
+                    H.assert_bits_equal(env.hvel.cpu().numpy(), got, "hvel")
+                    H.assert_bits_equal(env.hpos.cpu().numpy(), nxt, "hpos")
+                else:
+                    H.assert_bits_equal(env.nobs_vel.cpu().numpy(), got, "nobs_vel")
+                    H.assert_bits_equal(env.nobs_pos.cpu().numpy(), nxt, "nobs_pos")
+                    H.assert_state_equal(H.download(env), st, fields=STATE_FIELDS, what="look-ahead left the state")
+    print("N=%d: largest observed error / tolerance over all forms %.4f" % (N, worst))
+
+
+# ------------------------------------------------------------------------------------------ 2 downstream, bit for bit
+def _robot_actions(kin, st, seed):
+    """holonomic: (vx, vy).  unicycle: (v, r) and headings such that no value depends on device against host
+    trigonometry, as the ladder fixtures do it: rtheta + r is exactly 0 (cos and sin exact) for a moving robot, any
+    heading for a robot that turns on the spot."""
+    rng = np.random.RandomState(seed)
+    if kin == "holonomic":
+        a = rng.uniform(-0.7, 0.7, (st.E, 2))
+        return a[:, 0].copy(), a[:, 1].copy()
+    v, r = rng.uniform(0, 1, st.E), rng.uniform(-np.pi / 4, np.pi / 4, st.E)
+    st.rtheta[:] = rng.uniform(-7, 7, st.E)
+    flat = np.arange(st.E) % 2 == 0
+    st.rtheta[flat] = -r[flat]
+    v[~flat] = 0.0
+    assert ((st.rtheta + r)[flat] == 0).all()
+    return v, r
+
+
+@pytest.mark.parametrize("count_hh", (1, 0))
+@pytest.mark.parametrize("kin", ("holonomic", "unicycle"))
+def test_everything_after_the_velocity_is_bitwise(kin, count_hh, tuning):
+    torch = _torch()
+    infos, arrivals = set(), 0
+    for N in (5, 10):
+        for vis in (0, 1):
+            a = _sf_env(E, N, vis, kin)
+            b = H.make_vec_env(E, N, robot_visible=bool(vis), kinematics=kin)
+            a.count_hh = b.count_hh = bool(count_hh)
+            for block, update, generic in ((64, 1, 0), (256, 1, 1), (64, 0, 1), (256, 0, 0), (64, 1, 1), (256, 1, 0)):
+                what = "%s N=%d vis=%d block=%d update=%d hh=%d generic=%d" % (kin, N, vis, block, update, count_hh, generic)
+                tuning(step_block=block, force_generic=generic)
+                st = _state(N, seed=1 + vis).copy()
+                ax, ay = _robot_actions(kin, st, 17 * N + vis)
+                act = torch.from_numpy(np.stack([ax, ay], -1)).cuda()
+                H.upload(a, st); H.upload(b, st)
+                a.step(act, update=bool(update))
+                hact = a.human_act.clone()
+                b.step(act, update=bool(update), given_v=hact)
+                torch.cuda.synchronize()
+                ref_st = st.copy()
+                ref = cport.env_step(H.oracle_cfg_for(b, cport.HUMANS_GIVEN), ref_st, ax, ay, update=bool(update),
+                                     given_v=hact.cpu().numpy())
+                # swept distances and the goal test stay 1e-9 away from the ladder's thresholds
+                assert (np.abs(ref["dmin"]) > 1e-9).all() and (np.abs(ref["dmin"] - a.discomfort_dist) > 1e-9).all(), what
+                endx = st.rpx + (ax if kin == "holonomic" else ax * np.cos(st.rtheta + ay)) * DT
+                endy = st.rpy + (ay if kin == "holonomic" else ax * np.sin(st.rtheta + ay)) * DT
+                assert (np.abs(np.hypot(endx - st.rgx, endy - st.rgy) - st.rr) > 1e-9).all(), what
+                # device against device: every byte
+                _bytes_equal(a.step_rec.cpu().numpy(), b.step_rec.cpu().numpy(), what + " step records")
+                H.assert_bits_equal(b.human_act.cpu().numpy(), hact.cpu().numpy(), what + " human_act")
+                got = H.download(a)
+                H.assert_state_equal(got, H.download(b), fields=STATE_FIELDS, what=what + " vs given-velocity step")
+                # device against the C oracle
+                for k in ("reward", "dmin", "done", "info", "hh_count"):
+                    H.assert_bits_equal(getattr(a, k).cpu().numpy(), ref[k], what + " oracle " + k)
+                H.assert_state_equal(got, ref_st, fields=STATE_FIELDS, what=what + " vs oracle")
+                if update:
+                    arrivals += int(((got.human_times > 0) & (st.human_times == 0)).sum())
+                else:
+                    _bytes_equal(a.nobs_pos.cpu().numpy(), b.nobs_pos.cpu().numpy(), what + " nobs_pos")
+                    _bytes_equal(a.nobs_vel.cpu().numpy(), b.nobs_vel.cpu().numpy(), what + " nobs_vel")
+                    H.assert_bits_equal(a.nobs_pos.cpu().numpy(), np.stack([ref["nobs_px"], ref["nobs_py"]], -1), what)
+                    H.assert_bits_equal(a.nobs_vel.cpu().numpy(), np.stack([ref["nobs_vx"], ref["nobs_vy"]], -1), what)
+                    H.assert_state_equal(got, st, fields=STATE_FIELDS, what=what + " look-ahead left the state")
+                if count_hh:
+                    assert (ref["hh_count"] > 0).any(), what
+                else:
+                    assert (a.hh_count.cpu().numpy() == 0).all(), what
+                infos |= set(int(i) for i in ref["info"])
+    assert infos == {cport.INFO_NOTHING, cport.INFO_DANGER, cport.INFO_REACHGOAL, cport.INFO_COLLISION,
+                     cport.INFO_TIMEOUT}, infos
+    assert arrivals > 0, "no human reached its goal: first-arrival times were not exercised"
+
+
+# ------------------------------------------------------------------------------------------ 3 rollout == T steps
+SPLITS = ((0, 1), (1, 38), (38, 130))                          # 1 + 37 + 92 steps
+SENTINEL = 0xFF
+
+
+def _rollout_env(N, vis, null):
+    from modelcrowdnav_amd.envs import scenarios as S
+    env = _sf_env(E, N, vis)
+    env.time_limit = 6                                         # 24-step episodes: several per env in 130 steps
+    env.reset("test", test_cases=list(range(E)))
+    pool = S.scenario_pool(env.spec(), "test", range(300, 364), N, "circle_crossing")
+    bufs = env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=np.arange(E) * 5, fin_slots=2,
+                              danger_episodes=2, danger_short_from=101)
+    bufs["fin_return"].fill_(float("nan")); bufs["fin_time"].fill_(float("nan")); bufs["fin_info"].fill_(SENTINEL)
+    env.human_act.fill_(float("nan"))
+    if null == "human_act":
+        env.export_human_actions = False
+    elif null is not None:
+        setattr(env._roll, null, None)
+    return env
+
+
+def _same_bytes(a, b, what):
+    H.assert_state_equal(H.download(a), H.download(b), fields=STATE_FIELDS, what=what)
+    _bytes_equal(a.step_rec.cpu().numpy(), b.step_rec.cpu().numpy(), what + " step records")
+    _bytes_equal(a.human_act.cpu().numpy().reshape(E, -1), b.human_act.cpu().numpy().reshape(E, -1), what + " human_act")
+    for k in ("state", "fin_return", "fin_time", "fin_info"):
+        _bytes_equal(a.rollout_buffers[k].cpu().numpy().T if k != "state" else a.rollout_buffers[k].cpu().numpy(),
+                     b.rollout_buffers[k].cpu().numpy().T if k != "state" else b.rollout_buffers[k].cpu().numpy(),
+                     what + " " + k)
+
+
+@pytest.mark.parametrize("null", (None, "fin_return", "fin_time", "fin_info", "human_act"))
+@pytest.mark.parametrize("path", ("loop", "loop-run-time-N", "launches"))
+@pytest.mark.parametrize("N", (5, 10))
+def test_rollout_equals_single_steps(N, path, null, tuning):
+    torch = _torch()
+    from modelcrowdnav_amd import _hip
+    if path == "launches":
+        tuning(rollout_fused=0)
+    elif path == "loop-run-time-N":                            # the looped kernel without its 5- / 10-human forms
+        tuning(force_generic=1)
+    for vis in (0, 1):
+        a, b = _rollout_env(N, vis, null), _rollout_env(N, vis, null)
+        rng = np.random.RandomState(31 * N + vis)
+        acts = torch.from_numpy(rng.uniform(-0.7, 0.7, (SPLITS[-1][1], E, 2))).cuda()
+        for lo, hi in SPLITS:
+            a.rollout(acts[lo:hi])
+            ran = _hip.last_dispatch()
+            assert ran == ("env_step_loop_sf_kernel" if path != "launches" and hi - lo > 1 else "env_step_kernel"), (ran, lo, hi)
+            for t in range(lo, hi):
+                b.step(acts[t])
+            assert _hip.last_dispatch() == "env_step_kernel"
+            torch.cuda.synchronize()
+            _same_bytes(a, b, "N=%d vis=%d %s without %s after %d steps" % (N, vis, path, null, hi))
+        rec = a.rollout_buffers
+        fin = rec["fin_count"].cpu().numpy()
+        assert fin.max() >= 3 and (fin >= 1).all(), "episodes must end, restart from the pool and overflow the two slots"
+        assert rec["danger_count"].cpu().numpy().sum() > 0
+        for k in ("fin_return", "fin_time"):
+            got = rec[k].cpu().numpy()
+            assert np.isnan(got).all() if k == null else not np.isnan(got[0]).any(), k
+        info = rec["fin_info"].cpu().numpy()
+        assert (info == SENTINEL).all() if null == "fin_info" else (info[0] != SENTINEL).all()
+        assert np.isnan(a.human_act.cpu().numpy()).all() == (null == "human_act")
+
+
+# ------------------------------------------------------------------------------------------ 4 symmetry
+def test_mirrored_pair_gets_exactly_negated_actions(tuning):
+    torch = _torch()
+    rng = np.random.RandomState(3)
+    st = H.random_state(rng, E, 2, randomize=True)
+    for k in ("hpx", "hpy", "hvx", "hvy", "hgx", "hgy"):
+        getattr(st, k)[:, 1] = -getattr(st, k)[:, 0]
+    st.hr[:, 1], st.hvpref[:, 1] = st.hr[:, 0], st.hvpref[:, 0]
+    st.hpx[:40, 0] = rng.uniform(0.05, 0.6, 40); st.hpx[:40, 1] = -st.hpx[:40, 0]       # close, head-on along x
+    st.hpy[:40] = 0.0
+    env = _sf_env(E, 2, 0)
+    act = torch.from_numpy(_actions(9)).cuda()
+    for block in (64, 256):
+        tuning(step_block=block)
+        H.upload(env, st)
+        env.step(act, update=False)
+        got = env.human_act.cpu().numpy()
+        assert (got[:, 0] == -got[:, 1]).all() and (np.abs(got).sum(-1) > 0).any()
+        want, _ = R.batch_velocities(np.stack([st.hpx, st.hpy], -1), np.stack([st.hvx, st.hvy], -1),
+                                     np.stack([st.hgx, st.hgy], -1), st.hr, st.hvpref, *DEFAULT, DT)
+        assert np.abs(got - want).max() < 1e-12
+
+
+# ------------------------------------------------------------------------------------------ 5 the public surface
+def test_vec_env_reset_step_rollout():
+    torch = _torch()
+    from modelcrowdnav_amd import _hip
+    n = 64
+    a, b = _sf_env(n, 5, 1), _sf_env(n, 5, 1)
+    for env in (a, b):
+        ob = env.reset("test", test_cases=list(range(n)))
+        assert tuple(ob.pos.shape) == (n, 5, 2)
+    st = H.download(a)
+    acts = torch.from_numpy(np.random.RandomState(2).uniform(-0.7, 0.7, (9, n, 2))).cuda()
+    ob, reward, done, info = a.step(acts[0])
+    want, mag = R.batch_velocities(np.stack([st.hpx, st.hpy], -1), np.stack([st.hvx, st.hvy], -1),
+                                   np.stack([st.hgx, st.hgy], -1), st.hr, st.hvpref, *DEFAULT, DT,
+                                   np.stack([st.rpx, st.rpy], -1), st.rr)
+    assert (np.abs(a.human_act.cpu().numpy() - want) <= 8 * 2.0 ** -52 * mag[..., None]).all()
+    H.assert_bits_equal(ob.vel.cpu().numpy(), a.human_act.cpu().numpy(), "observation")
+    assert tuple(reward.shape) == (n,) and done.dtype == torch.uint8 and info.dtype == torch.uint8
+    a.rollout(acts[1:])
+    assert _hip.last_dispatch() == "env_step_loop_sf_kernel"
+    for t in range(9):
+        b.step(acts[t])
+    torch.cuda.synchronize()
+    H.assert_state_equal(H.download(a), H.download(b), fields=STATE_FIELDS, what="rollout vs steps")
+    _bytes_equal(a.step_rec.cpu().numpy(), b.step_rec.cpu().numpy(), "step records")
+    assert a.gtime.cpu().numpy().tolist() == [9 * DT] * n
+
+
+def _sarl(query_env=False):
+    torch = _torch()
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.policy.sarl import SARL
+    torch.manual_seed(11)
+    p = SARL()
+    p.configure(configs.policy_config(**({"action_space.query_env": "true"} if query_env else {})))
+    p.kinematics = "holonomic"
+    p.set_device(torch.device("cuda", 0))
+    p.set_phase("test")
+    p.time_step = DT
+    return p
+
+
+def _single_env(policy):
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.envs.crowd_sim import CrowdSim
+    from modelcrowdnav_amd.envs.utils.robot import Robot
+    cfg = configs.env_config(**{"sim.human_num": 5, "humans.policy": "socialforce"})
+    env = CrowdSim()
+    env.configure(cfg)
+    robot = Robot(cfg, "robot")
+    robot.set_policy(policy)
+    env.set_robot(robot)
+    return env, robot
+
+
+def test_explorer_batched_equals_sequential():
+    """Explorer.run_k_episodes(64, 'test') with a SARL robot among social-force humans: batched (VecExplorer) and
+    batched = False give the same success / collision / timeout rates and navigation time."""
+    torch = _torch()
+    from modelcrowdnav_amd.utils.explorer import Explorer
+    res = []
+    for batched in (True, False):
+        env, robot = _single_env(_sarl())
+        ex = Explorer(env, robot, torch.device("cuda", 0), gamma=0.9)
+        ex.batched = batched
+        res.append(ex.run_k_episodes(64, "test", returnNav=True))
+        assert ex.last_run_batched == batched
+    a, b = res
+    assert tuple(a[1:4]) == tuple(b[1:4]), (a, b)
+    assert abs(a[4] - b[4]) < 1e-9 and abs(a[0] - b[0]) < 1e-9, (a, b)
+
+
+def test_single_env_view_matches_the_batched_env():
+    torch = _torch()
+    from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
+    from modelcrowdnav_amd.envs.policy.socialforce import SocialForce
+    from modelcrowdnav_amd.envs.utils.action import ActionXY
+    pol = policy_factory["orca"]()
+    pol.multiagent_training = True
+    env, robot = _single_env(pol)
+    vec = _sf_env(4, 5, 0)
+    vec.reset("test", test_cases=[5, 6, 7, 8])
+    env.reset("test", test_case=7)
+    assert all(isinstance(h.policy, SocialForce) for h in env.humans)
+    moves = [(0.3, 0.4), (-0.1, 0.6), (0.0, 0.0)]
+    for vx, vy in moves:
+        ob, reward, done, info = env.step(ActionXY(vx, vy))
+        vob, vrew, _, _ = vec.step(torch.tensor([[vx, vy]] * 4, dtype=torch.float64).cuda())
+        want = vob.tensor()[2].cpu().numpy()
+        got = np.array([[o.px, o.py, o.vx, o.vy, o.radius] for o in ob])
+        H.assert_bits_equal(got, want, "observation of env 2")
+        assert reward == float(vrew[2])
+    assert any(o.vx != 0 or o.vy != 0 for o in ob)
+    robot.set_position((robot.gx, robot.gy))                    # arrived: the ORCA env would now simulate to the end
+    with pytest.raises(NotImplementedError, match="social-force"):
+        env.get_human_times()
+
+
+def test_query_env_lookahead_is_the_non_mutating_step():
+    """`query_env = true`: the humans' next states and the rewards the look-ahead is given are those of
+    step(update = False), for three envs and every action of the table."""
+    torch = _torch()
+    pol = _sarl(query_env=True)
+    vec = _sf_env(3, 5, 1)
+    vec.robot.set_policy(pol)
+    vec.reset("test", test_cases=[11, 12, 13])
+    warm = torch.from_numpy(np.random.RandomState(4).uniform(-0.5, 0.5, (6, 3, 2))).cuda()
+    for t in range(6):
+        vec.step(warm[t])                                      # moving humans, robot off its start
+    # env 0: the robot 0.15 m from a human (Danger, Collision for actions towards it); env 1: near its goal (ReachGoal)
+    vec.rpos[0] = vec.hpos[0, 0] + torch.tensor([0.75, 0.0], dtype=torch.float64, device=vec.device)
+    vec.rgoal[1] = vec.rpos[1] + torch.tensor([0.3, 0.1], dtype=torch.float64, device=vec.device)
+    before = H.download(vec)
+    actions, _ = pol.predict_batch(vec)
+    assert tuple(actions.shape) == (3, 2)
+    npos, nvel, rewards = pol._query_env(vec)
+    table = np.array([[a.vx, a.vy] for a in pol.action_space])
+    assert tuple(rewards.shape) == (3, len(table))
+    rewards = rewards.cpu().numpy()
+    for k, (vx, vy) in enumerate(table):
+        ob, rew, _, _ = vec.step(torch.tensor([[vx, vy]] * 3, dtype=torch.float64).cuda(), update=False)
+        H.assert_bits_equal(rew.cpu().numpy(), rewards[:, k], "reward of action %d" % k)
+        if k % 27 == 0:
+            H.assert_bits_equal(ob.pos.cpu().numpy(), npos.cpu().numpy(), "next positions")
+            H.assert_bits_equal(ob.vel.cpu().numpy(), nvel.cpu().numpy(), "next velocities")
+    assert np.abs(nvel.cpu().numpy()).max() > 0
+    assert (rewards[0] == vec.collision_penalty).any() and ((rewards[0] < 0) & (rewards[0] > vec.collision_penalty)).any()
+    assert (rewards[1] == vec.success_reward).any()
+    H.assert_state_equal(H.download(vec), before, fields=STATE_FIELDS, what="look-ahead left the state")

@@ -2,6 +2,7 @@
 """Kernel micro-benchmark (GPU box): per-launch time of mcn_env_step at several batch sizes and
 human-policy modes, measured with HIP events around a hipGraph of back-to-back launches.
     python tools/kbench.py [--humans 5] [--sizes 4096,65536,1048576] [--modes orca,given]
+    python tools/kbench.py --human-policy socialforce [--rollout 128 [--unfused]]   (mcn_env_step_sf / mcn_env_rollout_sf)
     python tools/kbench.py --sgan-predict --sizes 4096 --humans 10,5 --samples 1,20 --steps 8,12
     python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
 """
@@ -81,6 +82,9 @@ def main():
     ap.add_argument("--sizes", default="4096,65536,1048576")
     ap.add_argument("--modes", default="orca,given")
     ap.add_argument("--visible", action="store_true")
+    ap.add_argument("--human-policy", default="orca", choices=("orca", "socialforce"),
+                    help="the env's own humans in the 'orca' mode of --modes and in --rollout (socialforce: default parameters)")
+    ap.add_argument("--unfused", action="store_true", help="with --rollout: mcn_tuning.rollout_fused = 0 (T step launches)")
     ap.add_argument("--no-hh", action="store_true", help="no human-human overlap count (ModelCrowdSim.step does not count)")
     ap.add_argument("--pair-stream", type=int, default=-1, help="mcn_tuning.pair_stream")
     ap.add_argument("--lp3-defer", type=int, default=-1, help="mcn_tuning.lp3_defer")
@@ -133,6 +137,7 @@ def main():
     for E in [int(x) for x in a.sizes.split(",")]:
         env, _ = bench.build_env(E, N, 0, dev)
         env.robot.visible = a.visible
+        env.human_policy_name = a.human_policy
         if a.no_hh:
             env.count_hh = False
         if a.pair_stream >= 0:
@@ -163,6 +168,8 @@ def main():
                 s.record(); graph.replay(); e.record(); torch.cuda.synchronize()
                 best = min(best, s.elapsed_time(e) / a.iters)
             nb = bench.pairwise_bytes_per_env_step(N) if mode.startswith("given") else bench.algorithmic_bytes_per_env_step(N)
+            if mode.startswith("orca") and a.human_policy != "orca":
+                mode = a.human_policy + mode[4:]
             print("N=%d E=%8d mode=%-12s  %9.2f us/launch  %8.1f M env-steps/s  %7.1f GB/s (%.1f%% of 8 TB/s)" % (
                 N, E, mode, best * 1e3, E / best / 1e3, nb * E / best / 1e6, nb * E / best / 1e6 / 80.0))
         del env
@@ -175,10 +182,11 @@ def rollout_bench(a):
     dev = torch.device("cuda", 0)
     N, T = a.humans, a.rollout
     from modelcrowdnav_amd import _hip
-    _hip.set_tuning(rollout_fused=1)
+    _hip.set_tuning(rollout_fused=0 if a.unfused else 1)
     for E in [int(x) for x in a.sizes.split(",")]:
         env, _ = bench.build_env(E, N, 0, dev)
         env.robot.visible = a.visible
+        env.human_policy_name = a.human_policy
         acts = bench.make_actions(T, E, E, 0, dev)
         env.rollout(acts)
         torch.cuda.synchronize()
@@ -187,7 +195,8 @@ def rollout_bench(a):
         for rep in range(5):
             s.record(); env.rollout(acts); e.record(); torch.cuda.synchronize()
             best = min(best, s.elapsed_time(e) / T)
-        print("N=%d E=%8d rollout T=%d  %9.3f us/step  %8.1f M env-steps/s" % (N, E, T, best * 1e3, E / best / 1e3))
+        print("N=%d E=%8d %s rollout T=%d (%s)  %9.3f us/step  %8.1f M env-steps/s" % (
+            N, E, a.human_policy, T, _hip.last_dispatch(), best * 1e3, E / best / 1e3))
         del env
 
 
