@@ -572,7 +572,8 @@ typedef struct mcn_tuning {
     int32_t quad_max_envs;   /* mcn_env_step: lanes-per-neighbour ("quad") kernel up to this batch size (0 = never) */
     int32_t quad_split;      /* quad kernel: ORCA and float64 pairwise work on two cooperating wavefronts (0/1) */
     int32_t rollout_fused;   /* mcn_env_rollout: one T-step launch (1) or T single-step launches (0) */
-    int32_t rollout_split;   /* fused rollout: two cooperating wavefronts per env group (0/1) */
+    int32_t rollout_split;   /* fused rollout: 0 one wavefront per env group, 1 two cooperating ones, 2 workgroups of 8 envs on
+                              * four wavefronts (5 humans, invisible robot; other shapes take form 1) */
     int32_t step_block;      /* lane-per-human step kernels: workgroup of 64 or 256 lanes (-1: 64 up to 4096 wavefronts, 256 above) */
     int32_t diag_noop;       /* DIAGNOSTIC build only (make stamp): env kernels return at entry; MCN_EINVAL otherwise */
     int32_t pair_stream;     /* given-velocity step: streaming kernel (env_pair.hip) 1 wherever it applies / 0 never;
@@ -618,6 +619,14 @@ int64_t mcn_sizeof(int32_t which);                 /* sizeof the struct named by
  * mcn_env_rollout call (or social-force twin) dispatched to; "" before the first call.  bench.py attributes profiles to the kernel that really ran with it.
  */
 const char *mcn_last_dispatch(void);
+
+/*
+ * Diagnostic: which form of the fused rollout kernel the calling thread's latest mcn_env_rollout call launched, noted
+ * at the launch itself: 0 one wavefront per env group, 1 two cooperating wavefronts, 2 workgroups of 8 envs on four
+ * wavefronts (env_rollout_wg4_kernel).  -1 when that call did not take the fused quad path, and before the first call.
+ * mcn_tuning.rollout_split = 2 on a shape the four-wavefront form is not built for reports 1: what ran.
+ */
+int32_t mcn_last_rollout_form(void);
 
 #ifdef __cplusplus
 }

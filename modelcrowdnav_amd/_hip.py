@@ -185,6 +185,7 @@ def _load():
     lib.mcn_abi_version.restype = _i
     lib.mcn_sizeof.argtypes, lib.mcn_sizeof.restype = [_i], C.c_int64
     lib.mcn_last_dispatch.restype = C.c_char_p
+    lib.mcn_last_rollout_form.restype = _i
     _check_abi(lib)
     return lib
 
@@ -226,10 +227,16 @@ def last_dispatch():
     return lib.mcn_last_dispatch().decode()
 
 
+def last_rollout_form():
+    """Form of the fused rollout kernel the calling thread's latest mcn_env_rollout launched: 0, 1 or 2 (four
+    wavefronts); -1 when it did not take the fused quad path (mcn_last_rollout_form)."""
+    return int(lib.mcn_last_rollout_form())
+
+
 lib = _load()
 
 # every symbol include/mcn.h declares; tests/test_abi.py checks the .so exports each one
-EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
+EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_last_rollout_form", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict"]
 

@@ -21,6 +21,7 @@
 
 namespace mcn {
 void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispatch()
+void note_rollout_form(int form);                // mcn_api.hip: mcn_last_rollout_form()
 
 // Diagnostic build only (make -C modelcrowdnav_amd/csrc stamp -> build_stamp/libmcn_hip.so, tools/fixed_cost.py):
 // lane 0 of every wavefront writes the 100 MHz real-time counter at kernel entry (slot 0), after the state load
@@ -107,6 +108,333 @@ __device__ __forceinline__ KernargPtr kernarg_here()
     return q;
 }
 
+// Four-wavefront form (env_rollout_wg4_kernel): workgroups of EW envs on FOUR wavefronts -- three ORCA wavefronts
+// for the EW * NT quads, dealt in order
+// (quad q = env q / NT, human q % NT, so an env may straddle two wavefronts), and one float64 wavefront with one lane
+// per (env, human).  The two-wavefront form gives every 3 envs a float64 wavefront of their own, which repeats each
+// swept-circle test on 4 lanes and the ladder on 20; here 8 envs share it, and 4096 envs x 5 humans become 512
+// workgroups = exactly two wavefronts on each of the chip's 1024 SIMDs instead of two on some and three on others.
+// The roles meet only through LDS, as in the two-wavefront form and at the same two points of the step; the ORCA
+// lanes fetch their candidate neighbour from the hand-off arrays too (an env's quads need not share a wavefront, so
+// there is no ds_bpermute to take it from).  Same arithmetic per value, so the same bits.
+//
+// The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot integrate / restart and the
+// epilogue, and the ORCA wavefronts' human integrate / restart, are the TWIN of env_rollout_quad_kernel's below (the
+// older forms keep their code, hence their registers, so the text is not shared): a change to either is made to both.
+template <int NT>
+struct Wg4 {
+    static_assert(NT == 5, "the four-wavefront form is built for 5 humans only");
+    static constexpr int EW = 8;                              // envs per workgroup
+    static constexpr int NQ = EW * NT;                        // populated quads = populated float64 lanes: 40 of 48 / 64
+};
+
+template <int NT, int VIS, bool UNI>
+__device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
+{
+    static_assert(VIS == 0, "the four-wavefront form is built for an invisible robot only");
+    constexpr int EW = Wg4<NT>::EW, NQ = Wg4<NT>::NQ;
+    __shared__ double2 s_hpos[64], s_hvel[64];
+    __shared__ double s_hrad[64];
+    __shared__ int s_dn[16], s_case[16];
+    STAMP(0);
+    STAMP_WHERE();
+#ifdef MCN_DIAG
+    if (p.debug_noop) return;
+#endif
+    const int tid = threadIdx.x;
+    // wave-uniform by construction, and known to be: each role runs its own step loop, barriers included
+    const int role = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0-2: ORCA, 3: robot + ladder + records
+    const unsigned nb_ = gridDim.x, xcd_ = blockIdx.x & 7u, idx_ = blockIdx.x >> 3;       // XCD-aware chunking, as below
+    const unsigned qq_ = nb_ >> 3, rr__ = nb_ & 7u;
+    const unsigned chunk_ = (xcd_ < rr__ ? xcd_ * (qq_ + 1) : rr__ * (qq_ + 1) + (xcd_ - rr__) * qq_) + idx_;
+    const mcn_env_cfg &c = p.cfg;
+    const mcn_rollout &ro = p.roll;
+    const double dt = in_vgpr(c.time_step);
+    const bool do_reset = p.has_roll && ro.pool_hpos != nullptr;
+
+    if (role < 3) {
+        // ---------------- ORCA wavefronts: the humans ----------------
+        const int lane = tid & 63, k = tid & 3, q = tid >> 2;
+        const bool pop = q < NQ;                                 // idle quads (and envs >= E) alias env 0, store nothing
+        const int ge = q / NT, h = q - ge * NT;
+        const long e = (long)chunk_ * EW + ge;
+        const bool active = pop && e < p.E;
+        const long eb = active ? e : 0;
+        const long a = eb * NT + h;
+        const int gi = pop ? ge : 0, hi = pop ? q : 0;           // LDS slots of this quad's env / human
+        const bool hlead = active && k == 0;                     // owns the human's records
+        const bool track = c.track_human_times && p.st.human_times != nullptr;
+        const bool cand_h = k < NT - 1;                          // candidate is another human
+        const int j = cand_h ? k + (k >= h ? 1 : 0) : h;
+        const int ci = pop ? ge * NT + j : 0;
+
+        double2 pos = reinterpret_cast<const double2 *>(p.st.hpos)[a];
+        double2 vel = reinterpret_cast<const double2 *>(p.st.hvel)[a];
+        double2 goal = reinterpret_cast<const double2 *>(p.st.hgoal)[a];
+        double rad = p.st.hrad[a];
+        double vpref = p.st.hvpref[a];
+        double htime = p.st.human_times ? p.st.human_times[a] : 0.0;
+        double gtime = p.st.gtime[eb];                           // these wavefronts keep their own copy of the clock
+        double hax = 0, hay = 0;
+        const float inv_th = in_vgpr(1.0f / c.orca_time_horizon), inv_ts = in_vgpr(1.0f / (float)c.time_step);
+        // the first step's candidates: the loaded state goes through the hand-off arrays
+        if (pop && k == 0) { s_hpos[hi] = pos; s_hvel[hi] = vel; s_hrad[hi] = rad; }
+        __syncthreads();
+        STAMP(1);
+
+        for (int t = 0; t < T; ++t) {
+            // ---- candidate neighbour: published by the quad that owns it, behind the step's second barrier ----
+            const double2 cpos = s_hpos[ci], cvel = s_hvel[ci];
+            const double crd = s_hrad[ci];
+            float rx, ry;
+            quad_orca_velocity(c, lane, k, cand_h && active, pos, vel, goal, rad, vpref,
+                               make_float4((float)cpos.x, (float)cpos.y, (float)cvel.x, (float)cvel.y), crd, inv_th, inv_ts,
+                               rx, ry);
+            hax = (double)rx; hay = (double)ry;
+
+            __syncthreads();                                     // hand-off 1: done flag and restart case
+            const int dn = s_dn[gi], case_g = s_case[gi];
+
+            // ---- humans: integrate, or restart from the scenario pool ----
+            if (do_reset && dn) {
+                DIAG_COUNT(1);
+                if (active) {
+                    const long pa = (long)case_g * NT + h;
+                    const KernargPtr kp = kernarg_here();
+                    const double2 *pool_hvel = reinterpret_cast<const double2 *>(kp->roll.pool_hvel);
+                    pos = reinterpret_cast<const double2 *>(kp->roll.pool_hpos)[pa];
+                    goal = reinterpret_cast<const double2 *>(kp->roll.pool_hgoal)[pa];
+                    rad = kp->roll.pool_hrad[pa];
+                    vpref = kp->roll.pool_hvpref[pa];
+                    vel = pool_hvel ? pool_hvel[pa] : make_double2(0, 0);
+                }
+                htime = 0;
+            } else {
+                pos = make_double2(pos.x + hax * dt, pos.y + hay * dt);
+                vel = make_double2(hax, hay);
+                if (track && htime == 0 && norm2(pos.x - goal.x, pos.y - goal.y) < rad) htime = gtime + dt;
+            }
+            gtime = (do_reset && dn) ? 0.0 : gtime + dt;
+            if (pop && k == 0) { s_hpos[hi] = pos; s_hvel[hi] = vel; s_hrad[hi] = rad; }
+            __syncthreads();                                     // hand-off 2: the humans' new state
+            if (t < 37) STAMP(2 + t);
+        }
+
+        long a2 = a;
+        asm volatile("" : "+v"(a2));
+        const KernargPtr kp = kernarg_here();
+        if (hlead) {
+            reinterpret_cast<double2 *>(kp->st.hpos)[a2] = pos;
+            reinterpret_cast<double2 *>(kp->st.hvel)[a2] = vel;
+            if (do_reset) {
+                reinterpret_cast<double2 *>(kp->st.hgoal)[a2] = goal;
+                kp->st.hrad[a2] = rad;
+                kp->st.hvpref[a2] = vpref;
+            }
+            double *human_times = kp->st.human_times, *human_act = kp->out.human_act;
+            if (human_times) human_times[a2] = htime;
+            if (human_act) reinterpret_cast<double2 *>(human_act)[a2] = make_double2(hax, hay);
+        }
+    } else {
+        // ---------------- float64 wavefront: lane l = (env l / NT, human l % NT) ----------------
+        const int l = tid & 63;
+        const bool pop = l < NQ;
+        const int g = l / NT, h = l - g * NT, l0 = l - h;
+        const long e = (long)chunk_ * EW + g;
+        const bool active = pop && e < p.E;
+        const long eb = active ? e : 0;
+        const int gi = pop ? g : 0;
+        const bool lead = active && h == 0;                      // owns the per-env records
+        constexpr bool unicycle = UNI;
+        const bool has_state = p.has_roll && ro.state != nullptr;
+
+        double2 rpos = reinterpret_cast<const double2 *>(p.st.rpos)[eb];
+        double2 rvel = reinterpret_cast<const double2 *>(p.st.rvel)[eb];
+        double2 rgoal = reinterpret_cast<const double2 *>(p.st.rgoal)[eb];
+        const double rrad = p.st.rrad[eb];
+        double gtime = p.st.gtime[eb];
+        double rtheta = p.st.rtheta ? p.st.rtheta[eb] : 0.0;
+        // the robot, the clock and the Explorer record are held redundantly by the env's NT lanes
+        mcn_roll_rec rs = {0, 0, 0, 0, 0, 0};
+        if (has_state) rs = ro.state[eb];
+        const double2 *act_ptr = reinterpret_cast<const double2 *>(p.actions) + eb;
+        const long act_stride = in_vgpr((long)p.E);
+        const double *disc_table = in_vgpr(ro.disc_table);
+        const int disc_last = in_vgpr(ro.disc_len - 1);
+        const bool has_theta = p.st.rtheta != nullptr;
+        double2 act_next = *act_ptr;
+        double o_rew = 0, o_dmin = 0;
+        int o_dn = 0, o_inf = 0, o_hh = 0;
+        if (!pop) { s_hpos[l] = make_double2(0, 0); s_hvel[l] = make_double2(0, 0); s_hrad[l] = 0; }   // slots no quad writes
+        __syncthreads();
+        STAMP(1);
+
+        for (int t = 0; t < T; ++t) {
+            const double2 act = act_next;
+            act_ptr += act_stride;
+            if (t + 1 < T) act_next = *act_ptr;
+            double ep_disc = 0;
+            if (has_state) ep_disc = disc_table[rs.ep_steps < disc_last ? rs.ep_steps : disc_last];
+
+            const double2 pos = s_hpos[l], vel = s_hvel[l];
+            const double rad = s_hrad[l];
+
+            // ---- K2: the swept circle of human h; the env's unordered human pairs spread over its lanes ----
+            double2 eff = act;
+            if (unicycle) {
+                eff.x = act.x * cos(act.y + rtheta);
+                eff.y = act.x * sin(act.y + rtheta);
+            }
+            double cd;
+            {
+                const double px = pos.x - rpos.x, py = pos.y - rpos.y;
+                const double vx = vel.x - eff.x, vy = vel.y - eff.y;
+                cd = p2s_origin(px, py, px + vx * dt, py + vy * dt) - rad - rrad;
+            }
+            // Lane h takes the pairs (h, h + d mod NT) for d = 1 .. NT / 2: NT is odd, so that is every unordered pair
+            // exactly once.  The two-wavefront form tests a pair on the quad of its LOWER
+            // human a against candidate b > a: sqrt(s2) - rad_a - rad_b, so the radii are put in that order here; s2 itself
+            // does not see the order (the differences only change sign).  Same conservative screen for the sqrt.
+            int hh = 0;
+#pragma unroll
+            for (int d = 1; d <= NT / 2; ++d) {
+                const int jj = h + d >= NT ? h + d - NT : h + d;
+                const int pi = (l0 + jj) & 63;
+                const double2 ppos = s_hpos[pi];
+                const double prad = s_hrad[pi];
+                const double ra = jj > h ? rad : prad, rb = jj > h ? prad : rad;
+                const double dx = pos.x - ppos.x, dy = pos.y - ppos.y;
+                const bool counted = active & (c.count_hh != 0);
+                const double s2 = dx * dx + dy * dy, reach = ra + rb + 1e-6;
+                if (__any(counted & (s2 < reach * reach))) DIAG_COUNT(2);
+                if (__any(counted & (s2 < reach * reach)))
+                    hh += (counted & ((sqrt(s2) - ra - rb) < 0)) ? 1 : 0;
+            }
+            double dmin = INFINITY;
+            int hh_sum = 0;
+#pragma unroll
+            for (int qh = 0; qh < NT; ++qh) {
+                const int s = (l0 + qh) & 63;
+                dmin = fmin(dmin, __shfl(cd, s));
+                hh_sum += __shfl(hh, s);
+            }
+
+            // ---- K3: ladder, on every lane of the env ----
+            double endx, endy, new_theta = rtheta, nrvx, nrvy;
+            if (unicycle) {
+                const double th = rtheta + act.y;
+                endx = rpos.x + cos(th) * act.x * dt;
+                endy = rpos.y + sin(th) * act.x * dt;
+                new_theta = pymod(rtheta + act.y, 2 * M_PI);
+                nrvx = act.x * cos(new_theta); nrvy = act.x * sin(new_theta);
+            } else {
+                endx = rpos.x + act.x * dt; endy = rpos.y + act.y * dt;
+                nrvx = act.x; nrvy = act.y;
+            }
+            bool reaching = false;
+            {
+                const double gx = endx - rgoal.x, gy = endy - rgoal.y, near = rrad + 1e-6;
+                if (__any(gx * gx + gy * gy < near * near)) DIAG_COUNT(3);
+                if (__any(gx * gx + gy * gy < near * near)) reaching = norm2(gx, gy) < rrad;
+            }
+            const KernargPtr kc = kernarg_here();
+            const double k_time_limit = kc->cfg.time_limit, k_timeout_at = k_time_limit - 1;
+            const double k_collision = kc->cfg.collision_penalty, k_success = kc->cfg.success_reward;
+            const double k_discomfort = kc->cfg.discomfort_dist, k_factor = kc->cfg.discomfort_penalty_factor;
+            double rew; int inf, dn;
+            if (gtime >= k_timeout_at)          { rew = 0; dn = 1; inf = MCN_INFO_TIMEOUT; }
+            else if (dmin < 0)                  { rew = k_collision; dn = 1; inf = MCN_INFO_COLLISION; }
+            else if (reaching)                  { rew = k_success; dn = 1; inf = MCN_INFO_REACHGOAL; }
+            else if (dmin < k_discomfort)       { rew = (dmin - k_discomfort) * k_factor * dt; dn = 0; inf = MCN_INFO_DANGER; }
+            else                                { rew = 0; dn = 0; inf = MCN_INFO_NOTHING; }
+            o_rew = rew; o_dmin = dmin; o_dn = dn; o_inf = inf; o_hh = hh_sum;
+            const double t_new = gtime + dt;
+
+            // ---- Explorer accounting: every lane of the env updates its copy; the stores are the lead lane's ----
+            const int case_g = rs.next_case;
+            if (has_state) {
+                bool danger = inf == MCN_INFO_DANGER;
+                if (danger) {
+                    const KernargPtr kp = kernarg_here();
+                    const int lim = kp->roll.danger_episodes, sf = kp->roll.danger_short_from;
+                    danger = lim <= 0 || rs.fin_count < lim - ((sf > 0 && e >= sf - 1) ? 1 : 0);
+                }
+                rs.danger_count += danger ? 1 : 0;
+                rs.danger_dist_sum = danger ? rs.danger_dist_sum + dmin : rs.danger_dist_sum;
+                const double ret = rs.ep_return + ep_disc * rew;
+                if (lead && dn) {
+                    const int kf = rs.fin_count;
+                    const KernargPtr kp = kernarg_here();
+                    const int fin_slots = kp->roll.fin_slots;
+                    double *fin_return = kp->roll.fin_return, *fin_time = kp->roll.fin_time;
+                    uint8_t *fin_info = kp->roll.fin_info;
+                    const bool keep = (fin_slots == 1) || (kf < fin_slots);
+                    const long rec = (long)(fin_slots == 1 ? 0 : kf) * kp->E + e;
+                    if (keep && fin_return) fin_return[rec] = ret;
+                    if (keep && fin_time)   fin_time[rec] = (inf == MCN_INFO_TIMEOUT) ? k_time_limit : t_new;
+                    if (keep && fin_info)   fin_info[rec] = (uint8_t)inf;
+                }
+                rs.fin_count += dn;
+                rs.ep_return = dn ? 0.0 : ret;
+                rs.ep_steps = dn ? 0 : rs.ep_steps + 1;
+                if (do_reset) {
+                    const int k_stride = kc->roll.case_stride, k_pool = kc->roll.pool_size;
+                    int nc = rs.next_case + k_stride;
+                    nc = nc >= k_pool ? nc - k_pool : nc;
+                    rs.next_case = dn ? nc : rs.next_case;
+                }
+            }
+
+            // ---- robot: integrate, or back to the start pose ----
+            if (do_reset && dn) {
+                const KernargPtr kp = kernarg_here();
+                const double k_theta0 = kp->roll.robot_theta0;
+                rpos = make_double2(kp->roll.robot_start[0], kp->roll.robot_start[1]);
+                rgoal = make_double2(kp->roll.robot_goal[0], kp->roll.robot_goal[1]);
+                rvel = make_double2(0, 0);
+                if (has_theta) rtheta = k_theta0;
+                gtime = 0;
+            } else {
+                rpos = make_double2(endx, endy);
+                rvel = make_double2(nrvx, nrvy);
+                if (unicycle) rtheta = new_theta;
+                gtime = t_new;
+            }
+
+            if (pop && h == 0) { s_dn[gi] = dn; s_case[gi] = case_g; }
+            __syncthreads();                                     // hand-off 1
+            __syncthreads();                                     // hand-off 2: the next step reads the humans' new state
+            if (t < 37) STAMP(2 + t);
+        }
+
+        long e2 = e;
+        asm volatile("" : "+v"(e2));
+        const KernargPtr kp = kernarg_here();
+        if (lead) {
+            reinterpret_cast<double2 *>(kp->st.rpos)[e2] = rpos;
+            reinterpret_cast<double2 *>(kp->st.rvel)[e2] = rvel;
+            if (do_reset) reinterpret_cast<double2 *>(kp->st.rgoal)[e2] = rgoal;
+            double *rth = kp->st.rtheta;
+            if (rth) rth[e2] = rtheta;
+            kp->st.gtime[e2] = gtime;
+            store_step_rec(kp->out.rec + e2, o_rew, o_dmin, o_dn, o_inf, o_hh);
+            if (has_state) kp->roll.state[e2] = rs;
+        }
+    }
+    STAMP(39);
+}
+
+// The four-wavefront form as a kernel of its own: 256 lanes, two workgroups per CU.  (StepParams stays argument 0:
+// kernarg_here.)
+template <int NT, int VIS, bool UNI>
+__global__ __launch_bounds__(256, 2) void env_rollout_wg4_kernel(const StepParams p, const int T)
+{
+    rollout_wg4<NT, VIS, UNI>(p, T);
+}
+
+// TWIN: rollout_wg4 above carries a copy of this kernel's ladder, Explorer accounting, finished-episode stores, robot
+// and human integrate / restart and epilogue; a change to either is made to both (tests/test_rollout_wg4_gpu.py
+// compares their bytes).
 template <int NT, int VIS, bool UNI, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_quad_kernel(const StepParams p, const int T)
 {
@@ -430,10 +758,21 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_q
 template <int NT, int VIS, bool UNI>
 static void launch_rollout_kin(const StepParams &p, int T, int blocks, hipStream_t stream)
 {
+    // quad_split = 2: the four-wavefront form where it is built (5 humans, invisible robot); every other shape keeps
+    // the two-wavefront form
+    if constexpr (NT == 5 && VIS == 0) {
+        if (p.quad_split == 2) {
+            constexpr int EW = Wg4<NT>::EW;
+            hipLaunchKernelGGL((env_rollout_wg4_kernel<NT, VIS, UNI>), dim3((p.E + EW - 1) / EW), dim3(256), 0, stream, p, T);
+            note_rollout_form(2);
+            return;
+        }
+    }
     if (p.quad_split)
         hipLaunchKernelGGL((env_rollout_quad_kernel<NT, VIS, UNI, true>), dim3(blocks), dim3(128), 0, stream, p, T);
     else
         hipLaunchKernelGGL((env_rollout_quad_kernel<NT, VIS, UNI, false>), dim3(blocks), dim3(64), 0, stream, p, T);
+    note_rollout_form(p.quad_split ? 1 : 0);
 }
 
 template <int NT, int VIS>

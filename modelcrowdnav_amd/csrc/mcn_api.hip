@@ -139,6 +139,10 @@ int mcn_pack_x3(const float *wfrag, int32_t NT, int32_t KT, void *x3_out)
 static thread_local const char *g_last_dispatch = "";
 namespace mcn { void note_dispatch(const char *family) { g_last_dispatch = family; } }
 const char *mcn_last_dispatch(void) { return g_last_dispatch; }
+// mcn_last_rollout_form(): set where env_rollout_quad.hip launches, so it names the kernel that really went out
+static thread_local int32_t g_last_rollout_form = -1;
+namespace mcn { void note_rollout_form(int form) { g_last_rollout_form = form; } }
+int32_t mcn_last_rollout_form(void) { return g_last_rollout_form; }
 
 int32_t mcn_abi_version(void) { return MCN_ABI_VERSION; }
 int64_t mcn_sizeof(int32_t which)
@@ -232,7 +236,7 @@ int mcn_set_tuning(const mcn_tuning *t)
 {
     std::lock_guard<std::mutex> lock(g_tuning_mu);
     if (!t) { g_tuning = tuning_from_env(); g_tuning_init = true; return MCN_OK; }
-    if (t->quad_split > 1 || t->rollout_fused > 1 || t->rollout_split > 1 || t->pair_stream > 3 || t->force_generic < 0 || t->force_generic > 1) return MCN_EINVAL;
+    if (t->quad_split > 1 || t->rollout_fused > 1 || t->rollout_split > 2 || t->pair_stream > 3 || t->force_generic < 0 || t->force_generic > 1) return MCN_EINVAL;
     if (t->quad_max_envs < -1 || t->quad_split < -1 || t->rollout_fused < -1 || t->rollout_split < -1 || t->pair_stream < -1) return MCN_EINVAL;
     if (t->step_block != -1 && t->step_block != 64 && t->step_block != 256) return MCN_EINVAL;
     if (t->lp3_defer < -1 || t->lp3_defer > 1) return MCN_EINVAL;
@@ -279,14 +283,30 @@ int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const doubl
     // launches of the throughput kernel: measured cross-over on MI355X at ~45 k envs of 5 humans (19.2 vs 18.6 us per
     // step at 49 152 envs, 13.9 vs 15.3 at 32 768), i.e. ~14 k env groups; below that the fused launch wins by up to
     // 2.7x.  Two cooperating wavefronts per env group while the doubled grid still finds idle issue slots (measured:
-    // wins up to 1536 groups = 4608 envs, loses from 1707).
+    // wins up to 1536 groups = 4608 envs, loses from 1707).  The four-wavefront form (rollout_split = 2: workgroups of 8
+    // envs; built for 5 humans and an invisible robot) costs what its fullest CU holds and is taken only where it was
+    // measured to win (profiles/r12_rollout_wg4.txt, T = 1000 and T = 20, us per step at T = 1000 against the better of
+    // the other two forms):
+    //   holonomic robot (95 VGPRs, up to 4 workgroups per CU resident: 1.86 / 2.32 / 2.78 us at 2 / 3 / 4 per CU):
+    //     128 .. 512 workgroups (1024 envs 1.49 against 1.72, 4096 envs 1.86 against 2.10) and 768 .. 1024 (6144 / 8192
+    //     envs: 2.32 / 2.78 against 3.29 / 3.33).  Not below: at 64 and 256 envs no form shares a CU and the two-wavefront
+    //     form's shorter chain wins (1.43 against 1.47 / 1.51).  Not in between: at 4608 envs = 576 workgroups a quarter
+    //     of the CUs hold three and it loses (2.30 against 2.13).
+    //   unicycle robot (129 VGPRs: 3 wavefronts per SIMD, so the fourth workgroup of a CU waits; the other forms' 153 /
+    //     168 VGPRs cost them more): 8 .. 1024 workgroups, every size measured from 64 envs (1.96 against 2.11) over
+    //     4096 (2.32 against 3.37) and 4608 (3.06 against 3.39) to 8192 (4.18 against 5.45).
     // mcn_set_tuning (rollout_fused / rollout_split) overrides (tests, tuning).
     const mcn_tuning tu = tuning();
     const int envs_per_wave = 64 / (4 * N) > 0 ? 64 / (4 * N) : 1;
     const long waves = ((long)E + envs_per_wave - 1) / envs_per_wave;
     const bool fused = tu.rollout_fused >= 0 ? tu.rollout_fused != 0 : waves <= 14000;
     const int step_split = p.quad_split;              // the single-step kernel's own choice, for the T-launch path
-    p.quad_split = tu.rollout_split >= 0 ? tu.rollout_split : (waves <= 1536 ? 1 : 0);
+    const long wg4 = ((long)E + 7) / 8;
+    const bool wg4_wins = N == 5 && !cfg->robot_visible &&
+                          (cfg->robot_kinematics == MCN_KIN_UNICYCLE ? wg4 >= 8 && wg4 <= 1024
+                                                                     : (wg4 >= 128 && wg4 <= 512) || (wg4 >= 768 && wg4 <= 1024));
+    p.quad_split = tu.rollout_split >= 0 ? tu.rollout_split : wg4_wins ? 2 : (waves <= 1536 ? 1 : 0);
+    mcn::note_rollout_form(-1);
     if (fused && !p.force_generic && mcn::launch_env_rollout_quad(p, T, (hipStream_t)stream))
         return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
     p.quad_split = step_split;

@@ -15,6 +15,10 @@ outermost loop that has a child loop):
 Both are text ranges: the out-of-line IEEE fall-backs of fast_f32.hpp's range guards that the compiler places inside
 them are counted too (column `fallback`: how many of the region's instructions sit in such blocks, i.e. blocks with a
 v_sqrt_f32 or a v_div_scale_f32 of 1.0).  Static counts, not a measurement of time.
+
+The default kernel is the two-wavefront form.  The four-wavefront form (env_rollout_wg4_kernel, what 4096 envs x 5
+humans now run) has one step loop per role and no single nest for this census to pick: it stops with "no loop nest
+found" there; its counts in profiles/r12_kernel_resources.txt were read from the assembly by hand.
 """
 import argparse
 import os

@@ -3,7 +3,8 @@
 
     python tools/trace_launches.py <kernel_trace.csv> [kernel substring] > profiles/rNN_bench_rollout_launches.txt
 
-bench.py's headline kernel (mcn::env_rollout_quad_kernel) is launched with several lengths in one run -- the
+bench.py's headline kernel (mcn::env_rollout_wg4_kernel at 4096 envs x 5 humans, mcn::env_rollout_quad_kernel at other
+shapes; the default substring "env_rollout_" matches both) is launched with several lengths in one run -- the
 1000-step launches of the timed region and of the probe that sizes it, 20-step probe / `short_launch` passes, a few
 warm-up launches -- so the `--stats` average over all of them says nothing.  This lists every launch in dispatch order
 and averages each duration class (a launch's time is proportional to its steps), so that the class of the timed
@@ -15,7 +16,7 @@ import sys
 
 def main():
     path = sys.argv[1]
-    want = sys.argv[2] if len(sys.argv) > 2 else "env_rollout_quad_kernel"
+    want = sys.argv[2] if len(sys.argv) > 2 else "env_rollout_"
     rows = []
     with open(path, newline="") as fh:
         for r in csv.DictReader(fh):
