@@ -26,9 +26,10 @@ void note_rollout_form(int form);                // mcn_api.hip: mcn_last_rollou
 // Diagnostic build only (make -C modelcrowdnav_amd/csrc stamp -> build_stamp/libmcn_hip.so, tools/fixed_cost.py):
 // lane 0 of every wavefront writes the 100 MHz real-time counter at kernel entry (slot 0), after the state load
 // (slot 1), at the end of each of its first 36 steps (slots 2..37) and at exit (slot 39) to a buffer nothing else
-// reads.  The product build compiles none of it.
+// reads; the four-wavefront form also stamps each wavefront's arrival at hand-off 1 of its first 20 steps (slots
+// 40..59).  The product build compiles none of it.
 #ifdef MCN_DIAG
-#define MCN_STAMP_SLOTS 40
+#define MCN_STAMP_SLOTS 64
 #define MCN_STAMP_WAVES 8192
 __device__ unsigned long long g_stamps[MCN_STAMP_WAVES * MCN_STAMP_SLOTS];
 #define STAMP(slot)                                                                                              \
@@ -110,10 +111,15 @@ __device__ __forceinline__ KernargPtr kernarg_here()
 
 // Four-wavefront form (env_rollout_wg4_kernel): workgroups of EW envs on FOUR wavefronts -- three ORCA wavefronts
 // for the EW * NT quads, dealt in order
-// (quad q = env q / NT, human q % NT, so an env may straddle two wavefronts), and one float64 wavefront with one lane
-// per (env, human).  The two-wavefront form gives every 3 envs a float64 wavefront of their own, which repeats each
-// swept-circle test on 4 lanes and the ladder on 20; here 8 envs share it, and 4096 envs x 5 humans become 512
-// workgroups = exactly two wavefronts on each of the chip's 1024 SIMDs instead of two on some and three on others.
+// (quad q = env q / NT, human q % NT, so an env may straddle two wavefronts), and one float64 wavefront with eight
+// lanes per env: lane 8 g + h is (env g, human h) for h < NT, lanes h >= NT are idle (they hold no distance: +inf, and
+// no overlap), so an env's minimum distance and overlap count are three DPP exchanges inside its eight lanes.
+// The float64 wavefront is workgroup wave 3: the hardware deals a workgroup's waves one to each SIMD and starts the
+// two workgroups of a CU on different SIMDs, so their float64 wavefronts do not share one (census in
+// profiles/r13_rollout_roles.txt).
+// The two-wavefront form gives every 3 envs a float64 wavefront of their own, which repeats each swept-circle test on 4
+// lanes and the ladder on 20; here 8 envs share it, and 4096 envs x 5 humans become 512 workgroups = exactly two
+// wavefronts on each of the chip's 1024 SIMDs instead of two on some and three on others.
 // The roles meet only through LDS, as in the two-wavefront form and at the same two points of the step; the ORCA
 // lanes fetch their candidate neighbour from the hand-off arrays too (an env's quads need not share a wavefront, so
 // there is no ds_bpermute to take it from).  Same arithmetic per value, so the same bits.
@@ -128,13 +134,25 @@ struct Wg4 {
     static constexpr int NQ = EW * NT;                        // populated quads = populated float64 lanes: 40 of 48 / 64
 };
 
+// value of the lane a DPP control selects (all lanes of the wavefront active)
+template <int CTRL>
+__device__ __forceinline__ int dpp_i(int v) { return __builtin_amdgcn_mov_dpp(v, CTRL, 0xf, 0xf, true); }
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v)
+{
+    const long long b = __builtin_bit_cast(long long, v);
+    const int lo = dpp_i<CTRL>((int)b), hi = dpp_i<CTRL>((int)(b >> 32));
+    return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
+}
+constexpr int DPP_QUAD_XOR1 = 0xB1, DPP_QUAD_XOR2 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141;   // quad_perm [1,0,3,2], [2,3,0,1]
+
 template <int NT, int VIS, bool UNI>
 __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
 {
     static_assert(VIS == 0, "the four-wavefront form is built for an invisible robot only");
     constexpr int EW = Wg4<NT>::EW, NQ = Wg4<NT>::NQ;
-    __shared__ double2 s_hpos[64], s_hvel[64];
-    __shared__ double s_hrad[64];
+    __shared__ double2 s_hpos[NQ], s_hvel[NQ];
+    __shared__ double s_hrad[NQ];
     __shared__ int s_dn[16], s_case[16];
     STAMP(0);
     STAMP_WHERE();
@@ -192,6 +210,7 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                                rx, ry);
             hax = (double)rx; hay = (double)ry;
 
+            if (t < 20) STAMP(40 + t);
             __syncthreads();                                     // hand-off 1: done flag and restart case
             const int dn = s_dn[gi], case_g = s_case[gi];
 
@@ -236,14 +255,15 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
             if (human_act) reinterpret_cast<double2 *>(human_act)[a2] = make_double2(hax, hay);
         }
     } else {
-        // ---------------- float64 wavefront: lane l = (env l / NT, human l % NT) ----------------
+        // ---------------- float64 wavefront: lane 8 g + h = (env g, human h), h >= NT idle ----------------
+        static_assert(EW * 8 == 64, "eight lanes per env fill the wavefront");
         const int l = tid & 63;
-        const bool pop = l < NQ;
-        const int g = l / NT, h = l - g * NT, l0 = l - h;
+        const int g = l >> 3, h = l & 7;
+        const bool pop = h < NT;
+        const int hs = g * NT + (pop ? h : 0);                   // LDS slot of (env g, human h); idle lanes read human 0
         const long e = (long)chunk_ * EW + g;
         const bool active = pop && e < p.E;
-        const long eb = active ? e : 0;
-        const int gi = pop ? g : 0;
+        const long eb = e < p.E ? e : 0;                         // idle lanes carry the env's robot too: nothing is stored
         const bool lead = active && h == 0;                      // owns the per-env records
         constexpr bool unicycle = UNI;
         const bool has_state = p.has_roll && ro.state != nullptr;
@@ -265,7 +285,12 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         double2 act_next = *act_ptr;
         double o_rew = 0, o_dmin = 0;
         int o_dn = 0, o_inf = 0, o_hh = 0;
-        if (!pop) { s_hpos[l] = make_double2(0, 0); s_hvel[l] = make_double2(0, 0); s_hrad[l] = 0; }   // slots no quad writes
+        // the ladder's constants and the restart stride stay in vector registers: this role has them to spare
+        const double k_time_limit = in_vgpr(c.time_limit), k_timeout_at = in_vgpr(c.time_limit - 1);
+        const double k_collision = in_vgpr(c.collision_penalty), k_success = in_vgpr(c.success_reward);
+        const double k_discomfort = in_vgpr(c.discomfort_dist), k_factor = in_vgpr(c.discomfort_penalty_factor);
+        const int k_stride = in_vgpr(ro.case_stride), k_pool = in_vgpr(ro.pool_size);
+        const bool count_hh = c.count_hh != 0;
         __syncthreads();
         STAMP(1);
 
@@ -276,8 +301,8 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
             double ep_disc = 0;
             if (has_state) ep_disc = disc_table[rs.ep_steps < disc_last ? rs.ep_steps : disc_last];
 
-            const double2 pos = s_hpos[l], vel = s_hvel[l];
-            const double rad = s_hrad[l];
+            const double2 pos = s_hpos[hs], vel = s_hvel[hs];
+            const double rad = s_hrad[hs];
 
             // ---- K2: the swept circle of human h; the env's unordered human pairs spread over its lanes ----
             double2 eff = act;
@@ -291,33 +316,46 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 const double vx = vel.x - eff.x, vy = vel.y - eff.y;
                 cd = p2s_origin(px, py, px + vx * dt, py + vy * dt) - rad - rrad;
             }
+            cd = pop ? cd : INFINITY;
             // Lane h takes the pairs (h, h + d mod NT) for d = 1 .. NT / 2: NT is odd, so that is every unordered pair
             // exactly once.  The two-wavefront form tests a pair on the quad of its LOWER
             // human a against candidate b > a: sqrt(s2) - rad_a - rad_b, so the radii are put in that order here; s2 itself
             // does not see the order (the differences only change sign).  Same conservative screen for the sqrt.
+            // Both pairs go behind ONE screen: the exact tests are the same, taken only when some lane of the
+            // wavefront is within reach in either pair.
             int hh = 0;
+            {
+                static_assert(NT / 2 == 2, "two pairs per lane");
+                double s2[2], ra[2], rb[2];
+                bool near_any = false;
+                const bool counted = active & count_hh;
 #pragma unroll
-            for (int d = 1; d <= NT / 2; ++d) {
-                const int jj = h + d >= NT ? h + d - NT : h + d;
-                const int pi = (l0 + jj) & 63;
-                const double2 ppos = s_hpos[pi];
-                const double prad = s_hrad[pi];
-                const double ra = jj > h ? rad : prad, rb = jj > h ? prad : rad;
-                const double dx = pos.x - ppos.x, dy = pos.y - ppos.y;
-                const bool counted = active & (c.count_hh != 0);
-                const double s2 = dx * dx + dy * dy, reach = ra + rb + 1e-6;
-                if (__any(counted & (s2 < reach * reach))) DIAG_COUNT(2);
-                if (__any(counted & (s2 < reach * reach)))
-                    hh += (counted & ((sqrt(s2) - ra - rb) < 0)) ? 1 : 0;
-            }
-            double dmin = INFINITY;
-            int hh_sum = 0;
+                for (int d = 1; d <= NT / 2; ++d) {
+                    const int jj = h + d >= NT ? h + d - NT : h + d;
+                    const int pi = g * NT + (pop ? jj : 0);
+                    const double2 ppos = s_hpos[pi];
+                    const double prad = s_hrad[pi];
+                    ra[d - 1] = jj > h ? rad : prad; rb[d - 1] = jj > h ? prad : rad;
+                    const double dx = pos.x - ppos.x, dy = pos.y - ppos.y;
+                    s2[d - 1] = dx * dx + dy * dy;
+                    const double reach = ra[d - 1] + rb[d - 1] + 1e-6;
+                    near_any |= counted & (s2[d - 1] < reach * reach);
+                }
+                if (__any(near_any)) {
+                    DIAG_COUNT(2);
 #pragma unroll
-            for (int qh = 0; qh < NT; ++qh) {
-                const int s = (l0 + qh) & 63;
-                dmin = fmin(dmin, __shfl(cd, s));
-                hh_sum += __shfl(hh, s);
+                    for (int d = 0; d < NT / 2; ++d)
+                        hh += (counted & ((sqrt(s2[d]) - ra[d] - rb[d]) < 0)) ? 1 : 0;
+                }
             }
+            // the env's minimum and overlap count, on all eight of its lanes: min over numbers does not see the order
+            // (no operand is -0: a difference of equal values is +0; a NaN loses to any number, and the idle lanes'
+            // +inf keeps an all-NaN env at +inf, which is what min(+inf, NaN, ...) gave in lane order)
+            double dmin = cd;
+            int hh_sum = hh;
+            dmin = fmin(dmin, dpp_d<DPP_QUAD_XOR1>(dmin));       hh_sum += dpp_i<DPP_QUAD_XOR1>(hh_sum);
+            dmin = fmin(dmin, dpp_d<DPP_QUAD_XOR2>(dmin));       hh_sum += dpp_i<DPP_QUAD_XOR2>(hh_sum);
+            dmin = fmin(dmin, dpp_d<DPP_ROW_HALF_MIRROR>(dmin)); hh_sum += dpp_i<DPP_ROW_HALF_MIRROR>(hh_sum);
 
             // ---- K3: ladder, on every lane of the env ----
             double endx, endy, new_theta = rtheta, nrvx, nrvy;
@@ -337,10 +375,6 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 if (__any(gx * gx + gy * gy < near * near)) DIAG_COUNT(3);
                 if (__any(gx * gx + gy * gy < near * near)) reaching = norm2(gx, gy) < rrad;
             }
-            const KernargPtr kc = kernarg_here();
-            const double k_time_limit = kc->cfg.time_limit, k_timeout_at = k_time_limit - 1;
-            const double k_collision = kc->cfg.collision_penalty, k_success = kc->cfg.success_reward;
-            const double k_discomfort = kc->cfg.discomfort_dist, k_factor = kc->cfg.discomfort_penalty_factor;
             double rew; int inf, dn;
             if (gtime >= k_timeout_at)          { rew = 0; dn = 1; inf = MCN_INFO_TIMEOUT; }
             else if (dmin < 0)                  { rew = k_collision; dn = 1; inf = MCN_INFO_COLLISION; }
@@ -378,7 +412,6 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 rs.ep_return = dn ? 0.0 : ret;
                 rs.ep_steps = dn ? 0 : rs.ep_steps + 1;
                 if (do_reset) {
-                    const int k_stride = kc->roll.case_stride, k_pool = kc->roll.pool_size;
                     int nc = rs.next_case + k_stride;
                     nc = nc >= k_pool ? nc - k_pool : nc;
                     rs.next_case = dn ? nc : rs.next_case;
@@ -401,7 +434,8 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 gtime = t_new;
             }
 
-            if (pop && h == 0) { s_dn[gi] = dn; s_case[gi] = case_g; }
+            if (h == 0) { s_dn[g] = dn; s_case[g] = case_g; }
+            if (t < 20) STAMP(40 + t);
             __syncthreads();                                     // hand-off 1
             __syncthreads();                                     // hand-off 2: the next step reads the humans' new state
             if (t < 37) STAMP(2 + t);

@@ -4,8 +4,15 @@
   python tools/fixed_cost.py sweep            # product library: time per launch for T = 1..256, fit a + b*T
   MCN_HIP_LIB=modelcrowdnav_amd/csrc/build_diag/libmcn_hip.so python tools/fixed_cost.py stamps
                                               # diagnostic library: in-kernel time stamps per wavefront and step
+  MCN_HIP_LIB=... python tools/fixed_cost.py roles
+                                              # diagnostic library, four-wavefront form (rollout_split = 2): where each
+                                              # workgroup's waves sit, which SIMDs hold two float64 wavefronts, and which
+                                              # role reaches hand-off 1 last
 
 `sweep` times R back-to-back launches replayed from one hipGraph (HIP events on the launch stream).
+`roles` prints one launch's census of (SIMD, wave slot) per workgroup wave and CU (waves 0-2 ORCA, wave 3 float64), the
+number of SIMDs by what they hold, and per role the time from the start of a step to its arrival at hand-off 1 (slots
+40..59 of the stamps).
 `stamps` reads the 100 MHz real-time counter values the diagnostic build's rollout kernel stores (kernel entry,
 state loaded, end of each of the first 36 steps, exit) and prints, over all wavefronts: the spread of entry times,
 the state-load time, the duration of each step index, and the exit spread.
@@ -58,6 +65,87 @@ def sweep(E=4096, N=5):
     _hip.set_tuning()
 
 
+STAMP_SLOTS = 64            # must equal MCN_STAMP_SLOTS of env_rollout_quad.hip (mcn_debug_stamps copies raw slots)
+CYCLES_PER_TICK = 24        # nominal 2.4 GHz shader clock against the 100 MHz counter: a conversion, the clock is not read
+
+
+def roles(E=4096, N=5, T=20):
+    dev = torch.device("cuda", 0)
+    print(_hip.version())
+    if "DIAGNOSTIC" not in _hip.version():
+        raise SystemExit("needs the diagnostic build: MCN_HIP_LIB=.../build_diag/libmcn_hip.so")
+    fn = _hip.lib.mcn_debug_stamps
+    fn.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+    fn.restype = ctypes.c_int
+    acts = bench.make_actions(256, E, E, 0, dev)
+    _hip.set_tuning(rollout_fused=1, rollout_split=2)
+    us = lambda x: x * 0.01
+    print("cycles below are 100 MHz ticks x %d (a nominal 2.4 GHz shader clock, not measured in this run); %d stamp slots "
+          "per wavefront assumed" % (CYCLES_PER_TICK, STAMP_SLOTS))
+    env, _ = bench.build_env(E, N, 0, dev)
+    env.rollout(acts[:200])
+    torch.cuda.synchronize()
+    for trial in range(2):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record(); env.rollout(acts[:T]); e.record(); torch.cuda.synchronize()
+        assert _hip.last_rollout_form() == 2
+        buf = np.zeros(8192 * STAMP_SLOTS, dtype=np.uint64)
+        assert fn(buf.ctypes.data, buf.nbytes) > 0
+        wgs = (E + 7) // 8
+        st = buf.reshape(8192, STAMP_SLOTS)[:wgs * 4].astype(np.int64).reshape(wgs, 4, STAMP_SLOTS)
+        where = st[:, :, 38]
+        hw, xcc = where & 0xffffffff, (where >> 32) & 0xf
+        slot, simd, cu, sh, se = hw & 15, (hw >> 4) & 3, (hw >> 8) & 15, (hw >> 12) & 1, (hw >> 13) & 7
+        is_f64 = np.broadcast_to(np.arange(4)[None, :] == 3, slot.shape)     # role = workgroup wave
+        cu_key = (((xcc * 8 + se) * 2 + sh) * 16 + cu)
+        nsteps = min(T, 20)
+        step_us = us(st[:, :, 2 + nsteps - 1] - st[:, :, 1]).max(1) / nsteps
+        print("trial %d: event time %.2f us for %d steps; mean step %.3f us (median over workgroups), %d workgroups" % (
+            trial, s.elapsed_time(e) * 1e3, T, np.median(step_us), wgs))
+        perm = np.sort(simd, 1)
+        print("   workgroups whose four waves sit on four SIMDs of one CU: %d of %d" % (
+            int(((perm == np.arange(4)).all(1) & (cu_key == cu_key[:, :1]).all(1)).sum()), wgs))
+        # per CU: its workgroups in launch order, each as (simd.slot) of waves 0..3, float64 wave starred
+        cus = {}
+        for g in range(wgs):
+            cus.setdefault(int(cu_key[g, 0]), []).append(g)
+        def show(g):
+            return " ".join("%d.%d%s" % (simd[g, w], slot[g, w], "*" if is_f64[g, w] else "") for w in range(4))
+        pats = {}
+        for k, gs in cus.items():
+            pats.setdefault(" | ".join(show(g) for g in gs), []).append(k)
+        print("   %d CUs; workgroups per CU %s; (simd.slot of waves 0-3, * float64) patterns, most frequent first:" % (
+            len(cus), {int(a): int(b) for a, b in zip(*np.unique([len(v) for v in cus.values()], return_counts=True))}))
+        for pat, ks in sorted(pats.items(), key=lambda kv: -len(kv[1]))[:10]:
+            print("      %4d CUs: %s" % (len(ks), pat))
+        if trial == 0:
+            for k in sorted(cus)[:6]:
+                print("      CU %5d: %s   (workgroups %s)" % (k, " | ".join(show(g) for g in cus[k]), cus[k]))
+        simd_key = cu_key * 4 + simd
+        comp = {}
+        for key in np.unique(simd_key):
+            m = simd_key == key
+            comp_key = "%d float64 + %d ORCA" % (int((m & is_f64).sum()), int((m & ~is_f64).sum()))
+            comp[comp_key] = comp.get(comp_key, 0) + 1
+        print("   SIMDs by what they hold: %s" % comp)
+        # arrival at hand-off 1 after the start of the step (the end stamp of the step before), steps 1 ..
+        start = st[:, :, 2:2 + nsteps - 1]
+        arrive = st[:, :, 41:41 + nsteps - 1]
+        if (arrive > 0).all():
+            d = (arrive - start) * CYCLES_PER_TICK
+            df, do = d[is_f64], d[~is_f64]
+            print("   step start -> hand-off 1, cycles: float64 median %.0f p90 %.0f; ORCA median %.0f p90 %.0f (ORCA: latest of three, median %.0f)" % (
+                np.median(df), np.percentile(df, 90), np.median(do), np.percentile(do, 90),
+                np.median(np.where(is_f64[:, :, None], -1, d).max(1))))
+            last_f = np.where(is_f64[:, :, None], d, -1).max(1) >= np.where(is_f64[:, :, None], -1, d).max(1)
+            print("   the float64 wavefront is the last of its workgroup at hand-off 1 in %.1f %% of (workgroup, step)" % (100.0 * last_f.mean()))
+            print("   hand-off 1 -> end of step, cycles: median %.0f" % np.median((st[:, :, 3:3 + nsteps - 1] - arrive).min(1) * CYCLES_PER_TICK))
+        else:
+            print("   no hand-off stamps in this build")
+    del env
+    _hip.set_tuning()
+
+
 def stamps(E=4096, N=5, T=20):
     dev = torch.device("cuda", 0)
     print(_hip.version())
@@ -80,12 +168,12 @@ def stamps(E=4096, N=5, T=20):
             fc(cnt.ctypes.data, cnt.nbytes, 1)
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record(); env.rollout(acts[:T]); e.record(); torch.cuda.synchronize()
-            buf = np.zeros(8192 * 40, dtype=np.uint64)
+            buf = np.zeros(8192 * STAMP_SLOTS, dtype=np.uint64)
             n = fn(buf.ctypes.data, buf.nbytes)
             assert n > 0
             G = 64 // (4 * N)
             waves = ((E + G - 1) // G) * (2 if split else 1)
-            st = buf.reshape(8192, 40)[:waves].astype(np.int64)
+            st = buf.reshape(8192, STAMP_SLOTS)[:waves].astype(np.int64)
             t0 = st[:, 0].min()
             us = lambda x: x * 0.01                 # 100 MHz ticks -> us
             ent = us(st[:, 0] - t0)
@@ -151,4 +239,4 @@ def stamps(E=4096, N=5, T=20):
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "sweep"
-    {"sweep": sweep, "stamps": stamps}[mode]()
+    {"sweep": sweep, "stamps": stamps, "roles": roles}[mode]()

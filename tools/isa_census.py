@@ -17,8 +17,9 @@ them are counted too (column `fallback`: how many of the region's instructions s
 v_sqrt_f32 or a v_div_scale_f32 of 1.0).  Static counts, not a measurement of time.
 
 The default kernel is the two-wavefront form.  The four-wavefront form (env_rollout_wg4_kernel, what 4096 envs x 5
-humans now run) has one step loop per role and no single nest for this census to pick: it stops with "no loop nest
-found" there; its counts in profiles/r12_kernel_resources.txt were read from the assembly by hand.
+humans now run) has one step loop per role and no single nest for this census to pick: use --loops there, which
+prints one row per outermost loop (text range from its first to its last block, child loops and rare blocks placed
+inside it included) with the number of float64 instructions in it: the float64 role's step loop is the row with most.
 """
 import argparse
 import os
@@ -64,8 +65,9 @@ def kernel_lines(asm, want):
     if len(hits) != 1:
         sys.exit("isa_census: %d kernels match %r: %s" % (len(hits), want, [d for _, d in hits][:8]))
     start, name = hits[0]
-    end = next(j for j in range(start, len(lines)) if lines[j].strip().startswith("s_endpgm"))
-    return name, lines[start:end + 1]
+    # up to the end of the function, not the first s_endpgm: a kernel whose roles branch apart ends more than once
+    end = next(j for j in range(start, len(lines)) if lines[j].startswith(".Lfunc_end"))
+    return name, lines[start:end]
 
 
 def parse_blocks(lines):
@@ -139,12 +141,23 @@ def census(blocks):
     return {"common": [blocks[i] for i in common], "lp3 round": [blocks[i] for i in in_inner]}
 
 
+def outer_loops(blocks):
+    """{header: blocks of the text range of that depth-1 loop}, in text order."""
+    out = {}
+    for h in [b[1] for b in blocks if b[1] is not None and b[2] == 1]:
+        if h not in out:
+            idx = [i for i, b in enumerate(blocks) if b[1] == h]
+            out[h] = blocks[idx[0]:idx[-1] + 1]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--src", default=os.path.join(CSRC, "env_rollout_quad.hip"))
     ap.add_argument("--kernel", default="env_rollout_quad_kernel<5, 0, false, true>")
     ap.add_argument("--asm", help="use this gfx950 assembly file instead of compiling --src")
     ap.add_argument("--list", action="store_true", help="also print every block with its count")
+    ap.add_argument("--loops", action="store_true", help="one row per outermost loop instead of the common / lp3 regions")
     args = ap.parse_args()
     if args.asm:
         asm = args.asm
@@ -153,9 +166,10 @@ def main():
         asm = os.path.join(tmp, "tu.s")
         compile_asm(os.path.abspath(args.src), asm)
     name, lines = kernel_lines(asm, args.kernel)
-    regions = census(parse_blocks(lines))
+    regions = outer_loops(parse_blocks(lines)) if args.loops else census(parse_blocks(lines))
     print("kernel: %s" % name)
-    print("%-10s %6s " % ("region", "total") + " ".join("%10s" % c for c in CLASSES) + " %9s" % "fallback")
+    print("%-10s %6s " % ("region", "total") + " ".join("%10s" % c for c in CLASSES) + " %9s" % "fallback" +
+          (" %6s" % "f64" if args.loops else ""))
     for reg, bl in regions.items():
         counts = dict.fromkeys(CLASSES, 0)
         total = fb = 0
@@ -164,7 +178,9 @@ def main():
                 counts[classify(i)] += 1
             total += len(b[3])
             fb += len(b[3]) if is_fallback(b[3]) else 0
-        print("%-10s %6d " % (reg, total) + " ".join("%10d" % counts[c] for c in CLASSES) + " %9d" % fb)
+        f64 = sum(1 for b in bl for i in b[3] if re.match(r"^v_\w+_f64", i))
+        print("%-10s %6d " % (reg, total) + " ".join("%10d" % counts[c] for c in CLASSES) + " %9d" % fb +
+              (" %6d" % f64 if args.loops else ""))
         if args.list:
             for b in bl:
                 print("    %-12s %4d%s" % (b[0], len(b[3]), "  fallback" if is_fallback(b[3]) else ""))
