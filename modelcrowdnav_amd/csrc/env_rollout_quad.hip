@@ -12,6 +12,12 @@
 // mcn_env_step calls, bit for bit (tests/test_env_step_gpu.py::test_rollout_launch_equals_single_steps).
 //
 // Every lane runs exactly T iterations, there is no inter-wavefront dependency and no barrier: the grid drains.
+//
+// That is the one-wavefront form (env_rollout_quad_kernel<.., false>).  The two-wavefront form (<.., true>) gives the
+// float64 half of the step to a second wavefront of the workgroup, and the four-wavefront form (env_rollout_wg4_kernel,
+// 5 humans, invisible robot) gives 8 envs three float32 ORCA wavefronts and ONE float64 wavefront that owns all float64
+// state, the humans' too; their roles meet through LDS behind two barriers per step (see Wg4 below).  Same arithmetic
+// per value in all three, so the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/mcn.h"
@@ -120,13 +126,21 @@ __device__ __forceinline__ KernargPtr kernarg_here()
 // The two-wavefront form gives every 3 envs a float64 wavefront of their own, which repeats each swept-circle test on 4
 // lanes and the ladder on 20; here 8 envs share it, and 4096 envs x 5 humans become 512 workgroups = exactly two
 // wavefronts on each of the chip's 1024 SIMDs instead of two on some and three on others.
-// The roles meet only through LDS, as in the two-wavefront form and at the same two points of the step; the ORCA
-// lanes fetch their candidate neighbour from the hand-off arrays too (an env's quads need not share a wavefront, so
-// there is no ds_bpermute to take it from).  Same arithmetic per value, so the same bits.
 //
-// The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot integrate / restart and the
-// epilogue, and the ORCA wavefronts' human integrate / restart, are the TWIN of env_rollout_quad_kernel's below (the
-// older forms keep their code, hence their registers, so the text is not shared): a change to either is made to both.
+// The float64 wavefront OWNS every float64 value of the env: the robot, the clock, the records and the humans' position,
+// velocity, goal, radius, v_pref and human_times -- one human per lane, loaded in its prologue, integrated or restarted
+// from the pool by it, stored in its epilogue.  The ORCA wavefronts are float32 only: per step they read their human's
+// operand packs and their candidate's from LDS (quad_common.hpp: quad_orca_operands), run quad_orca_core and publish
+// the new velocity as two floats.  The four lanes of a quad would each repeat the float64 -> float32 conversions, the
+// integrate and the restart test; the float64 wavefront does them once per human and has the cycles to spare, and on a
+// SIMD that holds two wavefronts every instruction taken out of the ORCA stream is taken out of its neighbour's way too.
+// The roles meet through LDS at two points of the step: hand-off 1, ORCA -> float64, the new velocities; hand-off 2,
+// float64 -> ORCA, the next step's packs (the float64 wavefront integrates between the two).  Each value is produced by
+// the operation, on the operands, that the other forms use, so the same bits.
+//
+// The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot and human integrate / restart and
+// the epilogue are the TWIN of env_rollout_quad_kernel's below (the older forms keep their code, hence their registers,
+// so the text is not shared): a change to either is made to both.
 template <int NT>
 struct Wg4 {
     static_assert(NT == 5, "the four-wavefront form is built for 5 humans only");
@@ -151,9 +165,14 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
 {
     static_assert(VIS == 0, "the four-wavefront form is built for an invisible robot only");
     constexpr int EW = Wg4<NT>::EW, NQ = Wg4<NT>::NQ;
-    __shared__ double2 s_hpos[NQ], s_hvel[NQ];
+    // hand-off arrays, one slot per (env, human).  Written by the float64 wavefront between the step's two barriers: the
+    // float32 operand packs of quad_orca_core (quad_common.hpp: A = position and velocity, B = preferred velocity, frad,
+    // maximum speed) and the float64 position and radius its own overlap pairs read from partner lanes.  Written by the
+    // ORCA wavefronts outside that window, read by the float64 one inside it: the human's new velocity.
+    __shared__ float4 s_opa[NQ], s_opb[NQ];
+    __shared__ float2 s_res[NQ];
+    __shared__ double2 s_hpos[NQ];
     __shared__ double s_hrad[NQ];
-    __shared__ int s_dn[16], s_case[16];
     STAMP(0);
     STAMP_WHERE();
 #ifdef MCN_DIAG
@@ -161,120 +180,73 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
 #endif
     const int tid = threadIdx.x;
     // wave-uniform by construction, and known to be: each role runs its own step loop, barriers included
-    const int role = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0-2: ORCA, 3: robot + ladder + records
+    const int role = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0-2: ORCA, 3: float64 state, ladder, records
     const unsigned nb_ = gridDim.x, xcd_ = blockIdx.x & 7u, idx_ = blockIdx.x >> 3;       // XCD-aware chunking, as below
     const unsigned qq_ = nb_ >> 3, rr__ = nb_ & 7u;
     const unsigned chunk_ = (xcd_ < rr__ ? xcd_ * (qq_ + 1) : rr__ * (qq_ + 1) + (xcd_ - rr__) * qq_) + idx_;
     const mcn_env_cfg &c = p.cfg;
     const mcn_rollout &ro = p.roll;
-    const double dt = in_vgpr(c.time_step);
-    const bool do_reset = p.has_roll && ro.pool_hpos != nullptr;
 
     if (role < 3) {
-        // ---------------- ORCA wavefronts: the humans ----------------
+        // ---------------- ORCA wavefronts: the float32 solve, nothing else ----------------
         const int lane = tid & 63, k = tid & 3, q = tid >> 2;
-        const bool pop = q < NQ;                                 // idle quads (and envs >= E) alias env 0, store nothing
+        const bool pop = q < NQ;                                 // idle quads (and envs >= E) hold no half-plane, write nothing
         const int ge = q / NT, h = q - ge * NT;
-        const long e = (long)chunk_ * EW + ge;
-        const bool active = pop && e < p.E;
-        const long eb = active ? e : 0;
-        const long a = eb * NT + h;
-        const int gi = pop ? ge : 0, hi = pop ? q : 0;           // LDS slots of this quad's env / human
-        const bool hlead = active && k == 0;                     // owns the human's records
-        const bool track = c.track_human_times && p.st.human_times != nullptr;
+        const bool active = pop && (long)chunk_ * EW + ge < p.E;
+        const int hi = pop ? q : 0;                              // LDS slot of this quad's human (idle quads read slot 0)
         const bool cand_h = k < NT - 1;                          // candidate is another human
         const int j = cand_h ? k + (k >= h ? 1 : 0) : h;
         const int ci = pop ? ge * NT + j : 0;
+        const bool publish = pop && k == 0;
+        const float inv_th = in_vgpr(1.0f / c.orca_time_horizon), inv_ts = in_vgpr(1.0f / (float)c.time_step);
+        __syncthreads();                                         // the float64 wavefront has seeded the packs
+        STAMP(1);
 
+        for (int t = 0; t < T; ++t) {
+            // own operands and the candidate's, published behind the step's second barrier; one LDS round trip
+            const float4 A = s_opa[hi], B = s_opb[hi], o = s_opa[ci];
+            const float orad = s_opb[ci].z;                      // the candidate's own frad
+            float rx, ry;
+            quad_orca_core(c, lane, k, cand_h && active, A, B, o, orad, inv_th, inv_ts, rx, ry);
+            if (publish) s_res[hi] = make_float2(rx, ry);
+            if (t < 20) STAMP(40 + t);
+            __syncthreads();                                     // hand-off 1: the humans' new velocities
+            __syncthreads();                                     // hand-off 2: the next step's operand packs
+            if (t < 37) STAMP(2 + t);
+        }
+    } else {
+        // ---------------- float64 wavefront: lane 8 g + h = (env g, human h), h >= NT idle ----------------
+        static_assert(EW * 8 == 64, "eight lanes per env fill the wavefront");
+        const double dt = in_vgpr(c.time_step);
+        const bool do_reset = p.has_roll && ro.pool_hpos != nullptr;
+        const int l = tid & 63;
+        const int g = l >> 3, h = l & 7;
+        const bool pop = h < NT;
+        const int hs = g * NT + (pop ? h : 0);                   // LDS slot of (env g, human h); idle lanes alias human 0
+        const long e = (long)chunk_ * EW + g;
+        const bool active = pop && e < p.E;
+        const long eb = e < p.E ? e : 0;                         // idle lanes carry the env's robot too: nothing is stored
+        const long a = eb * NT + (pop ? h : 0);                  // ... and a human (envs >= E: env 0's), read-only
+        const bool lead = active && h == 0;                      // owns the per-env records
+        constexpr bool unicycle = UNI;
+        const bool has_state = p.has_roll && ro.state != nullptr;
+        const bool track = c.track_human_times && p.st.human_times != nullptr;
+
+        // the humans' float64 state lives here, one human per lane
         double2 pos = reinterpret_cast<const double2 *>(p.st.hpos)[a];
         double2 vel = reinterpret_cast<const double2 *>(p.st.hvel)[a];
         double2 goal = reinterpret_cast<const double2 *>(p.st.hgoal)[a];
         double rad = p.st.hrad[a];
         double vpref = p.st.hvpref[a];
         double htime = p.st.human_times ? p.st.human_times[a] : 0.0;
-        double gtime = p.st.gtime[eb];                           // these wavefronts keep their own copy of the clock
         double hax = 0, hay = 0;
-        const float inv_th = in_vgpr(1.0f / c.orca_time_horizon), inv_ts = in_vgpr(1.0f / (float)c.time_step);
-        // the first step's candidates: the loaded state goes through the hand-off arrays
-        if (pop && k == 0) { s_hpos[hi] = pos; s_hvel[hi] = vel; s_hrad[hi] = rad; }
-        __syncthreads();
-        STAMP(1);
-
-        for (int t = 0; t < T; ++t) {
-            // ---- candidate neighbour: published by the quad that owns it, behind the step's second barrier ----
-            const double2 cpos = s_hpos[ci], cvel = s_hvel[ci];
-            const double crd = s_hrad[ci];
-            float rx, ry;
-            quad_orca_velocity(c, lane, k, cand_h && active, pos, vel, goal, rad, vpref,
-                               make_float4((float)cpos.x, (float)cpos.y, (float)cvel.x, (float)cvel.y), crd, inv_th, inv_ts,
-                               rx, ry);
-            hax = (double)rx; hay = (double)ry;
-
-            if (t < 20) STAMP(40 + t);
-            __syncthreads();                                     // hand-off 1: done flag and restart case
-            const int dn = s_dn[gi], case_g = s_case[gi];
-
-            // ---- humans: integrate, or restart from the scenario pool ----
-            if (do_reset && dn) {
-                DIAG_COUNT(1);
-                if (active) {
-                    const long pa = (long)case_g * NT + h;
-                    const KernargPtr kp = kernarg_here();
-                    const double2 *pool_hvel = reinterpret_cast<const double2 *>(kp->roll.pool_hvel);
-                    pos = reinterpret_cast<const double2 *>(kp->roll.pool_hpos)[pa];
-                    goal = reinterpret_cast<const double2 *>(kp->roll.pool_hgoal)[pa];
-                    rad = kp->roll.pool_hrad[pa];
-                    vpref = kp->roll.pool_hvpref[pa];
-                    vel = pool_hvel ? pool_hvel[pa] : make_double2(0, 0);
-                }
-                htime = 0;
-            } else {
-                pos = make_double2(pos.x + hax * dt, pos.y + hay * dt);
-                vel = make_double2(hax, hay);
-                if (track && htime == 0 && norm2(pos.x - goal.x, pos.y - goal.y) < rad) htime = gtime + dt;
-            }
-            gtime = (do_reset && dn) ? 0.0 : gtime + dt;
-            if (pop && k == 0) { s_hpos[hi] = pos; s_hvel[hi] = vel; s_hrad[hi] = rad; }
-            __syncthreads();                                     // hand-off 2: the humans' new state
-            if (t < 37) STAMP(2 + t);
-        }
-
-        long a2 = a;
-        asm volatile("" : "+v"(a2));
-        const KernargPtr kp = kernarg_here();
-        if (hlead) {
-            reinterpret_cast<double2 *>(kp->st.hpos)[a2] = pos;
-            reinterpret_cast<double2 *>(kp->st.hvel)[a2] = vel;
-            if (do_reset) {
-                reinterpret_cast<double2 *>(kp->st.hgoal)[a2] = goal;
-                kp->st.hrad[a2] = rad;
-                kp->st.hvpref[a2] = vpref;
-            }
-            double *human_times = kp->st.human_times, *human_act = kp->out.human_act;
-            if (human_times) human_times[a2] = htime;
-            if (human_act) reinterpret_cast<double2 *>(human_act)[a2] = make_double2(hax, hay);
-        }
-    } else {
-        // ---------------- float64 wavefront: lane 8 g + h = (env g, human h), h >= NT idle ----------------
-        static_assert(EW * 8 == 64, "eight lanes per env fill the wavefront");
-        const int l = tid & 63;
-        const int g = l >> 3, h = l & 7;
-        const bool pop = h < NT;
-        const int hs = g * NT + (pop ? h : 0);                   // LDS slot of (env g, human h); idle lanes read human 0
-        const long e = (long)chunk_ * EW + g;
-        const bool active = pop && e < p.E;
-        const long eb = e < p.E ? e : 0;                         // idle lanes carry the env's robot too: nothing is stored
-        const bool lead = active && h == 0;                      // owns the per-env records
-        constexpr bool unicycle = UNI;
-        const bool has_state = p.has_roll && ro.state != nullptr;
-
         double2 rpos = reinterpret_cast<const double2 *>(p.st.rpos)[eb];
         double2 rvel = reinterpret_cast<const double2 *>(p.st.rvel)[eb];
         double2 rgoal = reinterpret_cast<const double2 *>(p.st.rgoal)[eb];
         const double rrad = p.st.rrad[eb];
         double gtime = p.st.gtime[eb];
         double rtheta = p.st.rtheta ? p.st.rtheta[eb] : 0.0;
-        // the robot, the clock and the Explorer record are held redundantly by the env's NT lanes
+        // the robot, the clock and the Explorer record are held redundantly by the env's eight lanes
         mcn_roll_rec rs = {0, 0, 0, 0, 0, 0};
         if (has_state) rs = ro.state[eb];
         const double2 *act_ptr = reinterpret_cast<const double2 *>(p.actions) + eb;
@@ -285,12 +257,19 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         double2 act_next = *act_ptr;
         double o_rew = 0, o_dmin = 0;
         int o_dn = 0, o_inf = 0, o_hh = 0;
-        // the ladder's constants and the restart stride stay in vector registers: this role has them to spare
-        const double k_time_limit = in_vgpr(c.time_limit), k_timeout_at = in_vgpr(c.time_limit - 1);
+        // the ladder's constants stay in vector registers (the humans' state took the room the rare time limit and the
+        // restart stride had there: those are a kernel-argument read and scalars again)
+        const double k_timeout_at = in_vgpr(c.time_limit - 1);
         const double k_collision = in_vgpr(c.collision_penalty), k_success = in_vgpr(c.success_reward);
         const double k_discomfort = in_vgpr(c.discomfort_dist), k_factor = in_vgpr(c.discomfort_penalty_factor);
-        const int k_stride = in_vgpr(ro.case_stride), k_pool = in_vgpr(ro.pool_size);
+        const int k_stride = ro.case_stride, k_pool = ro.pool_size;
         const bool count_hh = c.count_hh != 0;
+        // the first step's operands: the loaded state goes through the hand-off arrays
+        {
+            float4 A, B;
+            quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
+            if (pop) { s_opa[hs] = A; s_opb[hs] = B; s_hpos[hs] = pos; s_hrad[hs] = rad; }
+        }
         __syncthreads();
         STAMP(1);
 
@@ -300,9 +279,6 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
             if (t + 1 < T) act_next = *act_ptr;
             double ep_disc = 0;
             if (has_state) ep_disc = disc_table[rs.ep_steps < disc_last ? rs.ep_steps : disc_last];
-
-            const double2 pos = s_hpos[hs], vel = s_hvel[hs];
-            const double rad = s_hrad[hs];
 
             // ---- K2: the swept circle of human h; the env's unordered human pairs spread over its lanes ----
             double2 eff = act;
@@ -405,7 +381,7 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                     const bool keep = (fin_slots == 1) || (kf < fin_slots);
                     const long rec = (long)(fin_slots == 1 ? 0 : kf) * kp->E + e;
                     if (keep && fin_return) fin_return[rec] = ret;
-                    if (keep && fin_time)   fin_time[rec] = (inf == MCN_INFO_TIMEOUT) ? k_time_limit : t_new;
+                    if (keep && fin_time)   fin_time[rec] = (inf == MCN_INFO_TIMEOUT) ? kp->cfg.time_limit : t_new;
                     if (keep && fin_info)   fin_info[rec] = (uint8_t)inf;
                 }
                 rs.fin_count += dn;
@@ -434,16 +410,67 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 gtime = t_new;
             }
 
-            if (h == 0) { s_dn[g] = dn; s_case[g] = case_g; }
+            // ---- humans of a finished env: the pool case is fetched NOW, while this wavefront would wait at hand-off 1
+            //      for the ORCA ones anyway (it knows the done flag first), not on the chain between the hand-offs ----
+            double2 npos = pos, nvel = vel, ngoal = goal;
+            double nrad = rad, nvpref = vpref;
+            if (do_reset && dn) {
+                DIAG_COUNT(1);
+                if (active) {
+                    const long pa = (long)case_g * NT + h;
+                    const KernargPtr kp = kernarg_here();
+                    const double2 *pool_hvel = reinterpret_cast<const double2 *>(kp->roll.pool_hvel);
+                    nvel = make_double2(0, 0);                   // (before the loads: nothing here waits for one)
+                    if (pool_hvel) nvel = pool_hvel[pa];
+                    npos = reinterpret_cast<const double2 *>(kp->roll.pool_hpos)[pa];
+                    ngoal = reinterpret_cast<const double2 *>(kp->roll.pool_hgoal)[pa];
+                    nrad = kp->roll.pool_hrad[pa];
+                    nvpref = kp->roll.pool_hvpref[pa];
+                }
+            }
+
             if (t < 20) STAMP(40 + t);
-            __syncthreads();                                     // hand-off 1
-            __syncthreads();                                     // hand-off 2: the next step reads the humans' new state
+            __syncthreads();                                     // hand-off 1: the humans' new velocities
+            {
+                const float2 r = s_res[hs];
+                hax = (double)r.x; hay = (double)r.y;
+            }
+
+            // ---- humans: integrate, or restart from the scenario pool ----
+            if (do_reset && dn) {
+                pos = npos; vel = nvel; goal = ngoal; rad = nrad; vpref = nvpref;     // (idle lanes keep what they had)
+                htime = 0;
+            } else {
+                pos = make_double2(pos.x + hax * dt, pos.y + hay * dt);
+                vel = make_double2(hax, hay);
+                // the clock of the step just taken
+                if (track && htime == 0 && norm2(pos.x - goal.x, pos.y - goal.y) < rad) htime = t_new;
+            }
+            // the next step's operands, every float converted from the float64 state (a restart needs no second path)
+            {
+                float4 A, B;
+                quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
+                if (pop) { s_opa[hs] = A; s_opb[hs] = B; s_hpos[hs] = pos; s_hrad[hs] = rad; }
+            }
+            __syncthreads();                                     // hand-off 2: the next step's operand packs
             if (t < 37) STAMP(2 + t);
         }
 
-        long e2 = e;
-        asm volatile("" : "+v"(e2));
+        long a2 = a, e2 = e;
+        asm volatile("" : "+v"(a2), "+v"(e2));
         const KernargPtr kp = kernarg_here();
+        if (active) {
+            reinterpret_cast<double2 *>(kp->st.hpos)[a2] = pos;
+            reinterpret_cast<double2 *>(kp->st.hvel)[a2] = vel;
+            if (do_reset) {
+                reinterpret_cast<double2 *>(kp->st.hgoal)[a2] = goal;
+                kp->st.hrad[a2] = rad;
+                kp->st.hvpref[a2] = vpref;
+            }
+            double *human_times = kp->st.human_times, *human_act = kp->out.human_act;
+            if (human_times) human_times[a2] = htime;
+            if (human_act) reinterpret_cast<double2 *>(human_act)[a2] = make_double2(hax, hay);
+        }
         if (lead) {
             reinterpret_cast<double2 *>(kp->st.rpos)[e2] = rpos;
             reinterpret_cast<double2 *>(kp->st.rvel)[e2] = rvel;
@@ -466,9 +493,9 @@ __global__ __launch_bounds__(256, 2) void env_rollout_wg4_kernel(const StepParam
     rollout_wg4<NT, VIS, UNI>(p, T);
 }
 
-// TWIN: rollout_wg4 above carries a copy of this kernel's ladder, Explorer accounting, finished-episode stores, robot
-// and human integrate / restart and epilogue; a change to either is made to both (tests/test_rollout_wg4_gpu.py
-// compares their bytes).
+// TWIN: the float64 role of rollout_wg4 above carries a copy of this kernel's ladder, Explorer accounting,
+// finished-episode stores, robot and human integrate / restart and epilogue; a change to either is made to both
+// (tests/test_rollout_wg4_gpu.py and tests/test_rollout_owner_gpu.py compare their bytes).
 template <int NT, int VIS, bool UNI, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_quad_kernel(const StepParams p, const int T)
 {

@@ -163,15 +163,40 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float
 // inv_th / inv_ts = 1 / timeHorizon, 1 / timeStep: computed by the caller once per launch and handed over as opaque
 // values -- left to itself the compiler rewrites `apart ? 1 / a : 1 / b` into `1 / (apart ? a : b)`, i.e. one IEEE
 // division (11 instructions) on the critical path of EVERY step instead of two before the step loop.
-__device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lane, int k, bool cand_valid,
-                                                   double2 pos, double2 vel, double2 goal, double rad, double vpref,
-                                                   float4 o, double crd, float inv_th, float inv_ts, float &rx, float &ry)
+//
+// Two parts.  quad_orca_operands turns a human's float64 state into the solve's float32 operands: pack A =
+// (px, py, vx, vy), pack B = (prefx, prefy, frad, ms).  A candidate's `orad` is its own frad (the same expression on
+// the same radius) and its `o` its own pack A.  quad_orca_core is the float32 solve on those operands.  The
+// four-wavefront rollout form computes the packs on its float64 wavefront and runs the core alone on the ORCA ones.
+__device__ __forceinline__ void quad_orca_operands(const mcn_env_cfg &c, double2 pos, double2 vel, double2 goal, double rad,
+                                                   double vpref, float4 &A, float4 &B)
 {
     const float fpx = (float)pos.x, fpy = (float)pos.y, fvx = (float)vel.x, fvy = (float)vel.y;
     const float frad = (float)(rad + 0.01 + c.orca_safety_space);
     const float ms = (float)vpref;
     const float prefx = (float)(goal.x - pos.x), prefy = (float)(goal.y - pos.y);
+    A = make_float4(fpx, fpy, fvx, fvy);
+    B = make_float4(prefx, prefy, frad, ms);
+}
+
+__device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, int k, bool cand_valid, float4 A, float4 B,
+                                               float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry);
+
+__device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lane, int k, bool cand_valid,
+                                                   double2 pos, double2 vel, double2 goal, double rad, double vpref,
+                                                   float4 o, double crd, float inv_th, float inv_ts, float &rx, float &ry)
+{
+    float4 A, B;
+    quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
     const float orad = (float)(crd + 0.01 + c.orca_safety_space);
+    quad_orca_core(c, lane, k, cand_valid, A, B, o, orad, inv_th, inv_ts, rx, ry);
+}
+
+__device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, int k, bool cand_valid, float4 A, float4 B,
+                                               float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry)
+{
+    const float fpx = A.x, fpy = A.y, fvx = A.z, fvy = A.w;
+    const float prefx = B.x, prefy = B.y, frad = B.z, ms = B.w;
     const float range_sq = c.orca_neighbor_dist * c.orca_neighbor_dist;
     const float ddx = fpx - o.x, ddy = fpy - o.y;
     const float d = dot2(ddx, ddy, ddx, ddy);
