@@ -251,6 +251,43 @@ int mcn_orca_batch(const float *self, const float *others, const int32_t *n_othe
                    int32_t B, int32_t M, float neighbor_dist, int32_t max_neighbors,
                    float time_horizon, float time_step, void *stream);
 
+/*
+ * mcn_orca_finish -- CrowdSim.get_human_times (crowd_sim/envs/crowd_sim.py:219-258) for E envs in one launch: once
+ * the robot has arrived, everybody goes into ONE centralised ORCA simulation per env (the reference's
+ * rvo2.PyRVOSimulator(time_step, neighbor_dist, max_neighbors, time_horizon, ...)), agent 0 being the robot and agents
+ * 1 .. N the humans, each at its own plain radius and v_pref, and the simulation runs until every human has reached its
+ * goal.  The step loop and the "is everybody there" test run inside the kernel.
+ *   st        reads hpos, hgoal, hrad, hvpref, rpos, rgoal, rrad, rvpref, gtime, human_times (none may be NULL); writes
+ *             hpos, rpos, gtime, human_times.  hvel, rvel, rtheta and hcount are neither read nor written (the
+ *             reference leaves the agents' velocity fields alone here).
+ *   sim_vel   [E][N+1][2] float, in and out: the simulator's velocities.  The caller starts it from float32(rvel),
+ *             float32(hvel) and hands it back unchanged to continue after a capped call.
+ *   select    [E] bytes or NULL: envs with select[e] == 0 are not touched in any array (steps[e] = 0).
+ *   max_steps >= 1: the most steps this call simulates per env; it bounds every loop of the kernel.
+ *   steps     [E] int32 out: steps simulated by this call.
+ *   traj      [max_steps][E][N+1][2] float or NULL: positions after each simulated step; rows at or beyond steps[e]
+ *             keep what they held.
+ *   1 <= N <= MCN_MAX_HUMANS (at most 32 candidate neighbours per agent), 0 <= max_neighbors <= MCN_MAX_LINES,
+ *   time_step > 0, time_horizon > 0; anything else, or a NULL st / sim_vel / steps: MCN_EINVAL before any launch.
+ * Per selected env, with p64 the agent's float64 position in st and p32 = float32(p64) at entry: while some
+ * human_times[e][i] == 0 and fewer than max_steps steps have been taken, in this operation order and without fused
+ * multiply-add:
+ *   1  every agent: e = goal - p64 (float64); n = sqrt(e.x*e.x + e.y*e.y); if n > 1: e = (e.x / n, e.y / n);
+ *      pref = float32(e)
+ *   2  every agent: the ORCA solve of mcn_orca_batch with the other N agents as candidates in agent-index order, all
+ *      agents' p32 and sim_vel from before this step, radius float32(radius), max speed float32(v_pref), pref,
+ *      neighbor_dist, max_neighbors, time_horizon, float32(time_step)
+ *   3  sim_vel = the new velocity; p32 = p32 + sim_vel * float32(time_step) (one float32 product, one float32 sum)
+ *   4  gtime = gtime + time_step (float64)
+ *   5  every human with human_times == 0: d = p64 - goal with the position from BEFORE this step's update;
+ *      if sqrt(d.x*d.x + d.y*d.y) < radius (float64): human_times = gtime
+ *   6  p64 = float64(p32); written back to st when the env stops
+ * An env whose human_times are all non-zero at entry takes no step and nothing of it is written.  Two calls that
+ * together take as many steps as one uncapped call leave the same bytes.
+ */
+int mcn_orca_finish(const mcn_env_state *st, float *sim_vel, const uint8_t *select, int32_t max_steps, int32_t *steps,
+                    float *traj, double time_step, float neighbor_dist, int32_t max_neighbors, float time_horizon,
+                    int32_t E, int32_t N, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SARL attention value network: 81-action one-step look-ahead (crowd_nav/policy/sarl.py:28-65,

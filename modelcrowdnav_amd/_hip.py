@@ -142,6 +142,9 @@ def _load():
     lib.mcn_scenario_pool.restype = C.c_int
     lib.mcn_orca_batch.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _f, _i, _f, _f, _vp]
     lib.mcn_orca_batch.restype = C.c_int
+    # st, sim_vel, select, max_steps, steps, traj, time_step, neighbor_dist, max_neighbors, time_horizon, E, N, stream
+    lib.mcn_orca_finish.argtypes = [C.POINTER(EnvState), _vp, _vp, _i, _vp, _vp, _d, _f, _i, _f, _i, _i, _vp]
+    lib.mcn_orca_finish.restype = C.c_int
     fp, ip = C.POINTER(C.c_float), C.POINTER(C.c_int32)
     lib.mcn_pack_linear.argtypes = [fp, fp, _i, _i, ip, _i, ip, _i, fp, fp]
     lib.mcn_pack_linear.restype = C.c_int
@@ -236,7 +239,7 @@ def last_rollout_form():
 lib = _load()
 
 # every symbol include/mcn.h declares; tests/test_abi.py checks the .so exports each one
-EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_last_rollout_form", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
+EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_last_rollout_form", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_orca_finish", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict"]
 

@@ -56,6 +56,9 @@ int launch_sgan_predict(const mcn_sgan_net *net, const double *hist, int oldest,
 int launch_orca_batch(const float *self, const float *others, const int32_t *n_other, float *out,
                       int B, int M, float neighbor_dist, int max_neighbors, float time_horizon, float time_step,
                       hipStream_t stream);
+int launch_orca_finish(const mcn_env_state &st, float *sim_vel, const uint8_t *select, int max_steps, int32_t *steps,
+                       float *traj, double time_step, float neighbor_dist, int max_neighbors, float time_horizon,
+                       int E, int N, hipStream_t stream);
 #ifdef MCN_DIAG
 int read_stamps(void *dst, size_t bytes);
 int read_counts(void *dst, size_t bytes, int reset);
@@ -382,6 +385,19 @@ int mcn_orca_batch(const float *self, const float *others, const int32_t *n_othe
     if (!(time_horizon > 0) || !(time_step > 0)) return MCN_EINVAL;
     return mcn::launch_orca_batch(self, others, n_other, out, B, M, neighbor_dist, max_neighbors,
                                   time_horizon, time_step, (hipStream_t)stream);
+}
+
+int mcn_orca_finish(const mcn_env_state *st, float *sim_vel, const uint8_t *select, int32_t max_steps, int32_t *steps,
+                    float *traj, double time_step, float neighbor_dist, int32_t max_neighbors, float time_horizon,
+                    int32_t E, int32_t N, void *stream)
+{
+    if (!st || !sim_vel || !steps || max_steps < 1 || E <= 0 || N < 1 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
+    if (!st->hpos || !st->hgoal || !st->hrad || !st->hvpref || !st->rpos || !st->rgoal || !st->rrad || !st->rvpref ||
+        !st->gtime || !st->human_times) return MCN_EINVAL;
+    if (max_neighbors < 0 || max_neighbors > MCN_MAX_LINES) return MCN_EINVAL;
+    if (!(time_horizon > 0) || !(time_step > 0) || !((float)time_step > 0)) return MCN_EINVAL;
+    return mcn::launch_orca_finish(*st, sim_vel, select, max_steps, steps, traj, time_step, neighbor_dist, max_neighbors,
+                                   time_horizon, E, N, (hipStream_t)stream);
 }
 
 int mcn_pack_linear(const float *weight, const float *bias, int32_t nout, int32_t kin,

@@ -5,8 +5,8 @@ reset :261, step :331, onestep_lookahead :325, plus the attributes its callers r
 (case_size, case_counter, human_num, time_step, time_limit, global_time, humans, robot, states,
 sim_world, device, test_sim), `[humans] policy = socialforce` (not in the reference: social-force pedestrians,
 mcn_env_step_sf, parameters from the optional [social_force] section), get_human_times :219 (an all-ORCA simulation
-to the end: one mcn_orca_batch launch per simulated step).  render is host-only visual tooling and out of scope
-(SURVEY.md section 2, row 1).
+to the end: mcn_orca_finish, the step loop inside the kernel, for one env or a batch).  render is host-only visual
+tooling and out of scope.
 
   VecCrowdSim  tensors in / tensors out, E envs, SoA float64 state (layout: include/mcn.h)
   CrowdSim     the E = 1 gym-style view returning the reference's value types
@@ -346,6 +346,50 @@ class VecCrowdSim(object):
         finally:
             self.count_hh = keep
 
+    def _orca_finish(self, sim_vel, select, max_steps, steps, traj):
+        """One mcn_orca_finish launch on the env tensors with the reference's simulator parameters (crowd_sim.py:229:
+        neighborDist 10, maxNeighbors 10, timeHorizon 5)."""
+        rc = _hip.lib.mcn_orca_finish(self._st, _hip.ptr(sim_vel), _hip.ptr(select), int(max_steps), _hip.ptr(steps),
+                                      _hip.ptr(traj), self.time_step, 10.0, 10, 5.0, self.num_envs, self._alloc_N,
+                                      _hip.stream_ptr(self.device))
+        _hip.check(rc, "mcn_orca_finish")
+
+    def get_human_times(self, envs=None, max_steps=8000):
+        """crowd_sim.py:219-258 for many envs in one launch (mcn_orca_finish): every selected env, its robot arrived, runs
+        robot and humans in one centralised ORCA simulation until each human has reached its goal or `max_steps` steps
+        are taken.  envs: None = every env whose robot has arrived (sqrt(|rpos - rgoal|^2) < rrad in float64), or env
+        indices / a boolean mask [E]; selecting an env whose robot has not arrived raises ValueError.  hpos, rpos,
+        gtime and human_times advance in place (velocities stay, as in the reference).  Returns (human_times [E,N],
+        steps taken [E] int32)."""
+        if self.human_policy_name == "socialforce":
+            raise NotImplementedError("get_human_times runs the reference's all-ORCA simulation to the end: it is not "
+                                      "defined for social-force humans")
+        E, dev = self.num_envs, self.device
+        d = self.rpos - self.rgoal
+        arrived = torch.sqrt(d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) < self.rrad
+        if envs is None:
+            select = arrived
+        else:
+            envs = envs.cpu().numpy() if torch.is_tensor(envs) else np.asarray(envs)
+            if envs.dtype == np.bool_:
+                if envs.size != E:
+                    raise ValueError("expected a mask of %d envs, got %d" % (E, envs.size))
+                mask = envs.reshape(E)
+            else:
+                mask = np.zeros(E, np.bool_)
+                mask[envs.reshape(-1).astype(np.int64)] = True          # (an index outside the batch raises here)
+            select = torch.from_numpy(mask).to(dev)
+            if bool((select & ~arrived).any()):
+                raise ValueError("Episode is not done yet")
+        select = select.to(torch.uint8).contiguous()
+        sim_vel = torch.cat([self.rvel.unsqueeze(1), self.hvel], 1).to(torch.float32).contiguous()
+        steps = torch.zeros(E, dtype=torch.int32, device=dev)
+        self._orca_finish(sim_vel, select, max_steps, steps, None)
+        chosen = select.bool()
+        if bool((chosen & (((self.human_times == 0).any(1)) | (self.gtime > 1000))).any()):
+            logging.warning("Simulation cannot terminate!")          # crowd_sim.py:243-244
+        return self.human_times, steps
+
     # ---------------------------------------------------------------- fused rollout bookkeeping
     def attach_rollout(self, gamma, pool=None, case_stride=1, first_cases=None, fin_slots=1, danger_episodes=0,
                        danger_short_from=0):
@@ -599,11 +643,11 @@ class CrowdSim(object):
     def get_human_times(self, max_steps=8000):
         """crowd_sim.py:219-258: once the robot has arrived, run everybody (robot = agent 0, then the humans) to the end
         in ONE centralised ORCA simulation and return each human's first-arrival time.  The reference drives an
-        rvo2.PyRVOSimulator(time_step, 10, 10, 5, 5, 0.3, 1) with agents at their own radius / v_pref; here every
-        simulated step is one mcn_orca_batch launch (B = N + 1 agents, each with the other N as candidates in index
-        order) and the float32 position update rvo2 does inside doStep (velocity = newVelocity; position += velocity *
-        timeStep) is done on the host copies in float32.  ORCA parity vs rvo2 is unpinned (oracle/mcn_oracle.c); rvo2
-        enumerates neighbours in kd-tree order, which only matters for exactly equal distances.
+        rvo2.PyRVOSimulator(time_step, 10, 10, 5, 5, 0.3, 1) with agents at their own radius / v_pref and moves the
+        float32 positions inside doStep; here that is mcn_orca_finish (include/mcn.h), a few hundred simulated steps per
+        launch, and the recorded positions of every step come back in one copy per launch to refresh the agents and
+        `states`.  ORCA parity vs rvo2 is unpinned (oracle/mcn_oracle.c); rvo2 enumerates neighbours in kd-tree order,
+        which only matters for exactly equal distances.
         The reference loops for ever if somebody never arrives (it only logs past t = 1000); this stops after
         `max_steps` simulated steps with the same warning."""
         v, robot = self._vec, self._vec.robot
@@ -612,44 +656,35 @@ class CrowdSim(object):
                                       "defined for social-force humans")
         if not robot.reached_destination():
             raise ValueError("Episode is not done yet")
-        agents = [robot] + self.humans
-        B, f32, dev = len(agents), np.float32, v.device
-        M = B - 1
-        pos = np.array([a.get_position() for a in agents], np.float64).astype(f32)
-        vel = np.array([a.get_velocity() for a in agents], np.float64).astype(f32)
-        rad = np.array([a.radius for a in agents], np.float64).astype(f32)
-        vmax = np.array([a.v_pref for a in agents], np.float64).astype(f32)
-        dt32 = f32(v.time_step)
-        others_idx = np.array([[j for j in range(B) if j != i] for i in range(B)], np.int64).reshape(B, M)
-        d_n = torch.full((B,), M, dtype=torch.int32, device=dev)
-        d_out = torch.empty(B, 2, dtype=torch.float32, device=dev)
-        max_time, steps = 1000, 0
-        while not all(self.human_times):
-            pref = np.zeros((B, 2), np.float64)
-            for i, agent in enumerate(agents):
-                vel_pref = np.array(agent.get_goal_position()) - np.array(agent.get_position())
-                if np.linalg.norm(vel_pref) > 1:
-                    vel_pref /= np.linalg.norm(vel_pref)
-                pref[i] = vel_pref
-            me = np.concatenate([pos, vel, rad[:, None], vmax[:, None], pref.astype(f32)], 1).astype(f32)       # [B,8]
-            oth = np.concatenate([pos[others_idx], vel[others_idx], rad[others_idx][..., None]], 2).astype(f32)  # [B,M,5]
-            d_me, d_oth = torch.from_numpy(me).to(dev), torch.from_numpy(np.ascontiguousarray(oth)).to(dev)
-            _hip.check(_hip.lib.mcn_orca_batch(_hip.ptr(d_me), _hip.ptr(d_oth), _hip.ptr(d_n), _hip.ptr(d_out), B, max(M, 1),
-                                               10.0, 10, 5.0, float(v.time_step), _hip.stream_ptr(dev)), "mcn_orca_batch")
-            vel = d_out.cpu().numpy().astype(f32)
-            pos = (pos + vel * dt32).astype(f32)
-            self.global_time += v.time_step
-            steps += 1
-            if self.global_time > max_time:
-                logging.warning("Simulation cannot terminate!")
-            for i, human in enumerate(self.humans):
-                if self.human_times[i] == 0 and human.reached_destination():
-                    self.human_times[i] = self.global_time
-            robot.set_position((float(pos[0, 0]), float(pos[0, 1])))
-            for i, human in enumerate(self.humans):
-                human.set_position((float(pos[i + 1, 0]), float(pos[i + 1, 1])))
-            self.states.append([robot.get_full_state(), [h.get_full_state() for h in self.humans]])
-            if steps >= max_steps:
+        n, dev = len(self.humans), v.device
+        if len(self.human_times) != n:
+            raise ValueError("human_times holds %d entries for %d humans" % (len(self.human_times), n))
+        self._push_host_state()
+        sim_vel = torch.cat([v.rvel, v.hvel[0]]).to(torch.float32).reshape(1, n + 1, 2).contiguous()
+        chunk = min(int(max_steps), 256)
+        traj = torch.empty(chunk, 1, n + 1, 2, dtype=torch.float32, device=dev)
+        steps = torch.zeros(1, dtype=torch.int32, device=dev)
+        max_time, total = 1000, 0
+        while total < max_steps:
+            cap = min(chunk, max_steps - total)
+            v._orca_finish(sim_vel, None, cap, steps, traj)
+            # the step count, the arrival times and every recorded position of this launch in ONE synchronising copy
+            host = torch.cat([steps.to(torch.float64), v.human_times[0], traj[:cap].reshape(-1).to(torch.float64)]).cpu()
+            host = host.numpy()
+            took = int(host[0])
+            pos = host[1 + n:].reshape(cap, n + 1, 2)
+            for t in range(took):
+                self.global_time += v.time_step
+                if self.global_time > max_time:
+                    logging.warning("Simulation cannot terminate!")
+                robot.set_position((float(pos[t, 0, 0]), float(pos[t, 0, 1])))
+                for i, human in enumerate(self.humans):
+                    human.set_position((float(pos[t, i + 1, 0]), float(pos[t, i + 1, 1])))
+                self.states.append([robot.get_full_state(), [h.get_full_state() for h in self.humans]])
+            if took:
+                self.human_times = host[1:1 + n].tolist()
+            total += took
+            if took < cap:
                 break
         return self.human_times
 

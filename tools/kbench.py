@@ -5,6 +5,7 @@ human-policy modes, measured with HIP events around a hipGraph of back-to-back l
     python tools/kbench.py --human-policy socialforce [--rollout 128 [--unfused]]   (mcn_env_step_sf / mcn_env_rollout_sf)
     python tools/kbench.py --sgan-predict --sizes 4096 --humans 10,5 --samples 1,20 --steps 8,12
     python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
+    python tools/kbench.py --finish [--humans 5,10] [--sizes 4096]   (mcn_orca_finish vs one mcn_orca_batch launch per step)
 """
 import argparse
 import os
@@ -100,7 +101,17 @@ def main():
     ap.add_argument("--samples", default="1", help="with --sgan-predict: noise samples K per scene (a comma list)")
     ap.add_argument("--lstm-rl", action="store_true", help="time mcn_lstm_rl_predict at 4096 envs x --humans")
     ap.add_argument("--cadrl", action="store_true", help="time mcn_cadrl_predict at 4096 envs x --humans")
+    ap.add_argument("--finish", action="store_true",
+                    help="time VecCrowdSim.get_human_times (one mcn_orca_finish launch) at --sizes x --humans against one "
+                         "mcn_orca_batch launch + torch update per simulated step, and the E = 1 CrowdSim method against "
+                         "its former host loop")
     a = ap.parse_args()
+    if a.finish:
+        for N in [int(x) for x in str(a.humans).split(",")]:
+            for E in [int(x) for x in a.sizes.split(",")]:
+                finish_bench(E, N)
+            finish_bench_e1(N)
+        return
     if a.lstm_rl or a.cadrl:
         for N in [int(x) for x in str(a.humans).split(",")]:
             policy_bench("lstm_rl" if a.lstm_rl else "cadrl", 4096, N)
@@ -232,6 +243,173 @@ def sarl_bench(E=4096, N=5, iters=5, om=False):
     e.record(); torch.cuda.synchronize()
     ms = s.elapsed_time(e) / iters
     print("SARL-driven env step N=%d E=%d: %.3f ms/step  %.3f M env-steps/s" % (N, E, ms, E / ms / 1e3))
+
+
+def _finish_per_step(env, max_steps=8000):
+    """get_human_times for a batch as it could be written without mcn_orca_finish: per simulated step one mcn_orca_batch
+    launch over all E (N + 1) agents, a torch float32 position update, the float64 arrival test and one synchronising
+    "is anybody left" read.  Same arithmetic; returns (human_times, steps taken by the slowest env)."""
+    from modelcrowdnav_amd import _hip
+    E, N, dev = env.num_envs, env._alloc_N, env.device
+    A, f32 = N + 1, torch.float32
+    pos64 = torch.cat([env.rpos.unsqueeze(1), env.hpos], 1)
+    goal = torch.cat([env.rgoal.unsqueeze(1), env.hgoal], 1)
+    rad64 = torch.cat([env.rrad.unsqueeze(1), env.hrad], 1)
+    vmax = torch.cat([env.rvpref.unsqueeze(1), env.hvpref], 1).to(f32)
+    pos, vel = pos64.to(f32), torch.cat([env.rvel.unsqueeze(1), env.hvel], 1).to(f32)
+    rad = rad64.to(f32)
+    others = torch.tensor([[j for j in range(A) if j != i] for i in range(A)], device=dev)        # [A, N]
+    n_other = torch.full((E * A,), N, dtype=torch.int32, device=dev)
+    out = torch.empty(E * A, 2, dtype=f32, device=dev)
+    times, gtime = env.human_times.clone(), env.gtime.clone()
+    live = (times == 0).any(1)
+    steps, dt32 = 0, torch.tensor(env.time_step, dtype=f32, device=dev)
+    while steps < max_steps and bool(live.any()):
+        e = goal - pos64
+        n = torch.sqrt(e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]).unsqueeze(-1)
+        pref = torch.where(n > 1, e / n, e).to(f32)
+        me = torch.cat([pos, vel, rad.unsqueeze(-1), vmax.unsqueeze(-1), pref], 2).reshape(E * A, 8).contiguous()
+        oth = torch.cat([pos[:, others], vel[:, others], rad[:, others].unsqueeze(-1)], 3).reshape(E * A, N, 5).contiguous()
+        _hip.check(_hip.lib.mcn_orca_batch(_hip.ptr(me), _hip.ptr(oth), _hip.ptr(n_other), _hip.ptr(out), E * A, N, 10.0,
+                                           10, 5.0, float(env.time_step), _hip.stream_ptr(dev)), "mcn_orca_batch")
+        lv = live.view(E, 1, 1)
+        vel = torch.where(lv, out.view(E, A, 2), vel)
+        pos = torch.where(lv, pos + vel * dt32, pos)
+        gtime = torch.where(live, gtime + env.time_step, gtime)
+        d = pos64[:, 1:] - goal[:, 1:]
+        here = torch.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) < rad64[:, 1:]
+        times = torch.where(live.unsqueeze(1) & (times == 0) & here, gtime.unsqueeze(1), times)
+        pos64 = pos.to(torch.float64)
+        live = (times == 0).any(1)
+        steps += 1
+    return times, steps
+
+
+def finish_bench(E, N, reps=5):
+    """One VecCrowdSim.get_human_times call (mcn_orca_finish: the step loop inside the kernel) for E reset
+    circle-crossing scenes with the robot on its goal, against _finish_per_step on the same scenes, alternating, `reps`
+    times each; wall time around a device synchronise.  The two must return the same arrival times."""
+    import time
+    dev = torch.device("cuda", 0)
+    env, _ = bench.build_env(E, N, 0, dev)
+    env.detach_rollout()
+    start = {k: getattr(env, k).clone() for k in ("hpos", "rpos", "gtime", "human_times")}
+
+    def restart():
+        for k, v in start.items():
+            getattr(env, k).copy_(v)
+        env.rpos.copy_(env.rgoal)
+        torch.cuda.synchronize()
+
+    one, per = [], []
+    for rep in range(reps + 1):                      # the first round of each warms up
+        restart()
+        t0 = time.perf_counter()
+        times, steps = env.get_human_times()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        times = times.clone()
+        restart()
+        t2 = time.perf_counter()
+        times_ps, nsteps = _finish_per_step(env)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        if not (torch.equal(times, times_ps) and int(steps.max()) == nsteps):
+            print("finish N=%d E=%d: THE PER-STEP BASELINE DISAGREES (%d envs, %d vs %d steps)" % (
+                N, E, int((times != times_ps).any(1).sum()), int(steps.max()), nsteps), flush=True)
+        if rep:
+            one.append((t1 - t0) * 1e3); per.append((t3 - t2) * 1e3)
+    fmt = lambda v: "median %.2f ms (min %.2f, max %.2f)" % (sorted(v)[len(v) // 2], min(v), max(v))
+    print("finish N=%d E=%d: %d env-steps in all, slowest env %d steps; one launch %s; per-step launches %s; ratio of "
+          "medians %.1f x" % (N, E, int(steps.sum()), int(steps.max()), fmt(one), fmt(per),
+                              sorted(per)[len(per) // 2] / sorted(one)[len(one) // 2]), flush=True)
+
+
+def _e1_host_loop(env, max_steps=8000):
+    """CrowdSim.get_human_times as it was before mcn_orca_finish: per simulated step a numpy pack, two host-to-device
+    copies, one mcn_orca_batch launch, a synchronising copy back and the float32 update on the host."""
+    from modelcrowdnav_amd import _hip
+    v, robot = env._vec, env._vec.robot
+    agents = [robot] + env.humans
+    B, f32, dev = len(agents), np.float32, v.device
+    M = B - 1
+    pos = np.array([a.get_position() for a in agents], np.float64).astype(f32)
+    vel = np.array([a.get_velocity() for a in agents], np.float64).astype(f32)
+    rad = np.array([a.radius for a in agents], np.float64).astype(f32)
+    vmax = np.array([a.v_pref for a in agents], np.float64).astype(f32)
+    dt32 = f32(v.time_step)
+    others_idx = np.array([[j for j in range(B) if j != i] for i in range(B)], np.int64).reshape(B, M)
+    d_n = torch.full((B,), M, dtype=torch.int32, device=dev)
+    d_out = torch.empty(B, 2, dtype=torch.float32, device=dev)
+    steps = 0
+    while not all(env.human_times):
+        pref = np.zeros((B, 2), np.float64)
+        for i, agent in enumerate(agents):
+            vel_pref = np.array(agent.get_goal_position()) - np.array(agent.get_position())
+            if np.linalg.norm(vel_pref) > 1:
+                vel_pref /= np.linalg.norm(vel_pref)
+            pref[i] = vel_pref
+        me = np.concatenate([pos, vel, rad[:, None], vmax[:, None], pref.astype(f32)], 1).astype(f32)
+        oth = np.concatenate([pos[others_idx], vel[others_idx], rad[others_idx][..., None]], 2).astype(f32)
+        d_me, d_oth = torch.from_numpy(me).to(dev), torch.from_numpy(np.ascontiguousarray(oth)).to(dev)
+        _hip.check(_hip.lib.mcn_orca_batch(_hip.ptr(d_me), _hip.ptr(d_oth), _hip.ptr(d_n), _hip.ptr(d_out), B, max(M, 1),
+                                           10.0, 10, 5.0, float(v.time_step), _hip.stream_ptr(dev)), "mcn_orca_batch")
+        vel = d_out.cpu().numpy().astype(f32)
+        pos = (pos + vel * dt32).astype(f32)
+        env.global_time += v.time_step
+        steps += 1
+        for i, human in enumerate(env.humans):
+            if env.human_times[i] == 0 and human.reached_destination():
+                env.human_times[i] = env.global_time
+        robot.set_position((float(pos[0, 0]), float(pos[0, 1])))
+        for i, human in enumerate(env.humans):
+            human.set_position((float(pos[i + 1, 0]), float(pos[i + 1, 1])))
+        env.states.append([robot.get_full_state(), [h.get_full_state() for h in env.humans]])
+        if steps >= max_steps:
+            break
+    return env.human_times
+
+
+def finish_bench_e1(N, reps=5, cases=(0, 3, 7, 11)):
+    """CrowdSim.get_human_times (E = 1, through mcn_orca_finish) against its former host loop on the same scenes
+    (`test` cases, robot put on its goal), alternating, `reps` times each: wall time per call over the cases."""
+    import time
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.envs import CrowdSim
+    from modelcrowdnav_amd.envs.utils.robot import Robot
+    from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
+    cfg = configs.env_config(**{"sim.human_num": N})
+    env = CrowdSim()
+    env.configure(cfg)
+    robot = Robot(cfg, "robot")
+    pol = policy_factory["orca"]()
+    pol.configure(cfg)
+    robot.set_policy(pol)
+    env.set_robot(robot)
+
+    def run(fn):
+        total, got, nstates = 0.0, [], 0
+        for case in cases:
+            env.reset("test", case)
+            robot.set_position(robot.get_goal_position())
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got.append(list(fn()))
+            total += time.perf_counter() - t0
+            nstates += len(env.states)
+        return total * 1e3 / len(cases), got, nstates
+
+    new, old = [], []
+    for rep in range(reps + 1):                      # the first round of each warms up
+        a, got_a, na = run(env.get_human_times)
+        b, got_b, nb = run(lambda: _e1_host_loop(env))
+        if got_a != got_b or na != nb:
+            print("finish E=1 N=%d: THE FORMER HOST LOOP DISAGREES" % N, flush=True)
+        if rep:
+            new.append(a); old.append(b)
+    fmt = lambda v: "median %.2f ms (min %.2f, max %.2f)" % (sorted(v)[len(v) // 2], min(v), max(v))
+    print("finish E=1 N=%d: %.1f steps per call; through mcn_orca_finish %s; former host loop %s; ratio of medians %.1f x" % (
+        N, na / len(cases), fmt(new), fmt(old), sorted(old)[len(old) // 2] / sorted(new)[len(new) // 2]), flush=True)
 
 
 def policy_bench(kind, E=4096, N=5, iters=20):
