@@ -130,17 +130,35 @@ __device__ __forceinline__ KernargPtr kernarg_here()
 // The float64 wavefront OWNS every float64 value of the env: the robot, the clock, the records and the humans' position,
 // velocity, goal, radius, v_pref and human_times -- one human per lane, loaded in its prologue, integrated or restarted
 // from the pool by it, stored in its epilogue.  The ORCA wavefronts are float32 only: per step they read their human's
-// operand packs and their candidate's from LDS (quad_common.hpp: quad_orca_operands), run quad_orca_core and publish
-// the new velocity as two floats.  The four lanes of a quad would each repeat the float64 -> float32 conversions, the
-// integrate and the restart test; the float64 wavefront does them once per human and has the cycles to spare, and on a
-// SIMD that holds two wavefronts every instruction taken out of the ORCA stream is taken out of its neighbour's way too.
+// operands and their candidate's from LDS, run quad_orca_core (quad_common.hpp) and publish the new velocity as two
+// floats.  The four lanes of a quad would each repeat the float64 -> float32 conversions, the integrate and the restart
+// test; the float64 wavefront does them once per human and has the cycles to spare, and on a SIMD that holds two
+// wavefronts every instruction taken out of the ORCA stream is taken out of its neighbour's way too.
 // The roles meet through LDS at two points of the step: hand-off 1, ORCA -> float64, the new velocities; hand-off 2,
-// float64 -> ORCA, the next step's packs (the float64 wavefront integrates between the two).  Each value is produced by
-// the operation, on the operands, that the other forms use, so the same bits.
+// float64 -> ORCA, the new positions (the float64 wavefront integrates between the two).  Between the two all four
+// wavefronts wait for one serial chain, so only what depends on the new velocity is on it: read (rx, ry), two
+// conversions, the integrate, goal - pos, four conversions, one 16-byte write.  Everything else stays off it:
+//   * the velocity never leaves float32: the solve's velocity operands are the floats the ORCA wavefronts published
+//     (float32 -> float64 -> float32 gives the same bits back), read from s_res by owner and candidate alike;
+//   * frad and the maximum speed change only on a restart and live in s_inv, written in the prologue and by restart lanes;
+//   * what a restarted human publishes (position pack, start velocity, s_inv) is converted BEFORE hand-off 1, where the
+//     float64 wavefront would idle anyway, and stored between the hand-offs behind one wave-uniform branch;
+//   * the float64 wavefront's private arrays, its register update and the human_times test come after hand-off 2.
+// Each value is produced by the operation, on the operands, that the other forms use, so the same bits.
 //
-// The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot and human integrate / restart and
-// the epilogue are the TWIN of env_rollout_quad_kernel's below (the older forms keep their code, hence their registers,
-// so the text is not shared): a change to either is made to both.
+// s_res is double-buffered by step parity (parity 0 = the launch's first step): the ORCA wavefronts of step t write
+// buffer t & 1, the float64 wavefront reads (and a restart lane overwrites) buffer t & 1 between the hand-offs of step t,
+// and the top of step t + 1 reads buffer t & 1.  With one buffer a fast ORCA wavefront could publish step t + 1's
+// velocity while a slow one still reads step t's as its candidate's: no barrier lies between the two.  With two, the
+// next write to buffer t & 1 is step t + 2's, issued after hand-off 2 of step t + 1; its last readers are the tops of
+// step t + 1, whose values are consumed by a solve that ends before hand-off 1 of step t + 1: every reader has passed
+// two barriers since.  The prologue seeds buffer 1, which the top of step 0 reads.
+//
+// The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot integrate / restart and the epilogue
+// are the TWIN of env_rollout_quad_kernel's below (the older forms keep their code, hence their registers, so the text
+// is not shared): a change to either is made to both.  The humans' integrate / restart holds the twin's statements
+// (pos + (double)r * dt, the pool fetch, human_times) in another order: the restart before hand-off 1, the integrate
+// between the hand-offs, the velocity register and human_times after hand-off 2.
 template <int NT>
 struct Wg4 {
     static_assert(NT == 5, "the four-wavefront form is built for 5 humans only");
@@ -165,12 +183,14 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
 {
     static_assert(VIS == 0, "the four-wavefront form is built for an invisible robot only");
     constexpr int EW = Wg4<NT>::EW, NQ = Wg4<NT>::NQ;
-    // hand-off arrays, one slot per (env, human).  Written by the float64 wavefront between the step's two barriers: the
-    // float32 operand packs of quad_orca_core (quad_common.hpp: A = position and velocity, B = preferred velocity, frad,
-    // maximum speed) and the float64 position and radius its own overlap pairs read from partner lanes.  Written by the
-    // ORCA wavefronts outside that window, read by the float64 one inside it: the human's new velocity.
-    __shared__ float4 s_opa[NQ], s_opb[NQ];
-    __shared__ float2 s_res[NQ];
+    // hand-off arrays, one slot per (env, human).  Written by the float64 wavefront between the step's two barriers:
+    // s_pack = (px, py, prefx, prefy) of quad_orca_core's operands, every step; s_inv = (frad, maximum speed) and the
+    // start velocity in s_res, restart lanes only.  Written by the ORCA wavefronts outside that window, read by the
+    // float64 one inside it and by the ORCA ones at the top of the next step: s_res, the human's new velocity, two
+    // buffers by step parity (see above).  s_hpos / s_hrad, the float64 position and radius the overlap pairs read from
+    // partner lanes, are the float64 wavefront's own: written after the second barrier, read in its next step.
+    __shared__ float4 s_pack[NQ];
+    __shared__ float2 s_res[2 * NQ], s_inv[NQ];
     __shared__ double2 s_hpos[NQ];
     __shared__ double s_hrad[NQ];
     STAMP(0);
@@ -199,19 +219,31 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         const int ci = pop ? ge * NT + j : 0;
         const bool publish = pop && k == 0;
         const float inv_th = in_vgpr(1.0f / c.orca_time_horizon), inv_ts = in_vgpr(1.0f / (float)c.time_step);
+        int rd_h = hi + NQ, rd_c = ci + NQ;                      // s_res slots the top of the step reads: buffer 1 first
         __syncthreads();                                         // the float64 wavefront has seeded the packs
         STAMP(1);
 
         for (int t = 0; t < T; ++t) {
-            // own operands and the candidate's, published behind the step's second barrier; one LDS round trip
-            const float4 A = s_opa[hi], B = s_opb[hi], o = s_opa[ci];
-            const float orad = s_opb[ci].z;                      // the candidate's own frad
+            // own operands and the candidate's: positions published behind the step's second barrier, velocities by the
+            // last step's solves (buffer (t - 1) & 1; restart lanes overwritten), frad / ms since the last restart.  All
+            // six reads are issued before the first wait, one LDS round trip: the empty asm needs every value, and every
+            // use comes after it (left alone the compiler waits for the positions, starts on them and reads the rest then)
+            float4 P = s_pack[hi];
+            float2 cp = *reinterpret_cast<const float2 *>(s_pack + ci);
+            float2 v = s_res[rd_h], cv = s_res[rd_c];
+            float2 fm = s_inv[hi];
+            float orad = s_inv[ci].x;                            // the candidate's own frad
+            asm volatile("" : "+v"(P.x), "+v"(P.y), "+v"(P.z), "+v"(P.w), "+v"(cp.x), "+v"(cp.y), "+v"(v.x), "+v"(v.y),
+                              "+v"(cv.x), "+v"(cv.y), "+v"(fm.x), "+v"(fm.y), "+v"(orad));
             float rx, ry;
-            quad_orca_core(c, lane, k, cand_h && active, A, B, o, orad, inv_th, inv_ts, rx, ry);
-            if (publish) s_res[hi] = make_float2(rx, ry);
+            quad_orca_core(c, lane, k, cand_h && active, make_float4(P.x, P.y, v.x, v.y), make_float4(P.z, P.w, fm.x, fm.y),
+                           make_float4(cp.x, cp.y, cv.x, cv.y), orad, inv_th, inv_ts, rx, ry);
+            if (publish) s_res[(t & 1) * NQ + hi] = make_float2(rx, ry);
+            // the next step reads the buffer this one wrote; its addresses are ready before the barriers
+            rd_h = in_vgpr(hi + (t & 1) * NQ); rd_c = in_vgpr(ci + (t & 1) * NQ);
             if (t < 20) STAMP(40 + t);
             __syncthreads();                                     // hand-off 1: the humans' new velocities
-            __syncthreads();                                     // hand-off 2: the next step's operand packs
+            __syncthreads();                                     // hand-off 2: the next step's positions
             if (t < 37) STAMP(2 + t);
         }
     } else {
@@ -264,11 +296,16 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         const double k_discomfort = in_vgpr(c.discomfort_dist), k_factor = in_vgpr(c.discomfort_penalty_factor);
         const int k_stride = ro.case_stride, k_pool = ro.pool_size;
         const bool count_hh = c.count_hh != 0;
-        // the first step's operands: the loaded state goes through the hand-off arrays
+        // the first step's operands: the loaded state goes through the hand-off arrays (velocity: buffer 1, the one the
+        // top of step 0 reads)
         {
             float4 A, B;
             quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
-            if (pop) { s_opa[hs] = A; s_opb[hs] = B; s_hpos[hs] = pos; s_hrad[hs] = rad; }
+            if (pop) {
+                s_pack[hs] = make_float4(A.x, A.y, B.x, B.y); s_res[NQ + hs] = make_float2(A.z, A.w);
+                s_inv[hs] = make_float2(B.z, B.w);
+                s_hpos[hs] = pos; s_hrad[hs] = rad;
+            }
         }
         __syncthreads();
         STAMP(1);
@@ -410,50 +447,65 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 gtime = t_new;
             }
 
-            // ---- humans of a finished env: the pool case is fetched NOW, while this wavefront would wait at hand-off 1
-            //      for the ORCA ones anyway (it knows the done flag first), not on the chain between the hand-offs ----
-            double2 npos = pos, nvel = vel, ngoal = goal;
-            double nrad = rad, nvpref = vpref;
-            if (do_reset && dn) {
+            // ---- humans of a finished env restart from the scenario pool NOW, while this wavefront would wait at hand-off 1
+            //      for the ORCA ones anyway (it knows the done flag first): the case is fetched straight into the state
+            //      registers (nothing below reads the old one: the swept circle, the pairs and the ladder are done) and
+            //      converted; between the hand-offs a restart lane only stores what it holds here ----
+            const bool restart = do_reset && dn;
+            float4 n_pack = make_float4(0, 0, 0, 0);
+            float2 n_fvel = make_float2(0, 0), n_inv = make_float2(0, 0);
+            if (restart) {
                 DIAG_COUNT(1);
-                if (active) {
+                if (active) {                                    // (idle lanes keep what they had)
                     const long pa = (long)case_g * NT + h;
                     const KernargPtr kp = kernarg_here();
                     const double2 *pool_hvel = reinterpret_cast<const double2 *>(kp->roll.pool_hvel);
-                    nvel = make_double2(0, 0);                   // (before the loads: nothing here waits for one)
-                    if (pool_hvel) nvel = pool_hvel[pa];
-                    npos = reinterpret_cast<const double2 *>(kp->roll.pool_hpos)[pa];
-                    ngoal = reinterpret_cast<const double2 *>(kp->roll.pool_hgoal)[pa];
-                    nrad = kp->roll.pool_hrad[pa];
-                    nvpref = kp->roll.pool_hvpref[pa];
+                    vel = make_double2(0, 0);                    // (before the loads: nothing here waits for one)
+                    if (pool_hvel) vel = pool_hvel[pa];
+                    pos = reinterpret_cast<const double2 *>(kp->roll.pool_hpos)[pa];
+                    goal = reinterpret_cast<const double2 *>(kp->roll.pool_hgoal)[pa];
+                    rad = kp->roll.pool_hrad[pa];
+                    vpref = kp->roll.pool_hvpref[pa];
                 }
+                htime = 0;
+                // every float converted from the new float64 state, as the prologue does for a loaded one
+                float4 A, B;
+                quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
+                // (pinned: not to be sunk behind the barrier)
+                n_pack = make_float4(in_vgpr(A.x), in_vgpr(A.y), in_vgpr(B.x), in_vgpr(B.y));
+                n_fvel = make_float2(in_vgpr(A.z), in_vgpr(A.w));
+                n_inv = make_float2(in_vgpr(B.z), in_vgpr(B.w));
             }
+            const bool any_restart = __any(restart);             // roughly one workgroup-step in ten
 
             if (t < 20) STAMP(40 + t);
             __syncthreads();                                     // hand-off 1: the humans' new velocities
+            // ---- the chain every wavefront of the workgroup waits for: velocity -> position -> pack ----
+            float2 *vel_io = s_res + (t & 1) * NQ;
             {
-                const float2 r = s_res[hs];
-                hax = (double)r.x; hay = (double)r.y;
+                const float2 r = vel_io[hs];
+                hax = (double)r.x; hay = (double)r.y;            // (restart lanes too: the epilogue's human_act)
             }
-
-            // ---- humans: integrate, or restart from the scenario pool ----
-            if (do_reset && dn) {
-                pos = npos; vel = nvel; goal = ngoal; rad = nrad; vpref = nvpref;     // (idle lanes keep what they had)
-                htime = 0;
-            } else {
+            if (!restart) {
                 pos = make_double2(pos.x + hax * dt, pos.y + hay * dt);
+                if (pop) s_pack[hs] = quad_orca_position_pack(pos, goal);
+            }
+            if (any_restart) {                                   // (stores under their own mask: no select on the chain)
+                if (pop && restart) { s_pack[hs] = n_pack; vel_io[hs] = n_fvel; s_inv[hs] = n_inv; }
+            }
+            __syncthreads();                                     // hand-off 2: the next step's positions
+            if (t < 37) STAMP(2 + t);
+
+            // ---- off the chain: this wavefront's own arrays, the velocity register, the clock of the step just taken ----
+            if (pop) s_hpos[hs] = pos;
+            if (!restart) {
+                // (the solve's next operand is the ORCA wavefronts' float; (float)vel would give the same bits)
                 vel = make_double2(hax, hay);
-                // the clock of the step just taken
                 if (track && htime == 0 && norm2(pos.x - goal.x, pos.y - goal.y) < rad) htime = t_new;
             }
-            // the next step's operands, every float converted from the float64 state (a restart needs no second path)
-            {
-                float4 A, B;
-                quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
-                if (pop) { s_opa[hs] = A; s_opb[hs] = B; s_hpos[hs] = pos; s_hrad[hs] = rad; }
+            if (any_restart) {
+                if (pop && restart) s_hrad[hs] = rad;
             }
-            __syncthreads();                                     // hand-off 2: the next step's operand packs
-            if (t < 37) STAMP(2 + t);
         }
 
         long a2 = a, e2 = e;
@@ -494,8 +546,9 @@ __global__ __launch_bounds__(256, 2) void env_rollout_wg4_kernel(const StepParam
 }
 
 // TWIN: the float64 role of rollout_wg4 above carries a copy of this kernel's ladder, Explorer accounting,
-// finished-episode stores, robot and human integrate / restart and epilogue; a change to either is made to both
-// (tests/test_rollout_wg4_gpu.py and tests/test_rollout_owner_gpu.py compare their bytes).
+// finished-episode stores, robot integrate / restart and epilogue, and this kernel's human integrate / restart
+// statements arranged around its two hand-offs; a change to either is made to both (tests/test_rollout_wg4_gpu.py,
+// tests/test_rollout_owner_gpu.py and tests/test_rollout_chain_gpu.py compare their bytes).
 template <int NT, int VIS, bool UNI, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_quad_kernel(const StepParams p, const int T)
 {

@@ -179,6 +179,14 @@ __device__ __forceinline__ void quad_orca_operands(const mcn_env_cfg &c, double2
     B = make_float4(prefx, prefy, frad, ms);
 }
 
+// The part of the operands that changes with every step: (px, py, prefx, prefy), the same expressions as above.  The
+// four-wavefront rollout form recomputes only this per step (the velocity stays the float32 the solve produced, frad
+// and ms change on a restart only).
+__device__ __forceinline__ float4 quad_orca_position_pack(double2 pos, double2 goal)
+{
+    return make_float4((float)pos.x, (float)pos.y, (float)(goal.x - pos.x), (float)(goal.y - pos.y));
+}
+
 __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, int k, bool cand_valid, float4 A, float4 B,
                                                float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry);
 

@@ -1,0 +1,314 @@
+"""The chain between the two hand-offs of the four-wavefront rollout form (env_rollout_wg4_kernel, rollout_split = 2).
+
+Between hand-off 1 and hand-off 2 the float64 wavefront only turns the new velocity into the new position pack; the
+solve's velocity operands are the float32 values the ORCA wavefronts published (two LDS buffers by step parity), frad
+and the maximum speed are published on a restart only, and a restarted human's operands are converted before hand-off 1
+and stored behind a wave-uniform branch.  What the other rollout tests cannot see:
+
+  * a velocity that a float32 -> float64 -> float32 round trip done wrong would change (denormals, -0, NaN);
+  * a parity mix-up: odd and even launch lengths, one-step launches, every cut of one sequence;
+  * restarts on consecutive steps (both velocity buffers overwritten back to back), on the first and the last step of a
+    launch, of two envs of one workgroup at once, with start velocities that float32 cannot hold, with and without
+    pool_hvel, with radii and v_pref that change from case to case;
+  * human_times recorded behind hand-off 2: mid-launch, on the last step of a launch, on the step before a restart.
+
+Every comparison is of BYTES: full state, step record, Explorer records and finished-episode arrays of the forced
+four-wavefront form after EVERY launch against single mcn_env_step calls at that step, and of forms 1 and 0 at the end.
+Every forced launch asserts mcn_last_rollout_form().  Each test first shows, from the single-step run, that its inputs
+produce the situation it is about."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import cport
+from tests import edge_states as ES
+from tests import helpers as H
+
+N = 5
+_FIELDS = ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal", "rtheta", "gtime", "human_times",
+           "step_rec", "human_act")
+_ROLL = ("state", "fin_return", "fin_time", "fin_info")
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _torch():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch
+
+
+def _snapshot(env):
+    c = lambda t: t.detach().cpu().numpy().copy()
+    snap = {k: c(getattr(env, k)) for k in _FIELDS}
+    if env._roll is not None:
+        snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items() if k in _ROLL})
+    return snap
+
+
+def _assert_same_bytes(a, b, what=""):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
+
+
+def _single_steps(build, acts):
+    """T mcn_env_step calls: the snapshot after every step (snaps[t] = after step t) and the done flags [T, E]."""
+    torch = _torch()
+    env = build()
+    acts_d = torch.from_numpy(acts).to(env.device)
+    snaps, done = [], []
+    for t in range(len(acts)):
+        env.step(acts_d[t])
+        snaps.append(_snapshot(env))
+        done.append(env.done.cpu().numpy().astype(bool).copy())
+    return snaps, np.array(done)
+
+
+def _launches(build, acts, split, cuts, snaps, what=""):
+    """The sequence in launches acts[cuts[i]:cuts[i + 1]] of the forced form; after EVERY launch the bytes of the
+    single-step run at that step."""
+    torch = _torch()
+    from modelcrowdnav_amd import _hip
+    env = build()
+    acts_d = torch.from_numpy(acts).to(env.device)
+    _hip.set_tuning(rollout_fused=1, rollout_split=split)
+    for lo, hi in zip(cuts[:-1], cuts[1:]):
+        env.rollout(acts_d[lo:hi])
+        assert _hip.last_dispatch() == "env_rollout_quad_kernel" and _hip.last_rollout_form() == split
+        torch.cuda.synchronize()
+        _assert_same_bytes(_snapshot(env), snaps[hi - 1], "%s form %d cuts %s after step %d" % (what, split, cuts, hi - 1))
+
+
+def _all_forms(build, acts, snaps, cut_list, what=""):
+    T = len(acts)
+    for cuts in cut_list:
+        assert cuts[0] == 0 and cuts[-1] == T and all(a < b for a, b in zip(cuts[:-1], cuts[1:])), cuts
+        _launches(build, acts, 2, cuts, snaps, what)
+    for split in (1, 0):
+        _launches(build, acts, split, (0, T), snaps, what)
+
+
+def _still(T, E):
+    return np.zeros((T, E, 2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. velocities that a float64 round trip could change if done wrong
+_TINY = (1e-41, 1e-42, 1e-43, 1e-44, 1e-45, 1e-46, 1e-50)      # (float) of the last two is a zero
+
+
+def _velocity_state():
+    """9 envs.  Envs 0-6: human 0 sits (+d, -d) off its goal at the origin, d = 1e-41 .. 1e-50, so its preferred and
+    resulting velocity is (-d, +d) as float32: denormals, and -0 / +0 for the two smallest; humans 1-4 stand 4 m away
+    (in range) and walk outwards.  Env 7: the same with d = 1e-41 and a NaN goal for human 2, whose velocity and then
+    position are NaN.  Env 8: a packed-coincident env of tests/edge_states.py (a 0/0 half-plane in the 3-D LP)."""
+    E = 9
+    st = cport.EnvState(E, N)
+    out = np.array([(4.0, 0.0), (-4.0, 0.0), (0.0, 4.0), (0.0, -4.0)])
+    for e in range(E):
+        d = _TINY[e] if e < len(_TINY) else 1e-41
+        st.hpx[e, 0], st.hpy[e, 0], st.hgx[e, 0], st.hgy[e, 0] = d, -d, 0.0, 0.0
+        st.hpx[e, 1:], st.hpy[e, 1:] = out[:, 0], out[:, 1]
+        st.hgx[e, 1:], st.hgy[e, 1:] = 2 * out[:, 0], 2 * out[:, 1]
+    st.hvx[:] = 0; st.hvy[:] = 0
+    st.hr[:] = 0.3; st.hvpref[:] = 1.0
+    st.rpx[:], st.rpy[:], st.rgx[:], st.rgy[:] = 20.0, 20.0, 20.0, 25.0
+    st.rvx[:] = 0; st.rvy[:] = 0; st.rr[:] = 0.3
+    st.gtime[:] = 0
+    st.hgx[7, 2] = np.nan
+    src, _, _, names = ES.edge_batch(N, False)
+    j = names.index("packed-coincident")
+    for k in cport.EnvState.FIELDS_H + cport.EnvState.FIELDS_R + ("gtime", "rtheta", "human_times"):
+        getattr(st, k)[8] = getattr(src, k)[j]
+    return st
+
+
+@pytest.mark.gpu
+def test_velocities_keep_their_float32_bits(tuning):
+    """Denormal, -0 and NaN velocities through 6 steps cut as (6), (1, 5), (2, 4): the four-wavefront form hands the
+    ORCA wavefronts the float32 velocity itself where the other forms convert it to float64 and back; same bytes.
+    The NaN half-plane of the edge fixture (env 8) does not reach (rx, ry) -- a comparison with NaN never takes the
+    candidate; the oracle shows no NaN velocity for any env of edge_batch(5, False) over 8 steps -- so the NaN velocity
+    asserted below is that of a human with a NaN goal (env 7)."""
+    tuning(rollout_fused=1)
+    st = _velocity_state()
+    E, T = st.E, 6
+
+    def build():
+        env = H.make_vec_env(E, N)
+        H.upload(env, st)
+        env.attach_rollout(gamma=0.9, pool=None, fin_slots=2)
+        return env
+    acts = _still(T, E)
+    snaps, _ = _single_steps(build, acts)
+    v = np.concatenate([s["human_act"].ravel() for s in snaps] + [s["hvel"].ravel() for s in snaps])
+    v32 = v.astype(np.float32)
+    assert (v32.astype(np.float64).view(np.uint64) == v.view(np.uint64))[~np.isnan(v)].all(), "a velocity is no float32"
+    tiny = np.float32(2.0 ** -126)
+    assert ((np.abs(v32) > 0) & (np.abs(v32) < tiny)).any(), "no denormal velocity"
+    assert ((v32 == 0) & np.signbit(v32)).any(), "no -0 velocity"
+    assert np.isnan(v32).any(), "no NaN velocity"
+    _all_forms(build, acts, snaps, [(0, T), (0, 1, T), (0, 2, T)], "velocities")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. / 3. / 5. a pool whose cases 2 and 3 put a human on the robot's start pose: an env that restarts into one collides on
+# its next step and restarts again; time_limit 3 and a robot that stands still end every other episode at its ninth step
+_P, _LIMIT = 8, 3
+
+
+def _restart_env(E, kinematics, with_hvel):
+    torch = _torch()
+    from modelcrowdnav_amd.envs import scenarios as S
+    env = H.make_vec_env(E, N, kinematics=kinematics, **{"env.time_limit": _LIMIT, "env.randomize_attributes": "true"})
+    pool = S.scenario_pool(env.spec(), "test", range(_P), N, "circle_crossing").copy()
+    pool[:, :, S.VX], pool[:, :, S.VY] = 0.1, -0.3              # no float32 holds either
+    rr = env.spec().robot_row()
+    for case in (2, 3):
+        pool[case, 0, S.PX], pool[case, 0, S.PY] = rr[S.PX] + 0.125, rr[S.PY]
+    ids = np.arange(E)
+    env.load_scenarios(pool[ids % _P])
+    if with_hvel:
+        dpool = pool
+    else:
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(env.device)
+        dpool = dict(hpos=up(pool[:, :, [S.PX, S.PY]]), hgoal=up(pool[:, :, [S.GX, S.GY]]),
+                     hrad=up(pool[:, :, S.RAD]), hvpref=up(pool[:, :, S.VPREF]))
+    env.attach_rollout(gamma=0.9, pool=dpool, case_stride=1, first_cases=(ids + 1) % _P, fin_slots=3)
+    return env, pool
+
+
+_PARITY_CUTS = [(0, 37), (0, 1, 37), (0, 2, 37), (0, 1, 2, 3, 37), (0, 36, 37)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kinematics,E", [("holonomic", 1), ("holonomic", 8), ("holonomic", 9), ("unicycle", 9)])
+def test_parity_buffers_every_cut(kinematics, E, tuning):
+    """One 37-step sequence cut as (37), (1, 36), (2, 35), (1, 1, 1, 34) and (36, 1): odd and even launch lengths and
+    one-step launches; the velocity buffers' parity restarts at 0 in every launch, so every cut leaves the bytes of 37
+    single steps (compared after every launch)."""
+    tuning(rollout_fused=1)
+    T = 37
+    build = lambda: _restart_env(E, kinematics, True)[0]
+    acts = _still(T, E)
+    snaps, done = _single_steps(build, acts)
+    assert done.any(), "no env restarts"
+    _all_forms(build, acts, snaps, _PARITY_CUTS, "parity %s E=%d" % (kinematics, E))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kinematics,with_hvel", [("holonomic", True), ("holonomic", False), ("unicycle", True)])
+def test_restarts_through_the_side_path(kinematics, with_hvel, tuning):
+    """9 envs, 24 steps.  From the single-step run: an env restarts on consecutive steps; two envs of workgroup 0
+    restart on one step while others of it do not; consecutive pool cases differ in every human's radius and v_pref;
+    the start velocities are no float32 values.  The cuts put a restart on the last step of a launch, on the first
+    step of the next and into a one-step launch."""
+    from modelcrowdnav_amd.envs import scenarios as S
+    tuning(rollout_fused=1)
+    E, T = 9, 24
+    build = lambda: _restart_env(E, kinematics, with_hvel)[0]
+    pool = _restart_env(E, kinematics, with_hvel)[1]
+    for col in (S.RAD, S.VPREF):
+        assert (pool[:-1, :, col] != pool[1:, :, col]).all(), "consecutive cases share an attribute"
+    for col in (S.VX, S.VY):
+        assert (pool[:, :, col].astype(np.float32).astype(np.float64) != pool[:, :, col]).all()
+    acts = _still(T, E)
+    snaps, done = _single_steps(build, acts)
+    assert (done[:-1] & done[1:]).any(), "no env restarts on consecutive steps"
+    n0 = done[:, :8].sum(1)
+    assert ((n0 >= 2) & (n0 < 8)).any(), "never two envs of workgroup 0 alone: %s" % n0
+    steps = np.nonzero(done.any(1))[0]
+    assert steps[0] == 0, "no restart on the first step of the sequence"
+    late = steps[(steps >= 3) & (steps < T - 1)]
+    assert len(late) >= 2 and late[-1] > late[0] + 1, steps
+    ta, tb = int(late[0]), int(late[-1])
+    cuts = [(0, T),
+            (0, ta + 1, tb, T),                  # a launch ends on restart step ta, one begins with restart step tb
+            (0, ta, ta + 1, T),                  # restart step ta is a launch of its own
+            (0, tb + 1, T)]
+    if with_hvel:
+        vel = snaps[0]["hvel"][done[0]]
+        assert vel.size and (vel[..., 0] == 0.1).all() and (vel[..., 1] == -0.3).all()
+    else:
+        assert (snaps[0]["hvel"][done[0]] == 0).all()
+    _all_forms(build, acts, snaps, cuts, "restarts %s hvel=%s" % (kinematics, with_hvel))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. human_times, recorded behind hand-off 2
+def _arrival_state(E):
+    """Humans 3 m apart on parallel tracks, each 0.4 + 0.25 k m short of its goal (k = (2 e + h) mod 9): at v_pref 1.0
+    and 0.25 s a step human (e, h) is within its radius of the goal after step k."""
+    st = cport.EnvState(E, N)
+    for e in range(E):
+        for h in range(N):
+            k = (2 * e + h) % 9
+            st.hpx[e, h], st.hpy[e, h] = -(0.4 + 0.25 * k), 3.0 * h - 6.0
+            st.hgx[e, h], st.hgy[e, h] = 0.0, 3.0 * h - 6.0
+    st.hvx[:] = 0; st.hvy[:] = 0; st.hr[:] = 0.3; st.hvpref[:] = 1.0
+    st.rpx[:], st.rpy[:], st.rgx[:], st.rgy[:] = 20.0, 20.0, 20.0, 25.0
+    st.rvx[:] = 0; st.rvy[:] = 0; st.rr[:] = 0.3
+    st.gtime[:] = 0
+    return st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tracked", [True, False])
+def test_human_times_behind_hand_off_2(tracked, tuning):
+    """time_limit 3: every env times out, and restarts from the pool, at its ninth step (index 8).  Tracked: a human
+    arrives mid-launch, on the last step of a launch (the epilogue stores it) and on step 7, the step before its env
+    restarts (the launch cut after step 7 shows it, the one after step 8 shows it cleared); the times are the single
+    steps'.  Not tracked (the benchmark's variant: array allocated, no human_act export): nobody writes either."""
+    from modelcrowdnav_amd.envs import scenarios as S
+    tuning(rollout_fused=1)
+    E, T = 9, 14
+    st = _arrival_state(E)
+
+    def build():
+        env = H.make_vec_env(E, N, **{"env.time_limit": _LIMIT})
+        env.track_human_times = tracked
+        env.export_human_actions = tracked
+        H.upload(env, st)
+        if not tracked:
+            env.human_act.fill_(-7.0)
+        pool = S.scenario_pool(env.spec(), "test", range(_P), N, "circle_crossing")
+        env.attach_rollout(gamma=0.9, pool=pool, case_stride=1, first_cases=(np.arange(E) + 1) % _P, fin_slots=2)
+        return env
+    acts = _still(T, E)
+    snaps, done = _single_steps(build, acts)
+    assert done[8].all() and not done[:8].any(), "the envs do not all restart at step 8"
+    ht = np.array([s["human_times"] for s in snaps])                     # [T, E, N]
+    if tracked:
+        first = (ht[:8] > 0).argmax(0)                                       # arrival step, where there is one
+        arrived = (ht[:8] > 0).any(0)
+        assert (arrived & (first == 3)).any(), "no arrival on step 3"
+        assert (arrived & (first == 5)).any(), "no arrival on step 5"
+        assert (arrived & (first == 7)).any(), "no arrival on the step before the restart"
+        assert (ht[7][arrived & (first == 7)] == 2.0).all() and (ht[8] == 0).all()
+        cuts = [(0, T), (0, 6, T), (0, 8, T), (0, 8, 9, T), (0, 1, 7, T)]    # step 3 mid-launch, 5 and 7 last steps
+    else:
+        assert (ht == 0).all() and all((s["human_act"] == -7.0).all() for s in snaps)
+        cuts = [(0, T), (0, 8, T)]
+    _all_forms(build, acts, snaps, cuts, "human_times tracked=%s" % tracked)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# no GPU: registers and scratch of both instantiations
+def test_chain_kernels_registers_and_scratch():
+    """Both env_rollout_wg4_kernel instantiations run without scratch, the holonomic one in at most 128 VGPRs (four
+    wavefronts on a SIMD), the unicycle one in at most 168 (three); read from the built code objects."""
+    from modelcrowdnav_amd import _hip
+    assert os.path.exists(_hip.LIB_PATH)
+    assert os.path.exists(os.path.join(_ROOT, "modelcrowdnav_amd", "csrc", "env_rollout_quad.o")), \
+        "libmcn_hip.so is there but the objects it was linked from are not: rebuild (make -C modelcrowdnav_amd/csrc)"
+    out = subprocess.run([sys.executable, os.path.join(_ROOT, "tools", "kernel_resources.py"), "env_rollout_wg4_kernel<"],
+                         capture_output=True, text=True, check=True).stdout
+    rows = dict((uni, (int(vgpr), int(scratch), int(spill))) for uni, vgpr, scratch, spill in
+                re.findall(r"env_rollout_wg4_kernel<5, 0, (true|false)>.*vgpr\s+(\d+).*scratch\s+(\d+).*vspill (\d+)", out))
+    assert sorted(rows) == ["false", "true"], out
+    assert rows["false"][0] <= 128 and rows["false"][1:] == (0, 0), out
+    assert rows["true"][0] <= 168 and rows["true"][1:] == (0, 0), out
