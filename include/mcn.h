@@ -234,6 +234,14 @@ typedef struct mcn_scenario_cfg {
  * (crowd_sim/envs/crowd_sim.py:94-215): same placement rules and rejection tests, counter-based random numbers
  * keyed by (seed, first_case + i), so case i is the same whatever P or the partition.  The bit-exact generator
  * (numpy MT19937, host) stays in modelcrowdnav_amd/envs/scenarios.py.
+ * Where the reference would draw for ever, this does not: every rejection loop (a circle crossing's start, a square
+ * crossing's start and, independently, its goal) stops after 4096 tries and keeps the draw of try 4096; the stream
+ * goes on from there, and later humans are tested against that draw like against any other.  A dense crowd can
+ * therefore START with humans inside a comfort gap (radius_i + radius_j + discomfort_dist) of the robot or of an
+ * earlier human, i.e. with a discomfort penalty or a collision at step 0: on the shipped circle (radius 4) about 1
+ * case in 17 for 10 randomized humans, 1 in 8 for 20 humans of radius 0.3, every case for 20 randomized humans (rates:
+ * DESIGN.md, "Device scenario generator").  The arrays do not say which cases those are;
+ * VecCrowdSim.unplaced_cases (envs/crowd_sim.py) recomputes it from them.
  */
 int mcn_scenario_pool(const mcn_scenario_cfg *cfg, uint64_t seed, int64_t first_case, int32_t P, int32_t N,
                       double *hpos, double *hgoal, double *hrad, double *hvpref, void *stream);

@@ -198,7 +198,9 @@ class VecCrowdSim(object):
         """`count` scenarios generated ON the device (mcn_scenario_pool): the reference's placement rules with a
         counter-based random stream keyed by (seed, case id) -- statistically equivalent to CrowdSim.reset, not
         bit-identical to it (scenarios.py keeps the bit-exact host generator).  Returns the pool tensors that
-        load_device_scenarios / attach_rollout(pool=...) accept."""
+        load_device_scenarios / attach_rollout(pool=...) accept.  The kernel's rejection loops stop after 4096 tries
+        and keep their last draw, so a dense crowd (from about 10 humans on the shipped circle) can hold humans inside
+        a comfort gap: unplaced_cases(pool, rule) tells which cases those are."""
         N = int(human_num or self.human_num)
         sp, dev = self.spec(), self.device
         rr = sp.robot_row()
@@ -213,6 +215,30 @@ class VecCrowdSim(object):
                                         _hip.ptr(pool["hvpref"]), _hip.stream_ptr(dev))
         _hip.check(rc, "mcn_scenario_pool")
         return pool
+
+    def unplaced_cases(self, pool, rule="circle_crossing"):
+        """Which cases of a device_pool() hold a human that mcn_scenario_pool could not place (bool [P], on the pool's
+        device): one inside the comfort gap radius_i + radius_j + discomfort_dist of the robot or of an EARLIER
+        human, under the checks of the rule that built the pool -- circle crossing: its start against starts and
+        goals; square crossing: its start against starts and the robot's start, its goal against goals and the
+        robot's goal.  (Later humans were placed clear of it.)"""
+        pos, goal, rad = pool["hpos"], pool["hgoal"], pool["hrad"]
+        N, sp = rad.shape[1], self.spec()
+        rr = torch.tensor(sp.robot_row(), dtype=torch.float64, device=pos.device)
+        dist = lambda a, b: (a - b).square().sum(-1).sqrt()
+        gap = rad[:, :, None] + rad[:, None, :] + sp.discomfort_dist
+        rgap = rad + sp.robot_radius + sp.discomfort_dist
+        earlier = torch.ones(N, N, dtype=torch.bool, device=pos.device).tril(-1)         # [h, q]: q < h
+        hit = dist(pos[:, :, None], pos[:, None, :]) < gap
+        if rule == "circle_crossing":
+            hit |= dist(pos[:, :, None], goal[:, None, :]) < gap
+            robot = (dist(pos, rr[[S.PX, S.PY]]) < rgap) | (dist(pos, rr[[S.GX, S.GY]]) < rgap)
+        elif rule == "square_crossing":
+            hit |= dist(goal[:, :, None], goal[:, None, :]) < gap
+            robot = (dist(pos, rr[[S.PX, S.PY]]) < rgap) | (dist(goal, rr[[S.GX, S.GY]]) < rgap)
+        else:
+            raise ValueError("rule %r" % (rule,))
+        return ((hit & earlier).any(-1) | robot).any(-1)
 
     def load_device_scenarios(self, pool, rows):
         """Start every env from pool row rows[e] (device pool of device_pool()); robot at its start pose."""
