@@ -186,6 +186,38 @@ int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const doubl
                     const mcn_env_out *out, const mcn_rollout *roll, int32_t E, int32_t N, void *stream);
 
 /*
+ * mcn_env_rollout_orca -- T consecutive closed-loop steps with an ORCA-driven holonomic robot (the reference's
+ * imitation-learning demonstrator, crowd_nav/train.py:150-160, and `test.py --policy orca`) in ONE launch
+ * (env_step.hip: env_step_loop_orca_kernel), for any batch and any 1 <= N <= MCN_MAX_HUMANS.  Each step equals, bit for
+ * bit, this per-step sequence:
+ *   1  the robot's action, as mcn_orca_batch returns it for the robot as agent 0 with all N humans of its env as
+ *      candidates in index order (hcount is not consulted); every operand float64 -> float32: position, velocity,
+ *      radius float32(rrad + m), max speed float32(rvpref), preferred velocity float32(rgoal - rpos), the humans'
+ *      positions, velocities and radii float32(hrad + m), where m is the float64 sum 0.01 + robot_safety_space; with the
+ *      given neighbor_dist / max_neighbors / time_horizon and float32(cfg->time_step); the float32 result widened to
+ *      float64;
+ *   2  mcn_env_step(cfg, st, that action, NULL, out, roll, E, N, update = 1).
+ * The robot's parameters are its policy's own: they may differ from the humans' cfg->orca_* (imitation learning gives the
+ * robot a safety space, the humans none).  Optional traces, plain device pointers, each of which may be NULL:
+ *   tr_robot     [T][E][5]     robot px, py, vx, vy, theta BEFORE step t (theta 0 without st->rtheta)
+ *   tr_humans    [T][E][N][4]  px, py, vx, vy before step t
+ *   tr_hrad      [T][E][N]     radii before step t (a pool restart changes them)
+ *   tr_action    [T][E][2]     the robot's action of step t
+ *   tr_rec       [T][E]        that step's record
+ *   tr_human_act [T][E][N][2]  the velocities the humans chose in step t
+ * On return `st`, `out->rec`, `out->human_act` and `roll` are as after the T-th per-step call.  MCN_EINVAL before any
+ * launch: NULL cfg / st / out, a missing state array (st->rvpref included), T < 1, N outside 1 .. MCN_MAX_HUMANS,
+ * max_neighbors outside 0 .. MCN_MAX_LINES, time_horizon or time_step (also as float32) not positive, a robot_safety_space
+ * that is not finite, cfg->robot_kinematics other than MCN_KIN_HOLONOMIC, cfg->human_policy other than MCN_HUMANS_ORCA /
+ * MCN_HUMANS_LINEAR, and mcn_rollout's own rules (a `state` without a discount table, ...).
+ */
+int mcn_env_rollout_orca(const mcn_env_cfg *cfg, const mcn_env_state *st, double robot_safety_space,
+                         float neighbor_dist, int32_t max_neighbors, float time_horizon, int32_t T,
+                         const mcn_env_out *out, const mcn_rollout *roll, double *tr_robot, double *tr_humans,
+                         double *tr_hrad, double *tr_action, mcn_step_rec *tr_rec, double *tr_human_act,
+                         int32_t E, int32_t N, void *stream);
+
+/*
  * mcn_env_step_sf / mcn_env_rollout_sf -- mcn_env_step / mcn_env_rollout for social-force pedestrians
  * (cfg->human_policy == MCN_HUMANS_SOCIALFORCE; the reference has no such model, it is defined here).  Circular form of
  * Helbing, Farkas and Vicsek (2000) without body-contact or friction terms.  Human i with position p, velocity v, goal g,

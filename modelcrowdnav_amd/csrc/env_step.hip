@@ -37,6 +37,16 @@ void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispat
 // sqrt); larger ones keep the separate loop: the extra live values push their unrolled solver past 168 VGPRs
 constexpr int kHhPreMaxN = 6;
 
+// The ORCA robot of the closed loop (ROB, below) as agent 0 of its own solve: every human of the env is a candidate, in
+// index order, with the ROBOT policy's margin on the float64 radius (the staged float32 radii carry the humans' margin).
+struct RobotCand {
+    const float4 *sAg; const double *sRad;  // block-level staged humans (float32 state, float64 plain radii)
+    int gbase; double extra;                // tid of human 0 of my env; 0.01 + the robot policy's safety_space
+    __device__ __forceinline__ void fetch(int c, float4 &pv, float &rad) const {
+        pv = sAg[gbase + c]; rad = (float)(sRad[gbase + c] + extra);
+    }
+};
+
 struct GroupCand {
     const float4 *sAg; const float *sRad;   // block-level staged humans
     float4 rob; float rob_rad;              // robot as seen by humans (if visible)
@@ -57,10 +67,15 @@ struct GroupCand {
 // One env step for the workgroup's env slots: everything between the state in HBM before the step and after it.  A
 // device function so that two kernels can share it: env_step_kernel (one step per launch) and env_step_loop_kernel
 // (T steps per launch for the one-wavefront form, below).
-template <int BLOCK, int NT, int VIS, int MODE, int HH_T>
-__device__ __forceinline__ void env_step_body(const StepParams &p)
+// ROB: closed loop (env_step_loop_orca_kernel, run-time N only): the robot's action is not read from p.actions but solved
+// here, by the env's leader lane, as ORCA.predict_batch + mcn_orca_batch would (float32 operands converted where that
+// code converts them, the float32 result widened to float64); `cl` carries the robot policy's parameters and the trace
+// arrays, `t` is the step's row in them.
+template <int BLOCK, int NT, int VIS, int MODE, int HH_T, int ROB = 0>
+__device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedLoop *cl = nullptr, const int t = 0)
 {
-    constexpr bool kStageHumans = (MODE == MCN_HUMANS_ORCA) || (MODE == MCN_HUMANS_SOCIALFORCE) || (HH_T != 0);
+    static_assert(!ROB || NT == 0, "the closed loop runs the run-time-N body");
+    constexpr bool kStageHumans = (MODE == MCN_HUMANS_ORCA) || (MODE == MCN_HUMANS_SOCIALFORCE) || (HH_T != 0) || (ROB != 0);
 #ifdef MCN_DIAG
     if (p.debug_noop) return;      // diagnostic build only: launch-floor measurement
 #endif
@@ -119,7 +134,8 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
         rvel  = reinterpret_cast<const double2 *>(p.st.rvel)[e];
         rgoal = reinterpret_cast<const double2 *>(p.st.rgoal)[e];
         rattr.x = p.st.rrad[e];
-        act   = reinterpret_cast<const double2 *>(p.actions)[e];
+        if constexpr (ROB) rattr.y = p.st.rvpref[e];
+        else               act = reinterpret_cast<const double2 *>(p.actions)[e];
         gtime = p.st.gtime[e];
         if (c.robot_kinematics == MCN_KIN_UNICYCLE) rtheta = p.st.rtheta[e];
         // the rollout record is fetched now, so its latency hides under the ORCA solve instead of forming a
@@ -148,7 +164,7 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
     }
     if (leader) {
         sRobPos[slot] = rpos;
-        sRobAct[slot] = eff;
+        if constexpr (!ROB) sRobAct[slot] = eff;
         sRobRad[slot] = rattr.x;
         if constexpr (MODE == MCN_HUMANS_ORCA) {
             sRobF[slot] = make_float4((float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y);
@@ -156,6 +172,37 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
         }
     }
     __syncthreads();
+
+    if constexpr (ROB) {
+        // ---- K0: the robot's own ORCA solve against the staged humans, then the step's "before" traces ----
+        const size_t row = (size_t)t * (size_t)p.E + (size_t)e;                  // [T][E] index of this env's step
+        if (leader) {
+            const RobotCand rc{sAgF, sRadD, gbase, cl->extra};
+            const LdsLines RL{sL + tid, BLOCK};        // this lane's line slots: its human's solve (K1) reuses them afterwards
+            float rx = 0, ry = 0;
+            orca_solve(rc, N, (float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y, (float)(rattr.x + cl->extra),
+                       (float)rattr.y, (float)(rgoal.x - rpos.x), (float)(rgoal.y - rpos.y),
+                       cl->neighbor_dist, cl->max_neighbors, cl->time_horizon, (float)dt, RL, rx, ry);
+            act = make_double2((double)rx, (double)ry);
+            sRobAct[slot] = act;                       // holonomic: the swept test (K2) takes the action as it is
+            if (cl->tr_robot) {
+                double *d = cl->tr_robot + row * 5;
+                d[0] = rpos.x; d[1] = rpos.y; d[2] = rvel.x; d[3] = rvel.y;
+                d[4] = p.st.rtheta ? p.st.rtheta[e] : 0.0;
+            }
+            if (cl->tr_action) reinterpret_cast<double2 *>(cl->tr_action)[row] = act;
+        }
+        if (active) {
+            const size_t ha = row * (size_t)N + (size_t)h;
+            if (cl->tr_humans) {
+                reinterpret_cast<double2 *>(cl->tr_humans)[2 * ha] = pos;
+                reinterpret_cast<double2 *>(cl->tr_humans)[2 * ha + 1] = vel;
+            }
+            if (cl->tr_hrad) cl->tr_hrad[ha] = attr.x;
+        }
+        // the leader lane's sRobAct crosses to the other lanes of its env in K2
+        __syncthreads();
+    }
 
     // ---- K1: human action ----
     double hax = 0, hay = 0;
@@ -396,9 +443,14 @@ __device__ __forceinline__ void env_step_body(const StepParams &p)
         else if (dmin < c.discomfort_dist)  { rew = (dmin - c.discomfort_dist) * c.discomfort_penalty_factor * dt; dn = 0; inf = MCN_INFO_DANGER; }
         else                                { rew = 0; dn = 0; inf = MCN_INFO_NOTHING; }
         store_step_rec(p.out.rec + e, rew, dmin, dn, inf, hh_sum);   // 16 + 8 bytes
+        if constexpr (ROB)
+            if (cl->tr_rec) store_step_rec(cl->tr_rec + ((size_t)t * (size_t)p.E + (size_t)e), rew, dmin, dn, inf, hh_sum);
     }
     if (active && !deferred && p.out.human_act)
         reinterpret_cast<double2 *>(p.out.human_act)[a] = make_double2(hax, hay);
+    if constexpr (ROB)
+        if (active && cl->tr_human_act)
+            reinterpret_cast<double2 *>(cl->tr_human_act)[(size_t)t * (size_t)p.E * (size_t)N + (size_t)a] = make_double2(hax, hay);
 
     // ---- integrate / look ahead ----
     // (a human whose 3-D LP is parked has no velocity yet: it only tells env_lp3_kernel what to write for it --
@@ -521,6 +573,19 @@ __global__ __launch_bounds__(64) void env_step_loop_sf_kernel(StepParams p, cons
     for (int t = 0; t < T; ++t) {
         p.actions = acts + (size_t)t * (size_t)p.E * 2;
         env_step_body<64, 0, 0, MCN_HUMANS_SOCIALFORCE, HH_T>(p);
+        __syncthreads();                       // the next step restages the LDS tiles this one still reads
+    }
+}
+
+// Closed loop with an ORCA robot (mcn_env_rollout_orca): the run-time-N body T times, the robot's action solved inside it
+// (ROB) instead of read from an action sequence, and the step's traces stored by the lanes that own the values.  The
+// ordering argument is the one above; the robot's action reaches the lanes of its env through the LDS behind a barrier
+// of the body's own.  Every loop is bounded by T or N; nothing waits on a condition.
+template <int MODE>
+__global__ __launch_bounds__(64) void env_step_loop_orca_kernel(const StepParams p, const ClosedLoop cl, const int T)
+{
+    for (int t = 0; t < T; ++t) {
+        env_step_body<64, 0, 0, MODE, 2, 1>(p, &cl, t);
         __syncthreads();                       // the next step restages the LDS tiles this one still reads
     }
 }
@@ -748,6 +813,27 @@ bool launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream)
     if (p.cfg.count_hh) hipLaunchKernelGGL((env_step_loop_sf_kernel<1>), dim3(waves_total), dim3(64), sm, stream, q, T);
     else                hipLaunchKernelGGL((env_step_loop_sf_kernel<0>), dim3(waves_total), dim3(64), sm, stream, q, T);
     return true;
+}
+
+// mcn_env_rollout_orca: one env_step_loop_orca_kernel launch for any batch and any 1 <= N <= MCN_MAX_HUMANS (ORCA or
+// linear humans, holonomic robot: validated by the caller).
+int launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream)
+{
+    StepParams q = p;
+    q.lp3_defer = 0;
+    q.update = 1;
+    q.G = 64 / p.N;
+    // line slots per lane: the larger of what a human's solve and the robot's solve (all N humans as candidates) can fill
+    const int rob_nl = cl.max_neighbors < p.N ? cl.max_neighbors : p.N;
+    q.nl_cap = p.nl_cap > rob_nl ? p.nl_cap : rob_nl;
+    const int waves_total = (p.E + q.G - 1) / q.G;
+    const size_t sm = step_smem_bytes(64, q.nl_cap);
+    note_dispatch("env_step_loop_orca_kernel");
+    if (p.cfg.human_policy == MCN_HUMANS_ORCA)
+        hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_ORCA>), dim3(waves_total), dim3(64), sm, stream, q, cl, T);
+    else
+        hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_LINEAR>), dim3(waves_total), dim3(64), sm, stream, q, cl, T);
+    return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
 }
 
 bool launch_env_step_quad(const StepParams &p, hipStream_t stream);      // env_step_quad.hip

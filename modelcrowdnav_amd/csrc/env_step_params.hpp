@@ -25,4 +25,18 @@ struct StepParams {
     double sf_strength, sf_range, sf_relaxation_rate;
 };
 
+// mcn_env_rollout_orca only (env_step.hip: env_step_loop_orca_kernel): the robot's own ORCA parameters and the per-step
+// trace arrays, each of which may be NULL.  A second kernel argument, so that StepParams stays what the other kernels take.
+struct ClosedLoop {
+    double extra;                      // 0.01 + the robot policy's safety_space: added to a float64 radius before it goes float32
+    float neighbor_dist, time_horizon;
+    int max_neighbors;
+    double *tr_robot;                  // [T][E][5]
+    double *tr_humans;                 // [T][E][N][4]
+    double *tr_hrad;                   // [T][E][N]
+    double *tr_action;                 // [T][E][2]
+    mcn_step_rec *tr_rec;              // [T][E]
+    double *tr_human_act;              // [T][E][N][2]
+};
+
 }  // namespace mcn

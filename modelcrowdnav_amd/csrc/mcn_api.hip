@@ -16,6 +16,7 @@ int launch_env_step(const StepParams &p, hipStream_t stream);
 bool launch_env_rollout_quad(const StepParams &p, int T, hipStream_t stream);
 bool launch_env_step_loop(const StepParams &p, int T, hipStream_t stream);
 bool launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream);
+int launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream);
 int launch_scenario_pool(const mcn_scenario_cfg &c, uint64_t seed, int64_t first_case, int P, int N, double *hpos,
                          double *hgoal, double *hrad, double *hvpref, hipStream_t stream);
 struct SarlParams;
@@ -174,9 +175,9 @@ int64_t mcn_sizeof(int32_t which)
 // their social-force twins: `social_force` says which family the caller is, and the cfg's policy must belong to it.
 static int fill_step_params(mcn::StepParams &p, const mcn_env_cfg *cfg, const mcn_env_state *st, const double *actions,
                             const double *given_v, const mcn_env_out *out, const mcn_rollout *roll,
-                            int32_t E, int32_t N, int32_t update, bool social_force = false)
+                            int32_t E, int32_t N, int32_t update, bool social_force = false, bool needs_actions = true)
 {
-    if (!cfg || !st || !out || !actions) return MCN_EINVAL;
+    if (!cfg || !st || !out || (needs_actions && !actions)) return MCN_EINVAL;
     if (E <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
     if (!st->hpos || !st->hvel || !st->hgoal || !st->hrad || !st->hvpref || !st->rpos || !st->rvel || !st->rgoal ||
         !st->rrad || !st->gtime) return MCN_EINVAL;
@@ -323,6 +324,31 @@ int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const doubl
         if (r != MCN_OK) return r;
     }
     return MCN_OK;
+}
+
+int mcn_env_rollout_orca(const mcn_env_cfg *cfg, const mcn_env_state *st, double robot_safety_space,
+                         float neighbor_dist, int32_t max_neighbors, float time_horizon, int32_t T,
+                         const mcn_env_out *out, const mcn_rollout *roll, double *tr_robot, double *tr_humans,
+                         double *tr_hrad, double *tr_action, mcn_step_rec *tr_rec, double *tr_human_act,
+                         int32_t E, int32_t N, void *stream)
+{
+    if (!cfg || !st || !out || T < 1) return MCN_EINVAL;
+    if (max_neighbors < 0 || max_neighbors > MCN_MAX_LINES) return MCN_EINVAL;
+    if (!(time_horizon > 0) || !(cfg->time_step > 0) || !((float)cfg->time_step > 0)) return MCN_EINVAL;
+    if (!isfinite(robot_safety_space)) return MCN_EINVAL;
+    if (cfg->robot_kinematics != MCN_KIN_HOLONOMIC) return MCN_EINVAL;          // the ORCA robot is holonomic
+    if (cfg->human_policy != MCN_HUMANS_ORCA && cfg->human_policy != MCN_HUMANS_LINEAR) return MCN_EINVAL;
+    if (!st->rvpref) return MCN_EINVAL;                                         // the robot's max speed
+    mcn::StepParams p;
+    const int rc = fill_step_params(p, cfg, st, nullptr, nullptr, out, roll, E, N, 1, false, false);
+    if (rc != MCN_OK) return rc;
+    mcn::ClosedLoop cl;
+    memset(&cl, 0, sizeof(cl));
+    cl.extra = 0.01 + robot_safety_space;       // ORCA.predict_batch adds this sum, not its two terms, to the radii
+    cl.neighbor_dist = neighbor_dist; cl.time_horizon = time_horizon; cl.max_neighbors = max_neighbors;
+    cl.tr_robot = tr_robot; cl.tr_humans = tr_humans; cl.tr_hrad = tr_hrad; cl.tr_action = tr_action;
+    cl.tr_rec = tr_rec; cl.tr_human_act = tr_human_act;
+    return mcn::launch_env_step_loop_orca(p, cl, T, (hipStream_t)stream);
 }
 
 // the model's parameters (include/mcn.h): A >= 0, B > 0, k >= 0, all finite

@@ -60,6 +60,39 @@ def value_targets(states, rewards, dones, infos, imitation_learning, gamma_bar, 
     return flat_states[idx], flat_values[idx].float()
 
 
+def trace_env_view(tr, rrad, rgoal, rvpref):
+    """The [T, E] states of a closed-loop trace (VecCrowdSim.rollout_orca) as ONE batch of T * E envs: an object with
+    the attributes a policy's `transform_batch` reads from a VecCrowdSim.  rrad / rgoal / rvpref ([E] / [E,2] / [E]) are
+    the robot fields no step changes (a pool restart puts the robot back at the same goal)."""
+    from types import SimpleNamespace
+    T, E, N = tr["hrad"].shape
+    rob, hum = tr["robot"].reshape(T * E, 5), tr["humans"].reshape(T * E, N, 4)
+    const = lambda x: x.unsqueeze(0).expand(T, *x.shape).reshape(T * E, *x.shape[1:])
+    return SimpleNamespace(num_envs=T * E, _alloc_N=N, device=tr["hrad"].device, rpos=rob[:, 0:2], rvel=rob[:, 2:4],
+                           rtheta=rob[:, 4], rrad=const(rrad), rgoal=const(rgoal), rvpref=const(rvpref),
+                           hpos=hum[:, :, 0:2], hvel=hum[:, :, 2:4], hrad=tr["hrad"].reshape(T * E, N))
+
+
+def trace_state_rows(transformer, tr, rrad, rgoal, rvpref):
+    """`transformer.transform_batch` once over the T * E states of a trace: [T,E,...] rows, equal bit for bit to T
+    per-step calls because every torch op in it is element-wise (see rows_from_trace_ok)."""
+    T, E = tr["hrad"].shape[:2]
+    rows = transformer.transform_batch(trace_env_view(tr, rrad, rgoal, rvpref))
+    return rows.view(T, E, *rows.shape[1:])
+
+
+def rows_from_trace_ok(transformer, env):
+    """Whether `transformer.transform_batch` needs nothing but the traced tensors and the constant robot fields: the
+    plain rotated joint states of CADRL / MultiHumanRL (SARL).  Occupancy maps (a kernel on the env's own state struct),
+    LSTM-RL's device-side human order and an env that keeps an `hcount` stay on the per-step loop."""
+    from .policy.cadrl import CADRL
+    from .policy.multi_human_rl import MultiHumanRL
+    fn = getattr(type(transformer), "transform_batch", None)
+    if fn is not CADRL.transform_batch and fn is not MultiHumanRL.transform_batch:
+        return False
+    return not getattr(transformer, "with_om", False) and getattr(env, "hcount", None) is None
+
+
 class VecExplorer(object):
     def __init__(self, env, robot, device=None, gamma=0.9, policy=None, memory=None, target_policy=None):
         self.env, self.robot, self.gamma = env, robot, gamma
@@ -116,6 +149,23 @@ class VecExplorer(object):
                     for fr in frames:
                         fh.write("%s\t%s\t%s\t%s\n" % (fr[0], fr[1], fr[2], fr[3]))
 
+    def _closed_loop_ok(self, transformer, action_fn, action_seq, stay):
+        """The automatic rule of run_k_episodes(closed_loop=None): an ORCA robot policy (holonomic) choosing every
+        action, on a VecCrowdSim whose step is the plain mcn_env_step with ORCA or linear humans, and -- when memory rows are
+        wanted -- a transformer whose rows can be made from the trace."""
+        from .envs.crowd_sim import VecCrowdSim
+        from .envs.policy.orca import ORCA
+        env = self.env
+        if not isinstance(self.policy, ORCA) or action_fn is not None or action_seq is not None or stay:
+            return False
+        if type(self.policy).predict_batch is not ORCA.predict_batch:
+            return False
+        if type(env).step is not VecCrowdSim.step or env.human_policy_name not in ("orca", "linear"):
+            return False
+        if getattr(env.robot, "kinematics", "holonomic") == "unicycle":
+            return False
+        return transformer is None or rows_from_trace_ok(transformer, env)
+
     def _actions(self, step_actions):
         if step_actions is not None:
             return step_actions
@@ -125,7 +175,7 @@ class VecExplorer(object):
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None,
                        print_failure=False, returnRate=True, returnNav=False, action_fn=None, max_steps=None,
                        total_envs=None, action_seq=None, device_scenarios=None, stay=False, update_raw_ob=False,
-                       cacheFile=None, test_case=None):
+                       cacheFile=None, test_case=None, closed_loop=None):
         """Returns what Explorer.run_k_episodes returns (explorer.py:146-151):
         (avg cumulative reward, success rate, collision rate, timeout rate[, avg nav time])
         or counts instead of rates when returnRate is False.  `action_fn(env, t) -> [E,2]` overrides the
@@ -139,7 +189,11 @@ class VecExplorer(object):
         `self.raw_memory` set every step pushes `(ob, reward, done, info)` (ob = [N,5] array of the humans after the
         step, info = code) in episode order; `update_raw_ob` pushes world-model pairs into `self.rawob`; `cacheFile`
         (a directory) gets one SGAN text file per episode.
-        `test_case` plays that one case k times (explorer.py:54 hands it to every reset; the counter ends one past it)."""
+        `test_case` plays that one case k times (explorer.py:54 hands it to every reset; the counter ends one past it).
+        `closed_loop`: None = automatic -- with an ORCA robot policy (the imitation-learning demonstrator, `--policy orca`)
+        and no action_fn / action_seq / stay, the robot's solve and the env step run up to 128 steps per launch
+        (VecCrowdSim.rollout_orca); memory rows and collected rows then come from that launch's trace, and every result
+        equals the per-step loop's.  False forces the per-step loop; True raises where the closed loop does not apply."""
         env = self.env
         rank, ws = mdist.world()
         E_local = env.num_envs
@@ -213,6 +267,36 @@ class VecExplorer(object):
             keep_export, env.export_human_actions = env.export_human_actions, True
             col_cur, col_ob, col_r, col_d, col_i, col_m = [], [], [], [], [], []
         t = 0
+        use_loop = self._closed_loop_ok(transformer, action_fn, action_seq, stay) if closed_loop is None else bool(closed_loop)
+        if use_loop and not self._closed_loop_ok(transformer, action_fn, action_seq, stay):
+            raise ValueError("closed_loop=True needs an ORCA robot policy choosing every action, ORCA humans, a holonomic "
+                             "robot and memory rows that can be made from the trace")
+        self.last_run_closed_loop = use_loop
+        traces = []
+        if use_loop:
+            want_trace = update_memory or collect
+            while t < limit:
+                n = min(128, limit - t)                      # the chunk rule of the action_seq path below
+                tr = env.rollout_orca(self.policy, n, trace=want_trace)
+                if collect:
+                    tr["hrad_after"] = torch.cat([tr["hrad"][1:], env.hrad.unsqueeze(0)])      # radii after each step
+                if want_trace:
+                    traces.append(tr)
+                t += n
+                if int(bufs["fin_count"].min().item()) >= rounds:
+                    break
+            limit = t                                            # skip the per-step loop below
+            if traces:
+                tr = {k: torch.cat([c[k] for c in traces]) for k in traces[0]}
+                if update_memory:
+                    rec_s = trace_state_rows(transformer, tr, env.rrad, env.rgoal, env.rvpref)
+                    rec_r, rec_d, rec_i = tr["reward"], tr["done"].bool(), tr["info"]
+                if collect:
+                    # the arithmetic of the per-step loop below, over the whole trace at once
+                    col_cur = tr["humans"]
+                    col_ob = torch.cat([tr["humans"][..., 0:2] + tr["human_act"] * env.time_step, tr["human_act"],
+                                        tr["hrad_after"].unsqueeze(3)], 3)
+                    col_r, col_d, col_i, col_m = tr["reward"], tr["done"].bool(), tr["info"], tr["dmin"]
         if action_seq is not None:
             if update_memory:
                 raise ValueError("action_seq rollouts record no per-step states; use action_fn with update_memory")
@@ -251,12 +335,13 @@ class VecExplorer(object):
             raise RuntimeError("rollout did not finish %d episodes per env within %d steps" % (rounds, limit))
         if update_memory:
             # only the first `rounds` episodes of each env are the k requested ones: cut each env's trace there
-            dones = torch.stack(rec_d)
+            stacked = lambda x: x if torch.is_tensor(x) else torch.stack(x)      # (the closed loop hands whole traces)
+            dones = stacked(rec_d)
             order = torch.cumsum(dones.long(), 0) - dones.long()          # episode number each step belongs to
             valid = order < rounds
             gidx = (order * E_total + lo + torch.arange(E_local, device=dones.device).unsqueeze(0))
             valid &= gidx < k
-            s, v, idx = self._value_targets(torch.stack(rec_s), torch.stack(rec_r), dones & valid, torch.stack(rec_i),
+            s, v, idx = self._value_targets(stacked(rec_s), stacked(rec_r), dones & valid, stacked(rec_i),
                                             imitation_learning)
             # the reference pushes episode by episode (explorer.py:107-110): rows go to the memory in global episode
             # order (episode g = round * E_total + env), time order inside an episode -- a stable sort of the
@@ -271,10 +356,9 @@ class VecExplorer(object):
                     self.memory.push((row_s, row_v.reshape(1).to(self.device)))
         if collect:
             env.export_human_actions = keep_export
-            self._emit_collected(torch.stack(col_cur).cpu().numpy(), torch.stack(col_ob).cpu().numpy(),
-                                 torch.stack(col_r).cpu().numpy(), torch.stack(col_d).cpu().numpy(),
-                                 torch.stack(col_i).cpu().numpy(), torch.stack(col_m).cpu().numpy(), k, rounds, E_total,
-                                 update_raw_ob, cacheFile)
+            host = lambda x: (x if torch.is_tensor(x) else torch.stack(x)).cpu().numpy()
+            self._emit_collected(host(col_cur), host(col_ob), host(col_r), host(col_d), host(col_i), host(col_m), k,
+                                 rounds, E_total, update_raw_ob, cacheFile)
         env.case_counter[phase] = (first + k) % size if test_case is None else (test_case + 1) % size
         # records in global episode order: episode g = r * E_total + global_env
         # (the envs' "too close" counters ride in the same collective, in the rows of their first episode)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """GPU box: per-step cost of the batched Explorer with a SARL robot (BASELINE config 3's shape), with and without the
-training-time bookkeeping (update_memory: the rotated joint state of every step is stored, value targets at the end)."""
+training-time bookkeeping (update_memory: the rotated joint state of every step is stored, value targets at the end);
+`dropin`: the drop-in Explorer; `il`: imitation learning's data run, per-step loop against the closed loop."""
 import os
 import sys
 import time
@@ -79,8 +80,42 @@ def dropin():
     print("  returned (sequential, first %d cases):" % ks, out_s)
 
 
+def il(k=3000, E=1024, N=5, reps=5):
+    """Imitation learning's data run (train.py:150-160): run_k_episodes(3000, 'train', update_memory=True,
+    imitation_learning=True) with the ORCA demonstrator (safety_space 0.15) and a SARL target policy, the per-step loop
+    (closed_loop=False) against the automatic closed loop, alternated; wall time of the whole call, min / median / max."""
+    from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
+    dev = torch.device("cuda", 0)
+    env, _ = bench.build_env(E, N, 0, dev)
+    env.detach_rollout()
+    orca = policy_factory["orca"]()
+    orca.multiagent_training, orca.safety_space = True, 0.15
+    env.robot.set_policy(orca)
+    sarl = bench._sarl_policy(dev, env.time_step)
+    times = {False: [], None: []}
+    for rep in range(reps + 1):                      # the first repeat warms up
+        for mode in (False, None):
+            ex = VecExplorer(env, env.robot, gamma=0.9, policy=orca, memory=ReplayMemory(2000000, device=dev),
+                             target_policy=sarl)
+            env.case_counter["train"] = 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = ex.run_k_episodes(k, "train", update_memory=True, imitation_learning=True, closed_loop=mode)
+            torch.cuda.synchronize()
+            if rep:
+                times[mode].append(time.perf_counter() - t0)
+            assert ex.last_run_closed_loop == (mode is None)
+    for mode, name in ((False, "per-step loop"), (None, "closed loop (automatic)")):
+        v = sorted(times[mode])
+        print("run_k_episodes(%d, 'train', IL) on %d envs x %d humans, %-24s min %.3f  median %.3f  max %.3f s" % (
+            k, E, N, name, v[0], v[len(v) // 2], v[-1]))
+    print("  returned:", out)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "dropin":
         dropin()
+    elif len(sys.argv) > 1 and sys.argv[1] == "il":
+        il()
     else:
         main()

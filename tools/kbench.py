@@ -105,7 +105,15 @@ def main():
                     help="time VecCrowdSim.get_human_times (one mcn_orca_finish launch) at --sizes x --humans against one "
                          "mcn_orca_batch launch + torch update per simulated step, and the E = 1 CrowdSim method against "
                          "its former host loop")
+    ap.add_argument("--closed-loop", action="store_true",
+                    help="time one 128-step mcn_env_rollout_orca launch (with and without traces) at --sizes x --humans "
+                         "against 128 x (ORCA.predict_batch + env.step) and against the per-step Explorer loop body")
     a = ap.parse_args()
+    if a.closed_loop:
+        for N in [int(x) for x in str(a.humans).split(",")]:
+            for E in [int(x) for x in a.sizes.split(",")]:
+                closed_loop_bench(E, N)
+        return
     if a.finish:
         for N in [int(x) for x in str(a.humans).split(",")]:
             for E in [int(x) for x in a.sizes.split(",")]:
@@ -186,6 +194,49 @@ def main():
         del env
 
 
+
+
+def closed_loop_bench(E, N, T=128, reps=5):
+    """us per simulated step of the closed loop with an ORCA robot (safety_space 0.15, the imitation-learning
+    demonstrator): one T-step mcn_env_rollout_orca launch without / with traces, T x (predict_batch + step), and the
+    per-step loop body of VecExplorer.run_k_episodes(update_memory=True, imitation_learning=True) with a SARL target
+    policy.  The four forms alternate inside every repeat; min / median / max over the repeats."""
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
+    from modelcrowdnav_amd.policy.sarl import SARL
+    dev = torch.device("cuda", 0)
+    env, _ = bench.build_env(E, N, 0, dev)
+    pol = policy_factory["orca"]()
+    pol.multiagent_training, pol.safety_space = True, 0.15
+    env.robot.set_policy(pol)
+    sarl = SARL(); sarl.configure(configs.policy_config()); sarl.kinematics = "holonomic"; sarl.set_device(dev)
+
+    def per_step():
+        for _ in range(T):
+            a, _ = pol.predict_batch(env)
+            env.step(a)
+
+    def explorer_body():
+        rows = []
+        for _ in range(T):
+            rows.append(sarl.transform_batch(env))
+            a, _ = pol.predict_batch(env)
+            env.step(a)
+            rows.append((env.reward.clone(), env.done.bool(), env.info.clone()))
+
+    forms = [("closed loop", lambda: env.rollout_orca(pol, T)), ("closed loop + traces", lambda: env.rollout_orca(pol, T, trace=True)),
+             ("per step", per_step), ("explorer loop body", explorer_body)]
+    times = {k: [] for k, _ in forms}
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rep in range(reps + 1):                       # the first repeat warms up
+        for name, fn in forms:
+            torch.cuda.synchronize()
+            s.record(); fn(); e.record(); torch.cuda.synchronize()
+            if rep:
+                times[name].append(s.elapsed_time(e) * 1e3 / T)
+    for name, _ in forms:
+        v = sorted(times[name])
+        print("N=%d E=%6d T=%d %-22s min %8.2f  median %8.2f  max %8.2f us/step" % (N, E, T, name, v[0], v[len(v) // 2], v[-1]))
 
 
 def rollout_bench(a):
