@@ -192,10 +192,10 @@ int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const doubl
  * bit, this per-step sequence:
  *   1  the robot's action, as mcn_orca_batch returns it for the robot as agent 0 with all N humans of its env as
  *      candidates in index order (hcount is not consulted); every operand float64 -> float32: position, velocity,
- *      radius float32(rrad + m), max speed float32(rvpref), preferred velocity float32(rgoal - rpos), the humans'
- *      positions, velocities and radii float32(hrad + m), where m is the float64 sum 0.01 + robot_safety_space; with the
- *      given neighbor_dist / max_neighbors / time_horizon and float32(cfg->time_step); the float32 result widened to
- *      float64;
+ *      radius float32((rrad + 0.01) + robot_safety_space), max speed float32(rvpref), preferred velocity
+ *      float32(rgoal - rpos), the humans' positions, velocities and radii float32((hrad + 0.01) + robot_safety_space) --
+ *      two float64 additions in the reference's order (crowd_sim/envs/policy/orca.py:100,103); with the given
+ *      neighbor_dist / max_neighbors / time_horizon and float32(cfg->time_step); the float32 result widened to float64;
  *   2  mcn_env_step(cfg, st, that action, NULL, out, roll, E, N, update = 1).
  * The robot's parameters are its policy's own: they may differ from the humans' cfg->orca_* (imitation learning gives the
  * robot a safety space, the humans none).  Optional traces, plain device pointers, each of which may be NULL:

@@ -41,9 +41,9 @@ constexpr int kHhPreMaxN = 6;
 // index order, with the ROBOT policy's margin on the float64 radius (the staged float32 radii carry the humans' margin).
 struct RobotCand {
     const float4 *sAg; const double *sRad;  // block-level staged humans (float32 state, float64 plain radii)
-    int gbase; double extra;                // tid of human 0 of my env; 0.01 + the robot policy's safety_space
+    int gbase; double safety;               // tid of human 0 of my env; the robot policy's safety_space
     __device__ __forceinline__ void fetch(int c, float4 &pv, float &rad) const {
-        pv = sAg[gbase + c]; rad = (float)(sRad[gbase + c] + extra);
+        pv = sAg[gbase + c]; rad = (float)(sRad[gbase + c] + 0.01 + safety);      // (r + 0.01) + s, orca.py:103
     }
 };
 
@@ -177,10 +177,10 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
         // ---- K0: the robot's own ORCA solve against the staged humans, then the step's "before" traces ----
         const size_t row = (size_t)t * (size_t)p.E + (size_t)e;                  // [T][E] index of this env's step
         if (leader) {
-            const RobotCand rc{sAgF, sRadD, gbase, cl->extra};
+            const RobotCand rc{sAgF, sRadD, gbase, cl->safety_space};
             const LdsLines RL{sL + tid, BLOCK};        // this lane's line slots: its human's solve (K1) reuses them afterwards
             float rx = 0, ry = 0;
-            orca_solve(rc, N, (float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y, (float)(rattr.x + cl->extra),
+            orca_solve(rc, N, (float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y, (float)(rattr.x + 0.01 + cl->safety_space),
                        (float)rattr.y, (float)(rgoal.x - rpos.x), (float)(rgoal.y - rpos.y),
                        cl->neighbor_dist, cl->max_neighbors, cl->time_horizon, (float)dt, RL, rx, ry);
             act = make_double2((double)rx, (double)ry);

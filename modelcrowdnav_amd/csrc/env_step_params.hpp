@@ -28,7 +28,7 @@ struct StepParams {
 // mcn_env_rollout_orca only (env_step.hip: env_step_loop_orca_kernel): the robot's own ORCA parameters and the per-step
 // trace arrays, each of which may be NULL.  A second kernel argument, so that StepParams stays what the other kernels take.
 struct ClosedLoop {
-    double extra;                      // 0.01 + the robot policy's safety_space: added to a float64 radius before it goes float32
+    double safety_space;               // the robot policy's: a radius goes float32 as (radius + 0.01) + safety_space (orca.py:100,103)
     float neighbor_dist, time_horizon;
     int max_neighbors;
     double *tr_robot;                  // [T][E][5]

@@ -344,7 +344,7 @@ int mcn_env_rollout_orca(const mcn_env_cfg *cfg, const mcn_env_state *st, double
     if (rc != MCN_OK) return rc;
     mcn::ClosedLoop cl;
     memset(&cl, 0, sizeof(cl));
-    cl.extra = 0.01 + robot_safety_space;       // ORCA.predict_batch adds this sum, not its two terms, to the radii
+    cl.safety_space = robot_safety_space;       // added after the 0.01, in the reference's order (orca.py:100,103)
     cl.neighbor_dist = neighbor_dist; cl.time_horizon = time_horizon; cl.max_neighbors = max_neighbors;
     cl.tr_robot = tr_robot; cl.tr_humans = tr_humans; cl.tr_hrad = tr_hrad; cl.tr_action = tr_action;
     cl.tr_rec = tr_rec; cl.tr_human_act = tr_human_act;

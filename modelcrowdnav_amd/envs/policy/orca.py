@@ -70,10 +70,10 @@ class ORCA(Policy):
         from ... import _hip
         E, N, dev = env.num_envs, env._alloc_N, env.device
         f = torch.float32
-        extra = 0.01 + float(self.safety_space)
-        me = torch.cat([env.rpos.to(f), env.rvel.to(f), (env.rrad + extra).to(f).unsqueeze(1),
+        s = float(self.safety_space)         # (radius + 0.01) + safety_space, the reference's order (orca.py:100,103)
+        me = torch.cat([env.rpos.to(f), env.rvel.to(f), (env.rrad + 0.01 + s).to(f).unsqueeze(1),
                         env.rvpref.to(f).unsqueeze(1), (env.rgoal - env.rpos).to(f)], 1).contiguous()      # [E,8]
-        oth = torch.cat([env.hpos.to(f), env.hvel.to(f), (env.hrad + extra).to(f).unsqueeze(2)], 2).contiguous()
+        oth = torch.cat([env.hpos.to(f), env.hvel.to(f), (env.hrad + 0.01 + s).to(f).unsqueeze(2)], 2).contiguous()
         n = torch.full((E,), N, dtype=torch.int32, device=dev)
         out = torch.empty(E, 2, dtype=f, device=dev)
         _hip.check(_hip.lib.mcn_orca_batch(_hip.ptr(me), _hip.ptr(oth), _hip.ptr(n), _hip.ptr(out), E, N,
