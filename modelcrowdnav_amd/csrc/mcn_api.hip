@@ -61,8 +61,8 @@ int launch_orca_finish(const mcn_env_state &st, float *sim_vel, const uint8_t *s
                        float *traj, double time_step, float neighbor_dist, int max_neighbors, float time_horizon,
                        int E, int N, hipStream_t stream);
 #ifdef MCN_DIAG
-int read_stamps(void *dst, size_t bytes);
-int read_counts(void *dst, size_t bytes, int reset);
+int read_stamps(void *dst, size_t bytes, int form);
+int read_counts(void *dst, size_t bytes, int reset, int form);
 #endif
 }  // namespace mcn
 
@@ -677,9 +677,9 @@ int mcn_debug_pool_clock(void *dst_host, int64_t bytes) { return mcn::read_pool_
 // diagnostic build only: [resident wavefront][16] shader cycles per phase of sarl_value_kernel (tools/sarl_phases.py)
 int mcn_debug_sarl_phases(void *dst_host, int64_t bytes, int32_t reset) { return mcn::read_sarl_phases(dst_host, (size_t)bytes, reset); }
 // diagnostic build only: copies the rollout kernel's time stamps to host memory, returns the number of 8-byte words
-int mcn_debug_stamps(void *dst_host, int64_t bytes) { return mcn::read_stamps(dst_host, (size_t)bytes); }
+int mcn_debug_stamps(void *dst_host, int64_t bytes) { return mcn::read_stamps(dst_host, (size_t)bytes, g_last_rollout_form); }
 // per-wavefront counts of the data-dependent paths taken: [wave][4] = 3-D LP, restarts, overlap sqrt, goal sqrt
-int mcn_debug_counts(void *dst_host, int64_t bytes, int reset) { return mcn::read_counts(dst_host, (size_t)bytes, reset); }
+int mcn_debug_counts(void *dst_host, int64_t bytes, int reset) { return mcn::read_counts(dst_host, (size_t)bytes, reset, g_last_rollout_form); }
 #endif
 
 }  // extern "C"

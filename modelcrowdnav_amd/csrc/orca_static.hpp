@@ -68,12 +68,13 @@ __device__ __forceinline__ float4 orca_line_merged(float px, float py, float vx,
 // Every operation is odd-symmetric under swapping the two agents (relative position and velocity change sign, the
 // radius sum does not), so the pair's other half-plane is exactly (-u, -dir): env_step.hip builds each pair once.
 // `used`: lanes whose half-plane is consumed (an empty candidate slot's operands must not force the IEEE path).
-__device__ __forceinline__ float4 orca_u_dir(float px, float py, float vx, float vy, float radius, float4 o,
-                                             float orad, float inv_th, float inv_ts, bool used = true)
+//
+// orca_u_dir_rel is the block itself, on a relative position (rpx, rpy) = o - p and its squared length the caller holds
+// already (quad_orca_core ranks its candidates by that very number); orca_u_dir computes the two first.
+__device__ __forceinline__ float4 orca_u_dir_rel(float rpx, float rpy, float dist_sq, float vx, float vy, float radius,
+                                                 float4 o, float orad, float inv_th, float inv_ts, bool used = true)
 {
-    const float rpx = o.x - px, rpy = o.y - py;
     const float rvx = vx - o.z, rvy = vy - o.w;
-    const float dist_sq = dot2(rpx, rpy, rpx, rpy);
     const float cr = radius + orad;
     const float cr_sq = cr * cr;
     const bool apart = dist_sq > cr_sq;
@@ -118,6 +119,13 @@ __device__ __forceinline__ float4 orca_u_dir(float px, float py, float vx, float
     const float dx = circle ? uwy : gx, dy = circle ? -uwx : gy;
     const float ux = circle ? cux : lux, uy = circle ? cuy : luy;
     return make_float4(ux, uy, dx, dy);
+}
+
+__device__ __forceinline__ float4 orca_u_dir(float px, float py, float vx, float vy, float radius, float4 o,
+                                             float orad, float inv_th, float inv_ts, bool used = true)
+{
+    const float rpx = o.x - px, rpy = o.y - py;
+    return orca_u_dir_rel(rpx, rpy, dot2(rpx, rpy, rpx, rpy), vx, vy, radius, o, orad, inv_th, inv_ts, used);
 }
 
 __device__ __forceinline__ float4 orca_line_select(float px, float py, float vx, float vy, float radius, float4 o,

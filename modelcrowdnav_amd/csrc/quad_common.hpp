@@ -43,9 +43,28 @@ __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
     return i >= 2 ? b : a;
 }
 
+// How quad_orca_core shares a quad's sorted half-planes, chosen at compile time.
+//   QuadDpp    ds_permute to the rank's lane, then 16 DPP broadcasts: no LDS memory.  Every caller but the
+//              four-wavefront rollout form.
+//   QuadTable  through a table of 64 float4 slots in LDS that belongs to this wavefront alone: lane l writes its line to
+//              slot (l & ~3) | rank and reads its quad's four slots and its own, five 16-byte reads for the 16 DPP
+//              moves and four ds_permutes.  A quad touches only its own four slots, so idle quads disturb nobody.  The
+//              wavefront's LDS operations execute in order; a wavefront-scope release / acquire pair around a wave
+//              barrier keeps the compiler from moving a read above the writes, and a step's write follows the previous
+//              step's reads in program order: no s_barrier.  The 3-D LP reads its run-time line from the table too.
+//              This path also takes the step's small savings that would change the other callers' code (`slim`): one
+//              squared distance for rank and half-plane, the 1-D LP's clamp as two selects.
+struct QuadDpp {
+    static constexpr bool table = false, slim = false;
+};
+struct QuadTable {
+    static constexpr bool table = true, slim = true;
+    float4 *tab;                                                 // this wavefront's 64 slots
+};
+
 // linearProgram1 on line `no` (run-time, 0..3) against lines [0, no): uniform code, predicated steps.  `ln` is line
 // `no` itself (L[no]), handed over by the caller, who holds it without a run-time select (lane k's own sorted line).
-template <bool DIR>
+template <bool DIR, bool SELECT_CLAMP = false>
 __device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], const float4 &ln, int no, float radius, float optx, float opty,
                                        float &rx, float &ry)
 {
@@ -76,7 +95,14 @@ __device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], const float4 &ln, i
         t = (dot2(optx, opty, ln.z, ln.w) > 0.0f) ? tr : tl;
     } else {
         t = dot2(ln.z, ln.w, optx - ln.x, opty - ln.y);
-        if (t < tl) t = tl; else if (t > tr) t = tr;
+        if (SELECT_CLAMP) {
+            // the same two comparisons as selects (a NaN t, tl or tr answers both with false, as below): the branchy
+            // form compiles to two nested exec-mask regions
+            const float hi = (t > tr) ? tr : t;
+            t = (t < tl) ? tl : hi;
+        } else {
+            if (t < tl) t = tl; else if (t > tr) t = tr;
+        }
     }
     rx = ln.x + t * ln.z;
     ry = ln.y + t * ln.w;
@@ -187,8 +213,10 @@ __device__ __forceinline__ float4 quad_orca_position_pack(double2 pos, double2 g
     return make_float4((float)pos.x, (float)pos.y, (float)(goal.x - pos.x), (float)(goal.y - pos.y));
 }
 
+template <class Path = QuadDpp>
 __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, int k, bool cand_valid, float4 A, float4 B,
-                                               float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry);
+                                               float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry,
+                                               Path path = Path());
 
 __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lane, int k, bool cand_valid,
                                                    double2 pos, double2 vel, double2 goal, double rad, double vpref,
@@ -200,13 +228,17 @@ __device__ __forceinline__ void quad_orca_velocity(const mcn_env_cfg &c, int lan
     quad_orca_core(c, lane, k, cand_valid, A, B, o, orad, inv_th, inv_ts, rx, ry);
 }
 
+template <class Path>
 __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, int k, bool cand_valid, float4 A, float4 B,
-                                               float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry)
+                                               float4 o, float orad, float inv_th, float inv_ts, float &rx, float &ry,
+                                               Path path)
 {
     const float fpx = A.x, fpy = A.y, fvx = A.z, fvy = A.w;
     const float prefx = B.x, prefy = B.y, frad = B.z, ms = B.w;
     const float range_sq = c.orca_neighbor_dist * c.orca_neighbor_dist;
-    const float ddx = fpx - o.x, ddy = fpy - o.y;
+    // squared distance to the candidate.  Slim path: from o - p, which the half-plane construction needs anyway and takes
+    // together with this square; p - o is its exact negation, so the squares and their sum are the same bits
+    const float ddx = Path::slim ? o.x - fpx : fpx - o.x, ddy = Path::slim ? o.y - fpy : fpy - o.y;
     const float d = dot2(ddx, ddy, ddx, ddy);
     const bool in = cand_valid && (d < range_sq);
     // stable ascending order among the in-range candidates (RVO2 insertAgentNeighbor); the rest fill the remaining
@@ -220,16 +252,32 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     // in-range candidates of the quad: the quad's four bits of one ballot
     const int nin = __builtin_popcount((unsigned)(__builtin_amdgcn_ballot_w64(in) >> (lane & ~3)) & 0xfu);
     const int nl = nin < c.orca_max_neighbors ? nin : c.orca_max_neighbors;
-    const float4 mine = orca_line_select(fpx, fpy, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
+    float4 mine;
+    if constexpr (Path::slim) {
+        const float4 ud = orca_u_dir_rel(ddx, ddy, d, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
+        mine = make_float4(fvx + 0.5f * ud.x, fvy + 0.5f * ud.y, ud.z, ud.w);          // as orca_line_select
+    } else {
+        mine = orca_line_select(fpx, fpy, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
+    }
     // route my half-plane to lane `rank` of the quad, then share all four
-    const int dst = ((lane & ~3) | rank) << 2;
-    float4 srt;
-    srt.x = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.x)));
-    srt.y = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.y)));
-    srt.z = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.z)));
-    srt.w = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.w)));
+    float4 srt, L[4];
+    if constexpr (Path::table) {
+        path.tab[(lane & ~3) | rank] = mine;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const float4 *quad = path.tab + (lane & ~3);
+        L[0] = quad[0]; L[1] = quad[1]; L[2] = quad[2]; L[3] = quad[3];
+        srt = path.tab[lane];
+    } else {
+        const int dst = ((lane & ~3) | rank) << 2;
+        srt.x = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.x)));
+        srt.y = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.y)));
+        srt.z = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.z)));
+        srt.w = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.w)));
+    }
     // the starting point of the take steps, the clipped preferred velocity, first: it depends on no half-plane, so it
-    // is computed while the ds_permutes are in flight
+    // is computed while the ds_permutes (the table's reads) are in flight
     {
         const float pp = dot2(prefx, prefy, prefx, prefy);
         const bool clip = pp > ms * ms;
@@ -237,13 +285,15 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
         rx = clip ? ms * (prefx * inv) : prefx;
         ry = clip ? ms * (prefy * inv) : prefy;
     }
-    const float4 L[4] = {qb4<0>(srt), qb4<1>(srt), qb4<2>(srt), qb4<3>(srt)};
+    if constexpr (!Path::table) {
+        L[0] = qb4<0>(srt); L[1] = qb4<1>(srt); L[2] = qb4<2>(srt); L[3] = qb4<3>(srt);
+    }
 
     // speculative 1-D LPs, one per lane (lane k's line L[k] is its own `srt`); then the incremental LP is four
     // compare-and-take steps
     float cx, cy;
     // lane k's code for the take steps below: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
-    const int fcode = lp1_rt<false>(L, srt, k, ms, prefx, prefy, cx, cy) ? 4 : k;
+    const int fcode = lp1_rt<false, Path::slim>(L, srt, k, ms, prefx, prefy, cx, cy) ? 4 : k;
     // `fail` stays nl until a violated line's 1-D LP is infeasible and then is that line, so "line I is below nl and
     // nothing failed yet" is fail > I; a violation folds the line's code in (min: nl <= 4 keeps a feasible line's 4
     // from changing it), and the candidate is taken where fail is still above I afterwards
@@ -277,7 +327,9 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
             const unsigned m = (unsigned)(over >> (lane & ~3)) & 0xfu;
             if (m == 0) break;
             const int nxt = __builtin_ctz(m);
-            const float4 ln = sel4(L, nxt);
+            float4 ln;
+            if constexpr (Path::table) ln = path.tab[(lane & ~3) | nxt];      // one 16-byte read for sel4's 12 selects
+            else ln = sel4(L, nxt);
             float cx3, cy3;
             const bool ok3 = lp3_candidate_quad(ln, srt, nxt, k, ms, cx3, cy3);
             rx = ok3 ? cx3 : rx; ry = ok3 ? cy3 : ry;

@@ -65,7 +65,7 @@ def sweep(E=4096, N=5):
     _hip.set_tuning()
 
 
-STAMP_SLOTS = 64            # must equal MCN_STAMP_SLOTS of env_rollout_quad.hip (mcn_debug_stamps copies raw slots)
+STAMP_SLOTS = 64            # must equal MCN_STAMP_SLOTS of env_rollout_common.hpp (mcn_debug_stamps copies raw slots)
 CYCLES_PER_TICK = 24        # nominal 2.4 GHz shader clock against the 100 MHz counter: a conversion, the clock is not read
 
 

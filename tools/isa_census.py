@@ -17,7 +17,8 @@ them are counted too (column `fallback`: how many of the region's instructions s
 v_sqrt_f32 or a v_div_scale_f32 of 1.0).  Static counts, not a measurement of time.
 
 The default kernel is the two-wavefront form.  The four-wavefront form (env_rollout_wg4_kernel, what 4096 envs x 5
-humans now run) has one step loop per role and no single nest for this census to pick: use --loops there, which
+humans now run; --src modelcrowdnav_amd/csrc/env_rollout_wg4.hip) has one step loop per role and no single nest for
+this census to pick: use --loops there, which
 prints one row per outermost loop (text range from its first to its last block, child loops and rare blocks placed
 inside it included) with the number of float64 instructions in it: the float64 role's step loop is the row with most.
 """
@@ -39,16 +40,22 @@ ARITH = re.compile(r"^v_(pk_)?(add|sub|subrev|mul|fma|fmac|mac|min|max|min3|max3
                    r"fract|floor|ceil|trunc|rndne|cvt_\w+|exp|log|sin|cos)(_legacy)?_(f32|f64|f16)(_e32|_e64|_dpp)?$")
 
 
-def hipflags():
-    """HIPFLAGS as the Makefile sets them (the Makefile is the one place the product flags live)."""
+def hipflags(src=None):
+    """HIPFLAGS as the Makefile sets them (the Makefile is the one place the product flags live), with what it adds
+    for the object of `src` alone (`<objects>: HIPFLAGS += ...`)."""
     txt = open(os.path.join(CSRC, "Makefile")).read()
     m = re.search(r"^HIPFLAGS\s*\?=\s*(.*)$", txt, re.M)
     flags = m.group(1).replace("$(ARCH)", "gfx950")
+    if src:
+        obj = os.path.splitext(os.path.basename(src))[0] + ".o"
+        for targets, extra in re.findall(r"^([^#\n:]+):\s*HIPFLAGS\s*\+=\s*(.*)$", txt, re.M):
+            if obj in targets.split():
+                flags += " " + extra
     return shlex.split(flags)
 
 
 def compile_asm(src, out):
-    cmd = [HIPCC] + hipflags() + ["--cuda-device-only", "-S", src, "-o", out]
+    cmd = [HIPCC] + hipflags(src) + ["--cuda-device-only", "-S", src, "-o", out]
     subprocess.run(cmd, check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
 
 

@@ -7,6 +7,10 @@
 // so no instruction waits for its own result) from every wavefront of a 256-workgroup grid (one workgroup per CU,
 // 4 / 8 / 16 wavefronts = 1 / 2 / 4 per SIMD) and reports shader cycles (s_memtime) per instruction per wavefront
 // and per SIMD.  The instructions are pinned with inline asm so the compiler cannot fuse, pack or drop them.
+//
+// The *_DEP rows put all 64 instructions of an iteration on ONE chain: every instruction waits for the one before it,
+// which is how the ORCA solve's stream looks (short dependent runs, one or two wavefronts on the SIMD).  They price a
+// packed float32 instruction against the two scalar ones it stands for when the result is needed at once.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdio>
@@ -14,7 +18,8 @@
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-enum { FMA32, ADD32, CNDMASK, MOV, PKFMA, FMA64, MUL64, EXP32, RCP32, MAXI32, FMA32_DPP, MIX_FMA_CND };
+enum { FMA32, ADD32, CNDMASK, MOV, PKFMA, FMA64, MUL64, EXP32, RCP32, MAXI32, FMA32_DPP, MIX_FMA_CND,
+       ADD32_DEP, PKADD_DEP, PKMUL_DEP };
 
 template <int V>
 __global__ void k(float *out, unsigned long long *cyc, int iters)
@@ -46,6 +51,9 @@ __global__ void k(float *out, unsigned long long *cyc, int iters)
                 else if (V == RCP32)   asm volatile("v_rcp_f32 %0, %0" : "+v"(x[i]));
                 else if (V == MAXI32)  asm volatile("v_max_i32 %0, %0, %1" : "+v"(x[i]) : "v"(a));
                 else if (V == FMA32_DPP) asm volatile("v_add_f32_dpp %0, %1, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "+v"(x[i]) : "v"(b));
+                else if (V == ADD32_DEP) asm volatile("v_add_f32 %0, %1, %0" : "+v"(x[0]) : "v"(b));
+                else if (V == PKADD_DEP) asm volatile("v_pk_add_f32 %0, %1, %0" : "+v"(p[0]) : "v"(b2));
+                else if (V == PKMUL_DEP) asm volatile("v_pk_mul_f32 %0, %1, %0" : "+v"(p[0]) : "v"(a2));
                 else if (V == MIX_FMA_CND) {
                     if (i & 1) asm volatile("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(x[i]) : "v"(a), "s"(mask));
                     else       asm volatile("v_fma_f32 %0, %1, %0, %2" : "+v"(x[i]) : "v"(a), "v"(b));
@@ -60,10 +68,11 @@ __global__ void k(float *out, unsigned long long *cyc, int iters)
 }
 
 template <int V>
-static void run(const char *what, double flop_per_lane_inst)
+static void run(const char *what, double flop_per_lane_inst, int max_waves = 16)
 {
     const int iters = 2048, blocks = 256;
     for (int waves : {4, 8, 16}) {
+        if (waves > max_waves) break;
         float *out; unsigned long long *cyc;
         hipMalloc(&out, sizeof(float) * blocks * waves * 64);
         hipMalloc(&cyc, sizeof(unsigned long long) * blocks * waves);
@@ -97,5 +106,8 @@ int main()
     run<MUL64>("v_mul_f64", 1);
     run<EXP32>("v_exp_f32 (transcendental)", 0);
     run<RCP32>("v_rcp_f32 (transcendental)", 0);
+    run<ADD32_DEP>("v_add_f32, ONE dependent chain", 1, 8);
+    run<PKADD_DEP>("v_pk_add_f32, ONE dependent chain", 2, 8);
+    run<PKMUL_DEP>("v_pk_mul_f32, ONE dependent chain", 2, 8);
     return 0;
 }
