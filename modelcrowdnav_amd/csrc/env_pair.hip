@@ -13,11 +13,11 @@
 //   * the pieces are exchanged inside the wavefront through a private LDS slab (a wavefront's DS operations
 //     execute in order: no barrier), so EVERY lane of the env holds the robot state and runs the ladder and the
 //     Explorer accounting redundantly (the rollout kernel's idea);
-//   * the discount table (<= 128 entries) is copied to LDS by each wavefront at entry, next to its other loads,
-//     so the lookup by ep_steps is an LDS read instead of a dependent global load;
+//   * the discount factor is fetched only by lanes whose step earned a reward (a zero reward adds nothing to the
+//     return), so the load that depends on the record is off the path of almost every wavefront;
 //   * the results are written the same way: lane h stores 16-byte piece h of the env's outputs (new robot
 //     position, velocity, step record, two record halves), lanes 0 / 1 the 8-byte ones (clock, record tail).
-// Per wavefront: 6 load + 4 store instructions instead of 13 + 9, no workgroup barrier, no dependent global load.
+// Per wavefront: 6 load + 4 store instructions instead of 13 + 9, no workgroup barrier, rarely a dependent global load.
 //
 // Handles: compile-time N in {5, 10}, holonomic robot, update = 1, no human-human count, no first-arrival
 // bookkeeping, no human_act export; everything else stays on env_step_kernel.
@@ -33,25 +33,16 @@ void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispat
 __device__ __forceinline__ long long d2ll(double v) { return __builtin_bit_cast(long long, v); }
 __device__ __forceinline__ double ll2d(long long v) { return __builtin_bit_cast(double, v); }
 
+// longest discount table the dispatcher accepts (longer ones stay on env_step_kernel)
 constexpr int kPairDiscMax = 128;
-// where the per-step discount factor gamma^(t v_pref) of the Explorer return comes from (A/B switch):
-//   0  every wavefront copies the table to its own LDS slab at entry (2 global loads + 2 LDS stores per wavefront)
-//   1  one copy per workgroup + a workgroup barrier
-//   2  no copy: a reward of exactly 0 adds nothing to the return (x + d * 0 == x for every finite d, and the ladder's
-//      zero is +0), so only lanes whose step earned a reward fetch their ONE table entry from L2
-#ifndef MCN_PAIR_DISC
-#define MCN_PAIR_DISC 2
-#endif
 
 // Non-temporal loads / stores for the per-human streams (positions, velocities, given velocities, radii: 3/4 of the
 // bytes, each touched exactly once per step).  Measured (round 3, MI355X, 5 humans, with Explorer record and pool
 // restarts): 2^20 envs (660 MB per step, 2.6 x the 256 MB Infinity Cache) 125-145 -> 109-116 us; 2^22 envs 469-580 ->
 // 460-556 us; 65 536 envs (41 MB: the state of one step is still cached when the next one starts) 9.0 -> 9.3-10.1 us,
 // i.e. they only pay once the step's footprint no longer fits the memory-side cache.  Marking the per-env pieces and
-// outputs too loses the gain (141 us at 2^20): neighbouring wavefronts complete each other's partial lines in cache.
-#ifndef MCN_PAIR_NT_ALL
-#define MCN_PAIR_NT_ALL 0      // A/B: the per-env pieces and outputs non-temporal as well (round 3 at 2^20: loses; round 4 at 2^22: see DESIGN)
-#endif
+// outputs too loses the gain (141 us at 2^20): neighbouring wavefronts complete each other's partial lines in cache,
+// so those keep plain loads and stores.
 typedef double pair_d2v __attribute__((ext_vector_type(2)));
 template <bool NTMP> __device__ __forceinline__ double2 pair_ld(const double2 *ptr)
 {
@@ -85,18 +76,13 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
     __shared__ double2 s_piece[WPB][G][5];
     __shared__ double s_small[WPB][G][2];
     __shared__ double s_cd[WPB][64];
-    __shared__ double s_disc[MCN_PAIR_DISC == 0 ? WPB : 1][MCN_PAIR_DISC == 2 ? 1 : kPairDiscMax];
 #ifdef MCN_DIAG
     if (p.debug_noop) return;
 #endif
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane / NT;
     const int h = lane - g * NT;
-    // XCD-aware chunking, as env_step_kernel: every XCD (its own L2) owns one contiguous range of envs
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-    const unsigned qq = nb >> 3, rr_ = nb & 7u;
-    const unsigned chunk = (xcd < rr_ ? xcd * (qq + 1) : rr_ * (qq + 1) + (xcd - rr_) * qq) + idx;
-    const long e = (long)chunk * (WPB * G) + wave * G + g;
+    const long e = (long)xcd_chunk() * (WPB * G) + wave * G + g;
     const bool active = (g < G) && (e < p.E);
     const long eb = active ? e : 0;
     const long a = eb * NT + h;
@@ -120,21 +106,12 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
         src = h == 2 ? reinterpret_cast<const double2 *>(p.actions) : src;
         src = h >= 3 ? reinterpret_cast<const double2 *>(ro.state) : src;
         const long pi = h >= 3 ? 2 * eb + (h - 3) : eb;
-        if (h < 3 || (h < 5 && has_state)) piece = (MCN_PAIR_NT_ALL && NTMP) ? pair_ld<true>(src + pi) : src[pi];
+        if (h < 3 || (h < 5 && has_state)) piece = src[pi];
     }
     double small = 0;
     {
         const double *src = h == 0 ? p.st.rrad : p.st.gtime;
-        if (h < 2) small = (MCN_PAIR_NT_ALL && NTMP) ? pair_ld<true>(src + eb) : src[eb];
-    }
-    if (MCN_PAIR_DISC == 0 && has_state) {
-        const int len = ro.disc_len;
-        s_disc[wave][lane] = lane < len ? ro.disc_table[lane] : 0.0;
-        s_disc[wave][lane + 64] = lane + 64 < len ? ro.disc_table[lane + 64] : 0.0;
-    }
-    if (MCN_PAIR_DISC == 1 && has_state) {
-        const int t = threadIdx.x;
-        if (t < kPairDiscMax) s_disc[0][t] = t < ro.disc_len ? ro.disc_table[t] : 0.0;
+        if (h < 2) small = src[eb];
     }
 
     // ---- exchange inside the wavefront ----
@@ -156,7 +133,6 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    if (MCN_PAIR_DISC == 1) __syncthreads();              // the workgroup's discount table is in place
     double dmin = INFINITY;
     {
         const int l0 = (g < G ? g : 0) * NT;
@@ -167,6 +143,8 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
     // ---- goal test + reward ladder, on every lane of the env (crowd_sim.py:379-403) ----
     const double endx = rpos.x + act.x * dt, endy = rpos.y + act.y * dt;
     const bool reaching = norm2(endx - rgoal.x, endy - rgoal.y) < rrad;
+    // (reward_ladder(), env_common.hpp, written out: through the function this kernel's SGPR count moves from 96 to 94,
+    //  and tests/test_rollout_line_table_gpu.py pins every kernel's register counts)
     double rew; int dn, inf;
     if (gtime >= c.time_limit - 1)      { rew = 0; dn = 1; inf = MCN_INFO_TIMEOUT; }
     else if (dmin < 0)                  { rew = c.collision_penalty; dn = 1; inf = MCN_INFO_COLLISION; }
@@ -175,7 +153,8 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
     else                                { rew = 0; dn = 0; inf = MCN_INFO_NOTHING; }
     const double t_new = gtime + dt;
 
-    // ---- Explorer accounting (explorer.py:88-99,124), on every lane of the env ----
+    // ---- Explorer accounting, on every lane of the env: explorer_account() (env_common.hpp) is the contract, this is
+    //      its form on the packed record ----
     double2 rs_lo = make_double2(0, 0), rs_hi = make_double2(0, 0);
     int case_g = 0;
     if (has_state) {
@@ -186,9 +165,10 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
         double danger_sum = rs_hi.y;
         case_g = next_case;
         const int di = ep_steps < ro.disc_len ? ep_steps : ro.disc_len - 1;
+        // a reward of exactly 0 adds nothing to the return (x + d * 0 == x for every finite d, and the ladder's zero is
+        // +0), so only lanes whose step earned a reward fetch their ONE table entry from L2
         double ep_disc = 0.0;
-        if (MCN_PAIR_DISC == 2) { if (rew != 0.0) ep_disc = ro.disc_table[di]; }
-        else ep_disc = s_disc[MCN_PAIR_DISC == 0 ? wave : 0][di];
+        if (rew != 0.0) ep_disc = ro.disc_table[di];
         if (inf == MCN_INFO_DANGER && (ro.danger_episodes <= 0 ||
             fin_count < ro.danger_episodes - ((ro.danger_short_from > 0 && e >= ro.danger_short_from - 1) ? 1 : 0))) {
             danger_count += 1; danger_sum += dmin;
@@ -218,6 +198,8 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
     const bool restart = do_reset && dn;
     if (active) {
         if (restart) {
+            // (restart_human_from_pool(), env_common.hpp, written out: through the function the kernel comes out 10 instructions
+            //  shorter and its 65 536-env line ran a shade above the parent in both orders, profiles/r19_env_refactor.txt)
             const long pa = (long)case_g * NT + h;
             reinterpret_cast<double2 *>(p.st.hpos)[a]  = reinterpret_cast<const double2 *>(ro.pool_hpos)[pa];
             reinterpret_cast<double2 *>(p.st.hgoal)[a] = reinterpret_cast<const double2 *>(ro.pool_hgoal)[pa];
@@ -248,11 +230,11 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
         if (h == 2) { dst = reinterpret_cast<double2 *>(reinterpret_cast<double *>(p.out.rec) + 3 * eb); val = make_double2(rew, dmin); }
         if (h == 3) { dst = reinterpret_cast<double2 *>(ro.state) + 2 * eb; val = rs_lo; }
         if (h == 4) { dst = reinterpret_cast<double2 *>(ro.state) + 2 * eb + 1; val = rs_hi; }
-        if (active && (h < 3 || (h < 5 && has_state))) { if (MCN_PAIR_NT_ALL && NTMP) pair_st<true>(dst, val); else *dst = val; }
+        if (active && (h < 3 || (h < 5 && has_state))) *dst = val;
         double *d8 = p.st.gtime + eb;                                                     // h == 0
         double v8 = o_time;
         if (h == 1) { d8 = reinterpret_cast<double *>(p.out.rec) + 3 * eb + 2; v8 = ll2d((long long)tail); }
-        if (active && h < 2) { if (MCN_PAIR_NT_ALL && NTMP) __builtin_nontemporal_store(v8, d8); else *d8 = v8; }
+        if (active && h < 2) *d8 = v8;
     }
 }
 

@@ -47,7 +47,11 @@ int read_stamps(void *dst, size_t bytes, int form)
 // TWIN: the float64 role of rollout_wg4 (env_rollout_wg4.hip) carries a copy of this kernel's ladder, Explorer accounting,
 // finished-episode stores, robot integrate / restart and epilogue, and this kernel's human integrate / restart
 // statements arranged around its two hand-offs; a change to either is made to both (tests/test_rollout_wg4_gpu.py,
-// tests/test_rollout_owner_gpu.py and tests/test_rollout_chain_gpu.py compare their bytes).
+// tests/test_rollout_owner_gpu.py and tests/test_rollout_chain_gpu.py compare their bytes).  The contract is the one
+// the step kernels share as functions (env_common.hpp: reward_ladder, explorer_account, ...), on state that stays in
+// registers across the steps.  Sharing the text through such functions was tried and cost registers: allocation moved
+// in 35 of the 36 instantiations here, <5,0,true,true> and <3,1,true,true> gained 12 B of scratch, <5,0,true,false>
+// and <3,1,true,false> four spilled VGPRs (profiles/r19_env_refactor.txt, section 4).  So the two copies stay.
 template <int NT, int VIS, bool UNI, bool SPLIT>
 __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_quad_kernel(const StepParams p, const int T)
 {
@@ -69,18 +73,7 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_q
     const int g = lane / LPE;
     const int r = lane - g * LPE;
     const int h = r >> 2, k = r & 3;
-    // XCD-aware chunking (as env_step_kernel): workgroups are dealt round-robin over the 8 XCDs, each with a private
-    // L2, and a workgroup's envs cover only part of a cache line of the per-env arrays (3 envs x 16 B at 5 humans):
-    // give every XCD one contiguous range of envs so that a line is fetched into ONE L2 instead of two or three.
-    // A/B switch MCN_QUAD_XCD (1 = on).
-#ifndef MCN_QUAD_XCD
-#define MCN_QUAD_XCD 1
-#endif
-    const unsigned nb_ = gridDim.x, xcd_ = blockIdx.x & 7u, idx_ = blockIdx.x >> 3;
-    const unsigned qq_ = nb_ >> 3, rr__ = nb_ & 7u;
-    const unsigned chunk_ = MCN_QUAD_XCD ? (xcd_ < rr__ ? xcd_ * (qq_ + 1) : rr__ * (qq_ + 1) + (xcd_ - rr__) * qq_) + idx_
-                                         : blockIdx.x;
-    const long e = (long)chunk_ * G + g;
+    const long e = (long)xcd_chunk() * G + g;
     const bool active = (g < G) && (e < p.E);
     const long eb = active ? e : 0;
     const long a = eb * NT + h;

@@ -48,8 +48,10 @@ namespace mcn {
 // two barriers since.  The prologue seeds buffer 1, which the top of step 0 reads.
 //
 // The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot integrate / restart and the epilogue
-// are the TWIN of env_rollout_quad_kernel's (env_rollout_quad.hip; the older forms keep their code, hence their registers, so the text
-// is not shared): a change to either is made to both.  The humans' integrate / restart holds the twin's statements
+// are the TWIN of env_rollout_quad_kernel's (env_rollout_quad.hip): a change to either is made to both.  The text is
+// not shared: with the tail in common functions this kernel's two forms came out at 1791 and 2811 instructions for
+// 1804 and 2840 with another SGPR use, and the older kernel lost registers to scratch (profiles/r19_env_refactor.txt,
+// section 4), on the path the benchmark's headline runs.  The humans' integrate / restart holds the twin's statements
 // (pos + (double)r * dt, the pool fetch, human_times) in another order: the restart before hand-off 1, the integrate
 // between the hand-offs, the velocity register and human_times after hand-off 2.
 template <int NT>
@@ -96,9 +98,7 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
     const int tid = threadIdx.x;
     // wave-uniform by construction, and known to be: each role runs its own step loop, barriers included
     const int role = __builtin_amdgcn_readfirstlane(tid >> 6);      // 0-2: ORCA, 3: float64 state, ladder, records
-    const unsigned nb_ = gridDim.x, xcd_ = blockIdx.x & 7u, idx_ = blockIdx.x >> 3;       // XCD-aware chunking, as below
-    const unsigned qq_ = nb_ >> 3, rr__ = nb_ & 7u;
-    const unsigned chunk_ = (xcd_ < rr__ ? xcd_ * (qq_ + 1) : rr__ * (qq_ + 1) + (xcd_ - rr__) * qq_) + idx_;
+    const unsigned chunk_ = xcd_chunk();
     const mcn_env_cfg &c = p.cfg;
     const mcn_rollout &ro = p.roll;
 

@@ -100,14 +100,7 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
     const int g = lane / N;
     const int h = lane - g * N;
     const int slot = wave * G + g;                          // env slot inside the block
-    // XCD-aware chunking: workgroups are dealt round-robin over the 8 XCDs (b and b+8 share one), each with a
-    // private L2.  Give every XCD one contiguous range of envs so that the cache lines of the narrow per-env
-    // outputs (u8 done/info, i32 counters), which straddle neighbouring workgroups, are completed inside ONE
-    // L2 instead of being written back partially from several.  Bijective for any grid size.
-    const unsigned nb = gridDim.x, xcd = blockIdx.x & 7u, idx = blockIdx.x >> 3;
-    const unsigned qq = nb >> 3, rr_ = nb & 7u;
-    const unsigned chunk = (xcd < rr_ ? xcd * (qq + 1) : rr_ * (qq + 1) + (xcd - rr_) * qq) + idx;
-    const long e = (long)chunk * ((BLOCK / 64) * G) + slot;
+    const long e = (long)xcd_chunk() * ((BLOCK / 64) * G) + slot;
     const bool active = (g < G) && (e < p.E);
     const bool leader = active && (h == 0);
     const long a = active ? e * N + h : 0;
@@ -436,12 +429,7 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
             nrvx = act.x; nrvy = act.y;
         }
         const bool reaching = norm2(endx - rgoal.x, endy - rgoal.y) < rattr.x;
-        const bool collision = dmin < 0;
-        if (gtime >= c.time_limit - 1)      { rew = 0; dn = 1; inf = MCN_INFO_TIMEOUT; }
-        else if (collision)                 { rew = c.collision_penalty; dn = 1; inf = MCN_INFO_COLLISION; }
-        else if (reaching)                  { rew = c.success_reward; dn = 1; inf = MCN_INFO_REACHGOAL; }
-        else if (dmin < c.discomfort_dist)  { rew = (dmin - c.discomfort_dist) * c.discomfort_penalty_factor * dt; dn = 0; inf = MCN_INFO_DANGER; }
-        else                                { rew = 0; dn = 0; inf = MCN_INFO_NOTHING; }
+        reward_ladder(c, gtime, dmin, reaching, dt, rew, dn, inf);
         store_step_rec(p.out.rec + e, rew, dmin, dn, inf, hh_sum);   // 16 + 8 bytes
         if constexpr (ROB)
             if (cl->tr_rec) store_step_rec(cl->tr_rec + ((size_t)t * (size_t)p.E + (size_t)e), rew, dmin, dn, inf, hh_sum);
@@ -473,14 +461,7 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
     const int case_g = __shfl(next_case, l0 & 63);
     if (active) {
         if (do_reset && dn_g) {
-            const long pa = (long)case_g * N + h;
-            reinterpret_cast<double2 *>(p.st.hpos)[a]  = reinterpret_cast<const double2 *>(p.roll.pool_hpos)[pa];
-            reinterpret_cast<double2 *>(p.st.hgoal)[a] = reinterpret_cast<const double2 *>(p.roll.pool_hgoal)[pa];
-            p.st.hrad[a] = p.roll.pool_hrad[pa];
-            p.st.hvpref[a] = p.roll.pool_hvpref[pa];
-            reinterpret_cast<double2 *>(p.st.hvel)[a]  = p.roll.pool_hvel
-                ? reinterpret_cast<const double2 *>(p.roll.pool_hvel)[pa] : make_double2(0, 0);
-            if (p.st.human_times) p.st.human_times[a] = 0;
+            restart_human_from_pool(p.st, p.roll, a, (long)case_g * N + h);
             if (deferred) lp3_queue_view(p.out.lp3_queue, p.E, N).flag[qidx] = 0;
         } else if (deferred) {
             lp3_queue_view(p.out.lp3_queue, p.E, N).flag[qidx] = 1;
@@ -496,45 +477,10 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
         }
     }
     if (leader) {
-        if (p.has_roll) {
-            const mcn_rollout &r = p.roll;
-            if (r.state) {
-                if (inf == MCN_INFO_DANGER && (r.danger_episodes <= 0 ||
-            rs.fin_count < r.danger_episodes - ((r.danger_short_from > 0 && e >= r.danger_short_from - 1) ? 1 : 0))) {
-                    rs.danger_count += 1; rs.danger_dist_sum += dmin;
-                }
-                const double ret = rs.ep_return + ep_disc * rew;
-                if (dn) {
-                    const int k = rs.fin_count;
-                    // fin_slots == 1: keep the latest episode; otherwise keep the first fin_slots episodes
-                    const bool keep = (r.fin_slots == 1) || (k < r.fin_slots);
-                    const long rec = (long)(r.fin_slots == 1 ? 0 : k) * p.E + e;
-                    if (keep && r.fin_return) r.fin_return[rec] = ret;
-                    if (keep && r.fin_time)   r.fin_time[rec] = (inf == MCN_INFO_TIMEOUT) ? c.time_limit : t_new;
-                    if (keep && r.fin_info)   r.fin_info[rec] = (uint8_t)inf;
-                    rs.fin_count = k + 1; rs.ep_return = 0; rs.ep_steps = 0;
-                    if (do_reset) {                          // both < pool_size (validated on the host): no division
-                        const int nc = next_case + r.case_stride;
-                        rs.next_case = nc >= r.pool_size ? nc - r.pool_size : nc;
-                    }
-                } else {
-                    rs.ep_return = ret; rs.ep_steps += 1;
-                }
-                r.state[e] = rs;                         // one 32-byte store
-            }
-        }
-        if (do_reset && dn) {
-            reinterpret_cast<double2 *>(p.st.rpos)[e]  = make_double2(p.roll.robot_start[0], p.roll.robot_start[1]);
-            reinterpret_cast<double2 *>(p.st.rgoal)[e] = make_double2(p.roll.robot_goal[0], p.roll.robot_goal[1]);
-            reinterpret_cast<double2 *>(p.st.rvel)[e]  = make_double2(0, 0);
-            if (p.st.rtheta) p.st.rtheta[e] = p.roll.robot_theta0;
-            p.st.gtime[e] = 0;
-        } else {
-            reinterpret_cast<double2 *>(p.st.rpos)[e] = make_double2(endx, endy);
-            reinterpret_cast<double2 *>(p.st.rvel)[e] = make_double2(nrvx, nrvy);
-            if (c.robot_kinematics == MCN_KIN_UNICYCLE) p.st.rtheta[e] = new_theta;
-            p.st.gtime[e] = t_new;
-        }
+        if (p.has_roll && p.roll.state)
+            explorer_account(c, p.roll, rs, e, p.E, next_case, ep_disc, rew, dmin, dn, inf, t_new, do_reset);
+        if (do_reset && dn) restart_robot(p.st, p.roll, e);
+        else                store_robot(c, p.st, e, endx, endy, nrvx, nrvy, new_theta, t_new);
     }
 }
 
@@ -593,15 +539,11 @@ __global__ __launch_bounds__(64) void env_step_loop_orca_kernel(const StepParams
 // The deferred 3-D LPs of one step (lp3_queue.hpp).  Finishes each parked solve exactly as the step kernel would have
 // (same sorted half-planes, same running result) and then does for that human what the step kernel skipped: the
 // exported action, and -- by the flag the step kernel left -- the integration (crowd_sim.py:416-421) or the look-ahead
-// observation (agent.py:63-74).  Workgroup b serves sub-queue b % 256.  Two forms (A/B switch MCN_LP3_KB_COOP):
-//   0  one problem per lane, the register-resident unrolled solver (lp3_static): every lane busy, but a wavefront of
-//      64 different problems walks the union of all their paths through the O(n^3) code;
-//   1  eight problems per wavefront, eight lanes each (lp3_wave_coop, orca_coop.hpp): a ~4x shorter dependent chain,
-//      which is what bounds this launch -- it holds a few % of the step's humans and runs far below the chip's width.
-// The last workgroup to finish empties the queue for the next step.
-#ifndef MCN_LP3_KB_COOP
-#define MCN_LP3_KB_COOP 1
-#endif
+// observation (agent.py:63-74).  Workgroup b serves sub-queue b % 256.  A wavefront takes eight problems per pass,
+// eight lanes each (lp3_wave_coop, orca_coop.hpp): against one problem per lane in the unrolled solver (lp3_static),
+// where a wavefront of 64 different problems walks the union of all their paths through the O(n^3) code, that is a ~4x
+// shorter dependent chain, which is what bounds this launch -- it holds a few % of the step's humans and runs far
+// below the chip's width.  The last workgroup to finish empties the queue for the next step.
 template <int NL>
 __global__ __launch_bounds__(256) void env_lp3_kernel(const StepParams p, const int per_queue)
 {
@@ -612,21 +554,12 @@ __global__ __launch_bounds__(256) void env_lp3_kernel(const StepParams p, const 
     const long qbase = (long)sub * q.subcap;
     const double dt = p.cfg.time_step;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#if MCN_LP3_KB_COOP
     __shared__ CoopLds s_coop[4];
     constexpr int kPerWave = kCoopSlots;                          // problems a wavefront takes per pass
-    const bool holder = lane < kPerWave;
     for (int i0 = (rep * 4 + wave) * kPerWave; i0 < count; i0 += per_queue * 4 * kPerWave) {
         const int i = i0 + lane;
-        const bool mine = holder && i < count;
+        const bool mine = lane < kPerWave && i < count;
         const long s = qbase + (mine ? i : 0);
-#else
-    constexpr bool holder = true;
-    for (int i0 = rep * 256; i0 < count; i0 += per_queue * 256) {
-        const int i = i0 + threadIdx.x;
-        const bool mine = i < count;
-        const long s = qbase + (mine ? i : 0);
-#endif
         int4 hd = make_int4(0, 0, 0, 0);
         float4 L[NL];
         float2 r0 = make_float2(0, 0);
@@ -643,11 +576,7 @@ __global__ __launch_bounds__(256) void env_lp3_kernel(const StepParams p, const 
         const int nl = hd.y & 255, fail = mine ? ((hd.y >> 8) & 255) : 0;
         const float ms = __int_as_float(hd.z);
         float rx = r0.x, ry = r0.y;
-#if MCN_LP3_KB_COOP
         lp3_wave_coop<NL>(s_coop[wave], L, mine ? nl : 0, fail, ms, rx, ry);       // every lane of the wavefront
-#else
-        if (mine) lp3_static<NL>(L, nl, fail, ms, rx, ry);
-#endif
         if (mine) {
             const double hax = (double)rx, hay = (double)ry;
             if (p.out.human_act) reinterpret_cast<double2 *>(p.out.human_act)[a] = make_double2(hax, hay);
@@ -671,7 +600,6 @@ __global__ __launch_bounds__(256) void env_lp3_kernel(const StepParams p, const 
             }
         }
     }
-    (void)holder;
     // every workgroup has read its sub-queue's count before it arrives here, so the last one may clear them all
     __shared__ int s_last;
     __syncthreads();

@@ -49,18 +49,7 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
     const int g = lane / LPE;
     const int r = lane - g * LPE;
     const int h = r >> 2, k = r & 3;
-    // XCD-aware chunking (as env_step_kernel): workgroups are dealt round-robin over the 8 XCDs, each with a private
-    // L2, and a workgroup's envs cover only part of a cache line of the per-env arrays (3 envs x 16 B at 5 humans):
-    // give every XCD one contiguous range of envs so that a line is fetched into ONE L2 instead of two or three.
-    // A/B switch MCN_QUAD_XCD (1 = on).
-#ifndef MCN_QUAD_XCD
-#define MCN_QUAD_XCD 1
-#endif
-    const unsigned nb_ = gridDim.x, xcd_ = blockIdx.x & 7u, idx_ = blockIdx.x >> 3;
-    const unsigned qq_ = nb_ >> 3, rr__ = nb_ & 7u;
-    const unsigned chunk_ = MCN_QUAD_XCD ? (xcd_ < rr__ ? xcd_ * (qq_ + 1) : rr__ * (qq_ + 1) + (xcd_ - rr__) * qq_) + idx_
-                                         : blockIdx.x;
-    const long e = (long)chunk_ * G + g;
+    const long e = (long)xcd_chunk() * G + g;
     const bool active = (g < G) && (e < p.E);
     const long eb = active ? e : 0;
     const long a = eb * NT + h;
@@ -166,11 +155,7 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
         nrvx = act.x; nrvy = act.y;
     }
     const bool reaching = norm2(endx - rgoal.x, endy - rgoal.y) < rrad;
-    if (gtime >= c.time_limit - 1)      { rew = 0; dn = 1; inf = MCN_INFO_TIMEOUT; }
-    else if (dmin < 0)                  { rew = c.collision_penalty; dn = 1; inf = MCN_INFO_COLLISION; }
-    else if (reaching)                  { rew = c.success_reward; dn = 1; inf = MCN_INFO_REACHGOAL; }
-    else if (dmin < c.discomfort_dist)  { rew = (dmin - c.discomfort_dist) * c.discomfort_penalty_factor * dt; dn = 0; inf = MCN_INFO_DANGER; }
-    else                                { rew = 0; dn = 0; inf = MCN_INFO_NOTHING; }
+    reward_ladder(c, gtime, dmin, reaching, dt, rew, dn, inf);
     if (lead) {
         store_step_rec(p.out.rec + e, rew, dmin, dn, inf, hh_sum);   // 16 + 8 bytes
     }
@@ -196,14 +181,7 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
     const int case_g = SPLIT ? next_case : __shfl(next_case, l0 & 63);
     if (hlead) {
         if (do_reset && dn) {
-            const long pa = (long)case_g * NT + h;
-            reinterpret_cast<double2 *>(p.st.hpos)[a]  = reinterpret_cast<const double2 *>(p.roll.pool_hpos)[pa];
-            reinterpret_cast<double2 *>(p.st.hgoal)[a] = reinterpret_cast<const double2 *>(p.roll.pool_hgoal)[pa];
-            p.st.hrad[a] = p.roll.pool_hrad[pa];
-            p.st.hvpref[a] = p.roll.pool_hvpref[pa];
-            reinterpret_cast<double2 *>(p.st.hvel)[a]  = p.roll.pool_hvel
-                ? reinterpret_cast<const double2 *>(p.roll.pool_hvel)[pa] : make_double2(0, 0);
-            if (p.st.human_times) p.st.human_times[a] = 0;
+            restart_human_from_pool(p.st, p.roll, a, (long)case_g * NT + h);
         } else {
             reinterpret_cast<double2 *>(p.st.hpos)[a] = make_double2(npx, npy);
             reinterpret_cast<double2 *>(p.st.hvel)[a] = make_double2(hax, hay);
@@ -214,6 +192,8 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
         }
     }
     if (lead) {
+        // explorer_account() (env_common.hpp) written out: through the function <5, 0, true> spills two more SGPRs and the
+        // 1000-step unfused rollout at 4096 envs ran 0.6 - 0.9 % above the parent in both orders (profiles/r19_env_refactor.txt)
         if (p.has_roll) {
             const mcn_rollout &ro = p.roll;
             if (ro.state) {
@@ -241,18 +221,8 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
                 ro.state[e] = rs;                         // one 32-byte store
             }
         }
-        if (do_reset && dn) {
-            reinterpret_cast<double2 *>(p.st.rpos)[e]  = make_double2(p.roll.robot_start[0], p.roll.robot_start[1]);
-            reinterpret_cast<double2 *>(p.st.rgoal)[e] = make_double2(p.roll.robot_goal[0], p.roll.robot_goal[1]);
-            reinterpret_cast<double2 *>(p.st.rvel)[e]  = make_double2(0, 0);
-            if (p.st.rtheta) p.st.rtheta[e] = p.roll.robot_theta0;
-            p.st.gtime[e] = 0;
-        } else {
-            reinterpret_cast<double2 *>(p.st.rpos)[e] = make_double2(endx, endy);
-            reinterpret_cast<double2 *>(p.st.rvel)[e] = make_double2(nrvx, nrvy);
-            if (c.robot_kinematics == MCN_KIN_UNICYCLE) p.st.rtheta[e] = new_theta;
-            p.st.gtime[e] = t_new;
-        }
+        if (do_reset && dn) restart_robot(p.st, p.roll, e);
+        else                store_robot(c, p.st, e, endx, endy, nrvx, nrvy, new_theta, t_new);
     }
 }
 

@@ -17,13 +17,9 @@
 // not bit by bit.  Outside those ranges (zero, denormals, huge, inf, NaN) the guarded wrappers below take the IEEE
 // expansion: ONE wave-uniform branch per guard, so the float state stays bit-identical to the oracle for every input.
 // `used` = lanes whose result is consumed; the operands of the others (empty neighbour slots, discarded select sides)
-// never force the slow path.  MCN_FAST_F32 = 0 compiles the IEEE expansions everywhere (A/B runs).
+// never force the slow path.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#ifndef MCN_FAST_F32
-#define MCN_FAST_F32 1
-#endif
 
 namespace mcn {
 
@@ -70,9 +66,7 @@ __device__ __forceinline__ bool wave_fast(bool used, bool ok) { return wave_fast
 template <class U = bool>
 __device__ __forceinline__ float sqrt_f32(float x, U used = true)
 {
-#if MCN_FAST_F32
     if (wave_fast(used, sqrt5_ok(x))) return sqrt5(x);
-#endif
     return sqrtf(x);
 }
 
@@ -80,9 +74,7 @@ __device__ __forceinline__ float sqrt_f32(float x, U used = true)
 template <class U = bool>
 __device__ __forceinline__ float rcp_f32(float x, U used = true)
 {
-#if MCN_FAST_F32
     if (wave_fast(used, rcp3_ok(x))) return rcp3(x);
-#endif
     return 1.0f / x;
 }
 
@@ -91,9 +83,7 @@ __device__ __forceinline__ float rcp_f32(float x, U used = true)
 template <class U = bool>
 __device__ __forceinline__ float rcp_sqrt_f32(float x, U used = true)
 {
-#if MCN_FAST_F32
     if (wave_fast(used, sqrt5_ok(x))) return rcp3(sqrt5(x));
-#endif
     return 1.0f / sqrtf(x);
 }
 

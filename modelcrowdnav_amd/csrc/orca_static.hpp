@@ -17,53 +17,10 @@
 
 namespace mcn {
 
-// half-plane construction used by the lane-per-human solver: branchy (orca_line_merged) or straight-line
-// (orca_line_select); same bits either way
-#ifndef MCN_STATIC_LINE
-#define MCN_STATIC_LINE orca_line_select
-#endif
-
-// Half-plane induced by one neighbour.  The cut-off-circle case and the already-colliding case differ only in
-// the inverse time constant (1/timeHorizon vs 1/timeStep), so they share one code path.
-__device__ __forceinline__ float4 orca_line_merged(float px, float py, float vx, float vy, float radius, float4 o,
-                                                   float orad, float inv_th, float inv_ts)
-{
-        const float rpx = o.x - px, rpy = o.y - py;
-    const float rvx = vx - o.z, rvy = vy - o.w;
-    const float dist_sq = dot2(rpx, rpy, rpx, rpy);
-    const float cr = radius + orad;
-    const float cr_sq = cr * cr;
-    const bool apart = dist_sq > cr_sq;
-    const float inv = apart ? inv_th : inv_ts;          // collision case uses 1/timeStep
-    const float wx = rvx - inv * rpx, wy = rvy - inv * rpy;
-    const float wl_sq = dot2(wx, wy, wx, wy);
-    const float dp1 = dot2(wx, wy, rpx, rpy);
-    float dx, dy, ux, uy;
-    if (!apart || (dp1 < 0.0f && dp1 * dp1 > cr_sq * wl_sq)) {
-        const float wl = sqrtf(wl_sq);
-        const float iw = 1.0f / wl;
-        const float uwx = wx * iw, uwy = wy * iw;
-        dx = uwy; dy = -uwx;
-        const float s = cr * inv - wl;
-        ux = s * uwx; uy = s * uwy;
-    } else {
-        const float leg = sqrtf(dist_sq - cr_sq);
-        const float id = 1.0f / dist_sq;
-        if (det2(rpx, rpy, wx, wy) > 0.0f) {
-            dx = (rpx * leg - rpy * cr) * id;
-            dy = (rpx * cr + rpy * leg) * id;
-        } else {
-            dx = -((rpx * leg + rpy * cr) * id);
-            dy = -((-rpx * cr + rpy * leg) * id);
-        }
-        const float dp2 = dot2(rvx, rvy, dx, dy);
-        ux = dp2 * dx - rvx; uy = dp2 * dy - rvy;
-    }
-    return make_float4(vx + 0.5f * ux, vy + 0.5f * uy, dx, dy);
-}
-
-// orca_line_merged as one straight-line block: the cut-off-circle and the leg projections are both
-// evaluated and the result selected.  Same operations on the selected side, so the same bits.
+// Half-plane induced by one neighbour (RVO2 computeNewVelocity), as one straight-line block.  The cut-off-circle case
+// and the already-colliding case differ only in the inverse time constant (1/timeHorizon vs 1/timeStep), so they share
+// one code path; the cut-off-circle and the leg projections are both evaluated and the result selected.  Same
+// operations on the selected side as the branchy form, so the same bits.
 // Returns (u.x, u.y, dir.x, dir.y): the half-plane is point = v + u / 2, direction = dir.
 // Every operation is odd-symmetric under swapping the two agents (relative position and velocity change sign, the
 // radius sum does not), so the pair's other half-plane is exactly (-u, -dir): env_step.hip builds each pair once.
@@ -88,7 +45,6 @@ __device__ __forceinline__ float4 orca_u_dir_rel(float rpx, float rpy, float dis
     // normal -- below 2^126.  Same bits as the IEEE expansions either way.
     const float leg_sq = dist_sq - cr_sq;
     float wl, iw, leg, id;
-#if MCN_FAST_F32
     // (a lane that takes the cut-off circle -- every colliding pair does -- only needs |w|, one that takes a leg only
     //  the leg and dist^2: a negative squared leg of an overlapping pair must not send the wavefront down the slow path)
     // (lane masks combined on the scalar unit: as booleans the compiler materialises them in vector registers)
@@ -100,9 +56,7 @@ __device__ __forceinline__ float4 orca_u_dir_rel(float rpx, float rpy, float dis
     const unsigned long long m_l = __builtin_amdgcn_ballot_w64(sqrt5_ok(leg_sq)) & __builtin_amdgcn_ballot_w64(dist_sq < 0x1p126f);
     if ((m_used & ~((m_circle & m_w) | (~m_circle & m_l))) == 0) {
         wl = sqrt5(wl_sq); iw = rcp3(wl); leg = sqrt5(leg_sq); id = rcp3(dist_sq);
-    } else
-#endif
-    {
+    } else {
         wl = sqrtf(wl_sq); iw = 1.0f / wl; leg = sqrtf(leg_sq); id = 1.0f / dist_sq;
     }
     // cut-off circle
@@ -290,7 +244,7 @@ __device__ __forceinline__ void orca_solve_static(float4 (&cpv)[NC > 0 ? NC : 1]
 #pragma unroll
     for (int k = 0; k < NL; ++k) {
         if (k < NC) {
-            L[k] = MCN_STATIC_LINE(px, py, vx, vy, radius, cpv[k], crad[k], inv_th, inv_ts);
+            L[k] = orca_line_select(px, py, vx, vy, radius, cpv[k], crad[k], inv_th, inv_ts);
         } else {
             L[k] = make_float4(0, 0, 1, 0);
         }

@@ -1,8 +1,10 @@
 """Every step kernel's Explorer accounting (include/mcn.h: mcn_rollout) against a host replay, bit for bit.
 
 The discounted return, the finished-episode records, the gated "too close" counters and the in-kernel restart from the
-scenario pool exist four times in device code (env_step.hip, env_step_quad.hip, env_rollout_quad.hip, env_pair.hip), each
-written differently.  tests/rollout_ref.py replays the contract in plain Python on the C oracle's steps; here every
+scenario pool exist in these forms in device code, each written differently: the memory-resident functions of
+env_common.hpp (explorer_account for env_step.hip, of which env_step_quad.hip keeps a written-out copy;
+restart_human_from_pool and the robot stores for both), env_pair.hip's form on the packed record, and the
+register-resident twin of env_rollout_quad.hip and env_rollout_wg4.hip.  tests/rollout_ref.py replays the contract in plain Python on the C oracle's steps; here every
 decomposition of mcn_env_step (ORCA humans and given velocities) and every path of mcn_env_rollout runs 130 steps of 251
 envs under ten parameter sets and must leave the same bytes: the whole mcn_roll_rec, all of fin_return / fin_time /
 fin_info (sentinel-filled before the run: NaN / 0xFF), every step record and the env state with the restarts replayed.
@@ -30,10 +32,10 @@ Which test catches which break (value-only changes of one body; none of them mov
   return with a fused multiply-add, or the wrong table entry    ep_return / fin_return of every set
   no clamp at disc_len - 1 (reads past the table)               short-table (clamped)
   streaming kernel taken beyond its 128-entry table limit,      table-128 / table-129 on the given-velocity paths
-  or a table entry >= 64 misread                                (mcn_last_dispatch; disc_index_ge64.  As shipped,
-                                                                MCN_PAIR_DISC = 2, the kernel reads the entry from
-                                                                global memory; the LDS copies that could be cut at 64
-                                                                entries are the A/B forms 0 / 1, not compiled in)
+  or a table entry >= 64 misread                                (mcn_last_dispatch; disc_index_ge64.  The kernel
+                                                                reads the entry from global memory; the LDS copies
+                                                                of the table that could be cut at 64 entries were
+                                                                A/B forms and are no longer in the sources)
   episode k >= fin_slots overwrites a slot, or is counted out   explorer-*, device-pool, no-pool (dropped): sentinel
                                                                 slots and fin_count
   one slot keeps the first episode instead of the latest        latest-wins (overwritten counts only records that change
