@@ -88,7 +88,8 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
     __shared__ float2 s_res[2 * NQ], s_inv[NQ];
     __shared__ double2 s_hpos[NQ];
     __shared__ double s_hrad[NQ];
-    // the ORCA wavefronts' sorted half-planes (quad_common.hpp: QuadTable): 64 slots each, private to the wavefront
+    // the ORCA wavefronts' sorted half-planes (quad_common.hpp: QuadTable): 64 slots each, private to the wavefront.  A lane
+    // reads its quad's four slots, its own, and the two operands of its pass-A intersection (lp1_spread): seven reads
     __shared__ float4 s_lines[3 * 64];
     STAMP(0);
     STAMP_WHERE();

@@ -54,11 +54,13 @@ __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
 //              step's reads in program order: no s_barrier.  The 3-D LP reads its run-time line from the table too.
 //              This path also takes the step's small savings that would change the other callers' code (`slim`): one
 //              squared distance for rank and half-plane, the 1-D LP's clamp as two selects.
+//              And it spreads the 1-D LP's six (line, earlier line) intersections over the quad as 2 + 2 + 1 + 1
+//              (`spread`, lp1_spread below) where the other callers run 0 + 1 + 2 + 3 as three passes on every lane.
 struct QuadDpp {
-    static constexpr bool table = false, slim = false;
+    static constexpr bool table = false, slim = false, spread = false;
 };
 struct QuadTable {
-    static constexpr bool table = true, slim = true;
+    static constexpr bool table = true, slim = true, spread = true;
     float4 *tab;                                                 // this wavefront's 64 slots
 };
 
@@ -103,6 +105,62 @@ __device__ __forceinline__ bool lp1_rt(const float4 (&L)[4], const float4 &ln, i
         } else {
             if (t < tl) t = tl; else if (t > tr) t = tr;
         }
+    }
+    rx = ln.x + t * ln.z;
+    ry = ln.y + t * ln.w;
+    return ok;
+}
+
+// One bound update of the 1-D LP from an intersection (t = num / den) that is handed over: the statements of lp1_rt's
+// loop body after the quotient.
+__device__ __forceinline__ void lp1_cut(bool live, float t, float den, float num, float &tl, float &tr, bool &ok)
+{
+    const bool par = fabsf(den) <= kRvoEps;
+    const bool cut = live & !par;
+    const float ntr = fminf(tr, t), ntl = fmaxf(tl, t);
+    tr = (cut & (den >= 0.0f)) ? ntr : tr;
+    tl = (cut & !(den >= 0.0f)) ? ntl : tl;
+    ok = ok & !(live & ((par ? 0.0f : tl) > (par ? num : tr)));          // parallel: 0 > num, else tl > tr
+}
+
+// lp1_rt<false> of lane k's own sorted line `ln` (no = k) with the quad's six intersections (k, i), i < k, dealt
+// 2 + 2 + 1 + 1 over the lanes instead of 0 + 1 + 2 + 3: two passes where lp1_rt runs three.
+//   pass A  lane k intersects (lnA, liA): lanes 1 - 3 their own line with line 0, as lp1_rt's i = 0; lane 0, whose own
+//           1-D LP has no earlier line, line 3 with line 2.  The caller reads both operands from the line table at
+//           addresses that differ per lane and never change (lane 0: slots 3 and 2 of its quad; the others: their own
+//           slot and slot 0), so no select picks them.
+//   pass B  lanes 2 and 3 intersect their own line with line 1 (`liB`); lanes 0 and 1 compute a value nobody reads, as
+//           every lane above its `no` does in lp1_rt.
+//   then    lane 3 takes lane 0's (t, den, num) of pass A by three quad broadcasts and applies it as its update i = 2,
+//           after its own i = 0 and i = 1: the order lp1_rt has.
+// Lane 0 forms den, num and num / den of pair (3, 2) by the expressions, on the operands, that lane 3 forms them with
+// in lp1_rt's pass i = 2 (ln = line 3, li = line 2: the table's slots hold the bits lane 3's `srt` and L[2] are), and a
+// DPP move copies bits, NaN payloads included: every bound, `ok` and the candidate are bit for bit lp1_rt's.
+template <bool SELECT_CLAMP>
+__device__ __forceinline__ bool lp1_spread(const float4 &ln, const float4 &lnA, const float4 &liA, const float4 &liB, int k,
+                                           float radius, float optx, float opty, float &rx, float &ry)
+{
+    const float dp = dot2(ln.x, ln.y, ln.z, ln.w);
+    const float disc = dp * dp + radius * radius - dot2(ln.x, ln.y, ln.x, ln.y);
+    bool ok = !(disc < 0.0f);
+    const float sq = sqrt_f32(disc, ok);
+    float tl = -dp - sq;
+    float tr = -dp + sq;
+    const float denA = det2(lnA.z, lnA.w, liA.z, liA.w);
+    const float numA = det2(liA.z, liA.w, lnA.x - liA.x, lnA.y - liA.y);
+    const float tA = numA / denA;
+    lp1_cut(0 < k, tA, denA, numA, tl, tr, ok);
+    const float denB = det2(ln.z, ln.w, liB.z, liB.w);
+    const float numB = det2(liB.z, liB.w, ln.x - liB.x, ln.y - liB.y);
+    const float tB = numB / denB;
+    lp1_cut(1 < k, tB, denB, numB, tl, tr, ok);
+    lp1_cut(k == 3, qbf<0>(tA), qbf<0>(denA), qbf<0>(numA), tl, tr, ok);
+    float t = dot2(ln.z, ln.w, optx - ln.x, opty - ln.y);
+    if (SELECT_CLAMP) {
+        const float hi = (t > tr) ? tr : t;                      // (as lp1_rt: a NaN answers both comparisons with false)
+        t = (t < tl) ? tl : hi;
+    } else {
+        if (t < tl) t = tl; else if (t > tr) t = tr;
     }
     rx = ln.x + t * ln.z;
     ry = ln.y + t * ln.w;
@@ -261,6 +319,7 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     }
     // route my half-plane to lane `rank` of the quad, then share all four
     float4 srt, L[4];
+    [[maybe_unused]] float4 lnA, liA;                            // lp1_spread's pass A operands (Path::spread)
     if constexpr (Path::table) {
         path.tab[(lane & ~3) | rank] = mine;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -269,6 +328,12 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
         const float4 *quad = path.tab + (lane & ~3);
         L[0] = quad[0]; L[1] = quad[1]; L[2] = quad[2]; L[3] = quad[3];
         srt = path.tab[lane];
+        if constexpr (Path::spread) {
+            // lane 0 of the quad: lines 3 and 2; lanes 1 - 3: their own line and line 0.  Two more reads at addresses
+            // that do not change from step to step, issued with the five above
+            lnA = path.tab[k == 0 ? (lane | 3) : lane];
+            liA = quad[k == 0 ? 2 : 0];
+        }
     } else {
         const int dst = ((lane & ~3) | rank) << 2;
         srt.x = __builtin_bit_cast(float, __builtin_amdgcn_ds_permute(dst, __builtin_bit_cast(int, mine.x)));
@@ -293,7 +358,10 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     // compare-and-take steps
     float cx, cy;
     // lane k's code for the take steps below: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
-    const int fcode = lp1_rt<false, Path::slim>(L, srt, k, ms, prefx, prefy, cx, cy) ? 4 : k;
+    bool ok1;
+    if constexpr (Path::spread) ok1 = lp1_spread<Path::slim>(srt, lnA, liA, L[1], k, ms, prefx, prefy, cx, cy);
+    else ok1 = lp1_rt<false, Path::slim>(L, srt, k, ms, prefx, prefy, cx, cy);
+    const int fcode = ok1 ? 4 : k;
     // `fail` stays nl until a violated line's 1-D LP is infeasible and then is that line, so "line I is below nl and
     // nothing failed yet" is fail > I; a violation folds the line's code in (min: nl <= 4 keeps a feasible line's 4
     // from changing it), and the candidate is taken where fail is still above I afterwards
