@@ -9,7 +9,7 @@ scenarios = test cases 1000 + (global_env_id mod 500), auto-reset on done from a
 pool of the same 500 scenarios, Explorer-style discounted returns accumulated in-kernel.
 A "step" is one CrowdSim.step of the whole batch.  The robot's actions are a pre-drawn sequence, so the K
 timed steps go to the device as ceil(K / 1000) mcn_env_rollout launches (env state in registers between the steps
-of a launch; --steps-per-launch 1 = one mcn_env_step launch per step, also reported as single_step_launch).
+of a launch; --steps-per-launch 1 = one mcn_env_step launch per step, which --full also reports as single_step_launch).
 Inputs (states, the action tensor) are resident in HBM before the timed region; the launches are replayed from one
 hipGraph.  After W warm-up steps, one untimed pass of the K steps warms every launch shape (and the graph); then
 exactly K steps are timed and ms_per_step = elapsed / K.  For K above ACTION_PERIOD_CAP the action sequence repeats
@@ -20,9 +20,13 @@ straggling wavefronts of a launch -- a sub-batch launch is as latency-bound as t
 Envs shard across ranks with no per-step communication (weak scaling); at the end of the
 rollout one RCCL all_gather collects episode returns + outcome codes.
 
-Prints ONE JSON line (rank 0).  Extra objects: roofline (dominant kernel, live HIP-event timing),
-roofline_sweep (same kernel at larger batches, where HBM rather than launch latency bounds it),
-cpu_baseline (the C oracle on this host's cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run does what the headline figure needs and no more: set-up, warm-up, the K timed
+steps, --dump-outputs, the line.  Its roofline / roofline_valu objects price the timed region's own HIP-event time with
+the committed counter summaries and cost no run of their own.  --full (off by default, one rank only) adds every
+measurement that does take runs of its own -- see FULL_SECTIONS: single_step_launch (one mcn_env_step launch per step),
+roofline_sweep (same kernel at larger batches, where HBM rather than launch latency bounds it), extra_configs (the SARL /
+SGAN / 10-human configurations), cpu_baseline (the C oracle on this host's cores, bounded sample) -- after the line's
+headline fields are final; --no-sweep / --no-extra / --no-cpu-baseline drop single sections of a --full run.
 """
 import argparse
 import json
@@ -46,7 +50,11 @@ def algorithmic_bytes_per_env_step(N):
     return (17 + 12 * N) * 8 + 6
 
 
-def parse():
+# what --full adds to the line, in the order it runs; each takes GPU or CPU runs of its own after the timed region
+FULL_SECTIONS = ("single_step_launch", "roofline_sweep", "extra_configs", "cpu_baseline")
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
@@ -57,23 +65,36 @@ def parse():
     ap.add_argument("--steps-per-launch", type=int, default=1000,
                     help="env steps handed to one mcn_env_rollout call (the action sequence is known up front); "
                          "1 = one mcn_env_step launch per step")
-    ap.add_argument("--sweep", type=str, default="65536,1048576,4194304", help="extra batch sizes for roofline_sweep")
-    ap.add_argument("--no-sweep", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the SARL / SGAN configurations")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run, also measure %s (runs of their own; one rank only)" % ", ".join(FULL_SECTIONS))
+    ap.add_argument("--sweep", type=str, default="65536,1048576,4194304",
+                    help="--full: extra batch sizes for roofline_sweep")
+    ap.add_argument("--no-sweep", action="store_true", help="--full without roofline_sweep")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without extra_configs (SARL / SGAN / 10 humans)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: length of the cpu_baseline sample")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy "
                          "(float64, at most %d MB; a seeded sample of envs beyond that)" % (DUMP_LIMIT_BYTES >> 20))
     ap.add_argument("--force-collective", action="store_true",
                     help="run the N > 1 branches (process group, the one all_gather of episode records, the MAX / SUM "
                          "all-reduces) with a single rank too: exercises RCCL on a one-GPU box")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.warmup < 0:
         ap.error("--warmup must not be negative")
     return args
+
+
+def full_sections(args, rank, world, steps_per_launch):
+    """The FULL_SECTIONS this run measures: none without --full, none on more than one rank; single_step_launch only
+    where the headline itself is not one launch per step."""
+    if not args.full or rank != 0 or world != 1:
+        return ()
+    skip = {"single_step_launch": steps_per_launch <= 1, "roofline_sweep": args.no_sweep, "extra_configs": args.no_extra,
+            "cpu_baseline": args.no_cpu_baseline}
+    return tuple(s for s in FULL_SECTIONS if not skip[s])
 
 
 def build_env(E, N, rank_offset, device):
@@ -799,14 +820,15 @@ def main():
         "roofline_valu": valu,
     }
 
-    if rank == 0 and world == 1 and S > 1:
+    sections = full_sections(args, rank, world, S)
+    if "single_step_launch" in sections:
         # the same workload stepped one mcn_env_step launch at a time (policy-in-the-loop callers pay this)
         one_ms, _ = time_kernel_events(env, acts, 200)
         result["single_step_launch"] = roofline_entry(E, N, one_ms, {
             "mode": "one mcn_env_step launch per step, hipGraph of 200", "env_steps_per_sec": round(E / (one_ms * 1e-3), 1),
             "roofline_valu": valu_roofline(E, N, one_ms, 1, rollout=False)})
 
-    if rank == 0 and world == 1 and not args.no_sweep:
+    if "roofline_sweep" in sections:
         sweep = []
         del env
         for Es in [int(x) for x in args.sweep.split(",") if x]:
@@ -842,11 +864,11 @@ def main():
             del env_s, a_s
         result["roofline_sweep"] = sweep
 
-    if rank == 0 and world == 1 and not args.no_extra:
+    if "extra_configs" in sections:
         torch.cuda.empty_cache()
         result["extra_configs"] = extra_configs(device)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if "cpu_baseline" in sections:
         result["cpu_baseline"] = cpu_baseline(N, args.cpu_seconds)
     elif rank == 0:
         result["cpu_baseline"] = None

@@ -254,3 +254,24 @@ def test_dump_outputs_samples_a_fixed_set_of_envs_above_the_size_limit(tmp_path,
         assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))), f
     assert np.array_equal(np.load(str(tmp_path / "a" / "obs_human_pos_rank1.npy")), env.hpos.numpy()[rows])
     assert np.array_equal(np.load(str(tmp_path / "a" / "finished_time_rank1.npy")), env.rollout_buffers["fin_time"].numpy()[:, rows])
+
+
+def test_full_sections_run_only_behind_the_full_option():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures nothing besides its headline; --full adds every section
+    that takes runs of its own, minus those a --no-* option names, on one rank only; single_step_launch only where the
+    headline is not already one launch per step."""
+    import bench
+    plain = ["--gpus", "1", "--steps", "20", "--warmup", "5"]
+    assert bench.parse(plain).full is False
+    assert bench.full_sections(bench.parse(plain), 0, 1, 20) == ()
+    assert bench.full_sections(bench.parse(plain + ["--no-sweep", "--no-extra", "--no-cpu-baseline"]), 0, 1, 20) == ()
+    full = bench.parse(plain + ["--full"])
+    assert full.full is True and (full.steps, full.warmup, full.dump_outputs) == (20, 5, None)
+    assert bench.full_sections(full, 0, 1, 20) == bench.FULL_SECTIONS
+    assert bench.FULL_SECTIONS == ("single_step_launch", "roofline_sweep", "extra_configs", "cpu_baseline")
+    assert bench.full_sections(full, 0, 1, 1) == bench.FULL_SECTIONS[1:]
+    assert bench.full_sections(full, 0, 2, 20) == () and bench.full_sections(full, 1, 2, 20) == ()
+    assert bench.full_sections(bench.parse(plain + ["--full", "--no-sweep"]), 0, 1, 20) == \
+        ("single_step_launch", "extra_configs", "cpu_baseline")
+    assert bench.full_sections(bench.parse(plain + ["--full", "--no-extra", "--no-cpu-baseline"]), 0, 1, 20) == \
+        ("single_step_launch", "roofline_sweep")

@@ -100,18 +100,22 @@ def test_bench_collective_branches_on_rccl():
 
 def test_bench_times_exactly_the_given_steps_and_dumps_the_same_outputs_twice(tmp_path):
     """bench.py --steps K times K steps (here 30 as launches of 7, 7, 7, 7, 2 steps) and --dump-outputs writes what the
-    timed path returned after its last step; two runs with the same arguments write identical arrays."""
+    timed path returned after its last step; two runs with the same arguments write identical arrays.  These are plain
+    runs (no --full): the line carries the headline and nothing that takes a run of its own."""
     import numpy as np
     lines, dumps = [], []
     for run in ("a", "b"):
         d = str(tmp_path / run)
         out = _run_child([sys.executable, "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "3",
-                          "--steps-per-launch", "7", "--no-sweep", "--no-extra", "--no-cpu-baseline", "--dump-outputs", d])
+                          "--steps-per-launch", "7", "--dump-outputs", d])
         lines.append(json.loads([ln for ln in out.splitlines() if ln.startswith("{")][-1]))
         dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))})
     for line in lines:
         assert line["steps"] == 30 and line["config"]["timed_steps"] == 30 and line["config"]["steps_per_launch"] == 7
         assert "5 launches" in line["roofline"]["timing"]
+        assert not {"single_step_launch", "roofline_sweep", "extra_configs"} & set(line) and line["cpu_baseline"] is None
+        assert line["metric"].startswith("env-steps/sec") and line["unit"] == "env-steps/sec" and line["dtype"] == "f64"
+        assert line["higher_is_better"] is True and line["value"] > 1e6
         assert line["ms_per_step"] > 0 and abs(line["ms_per_step"] * 30 - line["config"]["timed_region_ms"]) < 1e-2
     a, b = dumps
     assert sorted(a) == sorted(b) and {"reward", "done", "info", "obs_human_pos", "finished_count"} <= set(a)

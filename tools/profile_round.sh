@@ -72,10 +72,10 @@ cd "$ROOT"
 mkdir -p "$OUT/mfma_all" && cp -r "$OUT/mfma_sarl" "$OUT/mfma_sgan" "$OUT/mfma_all/"
 python3 tools/pmc_mfma.py "$OUT/mfma_all" "$DST/${TAG}_pmc_mfma.json"
 echo "pmc MFMA done"
-# 2. the bench command itself under kernel tracing (same flags as the driver's N=1 run), PMC summaries in place
+# 2. the bench command itself under kernel tracing (the driver's N=1 run plus --full: every section's kernels), PMC summaries in place
 cp "$DST/${TAG}_pmc_env_step.json" "$DST/${TAG}_pmc_env_rollout.json" "$DST/${TAG}_pmc_sq.json" "$DST/${TAG}_pmc_nets.json" "$ROOT/profiles/"
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 \
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --full \
     > "$DST/${TAG}_bench_stdout.json" 2> "$OUT/bench.err" || { tail -5 "$OUT/bench.err"; exit 1; }
 cp "$(find "$OUT/stats" -name '*kernel_stats.csv' | head -1)" "$DST/${TAG}_bench_kernel_stats.csv"
 # the headline kernel is launched with several lengths in one run: per-launch durations by class, from the trace
