@@ -225,6 +225,57 @@ def _build_batch(N, visible, variant, seed):
     return st, np.concatenate(axs + [pax]), np.concatenate(ays + [pay]), nms + ["pad"] * PAD
 
 
+# The ORCA variants a 5-human, invisible-robot quad path can run (max_neighbors >= 4): what the four-wavefront rollout
+# form is built for.
+WG4_VARIANTS = tuple(v for v in ORCA_VARIANTS if orca_cfg(v)["max_neighbors"] >= 4)
+# tests/test_oracle_edges.py CASES["parallel_same_lp3"] (searched): the agent, then its three neighbours
+_PARALLEL_SAME_LP3 = dict(pos=(-1.75, 1.875), vel=(0.1875, 1.0), vpref=0.5, pref=(0.6875, 0.125),
+                          opos=((2.375, 1.125), (-0.25, 1.25), (0.5, 1.25)),
+                          ovel=((0.25, 0.25), (-0.5, -0.9375), (-0.625, 0.875)))
+SUPPLEMENT = 8                   # one env per slot of an 8-env workgroup
+
+
+def lp3_parallel_supplement():
+    """SUPPLEMENT 5-human envs (robot invisible, default ORCA parameters) whose first step reaches parallel_same_lp3,
+    the one quad event that edge_batch(5, False, .) reaches under no variant.  The searched single-agent case is laid out
+    as an env: the agent (v_pref 0.5, goal = position + preferred velocity), its three neighbours (at rest on their
+    goals as far as their own preference goes), a fifth human at (40, 40) and the robot at (-40, -40), both out of
+    range.  Env c holds the five roles rotated by c human slots, so that the agent sits in each lane group of a quad
+    layout.  It is a batch of its own: edge_batch and its blocks are what they were.
+    Returns (EnvState, ax, ay, names)."""
+    c = _PARALLEL_SAME_LP3
+    N, E = 5, SUPPLEMENT
+    pos = np.array((c["pos"],) + c["opos"] + ((40.0, 40.0),))
+    vel = np.array((c["vel"],) + c["ovel"] + ((0.0, 0.0),))
+    goal = pos.copy()
+    goal[0] += c["pref"]
+    vpref = np.array([c["vpref"], 1.0, 1.0, 1.0, 1.0])
+    st = cport.EnvState(E, N)
+    for e in range(E):
+        k = (np.arange(N) + e) % N           # role i sits in human slot k[i]
+        st.hpx[e, k], st.hpy[e, k] = pos[:, 0], pos[:, 1]
+        st.hvx[e, k], st.hvy[e, k] = vel[:, 0], vel[:, 1]
+        st.hgx[e, k], st.hgy[e, k] = goal[:, 0], goal[:, 1]
+        st.hvpref[e, k] = vpref
+    st.hr[:] = HR
+    st.rpx[:], st.rpy[:], st.rgx[:], st.rgy[:] = -40.0, -40.0, -40.0, -35.0
+    st.rvx[:] = 0; st.rvy[:] = 0; st.rr[:] = HR
+    st.gtime[:] = 0
+    return st, np.zeros(E), np.zeros(E), ["parallel-same-lp3"] * E
+
+
+def with_supplement(batch):
+    """An edge_batch(5, False, .) result with lp3_parallel_supplement() appended."""
+    st, ax, ay, names = batch
+    s, sax, say, snames = lp3_parallel_supplement()
+    return _concat([st, s]), np.concatenate([ax, sax]), np.concatenate([ay, say]), names + snames
+
+
+def take(st, idx):
+    """The envs idx of st, in that order (a copy)."""
+    return _take(st, np.asarray(idx))
+
+
 def oracle_cfg(robot_visible, variant=None, **kw):
     """The oracle config of an edge batch (ModelCrowdNav env defaults + the ORCA variant)."""
     return _oracle_cfg(1 if robot_visible else 0, variant or {}, **kw)

@@ -15,7 +15,8 @@ pytestmark = pytest.mark.gpu
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
 from tests import ladder_states as LS  # noqa: E402
-from tests.test_orca_edges_gpu import ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel, _snapshot  # noqa: E402
+from tests.test_orca_edges_gpu import (ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel, _snapshot,  # noqa: E402
+                                       forced_form, launch, rolled_wg4_battery)
 
 STEP_EVENTS = ("swept_touch", "swept_point", "swept_u_zero", "swept_u_one", "dmin_tie", "danger_edge", "reach_edge",
                "reach_band", "collision_and_reach", "timeout_and_collision", "timeout_edge", "timeout_below",
@@ -198,10 +199,13 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
     """mcn_env_rollout over 8 steps (3 + 5) == 8 mcn_env_step calls, every byte, with and without a scenario pool
     (Explorer records: danger count and distance sum, fin_info / fin_time / fin_return); without a pool also == the
     oracle's trajectory (holonomic: bitwise; unicycle: the heading bitwise); a one-step launch == the oracle's boundary
-    step, bitwise (unicycle: the ladder, the heading and the clock)."""
+    step, bitwise (unicycle: the ladder, the heading and the clock).  Every launch of a quad path asserts the form that
+    went out.  The four-wavefront form double-buffers velocities by step parity, from 0 in every launch: 3 + 5 begins
+    its second launch on an odd step of the sequence (tests/test_orca_edges_gpu.py cuts an even launch too)."""
     torch = _torch()
     from modelcrowdnav_amd.envs import scenarios as S
     Ns, quad, tu = ROLLOUT_PATHS[path]
+    form = forced_form(path)
     tuning(**tu)
     T = 8
     total = {}
@@ -222,7 +226,7 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
                     pool = S.scenario_pool(env.spec(), "test", range(16), N, "circle_crossing")
                     env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=np.arange(E) % 16, fin_slots=2)
             acts_d = acts.to(a.device)
-            a.rollout(acts_d[:3]); a.rollout(acts_d[3:])
+            launch(a, acts_d[:3], form); launch(a, acts_d[3:], form)
             for t in range(T):
                 b.step(acts_d[t])
             torch.cuda.synchronize()
@@ -255,7 +259,7 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
         # trajectories above only show the last step's record and what the Explorer accumulates)
         c = _env(N, visible, dd, count_hh, E, unicycle)
         H.upload(c, st)
-        c.rollout(acts.to(c.device)[:1])
+        launch(c, acts.to(c.device)[:1], form)
         torch.cuda.synchronize()
         ref_st = st.copy()
         ref = cport.env_step(H.oracle_cfg_for(c), ref_st, ax[0], ay[0], update=True)
@@ -267,6 +271,57 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
                              what=what + " first step")
     events = UNICYCLE_EVENTS if unicycle else STEP_EVENTS
     _assert_reached(total, events, path)
+
+
+_LADDER_KEYS = ("reward", "done", "info", "dmin", "hh_count")
+_TRIG_FIELDS = ("rpx", "rpy", "rvx", "rvy", "hpx", "hpy", "hvx", "hvy", "human_times")
+
+
+@pytest.mark.parametrize("unicycle", [False, True])
+def test_wg4_rollout_on_rolled_ladder_batch(unicycle, tuning):
+    """tests/test_orca_edges_gpu.py rolled_wg4_battery on the dyadic ladder batch of 5 humans (discomfort_dist 0.25,
+    overlap count on: alone it reaches every rung event, E = 373), 8 steps as 3 + 1 + 4.  The boundary step is the first:
+    the one-step launch of every roll is held to the equally rolled oracle step bitwise (unicycle: the ladder, the
+    heading and the clock), the trajectories of two rolls to the rolled single steps byte for byte and to the oracle
+    with the field exclusions of test_rollout_on_ladder_batches_equals_single_steps_and_oracle.  The oracle replays
+    the unrolled batch once."""
+    N, T, dd, count_hh = 5, 8, 0.25, True
+    tuning(rollout_fused=1, rollout_split=2)
+    st, ax0, ay0, _, names = LS.ladder_batch(N, False, dd, unicycle)
+    E = st.E
+    rng = np.random.RandomState(N * 2)
+    ax = np.concatenate([ax0[None], rng.randint(0, 17, (T - 1, E)) / 16.0])
+    ay = np.concatenate([ay0[None], (rng.randint(-4, 5, (T - 1, E)) / 16.0) if not unicycle else np.zeros((T - 1, E))])
+    ref_st = st.copy()
+    cfg = H.oracle_cfg_for(_env(N, False, dd, count_hh, E, unicycle))
+    total = {}
+    cport.ladder_counts(reset=True)
+    for t in range(T):
+        ref = cport.env_step(cfg, ref_st, ax[t], ay[t], update=True)
+        if t == 0:
+            ref0, ref_st0 = ref, ref_st.copy()
+            _add(total)
+    cport.ladder_counts(reset=True)
+    _assert_reached(total, UNICYCLE_EVENTS if unicycle else STEP_EVENTS, "rolled ladder batch")
+
+    def check(env, r, r_st, perm, rolled, what, keys, fields):
+        for k in keys:
+            bad = H.bit_mismatch(getattr(env, k).cpu().numpy(), r[k][perm])
+            assert len(bad) == 0, (what, k, len(bad), _where(rolled, bad))
+        H.assert_state_equal(H.download(env), LS.take(r_st, perm), fields=fields, what=what)
+
+    def check_first(env, perm, rolled, what):
+        check(env, ref0, ref_st0, perm, rolled, what, _LADDER_KEYS if unicycle else _LADDER_KEYS + ("human_act",),
+              ("rtheta", "gtime") if unicycle else H.STATE_FIELDS + ("rtheta",))
+
+    def check_last(env, perm, rolled, what):
+        # unicycle: later steps see device-trig robot positions, so only the heading, the clock and what does not move
+        fields = H.STATE_FIELDS + ("rtheta",)
+        check(env, ref, ref_st, perm, rolled, what, () if unicycle else _LADDER_KEYS + ("human_act",),
+              tuple(f for f in fields if f not in _TRIG_FIELDS) if unicycle else fields)
+
+    rolled_wg4_battery(lambda: _env(N, False, dd, count_hh, E, unicycle), LS.take, st, np.stack([ax, ay], -1), names,
+                       (0, 3, 4, T), check_first, check_last, "rolled ladder batch unicycle=%d" % unicycle)
 
 
 def _sarl(seed=0, zero=True):

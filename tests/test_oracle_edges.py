@@ -151,6 +151,83 @@ def test_edge_batches_reach_every_counter(family):
     assert not missing, total
 
 
+def test_edge_batches_are_the_recorded_ones(golden_dir):
+    """edge_batch(N, visible, variant) returns the arrays and names it returned when tests/golden/edge_batch_sha256.json
+    was recorded (before the supplement was added): other tests pick envs by block name and hold step ranges found on
+    these scenes (tests/test_rollout_chain_gpu.py, tests/closed_loop_states.py), so the blocks must not move."""
+    import hashlib
+    import json
+    with open(os.path.join(golden_dir, "edge_batch_sha256.json")) as f:
+        want = json.load(f)
+    assert len(want) == 10 * 2 * len(ES.ORCA_VARIANTS)
+    for key in sorted(want):
+        N, visible, vidx = (int(x) for x in key.split("-"))
+        st, ax, ay, names = ES.edge_batch(N, bool(visible), ES.ORCA_VARIANTS[vidx])
+        h = hashlib.sha256()
+        for v in [getattr(st, k) for k in ES._fields()] + [ax, ay]:
+            h.update(np.ascontiguousarray(v, dtype=np.float64).tobytes())
+        h.update("|".join(names).encode())
+        assert h.hexdigest() == want[key], key
+
+
+def test_parallel_same_lp3_supplement():
+    """Every env of the supplement moves parallel_same_lp3 on its first step, whichever human slot holds the agent, and
+    nothing else; edge_batch(5, False, .) reaches it under no variant the quad kernels take (why the supplement exists)."""
+    st, ax, ay, names = ES.lp3_parallel_supplement()
+    assert st.E == ES.SUPPLEMENT == len(names) == len(ax) == 8 and st.N == 5
+    for e in range(st.E):
+        cport.edge_counts(reset=True)
+        cport.env_step(ES.oracle_cfg(False), ES.take(st, [e]), ax[e:e + 1], ay[e:e + 1], update=False)
+        moved = {k: v for k, v in cport.edge_counts(reset=True).items() if v}
+        assert moved == {"parallel_same_lp3": 1}, (e, moved)
+    for variant in ES.WG4_VARIANTS:
+        b = ES.edge_batch(5, False, variant)
+        cport.edge_counts(reset=True)
+        cport.env_step(ES.oracle_cfg(False, variant), b[0], b[1], b[2], update=False)
+        assert cport.edge_counts(reset=True)["parallel_same_lp3"] == 0, variant
+    both = ES.with_supplement(ES.edge_batch(5, False))
+    assert both[0].E == 629 + 8 == len(both[3]) == len(both[1]) and both[0].E % 8 == 5
+    assert both[3][:629] == ES.edge_batch(5, False)[3]
+
+
+def test_four_wavefront_inputs_reach_every_event():
+    """The four-wavefront rollout form runs one shape only (5 humans, robot invisible, max_neighbors >= 4), so its GPU
+    tests have no other human count to borrow an event from.  Its inputs alone -- edge_batch(5, False, .) under the three
+    variants it takes plus the supplement, and ladder_batch(5, False, ., .) -- reach all 13 quad ORCA events on the first
+    step, all 16 rung events, and with a unicycle robot the two heading events as well."""
+    from tests.test_ladder_gpu import STEP_EVENTS, UNICYCLE_EVENTS, _configs
+    from tests.test_orca_edges_gpu import QUAD_EVENTS
+    from tests import ladder_states as LS
+    assert ES.WG4_VARIANTS == ({}, {"neighbor_dist": 1.5}, {"safety_space": 0.0625})
+    total = dict.fromkeys(cport.EDGE_NAMES, 0)
+    for variant in ES.WG4_VARIANTS:
+        batch = ES.edge_batch(5, False, variant)
+        st, ax, ay, names = ES.with_supplement(batch) if not variant else batch
+        cport.edge_counts(reset=True)
+        cport.env_step(ES.oracle_cfg(False, variant), st, ax, ay, update=False)
+        for k, v in cport.edge_counts(reset=True).items():
+            total[k] += v
+    assert len(QUAD_EVENTS) == 13
+    missing = [k for k in QUAD_EVENTS if total[k] == 0]
+    assert not missing, total
+    assert total["tie_at_cut"] == 0          # no cut of the neighbour list with max_neighbors >= 4 candidates
+    for unicycle, events in ((False, STEP_EVENTS), (True, UNICYCLE_EVENTS)):
+        total = {}
+        sizes = []
+        for N, visible, dd, count_hh in _configs([5], True):
+            assert not visible
+            st, ax, ay, _, names = LS.ladder_batch(N, visible, dd, unicycle)
+            sizes.append(st.E)
+            cport.ladder_counts(reset=True)
+            cport.env_step(LS.cfg(visible, dd, count_hh, unicycle), st, ax, ay, update=True)
+            for k, v in cport.ladder_counts(reset=True).items():
+                total[k] = total.get(k, 0) + v
+        assert sizes == [341, 373]           # ragged against workgroups of 8 envs
+        missing = [k for k in events if total.get(k, 0) == 0]
+        assert not missing, (unicycle, total)
+    assert len(STEP_EVENTS) == 16 and len(UNICYCLE_EVENTS) == 18
+
+
 def test_edge_batches_are_dyadic_and_deterministic():
     st, ax, ay, names = ES.edge_batch(5, True)
     st2, ax2, ay2, _ = ES._build_batch(5, True, {}, 0)

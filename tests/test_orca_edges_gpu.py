@@ -123,25 +123,66 @@ ROLLOUT_PATHS = {
     "step-loop": (range(6, 11), False, dict(rollout_fused=1, lp3_defer=0)),
     "lp3-defer": (range(2, 11), False, dict(rollout_fused=1, lp3_defer=1)),
     "unfused": (range(1, 11), False, dict(rollout_fused=0)),
+    # the four-wavefront form (env_rollout_wg4.hip): built for 5 humans and an invisible robot only
+    "quad-rollout-wg4": ((5,), True, dict(rollout_fused=1, rollout_split=2)),
 }
+WG4_SLOTS = 8                     # envs per workgroup of the four-wavefront form
+WG4_STRADDLERS = (3, 6)           # quad q = 5 env + human: the envs in these slots have quads in two ORCA wavefronts
+# the four-wavefront form double-buffers velocities by step parity, from 0 in every launch: an odd launch, a one-step
+# launch and an even one
+WG4_EDGE_CUTS = (0, 9, 10, 24)
+_SLOT_MAJOR = ("roll_fin_return", "roll_fin_time", "roll_fin_info")      # [fin_slots, E]; everything else is [E, ...]
+_STEP_KEYS = ("reward", "done", "info", "dmin", "hh_count", "human_act")
+
+
+def forced_form(path):
+    """The rollout form a quad path forces (mcn_tuning.rollout_split), None for the other paths."""
+    Ns, quad, tu = ROLLOUT_PATHS[path]
+    return tu["rollout_split"] if quad else None
+
+
+def launch(env, acts, form):
+    """env.rollout(acts); a quad path must have gone out as the form it forces: the three forms share one dispatch
+    family and leave the same bytes, so nothing else would show that another kernel stood in."""
+    from modelcrowdnav_amd import _hip
+    env.rollout(acts)
+    if form is not None:
+        assert _hip.last_dispatch() == "env_rollout_quad_kernel", _hip.last_dispatch()
+        assert _hip.last_rollout_form() == form, (_hip.last_rollout_form(), form)
+
+
+def _assert_step_equals_oracle(env, ref, ref_st, names, what, keys=_STEP_KEYS, fields=H.STATE_FIELDS):
+    for k in keys:
+        bad = H.bit_mismatch(getattr(env, k).cpu().numpy(), ref[k])
+        assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+    H.assert_state_equal(H.download(env), ref_st, fields=fields, what=what)
 
 
 @pytest.mark.parametrize("path", sorted(ROLLOUT_PATHS))
 def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
-    """mcn_env_rollout over 24 steps in two launches (10 + 14) == 24 mcn_env_step calls, every byte; without a scenario
-    pool also == the oracle's 24-step trajectory, bitwise; with one (episodes that end restart from it) the launch and
-    the single steps still agree byte for byte."""
+    """mcn_env_rollout over 24 steps in two launches (10 + 14; the four-wavefront form 9 + 1 + 14) == 24 mcn_env_step
+    calls, every byte; without a scenario pool also == the oracle's 24-step trajectory, bitwise; with one (episodes that
+    end restart from it) the launch and the single steps still agree byte for byte.  Every launch of a quad path asserts
+    the form that went out.  The four-wavefront form has one shape only, so it runs every ORCA variant that shape takes,
+    the parallel_same_lp3 supplement with the default one, and a one-step launch of its own against the oracle's first
+    step."""
     torch = _torch()
     from modelcrowdnav_amd.envs import scenarios as S
     Ns, quad, tu = ROLLOUT_PATHS[path]
+    form = forced_form(path)
+    wg4 = form == 2
     tuning(**tu)
     T = 24
+    cuts = WG4_EDGE_CUTS if wg4 else (0, 10, T)
     total = dict.fromkeys(ALL_EVENTS, 0)
     for N in Ns:
-        # the default ORCA parameters and one of the others, in turn
-        variants = (ES.ORCA_VARIANTS[0], ES.ORCA_VARIANTS[1 + N % 4])
+        # the default ORCA parameters and one of the others, in turn (at N = 5 that one is max_neighbors = 3, which no
+        # quad path takes)
+        variants = ES.WG4_VARIANTS if wg4 else (ES.ORCA_VARIANTS[0], ES.ORCA_VARIANTS[1 + N % 4])
         for n_, visible, variant in _configs([N], quad, variants):
             st, ax0, ay0, names = ES.edge_batch(N, visible, variant)
+            if wg4 and not variant:
+                st, ax0, ay0, names = ES.with_supplement((st, ax0, ay0, names))
             E = st.E
             rng = np.random.RandomState(N * 2 + visible)
             ax = np.concatenate([ax0[None], rng.randint(-16, 17, (T - 1, E)) / 16.0])
@@ -157,7 +198,8 @@ def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
                         env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=np.arange(E) % 16,
                                            fin_slots=2)
                 acts_d = acts.to(a.device)
-                a.rollout(acts_d[:10]); a.rollout(acts_d[10:])
+                for lo, hi in zip(cuts[:-1], cuts[1:]):
+                    launch(a, acts_d[lo:hi], form)
                 for t in range(T):
                     b.step(acts_d[t])
                 torch.cuda.synchronize()
@@ -171,14 +213,127 @@ def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
                 cport.edge_counts(reset=True)
                 for t in range(T):
                     ref = cport.env_step(cfg, ref_st, ax[t], ay[t], update=True)
+                    if t == 0:
+                        ref0, ref_st0 = ref, ref_st.copy()
                 for k, v in cport.edge_counts(reset=True).items():
                     total[k] += v
-                H.assert_state_equal(H.download(a), ref_st, what=what)
-                for k, v in (("reward", a.reward), ("done", a.done), ("info", a.info), ("dmin", a.dmin),
-                             ("hh_count", a.hh_count), ("human_act", a.human_act)):
-                    bad = H.bit_mismatch(v.cpu().numpy(), ref[k])
-                    assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+                _assert_step_equals_oracle(a, ref, ref_st, names, what)
+                if wg4:
+                    c = _env(N, visible, variant, E)
+                    H.upload(c, st)
+                    launch(c, acts_d[:1], form)
+                    torch.cuda.synchronize()
+                    _assert_step_equals_oracle(c, ref0, ref_st0, names, what + " first step")
     _assert_reached(total, QUAD_EVENTS if quad else ALL_EVENTS, path)
+
+
+def _roll_snapshot(snap, perm):
+    return {k: np.take(v, perm, axis=1 if k in _SLOT_MAJOR else 0) for k, v in snap.items()}
+
+
+def rolled_wg4_battery(build, take, st, acts, names, cuts, check_first, check_last, what, odd_roll=3):
+    """The four-wavefront form on one batch under np.roll of the env order by 0 .. 7, so that every env meets every slot
+    of an 8-env workgroup (each of the three ORCA wavefronts sees other envs, and the envs in slots 3 and 6 straddle
+    two of them); the rare events sit at fixed offsets of their 16-env blocks and would otherwise only ever meet the
+    same slots.  Actions and first_cases roll with the envs.
+
+      every roll              a one-step launch; check_first(env, perm, rolled names, what) holds it to the oracle
+      roll 0 and odd_roll     the whole sequence in the launches `cuts`, without and with a scenario pool: every byte of
+                              the equally rolled result of single mcn_env_step calls (run once, unrolled), and without
+                              a pool check_last(...) against the oracle
+
+    build() gives a configured env, take(st, perm) the envs of an oracle state in another order."""
+    torch = _torch()
+    from modelcrowdnav_amd.envs import scenarios as S
+    E, T = st.E, len(acts)
+    assert cuts[0] == 0 and cuts[-1] == T
+    cases = np.arange(E) % 16
+    ident = np.arange(E)
+
+    def start(perm, with_pool):
+        env = build()
+        H.upload(env, take(st, perm))
+        if with_pool:
+            pool = S.scenario_pool(env.spec(), "test", range(16), st.N, "circle_crossing")
+            env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=cases[perm], fin_slots=2)
+        return env, torch.from_numpy(np.ascontiguousarray(acts[:, perm])).to(env.device)
+
+    singles = {}
+    for with_pool in (False, True):
+        env, a = start(ident, with_pool)
+        for t in range(T):
+            env.step(a[t])
+        torch.cuda.synchronize()
+        singles[with_pool] = _snapshot(env)
+    assert set(_SLOT_MAJOR) <= set(singles[True])
+    seen = [set() for _ in range(E)]
+    for r in range(WG4_SLOTS):
+        perm = np.roll(ident, r)
+        rolled = [names[i] for i in perm]
+        for pos, i in enumerate(perm):
+            seen[i].add(pos % WG4_SLOTS)
+        env, a = start(perm, False)
+        launch(env, a[:1], 2)
+        torch.cuda.synchronize()
+        check_first(env, perm, rolled, "%s roll %d first step" % (what, r))
+        if r not in (0, odd_roll):
+            continue
+        for with_pool in (False, True):
+            env, a = start(perm, with_pool)
+            for lo, hi in zip(cuts[:-1], cuts[1:]):
+                launch(env, a[lo:hi], 2)
+            torch.cuda.synchronize()
+            got, want = _snapshot(env), _roll_snapshot(singles[with_pool], perm)
+            for k in got:
+                assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), (what, "roll", r, with_pool, k)
+            if not with_pool:
+                check_last(env, perm, rolled, "%s roll %d" % (what, r))
+    # over the rolls every env but the last few (which wrap to the front) sat in every slot, and an env of every block
+    # sat in the two straddling ones
+    assert all(s == set(range(WG4_SLOTS)) for s in seen[:E - WG4_SLOTS + 1])
+    for block in sorted(set(names)):
+        slots = set().union(*(seen[i] for i in range(E) if names[i] == block))
+        assert set(WG4_STRADDLERS) <= slots, (what, block, sorted(slots))
+
+
+def test_wg4_rollout_on_rolled_edge_batch(tuning):
+    """rolled_wg4_battery on the default-variant edge batch of 5 humans plus the parallel_same_lp3 supplement (E = 637,
+    24 steps as 9 + 1 + 14); the oracle replays the unrolled batch once and its outputs are rolled."""
+    N, T, variant = 5, 24, ES.ORCA_VARIANTS[0]
+    tuning(rollout_fused=1, rollout_split=2)
+    st, ax0, ay0, names = ES.with_supplement(ES.edge_batch(N, False, variant))
+    E = st.E
+    rng = np.random.RandomState(N * 2)
+    ax = np.concatenate([ax0[None], rng.randint(-16, 17, (T - 1, E)) / 16.0])
+    ay = np.concatenate([ay0[None], rng.randint(-16, 17, (T - 1, E)) / 16.0])
+    ref_st = st.copy()
+    cfg = H.oracle_cfg_for(_env(N, False, variant, E))
+    cport.edge_counts(reset=True)
+    for t in range(T):
+        ref = cport.env_step(cfg, ref_st, ax[t], ay[t], update=True)
+        if t == 0:
+            ref0, ref_st0, first = ref, ref_st.copy(), cport.edge_counts(reset=False)
+    total = cport.edge_counts(reset=True)
+    # what the default variant reaches at N = 5 (tests/test_oracle_edges.py holds the counts); the one-step launches of
+    # all eight rolls see every one of these but the events of later steps
+    events = [k for k in QUAD_EVENTS if k != "parallel_opposite_lp3"]
+    _assert_reached(first, events, "rolled edge batch, first step")
+    _assert_reached(total, events, "rolled edge batch")
+
+    def build():
+        return _env(N, False, variant, E)
+
+    def rolled_ref(r, perm):
+        return {k: r[k][perm] for k in _STEP_KEYS}
+
+    def check_first(env, perm, rolled, what):
+        _assert_step_equals_oracle(env, rolled_ref(ref0, perm), ES.take(ref_st0, perm), rolled, what)
+
+    def check_last(env, perm, rolled, what):
+        _assert_step_equals_oracle(env, rolled_ref(ref, perm), ES.take(ref_st, perm), rolled, what)
+
+    rolled_wg4_battery(build, ES.take, st, np.stack([ax, ay], -1), names, WG4_EDGE_CUTS, check_first, check_last,
+                       "rolled edge batch")
 
 
 def _lattice_scene(rng, n, spacing, max_neighbors):

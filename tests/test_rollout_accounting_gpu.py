@@ -58,7 +58,8 @@ pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
 from tests import rollout_ref as R  # noqa: E402
-from tests.test_orca_edges_gpu import ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel  # noqa: E402
+from tests.test_orca_edges_gpu import (ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel, forced_form,  # noqa: E402
+                                       launch)
 
 STEP_DTYPE = np.dtype([("reward", "f8"), ("dmin", "f8"), ("done", "u1"), ("info", "u1"), ("reserved", "u2"),
                        ("hh_count", "i4")])                                             # mcn_step_rec
@@ -67,8 +68,8 @@ STEP_DTYPE = np.dtype([("reward", "f8"), ("dmin", "f8"), ("done", "u1"), ("info"
 ORCA_STEP = ([(k, 5) for k in STEP_KERNELS] + [(k, 7) for k in STEP_KERNELS if k != "auto" and not k.startswith("quad")] +
              [("auto", 10), ("deferred-lp3", 10), ("run-time-N-256", 10)])
 GIVEN_STEP = [(ps, N) for N in (5, 10) for ps in (0, 1, 2)]
-ROLLOUT = [("quad-rollout", 5), ("quad-rollout-split", 5), ("step-loop", 7), ("lp3-defer", 7), ("lp3-defer", 10),
-           ("unfused", 5), ("unfused", 10)]
+ROLLOUT = [("quad-rollout", 5), ("quad-rollout-split", 5), ("quad-rollout-wg4", 5), ("step-loop", 7), ("lp3-defer", 7),
+           ("lp3-defer", 10), ("unfused", 5), ("unfused", 10)]
 assert {p for p, _ in ROLLOUT} == set(ROLLOUT_PATHS) and all(N in ROLLOUT_PATHS[p][0] for p, N in ROLLOUT)
 PATHS = ([("step",) + c for c in ORCA_STEP] + [("given",) + c for c in GIVEN_STEP] + [("rollout",) + c for c in ROLLOUT])
 PATH_IDS = ["%s-%s-N%d" % p for p in PATHS]
@@ -189,7 +190,7 @@ def _run(path, w, tuning, null=()):
     acts = torch.from_numpy(w.acts).to(env.device)
     if kind == "rollout":
         for a, b in SPLITS:
-            env.rollout(acts[a:b])
+            launch(env, acts[a:b], forced_form(which))      # a quad path: the forced form is the one that went out
             _compare(env, w, b, what, null)
             _compare_step_recs(env.step_rec.cpu().numpy()[None], w, [b - 1], what)
         return _hip.last_dispatch()
@@ -211,8 +212,8 @@ def _expected_dispatch(path, w):
         return "env_pair_kernel" if which and w.contract.disc_len <= 128 else "env_step_kernel"
     if kind == "rollout":
         return {"quad-rollout": "env_rollout_quad_kernel", "quad-rollout-split": "env_rollout_quad_kernel",
-                "step-loop": "env_step_loop_kernel", "lp3-defer": "env_step_kernel",
-                "unfused": "env_step_quad_kernel" if N == 5 else "env_step_kernel"}[which]
+                "quad-rollout-wg4": "env_rollout_quad_kernel", "step-loop": "env_step_loop_kernel",
+                "lp3-defer": "env_step_kernel", "unfused": "env_step_quad_kernel" if N == 5 else "env_step_kernel"}[which]
     return "env_step_quad_kernel" if which.startswith("quad") or (which == "auto" and N == 5) else "env_step_kernel"
 
 
