@@ -17,14 +17,14 @@ def main():
     from modelcrowdnav_amd import dist as mdist
     from modelcrowdnav_amd.rollout import VecExplorer
     from tests import helpers as H
-    from tests.test_rollout_gpu import _goal_seeking
+    from tests.rollout_harness import goal_seeking
     mdist.init_from_env("gloo")
     lo, hi = mdist.shard(E_total, rank, ws)
     env = H.make_vec_env(hi - lo, N)
     env.track_human_times = False
     env.export_human_actions = False
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-    res = ex.run_k_episodes(k, "test", action_fn=_goal_seeking, returnNav=True, total_envs=E_total)
+    res = ex.run_k_episodes(k, "test", action_fn=goal_seeking, returnNav=True, total_envs=E_total)
     json.dump({"result": list(res), "records": ex.last_records}, open(out, "w"))
     import torch.distributed as dist
     dist.barrier()

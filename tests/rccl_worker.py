@@ -15,7 +15,7 @@ def main():
     from modelcrowdnav_amd import dist as mdist
     from modelcrowdnav_amd.rollout import VecExplorer
     from tests import helpers as H
-    from tests.test_rollout_gpu import _goal_seeking
+    from tests.rollout_harness import goal_seeking
     rank, ws = mdist.init_from_env("nccl", force=True)
     res = {"backend": dist.get_backend(), "world": ws}
     dev = torch.device("cuda", 0)
@@ -29,7 +29,7 @@ def main():
     env.track_human_times = False
     env.export_human_actions = False
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-    r = ex.run_k_episodes(80, "test", action_fn=_goal_seeking, returnNav=True, total_envs=32)
+    r = ex.run_k_episodes(80, "test", action_fn=goal_seeking, returnNav=True, total_envs=32)
     res.update(result=list(r), records=ex.last_records)
     json.dump(res, open(out, "w"))
     dist.barrier()

@@ -177,8 +177,8 @@ class Replay(object):
 # ---------------------------------------------------------------------------------------------------------------------
 # the reference's own loop on one case (explorer.py:62-125 with the exact goal-seeking robot)
 
-def goal_seeking(st, speed=0.6):
-    """tests/test_rollout_gpu.py::_goal_seeking on the host: +-speed along each axis by the sign of the remaining goal
+def host_goal_seeking(st, speed=0.6):
+    """tests/rollout_harness.py goal_seeking on the host: +-speed along each axis by the sign of the remaining goal
     offset, 0 inside a 0.2 band.  Exact on any IEEE machine."""
     dx, dy = st.rgx - st.rpx, st.rgy - st.rpy
     ax = np.where(dx > 0.2, speed, 0.0) - np.where(dx < -0.2, speed, 0.0)
@@ -351,7 +351,7 @@ def _simulate(name, N, mode, short_from, shift=None):
     seeker = role != 2
     late = role == 1                    # these stand still for the first `wait` steps of every episode
     for t in range(T):
-        gx, gy = goal_seeking(st, speed)
+        gx, gy = host_goal_seeking(st, speed)
         wait = np.where(late, s.get("wait", 40), 0) + 2 * (rep.rec["fin_count"] % 5)
         hold = rep.rec["ep_steps"] < wait
         gx, gy = np.where(hold, 0.0, gx), np.where(hold, 0.0, gy)

@@ -41,18 +41,13 @@ from tests import closed_loop_ref as CR  # noqa: E402
 from tests import closed_loop_states as CS  # noqa: E402
 from tests import helpers as H  # noqa: E402
 from tests import rollout_ref as R  # noqa: E402
+from tests.rollout_harness import need_gpu  # noqa: E402
 from tests.test_closed_loop_ref_cpu import G16_CASES, g16_rows, g16_start, required_events  # noqa: E402
 
 GAMMA = 0.9
 STATE_FIELDS = H.STATE_FIELDS + ("rtheta",)
 REC_FIELDS = ("reward", "dmin", "done", "info", "hh_count")
 PLAIN_TRACES = ("robot", "humans", "hrad", "action", "human_act")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
 
 
 def _policy(pol):
@@ -65,7 +60,7 @@ def _policy(pol):
 
 def _env(st, rvpref, visible, humans=None, **over):
     """A VecCrowdSim holding the oracle state `st` (and the robot's max speeds); humans: the humans' own ORCA parameters."""
-    torch = _torch()
+    torch = need_gpu()
     env = H.make_vec_env(st.E, st.N, robot_visible=visible, **over)
     for k, v in (humans or {}).items():
         setattr(env._orca, k, v)
@@ -147,7 +142,7 @@ ROBOT = CR.RobotPolicy(0.15, 10.0, 10, 5.0)          # imitation learning: a saf
 def _shape_workload(N, visible):
     """Env, policy, rollout buffers and the host copy of everything the replay needs.  2 s time limit: an episode times
     out on its fifth step; every fourth env starts with its robot 0.875 m from the goal and arrives first."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs import scenarios as S
     E = SHAPES[N]
     over = {"env.time_limit": 2, "env.randomize_attributes": "true"}             # restarts change the radii
@@ -180,7 +175,7 @@ def _shape_workload(N, visible):
 @pytest.mark.parametrize("visible", [False, True])
 @pytest.mark.parametrize("N", sorted(SHAPES))
 def test_shapes_equal_the_replay(N, visible):
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     env, bufs, rep = _shape_workload(N, visible)
     st0, rvpref = H.download(env), env.rvpref.cpu().numpy()
@@ -204,7 +199,7 @@ def test_shapes_equal_the_replay(N, visible):
 # ------------------------------------------------------------------------------------------------------------ edge batches
 @pytest.mark.parametrize("N", CS.HUMAN_COUNTS)
 def test_edge_batches_equal_the_replay(N):
-    torch = _torch()
+    torch = need_gpu()
     total = {}
     for c, (mn, nd, ss, visible) in enumerate(CS.CONFIGS):
         r = CS.edge_replay(N, c)
@@ -263,7 +258,7 @@ SLOT_ROWS = [(2, 10, 10, False), (10, 2, 10, True), (0, 10, 5, False), (10, 0, 5
 
 @pytest.mark.parametrize("hmn,rmn,N,visible", SLOT_ROWS)
 def test_line_slots_robot_and_humans_need_different_counts(hmn, rmn, N, visible):
-    torch = _torch()
+    torch = need_gpu()
     st, vp = _packed(N, SLOT_ROWS.index((hmn, rmn, N, visible)))
     pol = CR.RobotPolicy(0.0625, 10.0, rmn, 5.0)
     env = _env(st, vp, visible, humans=dict(max_neighbors=hmn))
@@ -291,7 +286,7 @@ def test_line_slots_robot_and_humans_need_different_counts(hmn, rmn, N, visible)
 def test_line_slots_linear_humans_against_the_per_step_twin():
     """Linear humans have no line slots of their own (nl_cap 0), the robot needs 10 of them at 32 humans.  The oracle
     matches the linear humans' device trigonometry to 1e-12, not bitwise, so the yardstick is the per-step twin."""
-    torch = _torch()
+    torch = need_gpu()
     from tests.test_closed_loop_gpu import _assert_equal_traces, _per_step, _same, STATE
     st, vp = _packed(32, 9)
     pol = CR.RobotPolicy(0.0625, 10.0, 10, 5.0)
@@ -309,7 +304,7 @@ def test_line_slots_linear_humans_against_the_per_step_twin():
 # ------------------------------------------------------------------------------------------------------ reference episodes
 @pytest.mark.parametrize("visible", [0, 1])
 def test_reference_episodes_in_one_launch(visible, golden_dir):
-    torch = _torch()
+    torch = need_gpu()
     g = np.load(os.path.join(golden_dir, "g16_orca_robot.npz"))
     keys = ["v%d_c%d_" % (visible, c) for c in G16_CASES]
     lengths = [g[k + "actions"].shape[0] for k in keys]
@@ -359,7 +354,7 @@ def _opt_start():
 
 def _launch(env, pol, T, roll=None, out=None, st=None, null=()):
     """mcn_env_rollout_orca called directly; `null`: the traces passed as NULL.  Returns the trace tensors."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     E, N, dev = env.num_envs, env._alloc_N, env.device
     z = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float64, device=dev)
@@ -417,7 +412,7 @@ def test_optional_pointers_state_without_a_pool():
 
 
 def test_optional_pointers_no_human_act_no_rtheta_and_an_hcount():
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     env, st0, cfg = _opt_env()
     r = CS.replay(st0, np.ones(E_OPT), POL_OPT, cfg, T_OPT, count=False)
@@ -464,7 +459,7 @@ def test_margin_order_is_the_references_in_all_three_robots():
     """One human of a radius at which (r + 0.01) + 0.1 and r + (0.01 + 0.1) round to different float32 values, straight
     ahead of the robot: ORCA.predict (E = 1), ORCA.predict_batch and mcn_env_rollout_orca all take the action of the
     reference's order."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs.utils.state import FullState, JointState, ObservableState
     cases = CS.radius_order_cases()
     assert len(cases) >= 4

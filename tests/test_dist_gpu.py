@@ -16,13 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_two_rank_vec_explorer_equals_single_process(tmp_path, E_total):
     from modelcrowdnav_amd.rollout import VecExplorer
     from tests import helpers as H
-    from tests.test_rollout_gpu import _goal_seeking
+    from tests.rollout_harness import goal_seeking
     N, k = 5, 80
     env = H.make_vec_env(E_total, N)
     env.track_human_times = False
     env.export_human_actions = False
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-    want = list(ex.run_k_episodes(k, "test", action_fn=_goal_seeking, returnNav=True))
+    want = list(ex.run_k_episodes(k, "test", action_fn=goal_seeking, returnNav=True))
     want_rec = ex.last_records
     port = 30100 + (os.getpid() % 2000) + E_total % 7
     outs = [str(tmp_path / ("r%d.json" % r)) for r in range(2)]
@@ -73,12 +73,12 @@ def test_rccl_world_size_one_gather_on_device_tensors(tmp_path):
     # the rollout through the RCCL collective equals the same rollout without a process group
     from modelcrowdnav_amd.rollout import VecExplorer
     from tests import helpers as H
-    from tests.test_rollout_gpu import _goal_seeking
+    from tests.rollout_harness import goal_seeking
     env = H.make_vec_env(32, 5)
     env.track_human_times = False
     env.export_human_actions = False
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-    want = list(ex.run_k_episodes(80, "test", action_fn=_goal_seeking, returnNav=True))
+    want = list(ex.run_k_episodes(80, "test", action_fn=goal_seeking, returnNav=True))
     assert got["result"] == want
     for key in ("returns", "infos", "times"):
         assert got["records"][key] == ex.last_records[key], key

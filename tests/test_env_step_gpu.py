@@ -13,16 +13,12 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
+from tests.rollout_harness import (assert_same_bytes, need_gpu, oracle_rollout, pool_env, random_actions,  # noqa: E402
+                                   snapshot)
 
 
 def _step_both(env, st, ax, ay, update, policy=cport.HUMANS_ORCA, given=None):
-    torch = _torch()
+    torch = need_gpu()
     H.upload(env, st)
     act = torch.from_numpy(np.stack([ax, ay], -1)).to(env.device)
     gv = None if given is None else torch.from_numpy(np.ascontiguousarray(given)).to(env.device)
@@ -138,7 +134,7 @@ def test_roofline_sweep_sizes_every_env_against_the_oracle(E, N, mode):
     in the bounded queue by itself): one step of EVERY env against the C oracle, every byte of state and outputs -- the
     kernels that are measured at these sizes are the kernels that are right at these sizes (64-bit offsets, the
     XCD-chunked grid, the last partial workgroup)."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     rng = np.random.RandomState(E % 1000 + N)
     E = E - 3                      # ragged against every tile size
@@ -193,7 +189,7 @@ def test_streaming_pair_kernel_equals_lane_per_human(N, book, stream, tuning):
     and Explorer record on every lane) against env_step_kernel<GIVEN>: every byte of state, step record, Explorer
     record and finished-episode records over 130 steps with collisions, goals, timeouts and pool restarts; the first
     step also against the C oracle."""
-    torch = _torch()
+    torch = need_gpu()
     E, T = 1003, 130
     rng = np.random.RandomState(40 + N)
 
@@ -203,7 +199,7 @@ def test_streaming_pair_kernel_equals_lane_per_human(N, book, stream, tuning):
             from modelcrowdnav_amd.envs import scenarios as S
             env.load_scenarios(S.scenario_pool(env.spec(), "test", range(64), N, "circle_crossing")[np.arange(E) % 64])
         else:
-            env = _rollout_env(E, N, False, book == "pool", fin_slots=2)
+            env = pool_env(E, N, False, book == "pool")
         env.count_hh = False
         return env
     a, b = make(), make()
@@ -228,13 +224,11 @@ def test_streaming_pair_kernel_equals_lane_per_human(N, book, stream, tuning):
                 H.assert_state_equal(H.download(a), st0, what="streaming pair kernel vs oracle")
         if t % 13 == 0 or t == T - 1:
             torch.cuda.synchronize()
-            sa, sb = _snapshot(a) if book != "none" else None, _snapshot(b) if book != "none" else None
             if book == "none":
                 for k in ("hpos", "hvel", "rpos", "rvel", "gtime", "step_rec"):
                     assert np.array_equal(getattr(a, k).cpu().numpy().view(np.uint8), getattr(b, k).cpu().numpy().view(np.uint8)), (k, t)
             else:
-                for k in sa:
-                    assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), (k, t)
+                assert_same_bytes(snapshot(a), snapshot(b), t)
     if book != "none":
         assert int(a.rollout_buffers["fin_count"].sum().item()) > E // 2
 
@@ -244,7 +238,7 @@ def test_streaming_pair_kernel_equals_lane_per_human(N, book, stream, tuning):
                                          ("g2_step_orca_visible", cport.HUMANS_ORCA)])
 def test_step_matches_reference_fixtures(name, policy, golden_dir):
     """HIP path against values recorded from the real reference env (tests/golden_tools/gen_golden.py)."""
-    torch = _torch()
+    torch = need_gpu()
     g = np.load(os.path.join(golden_dir, name + ".npz"))
     visible = bool(g["robot_visible"])
     tol = 1e-12 if policy == cport.HUMANS_LINEAR else 0.0
@@ -295,7 +289,7 @@ def test_rollout_4096x5_bitexact_trajectory(kernel, tuning):
 def _rollout_4096x5():
     """BASELINE config 2 shape: 4096 envs x 5 humans, ORCA humans, random robot actions, 60 steps.
     Whole trajectories must stay bit-identical to the oracle (any 1-ulp slip would compound)."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs import scenarios as S
     E, N, T = 4096, 5, 60
     env = H.make_vec_env(E, N)
@@ -318,57 +312,32 @@ def _rollout_4096x5():
     assert done_total > 0
 
 
-def _rollout_env(E, N, visible, with_pool, kinematics="holonomic", fin_slots=1):
-    from modelcrowdnav_amd.envs import scenarios as S
-    env = H.make_vec_env(E, N, robot_visible=visible, kinematics=kinematics)
-    pool = S.scenario_pool(env.spec(), "test", range(64), N, "circle_crossing")
-    ids = np.arange(E) % 64
-    env.load_scenarios(pool[ids])
-    env.attach_rollout(gamma=0.9, pool=pool if with_pool else None, case_stride=3, first_cases=(ids + 7) % 64,
-                       fin_slots=fin_slots)
-    return env
-
-
-def _snapshot(env):
-    c = lambda t: t.detach().cpu().numpy().copy()
-    snap = {k: c(getattr(env, k)) for k in ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal",
-                                            "rtheta", "gtime", "human_times", "step_rec", "human_act")}
-    snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items() if k in ("state", "fin_return", "fin_time",
-                                                                                  "fin_info")})
-    return snap
-
-
 @pytest.mark.parametrize("N,visible", [(5, False), (4, True), (3, False), (1, True), (2, False)])
 @pytest.mark.parametrize("with_pool", [True, False])
 @pytest.mark.parametrize("split", ["0", "1"])
 def test_rollout_launch_equals_single_steps(N, visible, with_pool, split, tuning):
     """mcn_env_rollout (T steps in one launch, state in registers) == T mcn_env_step calls, every byte of state,
     step record, Explorer accounting and finished-episode records; episodes end and restart inside the sequence."""
-    torch = _torch()
+    torch = need_gpu()
     E, T = 1000, 110                    # ragged vs the envs-per-wavefront tiling; every env passes the time limit
-    rng = np.random.RandomState(N)
-    sp, aa = rng.uniform(0, 1, (T, E)), rng.uniform(0, 2 * np.pi, (T, E))
-    acts = torch.from_numpy(np.stack([sp * np.cos(aa), sp * np.sin(aa)], -1))
+    acts = torch.from_numpy(random_actions("holonomic", T, E, N))
     tuning(rollout_fused=1)
     tuning(rollout_split=int(split))     # one wavefront per env group / two cooperating ones
-    a = _rollout_env(E, N, visible, with_pool, fin_slots=2)
-    b = _rollout_env(E, N, visible, with_pool, fin_slots=2)
+    a = pool_env(E, N, visible, with_pool)
+    b = pool_env(E, N, visible, with_pool)
     acts_d = acts.to(a.device)
     a.rollout(acts_d[:30]); a.rollout(acts_d[30:31]); a.rollout(acts_d[31:])          # split launches compose
     for t in range(T):
         b.step(acts_d[t])
     torch.cuda.synchronize()
-    sa, sb = _snapshot(a), _snapshot(b)
-    for k in sa:
-        assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), k
+    sb = snapshot(b)
+    assert_same_bytes(snapshot(a), sb)
     assert int(a.rollout_buffers["fin_count"].min().item()) >= 1
     tuning(rollout_fused=0)                # the T-launch path of the same entry point
-    c = _rollout_env(E, N, visible, with_pool, fin_slots=2)
+    c = pool_env(E, N, visible, with_pool)
     c.rollout(acts_d)
     torch.cuda.synchronize()
-    sc = _snapshot(c)
-    for k in sa:
-        assert np.array_equal(sc[k].view(np.uint8), sb[k].view(np.uint8)), k
+    assert_same_bytes(snapshot(c), sb, "unfused")
 
 
 @pytest.mark.parametrize("N,visible", [(10, False), (7, True), (6, False), (5, True)])
@@ -379,13 +348,11 @@ def test_rollout_entry_point_with_larger_crowds(N, visible, defer, tuning):
     times inside ONE launch --, defer = 1 the T single-step launches with parked 3-D LPs; both must leave every byte as T
     mcn_env_step calls do (the oracle comparison over whole trajectories is test_larger_crowd_trajectories_match_oracle
     and, for the looped launch, test_looped_rollout_launch_matches_oracle_trajectory)."""
-    torch = _torch()
+    torch = need_gpu()
     E, T = 300, 110
-    rng = np.random.RandomState(N)
-    sp, aa = rng.uniform(0, 1, (T, E)), rng.uniform(0, 2 * np.pi, (T, E))
-    acts = torch.from_numpy(np.stack([sp * np.cos(aa), sp * np.sin(aa)], -1))
-    a = _rollout_env(E, N, visible, True, fin_slots=2)
-    b = _rollout_env(E, N, visible, True, fin_slots=2)
+    acts = torch.from_numpy(random_actions("holonomic", T, E, N))
+    a = pool_env(E, N, visible, True)
+    b = pool_env(E, N, visible, True)
     acts_d = acts.to(a.device)
     # defer = 1: a's launches park the 3-D LPs (pool restarts, first-arrival times and exported actions then come
     # from two kernels); b always solves them in the step kernel
@@ -395,9 +362,7 @@ def test_rollout_entry_point_with_larger_crowds(N, visible, defer, tuning):
     for t in range(T):
         b.step(acts_d[t])
     torch.cuda.synchronize()
-    sa, sb = _snapshot(a), _snapshot(b)
-    for k in sa:
-        assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), k
+    assert_same_bytes(snapshot(a), snapshot(b))
     assert int(a.rollout_buffers["fin_count"].min().item()) >= 1
 
 
@@ -406,7 +371,7 @@ def test_looped_rollout_launch_matches_oracle_trajectory(N, visible, tuning):
     """env_step_loop_kernel (mcn_env_rollout for 6-10 ORCA humans in a latency-bound batch: T steps in ONE launch, the
     state going through L2 between iterations) against the oracle stepping the same 60-step action sequence: the state
     after the launch, bit for bit -- and the same launch with rollout_fused = 0 (T step launches) for the record."""
-    torch = _torch()
+    torch = need_gpu()
     E, T = 700, 60
     rng = np.random.RandomState(100 + N)
     sp, aa = rng.uniform(0, 1, (T, E)), rng.uniform(0, 2 * np.pi, (T, E))
@@ -435,7 +400,7 @@ def test_larger_crowd_trajectories_match_oracle(N, block, tuning):
     wavefront-cooperative 3-D LP (what batches up to 4096 wavefronts get) and 4-wavefront workgroups with the
     register-resident one (larger batches).  The crossing is dense enough that hundreds of humans per step take the
     3-D LP."""
-    torch = _torch()
+    torch = need_gpu()
     E, T = 1024, 40
     tuning(quad_max_envs=0)
     if block == "deferred":
@@ -467,29 +432,26 @@ def test_larger_crowd_trajectories_match_oracle(N, block, tuning):
 def test_rollout_launch_unicycle_robot(split, tuning):
     """The (v, r) robot (float64 sin / cos on the device, agent.py:110-135) through the fused launch: same code as the
     single step, so the same bytes; the trig-free holonomic kernel is a separate instantiation."""
-    torch = _torch()
+    torch = need_gpu()
     E, N, T = 500, 5, 60
-    rng = np.random.RandomState(8)
-    acts = torch.from_numpy(np.stack([rng.uniform(0, 1, (T, E)), rng.uniform(-np.pi / 4, np.pi / 4, (T, E))], -1))
+    acts = torch.from_numpy(random_actions("unicycle", T, E, 8))
     tuning(rollout_fused=1)
     tuning(rollout_split=int(split))
-    a = _rollout_env(E, N, False, True, kinematics="unicycle")
-    b = _rollout_env(E, N, False, True, kinematics="unicycle")
+    a = pool_env(E, N, kinematics="unicycle", fin_slots=1)
+    b = pool_env(E, N, kinematics="unicycle", fin_slots=1)
     acts_d = acts.to(a.device)
     a.rollout(acts_d[:37]); a.rollout(acts_d[37:])
     for t in range(T):
         b.step(acts_d[t])
     torch.cuda.synchronize()
-    sa, sb = _snapshot(a), _snapshot(b)
-    for k in sa:
-        assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), k
+    assert_same_bytes(snapshot(a), snapshot(b))
     assert float(a.rtheta.abs().max()) > 0.1 and int(a.rollout_buffers["fin_count"].sum().item()) > 0
 
 
 def test_rollout_bench_configuration_equals_single_steps():
     """The benchmark's own workload (bench.build_env: 4096 envs x 5 humans, 500-case pool, 81-entry action table):
     250-step mcn_env_rollout launches against one mcn_env_step launch per step, every byte of state and records."""
-    torch = _torch()
+    torch = need_gpu()
     import bench
     dev = torch.device("cuda", 0)
     E, N, T = 4096, 5, 400
@@ -508,38 +470,6 @@ def test_rollout_bench_configuration_equals_single_steps():
     assert int(a.rollout_buffers["fin_count"].sum().item()) > 10000
 
 
-def _oracle_with_pool_restarts(env_ids, pool, N, acts_np, T, env_for_cfg):
-    """The oracle stepping the sampled envs through the bench workload: on done the env restarts from the scenario pool
-    exactly as the in-kernel reset does (mcn.h mcn_rollout: humans <- pool[next_case], zero velocity, first-arrival
-    times cleared, robot back to its start pose, clock 0, next_case += case_stride mod pool_size)."""
-    from modelcrowdnav_amd.envs import scenarios as S
-    n = len(env_ids)
-    st = cport.EnvState(n, N)
-
-    def load(rows, cases):
-        sc = pool[cases]
-        st.hpx[rows], st.hpy[rows], st.hgx[rows], st.hgy[rows] = sc[..., S.PX], sc[..., S.PY], sc[..., S.GX], sc[..., S.GY]
-        st.hvx[rows], st.hvy[rows] = sc[..., S.VX], sc[..., S.VY]
-        st.hr[rows], st.hvpref[rows] = sc[..., S.RAD], sc[..., S.VPREF]
-        st.human_times[rows] = 0
-        rr = env_for_cfg.spec().robot_row()
-        st.rpx[rows], st.rpy[rows], st.rgx[rows], st.rgy[rows] = rr[S.PX], rr[S.PY], rr[S.GX], rr[S.GY]
-        st.rvx[rows], st.rvy[rows], st.rr[rows], st.gtime[rows] = 0.0, 0.0, rr[S.RAD], 0.0
-    load(np.arange(n), env_ids % 500)
-    next_case = (env_ids + 1) % 500
-    cfg = H.oracle_cfg_for(env_for_cfg)
-    episodes = 0
-    for t in range(T):
-        a = acts_np[t][env_ids]
-        ref = cport.env_step(cfg, st, a[:, 0].copy(), a[:, 1].copy(), update=True)
-        d = np.nonzero(ref["done"])[0]
-        if len(d):
-            load(d, next_case[d])
-            next_case[d] = (next_case[d] + 1) % 500
-            episodes += len(d)
-    return st, ref, episodes
-
-
 @pytest.mark.parametrize("N,T", [(5, 1000), (10, 500)])
 def test_bench_timed_launch_shapes_against_single_steps_and_oracle(N, T):
     """bench.py's timed configuration ITSELF: 4096 envs from bench.build_env (500-case pool, in-kernel restarts, Explorer
@@ -547,7 +477,7 @@ def test_bench_timed_launch_shapes_against_single_steps_and_oracle(N, T):
     env_rollout_quad_kernel, state in registers) / ONE 500-step looped launch (N = 10: env_step_loop_kernel) -- against
     (a) one mcn_env_step launch per step, every byte of state and records, and (b) the C oracle's trajectory of 64
     sampled envs with the pool restarts replayed on the host, bit for bit."""
-    torch = _torch()
+    torch = need_gpu()
     import bench
     dev = torch.device("cuda", 0)
     E, K = 4096, 20
@@ -567,8 +497,8 @@ def test_bench_timed_launch_shapes_against_single_steps_and_oracle(N, T):
     assert int(a.rollout_buffers["fin_count"].sum().item()) > 4 * E
     # (b) the oracle on 64 envs spread over the batch
     ids = np.arange(64) * 64 + (np.arange(64) % 7)
-    st, ref, episodes = _oracle_with_pool_restarts(ids, pool, N, acts.cpu().numpy(), T, a)
-    assert episodes > 4 * 64
+    st, ref, restarts, _, _ = oracle_rollout(a.spec(), H.oracle_cfg_for(a), pool, ids, acts.cpu().numpy(), 1, 1)
+    assert restarts.sum() > 4 * 64
     got = {k: getattr(a, k).cpu().numpy()[ids] for k in ("hpos", "hvel", "hgoal", "hrad", "rpos", "rvel", "gtime")}
     assert H.bits_equal(got["hpos"][..., 0], st.hpx) and H.bits_equal(got["hpos"][..., 1], st.hpy)
     assert H.bits_equal(got["hvel"][..., 0], st.hvx) and H.bits_equal(got["hvel"][..., 1], st.hvy)
@@ -582,7 +512,7 @@ def test_bench_timed_launch_shapes_against_single_steps_and_oracle(N, T):
 def test_rollout_launch_matches_oracle_trajectory():
     """The fused T-step launch against the C oracle stepped T times (no pool: finished envs keep stepping, which the
     oracle does too)."""
-    torch = _torch()
+    torch = need_gpu()
     E, N, T = 513, 5, 40
     env = H.make_vec_env(E, N)
     env.reset("test", test_cases=[i % 500 for i in range(E)])
@@ -606,7 +536,7 @@ def test_rollout_launch_matches_oracle_trajectory():
 
 
 def test_rollout_rejects_bad_arguments():
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     env = H.make_vec_env(8, 5)
     env.reset("test", test_cases=list(range(8)))
@@ -619,7 +549,7 @@ def test_rollout_rejects_bad_arguments():
 def test_unicycle_robot_matches_oracle_and_reference(golden_dir):
     """Robot with (v, r) actions (agent.py:110-135, crowd_sim.py:353-355).  cos/sin differ between numpy, libm
     and the device by an ulp, so float state is held to 1e-12; masks stay exact on these inputs."""
-    torch = _torch()
+    torch = need_gpu()
     rng = np.random.RandomState(77)
     E, N = 500, 5
     env = H.make_vec_env(E, N, kinematics="unicycle")
@@ -667,7 +597,7 @@ def test_degenerate_configurations_match_oracle(kernel, tuning):
     must be the same NaNs), robot exactly on its goal, robot starting inside a human, zero robot action
     (degenerate swept segment).  Bit-exact including NaN positions."""
     tuning(quad_max_envs=0 if kernel == "lane-per-human" else 1 << 30)
-    torch = _torch()
+    torch = need_gpu()
     rng = np.random.RandomState(2024)
     E, N = 240, 5
     env = H.make_vec_env(E, N)
@@ -703,7 +633,7 @@ def test_degenerate_configurations_match_oracle(kernel, tuning):
 
 def test_single_env_and_tiny_batches():
     """E = 1, 2, 3: grids smaller than one wavefront."""
-    torch = _torch()
+    torch = need_gpu()
     rng = np.random.RandomState(3)
     for E in (1, 2, 3, 13):
         for N in (1, 5):
@@ -720,7 +650,7 @@ def test_config5_shape_32768x10_exact_and_shard_invariant():
     """BASELINE configs[4] shape on one GPU: 32768 envs x 10 humans (ORCA, 9 neighbours each).
     (a) 6 steps bit-exact against the C oracle for the whole batch; (b) stepping the batch as 8 shards of 4096
     (what 8 ranks do) gives bit-identical state to stepping it whole -- no cross-env coupling anywhere."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs import scenarios as S
     E, N, T = 32768, 10, 6
     env = H.make_vec_env(E, N)
@@ -758,7 +688,7 @@ def test_bench_kernel_attribution_matches_the_dispatcher(tuning):
     re-states the library's dispatch rules in Python.  Every launch shape bench.py reports is launched here once and the
     family the dispatcher REALLY took (mcn_last_dispatch) must be the one bench names (with the library's own defaults:
     a run of the suite under MCN_* overrides must not change what this test checks)."""
-    torch = _torch()
+    torch = need_gpu()
     import bench
     from modelcrowdnav_amd import _hip
     tuning(force_generic=0, quad_max_envs=-1, quad_split=-1, rollout_fused=-1, rollout_split=-1, step_block=-1,

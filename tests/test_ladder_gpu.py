@@ -15,31 +15,12 @@ pytestmark = pytest.mark.gpu
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
 from tests import ladder_states as LS  # noqa: E402
-from tests.test_orca_edges_gpu import (ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel, _snapshot,  # noqa: E402
-                                       forced_form, launch, rolled_wg4_battery)
+from tests.kernel_paths import (ROLLOUT_PATHS, STEP_EVENTS, STEP_KERNELS, UNICYCLE_EVENTS, forced_form,  # noqa: E402
+                                ladder_configs, rolled_wg4_battery, select_step_kernel)
+from tests.rollout_harness import assert_same_bytes, launch, need_gpu, snapshot  # noqa: E402
 
-STEP_EVENTS = ("swept_touch", "swept_point", "swept_u_zero", "swept_u_one", "dmin_tie", "danger_edge", "reach_edge",
-               "reach_band", "collision_and_reach", "timeout_and_collision", "timeout_edge", "timeout_below",
-               "hh_touch", "hh_band6", "hh_band3", "human_time_edge")
-UNICYCLE_EVENTS = STEP_EVENTS + ("theta_zero_rem", "theta_neg_rem")
 LA_EVENTS = ("la_touch", "la_danger_edge", "la_reach_edge", "la_collision_after_min")
 GENERIC_NS = (13, 32)          # only the run-time-N kernels (and the dispatcher) take more than 10 humans
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-def _configs(Ns, quad):
-    """(N, visible, dd, count_hh); the quad kernels take at most 4 candidate neighbours."""
-    for N in Ns:
-        for visible in (False, True):
-            if quad and N - 1 + visible > 4:
-                continue
-            for dd in LS.DISCOMFORT:
-                yield N, visible, dd, (N + visible) % 2 == 0 or dd == 0.25
 
 
 def _env(N, visible, dd, count_hh, E, unicycle=False):
@@ -65,7 +46,7 @@ def _add(total):
 
 def _step_and_compare(env, st, ax, ay, names, update, what, policy=cport.HUMANS_ORCA, given=None, total=None,
                       fields=H.STATE_FIELDS):
-    torch = _torch()
+    torch = need_gpu()
     H.upload(env, st)
     gv = None if given is None else torch.from_numpy(np.ascontiguousarray(given)).to(env.device)
     ob, reward, done, info = env.step(torch.from_numpy(np.stack([ax, ay], -1)).to(env.device), update=bool(update),
@@ -96,12 +77,12 @@ def _step_and_compare(env, st, ax, ay, names, update, what, policy=cport.HUMANS_
 def test_step_on_ladder_batches_matches_oracle_bitwise(kernel, update, tuning):
     """Reward, done, info, dmin, hh_count, human actions, the next observation or the state, first-arrival times."""
     quad = kernel.startswith("quad")
-    _select_step_kernel(kernel, tuning)
+    select_step_kernel(kernel, tuning)
     total = {}
     Ns = list(range(1, 6)) if quad else list(range(1, 11))
     if kernel in ("auto", "run-time-N"):
         Ns += list(GENERIC_NS)
-    for N, visible, dd, count_hh in _configs(Ns, quad):
+    for N, visible, dd, count_hh in ladder_configs(Ns, quad):
         st, ax, ay, _, names = LS.ladder_batch(N, visible, dd)
         env = _env(N, visible, dd, count_hh, st.E)
         _step_and_compare(env, st, ax, ay, names, update, "%s N=%d visible=%d dd=%g count_hh=%d" % (
@@ -114,11 +95,11 @@ def test_unicycle_step_on_ladder_batches(kernel, tuning):
     """(v, r) robots: headings whose remainder is zero (either sign) or negative; rtheta and the ladder bitwise.  Where
     rtheta + r is +-0 cos and sin are exact, so everything is bitwise; elsewhere the robot's position and velocity come
     from device trig and are held to 1e-12 (as tests/test_env_step_gpu.py::test_unicycle_robot_matches_oracle_...)."""
-    torch = _torch()
+    torch = need_gpu()
     quad = kernel.startswith("quad")
-    _select_step_kernel(kernel, tuning)
+    select_step_kernel(kernel, tuning)
     total = {}
-    for N, visible, dd, count_hh in _configs(range(1, 6) if quad else (1, 3, 5, 8, 10), quad):
+    for N, visible, dd, count_hh in ladder_configs(range(1, 6) if quad else (1, 3, 5, 8, 10), quad):
         st, ax, ay, _, names = LS.ladder_batch(N, visible, dd, unicycle=True)
         env = _env(N, visible, dd, count_hh, st.E, unicycle=True)
         what = "%s unicycle N=%d visible=%d dd=%g" % (kernel, N, visible, dd)
@@ -167,7 +148,7 @@ def test_given_velocity_paths_on_ladder_batches(stream, tuning):
 def test_linear_humans_on_ladder_batches():
     """Linear humans (device atan2 / cos / sin): the ladder fields bitwise (they do not depend on the humans' new
     velocities), the new positions within 1e-12."""
-    torch = _torch()
+    torch = need_gpu()
     total = {}
     for N in (1, 4, 7, 10):
         for visible in (False, True):
@@ -202,14 +183,14 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
     step, bitwise (unicycle: the ladder, the heading and the clock).  Every launch of a quad path asserts the form that
     went out.  The four-wavefront form double-buffers velocities by step parity, from 0 in every launch: 3 + 5 begins
     its second launch on an odd step of the sequence (tests/test_orca_edges_gpu.py cuts an even launch too)."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs import scenarios as S
     Ns, quad, tu = ROLLOUT_PATHS[path]
     form = forced_form(path)
     tuning(**tu)
     T = 8
     total = {}
-    for N, visible, dd, count_hh in _configs(Ns, quad):
+    for N, visible, dd, count_hh in ladder_configs(Ns, quad):
         st, ax0, ay0, _, names = LS.ladder_batch(N, visible, dd, unicycle)
         E = st.E
         rng = np.random.RandomState(N * 2 + visible)
@@ -230,9 +211,7 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
             for t in range(T):
                 b.step(acts_d[t])
             torch.cuda.synchronize()
-            sa, sb = _snapshot(a), _snapshot(b)
-            for k in sa:
-                assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), (what, with_pool, k)
+            assert_same_bytes(snapshot(a), snapshot(b), (what, with_pool))
             if with_pool:
                 assert int(a.rollout_buffers["fin_count"].sum().item()) > 0
                 continue

@@ -27,9 +27,10 @@ import pytest
 from oracle import cport
 from tests import helpers as H
 from tests import lp1_spread_states as S
-from tests import test_rollout_line_table_gpu as LT
+from tests.rollout_harness import every_cut, launches_against, single_steps
 
 SHAPES = (1, 8, 9, 19)
+LENGTHS = (1, 2, 3, 8)
 
 
 @pytest.mark.parametrize("E", SHAPES)
@@ -71,10 +72,15 @@ def test_spread_lp1_equals_single_steps(E, kinematics, tuning):
         H.upload(env, st)
         env.attach_rollout(gamma=0.9, pool=None, fin_slots=2)
         return env
-    env, snaps, _, _ = LT._single_steps(build, acts)
+    env, snaps, _, _ = single_steps(build, acts)
     want = S.replay(E)["states"][-1]
     # (the replay's robot is holonomic; the humans never see it)
     fields = None if kinematics == "holonomic" else cport.EnvState.FIELDS_H
     kw = {} if fields is None else {"fields": fields}
     H.assert_state_equal(H.download(env), want, what="single steps against the oracle, E=%d" % E, **kw)
-    LT._all_lengths(build, acts, snaps, "spread 1-D LP %s E=%d" % (kinematics, E))
+    what = "spread 1-D LP %s E=%d" % (kinematics, E)
+    for T in LENGTHS:
+        for cuts in every_cut(T):
+            launches_against(build, acts, 2, cuts, snaps, what)
+        for split in (1, 0):
+            launches_against(build, acts, split, (0, T), snaps, what)

@@ -195,8 +195,7 @@ def test_four_wavefront_inputs_reach_every_event():
     tests have no other human count to borrow an event from.  Its inputs alone -- edge_batch(5, False, .) under the three
     variants it takes plus the supplement, and ladder_batch(5, False, ., .) -- reach all 13 quad ORCA events on the first
     step, all 16 rung events, and with a unicycle robot the two heading events as well."""
-    from tests.test_ladder_gpu import STEP_EVENTS, UNICYCLE_EVENTS, _configs
-    from tests.test_orca_edges_gpu import QUAD_EVENTS
+    from tests.kernel_paths import QUAD_EVENTS, STEP_EVENTS, UNICYCLE_EVENTS, ladder_configs
     from tests import ladder_states as LS
     assert ES.WG4_VARIANTS == ({}, {"neighbor_dist": 1.5}, {"safety_space": 0.0625})
     total = dict.fromkeys(cport.EDGE_NAMES, 0)
@@ -214,7 +213,7 @@ def test_four_wavefront_inputs_reach_every_event():
     for unicycle, events in ((False, STEP_EVENTS), (True, UNICYCLE_EVENTS)):
         total = {}
         sizes = []
-        for N, visible, dd, count_hh in _configs([5], True):
+        for N, visible, dd, count_hh in ladder_configs([5], True):
             assert not visible
             st, ax, ay, _, names = LS.ladder_batch(N, visible, dd, unicycle)
             sizes.append(st.E)

@@ -14,46 +14,11 @@ pytestmark = pytest.mark.gpu
 from oracle import cport  # noqa: E402
 from tests import edge_states as ES  # noqa: E402
 from tests import helpers as H  # noqa: E402
+from tests.kernel_paths import (QUAD_EVENTS, ROLLOUT_PATHS, STEP_KERNELS, WG4_EDGE_CUTS, edge_configs,  # noqa: E402
+                                forced_form, rolled_wg4_battery, select_step_kernel)
+from tests.rollout_harness import assert_same_bytes, launch, need_gpu, snapshot  # noqa: E402
 
-STEP_KERNELS = ["auto", "lane-per-human", "lane-per-human-256", "deferred-lp3", "deferred-lp3-256", "run-time-N",
-                "run-time-N-256", "quad", "quad-split"]
-# what the quad kernels' inputs must reach (at most 4 neighbours and maxNeighbors >= 4: no cut of the neighbour list)
-QUAD_EVENTS = ("disc_zero_lp2", "disc_zero_lp3", "dist_tie", "nonfinite_line", "nonfinite_line_in_lp3",
-               "w_zero_collision", "parallel_lp1", "parallel_same_lp3", "parallel_opposite_lp3", "range_edge",
-               "leg_det_zero", "pref_on_disc", "outside_fast_range")
 ALL_EVENTS = cport.EDGE_NAMES
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-def _select_step_kernel(kernel, tuning):
-    """As tests/test_env_step_gpu.py::test_step_matches_oracle_bitexact pins each decomposition."""
-    if kernel.startswith("lane-per-human"):
-        tuning(quad_max_envs=0, lp3_defer=0)
-    elif kernel.startswith("deferred-lp3"):
-        tuning(quad_max_envs=0, lp3_defer=1)
-    elif kernel.startswith("run-time-N"):
-        tuning(quad_max_envs=0, force_generic=1)
-    elif kernel.startswith("quad"):
-        tuning(quad_max_envs=1 << 30, quad_split=1 if kernel == "quad-split" else 0)
-    if kernel.endswith("-256"):
-        tuning(step_block=256)
-
-
-def _configs(Ns, quad, variants=ES.ORCA_VARIANTS):
-    """(N, visible, variant) triples; the quad kernels take at most 4 candidate neighbours and 4 line slots."""
-    for N in Ns:
-        for visible in (False, True):
-            if quad and N - 1 + visible > 4:
-                continue
-            for variant in variants:
-                if quad and ES.orca_cfg(variant)["max_neighbors"] < 4:
-                    continue
-                yield N, visible, variant
 
 
 def _env(N, visible, variant, E):
@@ -75,12 +40,12 @@ def _where(names, bad):
 @pytest.mark.parametrize("update", [1, 0])
 @pytest.mark.parametrize("kernel", STEP_KERNELS)
 def test_step_on_edge_batches_matches_oracle_bitwise(kernel, update, tuning):
-    torch = _torch()
+    torch = need_gpu()
     quad = kernel.startswith("quad")
-    _select_step_kernel(kernel, tuning)
+    select_step_kernel(kernel, tuning)
     total = dict.fromkeys(ALL_EVENTS, 0)
     Ns = range(1, 6) if quad else range(1, 11)
-    for N, visible, variant in _configs(Ns, quad):
+    for N, visible, variant in edge_configs(Ns, quad):
         st, ax, ay, names = ES.edge_batch(N, visible, variant)
         env = _env(N, visible, variant, st.E)
         H.upload(env, st)
@@ -106,49 +71,7 @@ def test_step_on_edge_batches_matches_oracle_bitwise(kernel, update, tuning):
     _assert_reached(total, QUAD_EVENTS if quad else ALL_EVENTS, kernel)
 
 
-def _snapshot(env):
-    c = lambda t: t.detach().cpu().numpy().copy()
-    snap = {k: c(getattr(env, k)) for k in ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal",
-                                            "rtheta", "gtime", "human_times", "step_rec", "human_act")}
-    if env._roll is not None:
-        snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items()
-                     if k in ("state", "fin_return", "fin_time", "fin_info")})
-    return snap
-
-
-ROLLOUT_PATHS = {
-    # name: (human counts, quad layout, tuning)
-    "quad-rollout": (range(1, 6), True, dict(rollout_fused=1, rollout_split=0)),
-    "quad-rollout-split": (range(1, 6), True, dict(rollout_fused=1, rollout_split=1)),
-    "step-loop": (range(6, 11), False, dict(rollout_fused=1, lp3_defer=0)),
-    "lp3-defer": (range(2, 11), False, dict(rollout_fused=1, lp3_defer=1)),
-    "unfused": (range(1, 11), False, dict(rollout_fused=0)),
-    # the four-wavefront form (env_rollout_wg4.hip): built for 5 humans and an invisible robot only
-    "quad-rollout-wg4": ((5,), True, dict(rollout_fused=1, rollout_split=2)),
-}
-WG4_SLOTS = 8                     # envs per workgroup of the four-wavefront form
-WG4_STRADDLERS = (3, 6)           # quad q = 5 env + human: the envs in these slots have quads in two ORCA wavefronts
-# the four-wavefront form double-buffers velocities by step parity, from 0 in every launch: an odd launch, a one-step
-# launch and an even one
-WG4_EDGE_CUTS = (0, 9, 10, 24)
-_SLOT_MAJOR = ("roll_fin_return", "roll_fin_time", "roll_fin_info")      # [fin_slots, E]; everything else is [E, ...]
 _STEP_KEYS = ("reward", "done", "info", "dmin", "hh_count", "human_act")
-
-
-def forced_form(path):
-    """The rollout form a quad path forces (mcn_tuning.rollout_split), None for the other paths."""
-    Ns, quad, tu = ROLLOUT_PATHS[path]
-    return tu["rollout_split"] if quad else None
-
-
-def launch(env, acts, form):
-    """env.rollout(acts); a quad path must have gone out as the form it forces: the three forms share one dispatch
-    family and leave the same bytes, so nothing else would show that another kernel stood in."""
-    from modelcrowdnav_amd import _hip
-    env.rollout(acts)
-    if form is not None:
-        assert _hip.last_dispatch() == "env_rollout_quad_kernel", _hip.last_dispatch()
-        assert _hip.last_rollout_form() == form, (_hip.last_rollout_form(), form)
 
 
 def _assert_step_equals_oracle(env, ref, ref_st, names, what, keys=_STEP_KEYS, fields=H.STATE_FIELDS):
@@ -166,7 +89,7 @@ def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
     the form that went out.  The four-wavefront form has one shape only, so it runs every ORCA variant that shape takes,
     the parallel_same_lp3 supplement with the default one, and a one-step launch of its own against the oracle's first
     step."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs import scenarios as S
     Ns, quad, tu = ROLLOUT_PATHS[path]
     form = forced_form(path)
@@ -179,7 +102,7 @@ def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
         # the default ORCA parameters and one of the others, in turn (at N = 5 that one is max_neighbors = 3, which no
         # quad path takes)
         variants = ES.WG4_VARIANTS if wg4 else (ES.ORCA_VARIANTS[0], ES.ORCA_VARIANTS[1 + N % 4])
-        for n_, visible, variant in _configs([N], quad, variants):
+        for n_, visible, variant in edge_configs([N], quad, variants):
             st, ax0, ay0, names = ES.edge_batch(N, visible, variant)
             if wg4 and not variant:
                 st, ax0, ay0, names = ES.with_supplement((st, ax0, ay0, names))
@@ -203,9 +126,7 @@ def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
                 for t in range(T):
                     b.step(acts_d[t])
                 torch.cuda.synchronize()
-                sa, sb = _snapshot(a), _snapshot(b)
-                for k in sa:
-                    assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), (what, with_pool, k)
+                assert_same_bytes(snapshot(a), snapshot(b), (what, with_pool))
                 if with_pool:
                     continue
                 ref_st = st.copy()
@@ -225,75 +146,6 @@ def test_rollout_on_edge_batches_equals_single_steps_and_oracle(path, tuning):
                     torch.cuda.synchronize()
                     _assert_step_equals_oracle(c, ref0, ref_st0, names, what + " first step")
     _assert_reached(total, QUAD_EVENTS if quad else ALL_EVENTS, path)
-
-
-def _roll_snapshot(snap, perm):
-    return {k: np.take(v, perm, axis=1 if k in _SLOT_MAJOR else 0) for k, v in snap.items()}
-
-
-def rolled_wg4_battery(build, take, st, acts, names, cuts, check_first, check_last, what, odd_roll=3):
-    """The four-wavefront form on one batch under np.roll of the env order by 0 .. 7, so that every env meets every slot
-    of an 8-env workgroup (each of the three ORCA wavefronts sees other envs, and the envs in slots 3 and 6 straddle
-    two of them); the rare events sit at fixed offsets of their 16-env blocks and would otherwise only ever meet the
-    same slots.  Actions and first_cases roll with the envs.
-
-      every roll              a one-step launch; check_first(env, perm, rolled names, what) holds it to the oracle
-      roll 0 and odd_roll     the whole sequence in the launches `cuts`, without and with a scenario pool: every byte of
-                              the equally rolled result of single mcn_env_step calls (run once, unrolled), and without
-                              a pool check_last(...) against the oracle
-
-    build() gives a configured env, take(st, perm) the envs of an oracle state in another order."""
-    torch = _torch()
-    from modelcrowdnav_amd.envs import scenarios as S
-    E, T = st.E, len(acts)
-    assert cuts[0] == 0 and cuts[-1] == T
-    cases = np.arange(E) % 16
-    ident = np.arange(E)
-
-    def start(perm, with_pool):
-        env = build()
-        H.upload(env, take(st, perm))
-        if with_pool:
-            pool = S.scenario_pool(env.spec(), "test", range(16), st.N, "circle_crossing")
-            env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=cases[perm], fin_slots=2)
-        return env, torch.from_numpy(np.ascontiguousarray(acts[:, perm])).to(env.device)
-
-    singles = {}
-    for with_pool in (False, True):
-        env, a = start(ident, with_pool)
-        for t in range(T):
-            env.step(a[t])
-        torch.cuda.synchronize()
-        singles[with_pool] = _snapshot(env)
-    assert set(_SLOT_MAJOR) <= set(singles[True])
-    seen = [set() for _ in range(E)]
-    for r in range(WG4_SLOTS):
-        perm = np.roll(ident, r)
-        rolled = [names[i] for i in perm]
-        for pos, i in enumerate(perm):
-            seen[i].add(pos % WG4_SLOTS)
-        env, a = start(perm, False)
-        launch(env, a[:1], 2)
-        torch.cuda.synchronize()
-        check_first(env, perm, rolled, "%s roll %d first step" % (what, r))
-        if r not in (0, odd_roll):
-            continue
-        for with_pool in (False, True):
-            env, a = start(perm, with_pool)
-            for lo, hi in zip(cuts[:-1], cuts[1:]):
-                launch(env, a[lo:hi], 2)
-            torch.cuda.synchronize()
-            got, want = _snapshot(env), _roll_snapshot(singles[with_pool], perm)
-            for k in got:
-                assert np.array_equal(got[k].view(np.uint8), want[k].view(np.uint8)), (what, "roll", r, with_pool, k)
-            if not with_pool:
-                check_last(env, perm, rolled, "%s roll %d" % (what, r))
-    # over the rolls every env but the last few (which wrap to the front) sat in every slot, and an env of every block
-    # sat in the two straddling ones
-    assert all(s == set(range(WG4_SLOTS)) for s in seen[:E - WG4_SLOTS + 1])
-    for block in sorted(set(names)):
-        slots = set().union(*(seen[i] for i in range(E) if names[i] == block))
-        assert set(WG4_STRADDLERS) <= slots, (what, block, sorted(slots))
 
 
 def test_wg4_rollout_on_rolled_edge_batch(tuning):

@@ -17,19 +17,13 @@ import pytest
 
 from oracle import cport
 from tests import helpers as H
+from tests.rollout_harness import ROOT, assert_same_bytes, kernel_resources, need_gpu, pool_env, snapshot
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _packed_rollout_env(E, N, visible, with_pool, seed):
-    from modelcrowdnav_amd.envs import scenarios as S
-    env = H.make_vec_env(E, N, robot_visible=visible)
-    pool = S.scenario_pool(env.spec(), "test", range(64), N, "circle_crossing")
-    ids = np.arange(E) % 64
-    env.load_scenarios(pool[ids])
-    env.attach_rollout(gamma=0.9, pool=pool if with_pool else None, case_stride=3, first_cases=(ids + 7) % 64,
-                       fin_slots=2)
+    env = pool_env(E, N, visible, with_pool)
     st = H.download(env)
     # every env's humans inside a disc of radius 0.45 around one point (as the LP3-queue test packs them)
     rng = np.random.RandomState(seed)
@@ -40,22 +34,12 @@ def _packed_rollout_env(E, N, visible, with_pool, seed):
     return env, st
 
 
-def _snapshot(env):
-    c = lambda t: t.detach().cpu().numpy().copy()
-    snap = {k: c(getattr(env, k)) for k in ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal",
-                                            "rtheta", "gtime", "human_times", "step_rec", "human_act")}
-    snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items() if k in ("state", "fin_return", "fin_time",
-                                                                                  "fin_info")})
-    return snap
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,visible", [(5, False), (4, True)])
 @pytest.mark.parametrize("with_pool", [True, False])
 @pytest.mark.parametrize("split", [0, 1])
 def test_packed_crowd_rollout_equals_single_steps_and_oracle(N, visible, with_pool, split, tuning):
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    torch = need_gpu()
     E, T = 777, 40
     rng = np.random.RandomState(50 + N)
     sp, aa = rng.uniform(0, 1, (T, E)), rng.uniform(0, 2 * np.pi, (T, E))
@@ -69,9 +53,7 @@ def test_packed_crowd_rollout_equals_single_steps_and_oracle(N, visible, with_po
     for t in range(T):
         b.step(acts_d[t])
     torch.cuda.synchronize()
-    sa, sb = _snapshot(a), _snapshot(b)
-    for k in sa:
-        assert np.array_equal(sa[k].view(np.uint8), sb[k].view(np.uint8)), k
+    assert_same_bytes(snapshot(a), snapshot(b))
     if with_pool:
         return
     # no restarts: the oracle steps the same trajectory; the packed start drives it through the 3-D LP
@@ -114,14 +96,13 @@ def test_quad_kernels_registers_and_scratch():
     csrc = os.path.join(ROOT, "modelcrowdnav_amd", "csrc")
     if not os.path.exists(os.path.join(csrc, "env_rollout_quad.o")):
         pytest.skip("needs the built library (build())")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_resources.py"), "quad_kernel<"],
-                         capture_output=True, text=True, check=True).stdout
+    out = kernel_resources("quad_kernel<")
     seen = 0
-    for line in out.splitlines():
-        m = re.search(r"(env_rollout_quad_kernel|env_step_quad_kernel)<(\d+),.*vgpr\s+(\d+).*scratch\s+(\d+)", line)
+    for name, (vgpr, _, _, scratch, _, _) in out.items():
+        m = re.search(r"(env_rollout_quad_kernel|env_step_quad_kernel)<(\d+),", name)
         if not m or int(m.group(2)) not in (4, 5):
             continue
         seen += 1
-        assert int(m.group(3)) <= 168, line
-        assert int(m.group(4)) == 0, line
+        assert vgpr <= 168, (name, vgpr)
+        assert scratch == 0, (name, scratch)
     assert seen == 12 + 6, out

@@ -58,8 +58,8 @@ pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
 from tests import rollout_ref as R  # noqa: E402
-from tests.test_orca_edges_gpu import (ROLLOUT_PATHS, STEP_KERNELS, _select_step_kernel, forced_form,  # noqa: E402
-                                       launch)
+from tests.kernel_paths import ROLLOUT_PATHS, STEP_KERNELS, forced_form, select_step_kernel  # noqa: E402
+from tests.rollout_harness import launch, need_gpu  # noqa: E402
 
 STEP_DTYPE = np.dtype([("reward", "f8"), ("dmin", "f8"), ("done", "u1"), ("info", "u1"), ("reserved", "u2"),
                        ("hh_count", "i4")])                                             # mcn_step_rec
@@ -75,12 +75,6 @@ PATHS = ([("step",) + c for c in ORCA_STEP] + [("given",) + c for c in GIVEN_STE
 PATH_IDS = ["%s-%s-N%d" % p for p in PATHS]
 SPLITS = ((0, 1), (1, 38), (38, R.T_ACC))                   # the launches of the rollout paths: 1 + 37 + 92 steps
 assert tuple(b for _, b in SPLITS) == R.CHECKPOINTS
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
 
 
 def _env(w):
@@ -99,7 +93,7 @@ def _env(w):
 
 def _attach(env, w, null=()):
     """mcn_rollout as the parameter set says, every output buffer filled with a sentinel; `null`: pointers set to NULL."""
-    torch = _torch()
+    torch = need_gpu()
     s = w.set
     pool = None
     if s["pool"] == "host":
@@ -130,7 +124,7 @@ def _first(bad):
 
 def _compare(env, w, n, what, null=()):
     """Everything after n steps against the replay's snapshot."""
-    torch = _torch()
+    torch = need_gpu()
     torch.cuda.synchronize()
     ref_st, snap = w.snaps[n]
     what = "%s after %d steps" % (what, n)
@@ -174,13 +168,13 @@ def _compare_step_recs(recs, w, steps, what):
 
 def _run(path, w, tuning, null=()):
     """One path over the workload, compared after 1, 38 and 130 steps; returns the kernel family that ran last."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     kind, which, N = path
     assert N == w.N and (kind == "given") == (w.mode == "given")
     what = "%s %s N=%d set %s%s" % (kind, which, N, w.name, " without %s" % "/".join(null) if null else "")
     if kind == "step":
-        _select_step_kernel(which, tuning)
+        select_step_kernel(which, tuning)
     elif kind == "given":
         tuning(pair_stream=which)
     else:

@@ -16,80 +16,24 @@ Every comparison is of BYTES: full state, step record, Explorer records and fini
 four-wavefront form after EVERY launch against single mcn_env_step calls at that step, and of forms 1 and 0 at the end.
 Every forced launch asserts mcn_last_rollout_form().  Each test first shows, from the single-step run, that its inputs
 produce the situation it is about."""
-import os
-import re
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 from oracle import cport
 from tests import edge_states as ES
 from tests import helpers as H
+from tests.rollout_harness import as_device_pool, kernel_resources, launches_against, single_steps
 
 N = 5
-_FIELDS = ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal", "rtheta", "gtime", "human_times",
-           "step_rec", "human_act")
-_ROLL = ("state", "fin_return", "fin_time", "fin_info")
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-def _snapshot(env):
-    c = lambda t: t.detach().cpu().numpy().copy()
-    snap = {k: c(getattr(env, k)) for k in _FIELDS}
-    if env._roll is not None:
-        snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items() if k in _ROLL})
-    return snap
-
-
-def _assert_same_bytes(a, b, what=""):
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
-
-
-def _single_steps(build, acts):
-    """T mcn_env_step calls: the snapshot after every step (snaps[t] = after step t) and the done flags [T, E]."""
-    torch = _torch()
-    env = build()
-    acts_d = torch.from_numpy(acts).to(env.device)
-    snaps, done = [], []
-    for t in range(len(acts)):
-        env.step(acts_d[t])
-        snaps.append(_snapshot(env))
-        done.append(env.done.cpu().numpy().astype(bool).copy())
-    return snaps, np.array(done)
-
-
-def _launches(build, acts, split, cuts, snaps, what=""):
-    """The sequence in launches acts[cuts[i]:cuts[i + 1]] of the forced form; after EVERY launch the bytes of the
-    single-step run at that step."""
-    torch = _torch()
-    from modelcrowdnav_amd import _hip
-    env = build()
-    acts_d = torch.from_numpy(acts).to(env.device)
-    _hip.set_tuning(rollout_fused=1, rollout_split=split)
-    for lo, hi in zip(cuts[:-1], cuts[1:]):
-        env.rollout(acts_d[lo:hi])
-        assert _hip.last_dispatch() == "env_rollout_quad_kernel" and _hip.last_rollout_form() == split
-        torch.cuda.synchronize()
-        _assert_same_bytes(_snapshot(env), snaps[hi - 1], "%s form %d cuts %s after step %d" % (what, split, cuts, hi - 1))
 
 
 def _all_forms(build, acts, snaps, cut_list, what=""):
     T = len(acts)
     for cuts in cut_list:
         assert cuts[0] == 0 and cuts[-1] == T and all(a < b for a, b in zip(cuts[:-1], cuts[1:])), cuts
-        _launches(build, acts, 2, cuts, snaps, what)
+        launches_against(build, acts, 2, cuts, snaps, what)
     for split in (1, 0):
-        _launches(build, acts, split, (0, T), snaps, what)
+        launches_against(build, acts, split, (0, T), snaps, what)
 
 
 def _still(T, E):
@@ -144,7 +88,7 @@ def test_velocities_keep_their_float32_bits(tuning):
         env.attach_rollout(gamma=0.9, pool=None, fin_slots=2)
         return env
     acts = _still(T, E)
-    snaps, _ = _single_steps(build, acts)
+    _, snaps, _, _ = single_steps(build, acts)
     v = np.concatenate([s["human_act"].ravel() for s in snaps] + [s["hvel"].ravel() for s in snaps])
     v32 = v.astype(np.float32)
     assert (v32.astype(np.float64).view(np.uint64) == v.view(np.uint64))[~np.isnan(v)].all(), "a velocity is no float32"
@@ -162,7 +106,6 @@ _P, _LIMIT = 8, 3
 
 
 def _restart_env(E, kinematics, with_hvel):
-    torch = _torch()
     from modelcrowdnav_amd.envs import scenarios as S
     env = H.make_vec_env(E, N, kinematics=kinematics, **{"env.time_limit": _LIMIT, "env.randomize_attributes": "true"})
     pool = S.scenario_pool(env.spec(), "test", range(_P), N, "circle_crossing").copy()
@@ -172,13 +115,8 @@ def _restart_env(E, kinematics, with_hvel):
         pool[case, 0, S.PX], pool[case, 0, S.PY] = rr[S.PX] + 0.125, rr[S.PY]
     ids = np.arange(E)
     env.load_scenarios(pool[ids % _P])
-    if with_hvel:
-        dpool = pool
-    else:
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(env.device)
-        dpool = dict(hpos=up(pool[:, :, [S.PX, S.PY]]), hgoal=up(pool[:, :, [S.GX, S.GY]]),
-                     hrad=up(pool[:, :, S.RAD]), hvpref=up(pool[:, :, S.VPREF]))
-    env.attach_rollout(gamma=0.9, pool=dpool, case_stride=1, first_cases=(ids + 1) % _P, fin_slots=3)
+    env.attach_rollout(gamma=0.9, pool=pool if with_hvel else as_device_pool(env, pool), case_stride=1,
+                       first_cases=(ids + 1) % _P, fin_slots=3)
     return env, pool
 
 
@@ -195,7 +133,7 @@ def test_parity_buffers_every_cut(kinematics, E, tuning):
     T = 37
     build = lambda: _restart_env(E, kinematics, True)[0]
     acts = _still(T, E)
-    snaps, done = _single_steps(build, acts)
+    _, snaps, _, done = single_steps(build, acts)
     assert done.any(), "no env restarts"
     _all_forms(build, acts, snaps, _PARITY_CUTS, "parity %s E=%d" % (kinematics, E))
 
@@ -217,7 +155,7 @@ def test_restarts_through_the_side_path(kinematics, with_hvel, tuning):
     for col in (S.VX, S.VY):
         assert (pool[:, :, col].astype(np.float32).astype(np.float64) != pool[:, :, col]).all()
     acts = _still(T, E)
-    snaps, done = _single_steps(build, acts)
+    _, snaps, _, done = single_steps(build, acts)
     assert (done[:-1] & done[1:]).any(), "no env restarts on consecutive steps"
     n0 = done[:, :8].sum(1)
     assert ((n0 >= 2) & (n0 < 8)).any(), "never two envs of workgroup 0 alone: %s" % n0
@@ -279,7 +217,7 @@ def test_human_times_behind_hand_off_2(tracked, tuning):
         env.attach_rollout(gamma=0.9, pool=pool, case_stride=1, first_cases=(np.arange(E) + 1) % _P, fin_slots=2)
         return env
     acts = _still(T, E)
-    snaps, done = _single_steps(build, acts)
+    _, snaps, _, done = single_steps(build, acts)
     assert done[8].all() and not done[:8].any(), "the envs do not all restart at step 8"
     ht = np.array([s["human_times"] for s in snaps])                     # [T, E, N]
     if tracked:
@@ -301,14 +239,9 @@ def test_human_times_behind_hand_off_2(tracked, tuning):
 def test_chain_kernels_registers_and_scratch():
     """Both env_rollout_wg4_kernel instantiations run without scratch, the holonomic one in at most 128 VGPRs (four
     wavefronts on a SIMD), the unicycle one in at most 168 (three); read from the built code objects."""
-    from modelcrowdnav_amd import _hip
-    assert os.path.exists(_hip.LIB_PATH)
-    assert os.path.exists(os.path.join(_ROOT, "modelcrowdnav_amd", "csrc", "env_rollout_quad.o")), \
-        "libmcn_hip.so is there but the objects it was linked from are not: rebuild (make -C modelcrowdnav_amd/csrc)"
-    out = subprocess.run([sys.executable, os.path.join(_ROOT, "tools", "kernel_resources.py"), "env_rollout_wg4_kernel<"],
-                         capture_output=True, text=True, check=True).stdout
-    rows = dict((uni, (int(vgpr), int(scratch), int(spill))) for uni, vgpr, scratch, spill in
-                re.findall(r"env_rollout_wg4_kernel<5, 0, (true|false)>.*vgpr\s+(\d+).*scratch\s+(\d+).*vspill (\d+)", out))
+    out = kernel_resources("env_rollout_wg4_kernel<")
+    rows = {uni: (r[0], r[3], r[5]) for uni in ("true", "false") for name, r in out.items()
+            if "env_rollout_wg4_kernel<5, 0, %s>" % uni in name}
     assert sorted(rows) == ["false", "true"], out
     assert rows["false"][0] <= 128 and rows["false"][1:] == (0, 0), out
     assert rows["true"][0] <= 168 and rows["true"][1:] == (0, 0), out

@@ -9,17 +9,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
-
-
-def _goal_seeking(env, t):
-    """Deterministic, state-only robot policy whose arithmetic is exact on any IEEE machine: move at +-0.6 along
-    each axis according to the sign of the remaining goal offset (0 inside a 0.2 band)."""
-    import torch
-    d = env.rgoal - env.rpos
-    v, z = torch.full_like(d, 0.6), torch.zeros_like(d)          # float64 constants (python scalars would be f32)
-    return (torch.where(d > 0.2, v, z) - torch.where(d < -0.2, v, z)).contiguous()
-
-
+from tests.rollout_harness import goal_seeking  # noqa: E402
 from tests.rollout_ref import oracle_episode as _oracle_episode  # noqa: E402  (also held to the host replay there)
 
 
@@ -31,7 +21,7 @@ def test_vec_explorer_equals_sequential_loop():
     env = H.make_vec_env(E, N)
     env.track_human_times = False; env.export_human_actions = False
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-    avg, sr, cr, tr, nav = ex.run_k_episodes(k, "test", action_fn=_goal_seeking, returnNav=True)
+    avg, sr, cr, tr, nav = ex.run_k_episodes(k, "test", action_fn=goal_seeking, returnNav=True)
     want = [_oracle_episode(S.scenario_for_case(env.spec(), "test", c, N, "circle_crossing")) for c in range(k)]
     got = ex.last_records
     assert got["infos"] == [w[1] for w in want]
@@ -57,7 +47,7 @@ def test_vec_explorer_case_counter_wraps_mid_run():
     assert env.case_size["val"] == 100
     env.case_counter["val"] = 90
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-    avg, sr, cr, tr = ex.run_k_episodes(k, "val", action_fn=_goal_seeking)
+    avg, sr, cr, tr = ex.run_k_episodes(k, "val", action_fn=goal_seeking)
     cases = [(90 + i) % 100 for i in range(k)]
     want = [_oracle_episode(S.scenario_for_case(env.spec(), "val", c, N, "circle_crossing")) for c in cases]
     got = ex.last_records
@@ -530,7 +520,7 @@ def test_update_memory_value_targets(il):
     # an untrained SARL never finishes an episode (every case times out and timeouts do not feed the memory), so
     # the RL case drives the robot with the exact goal-seeking rule; states / targets still come from SARL
     ex.run_k_episodes(k, "train", update_memory=True, imitation_learning=il,
-                      action_fn=None if il else _goal_seeking)
+                      action_fn=None if il else goal_seeking)
     assert len(mem) > 0
     gbar = pow(0.9, 0.25 * 1.0)
     want_s, want_v = _reference_targets(rec["states"].cpu(), rec["rewards"].cpu().numpy(), rec["dones"].cpu().numpy(),
@@ -664,7 +654,7 @@ def test_vec_explorer_with_device_scenarios():
         env = H.make_vec_env(E, N)
         env.track_human_times = False; env.export_human_actions = False
         ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())
-        outs.append((ex.run_k_episodes(k, "train", action_fn=_goal_seeking, device_scenarios=11), ex.last_records))
+        outs.append((ex.run_k_episodes(k, "train", action_fn=goal_seeking, device_scenarios=11), ex.last_records))
     assert outs[0][0] == outs[1][0] and outs[0][1]["returns"] == outs[1][1]["returns"]
     assert len(outs[0][1]["returns"]) == k and len(set(outs[0][1]["infos"])) > 1
     assert env.case_counter["train"] == k % env.case_size["train"]

@@ -19,25 +19,20 @@ that step, for the first T = 1, 2, 3, 8 steps of one sequence cut at every posit
 """
 import functools
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from oracle import cport
 from tests import helpers as H
+from tests.rollout_harness import (ROOT, every_cut, kernel_resources, launches_against, parse_resources,
+                                   single_steps)
 
 N = 5
 T_MAX = 8
 LENGTHS = (1, 2, 3, 8)
 SHAPES = (1, 8, 9, 19)
 FAR = (40.0, 40.0)
-_FIELDS = ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal", "rtheta", "gtime", "human_times",
-           "step_rec", "human_act")
-_ROLL = ("state", "fin_return", "fin_time", "fin_info")
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32 = np.float32
 EPS = f32(1e-5)
 
@@ -294,65 +289,12 @@ def test_batch_holds_what_it_is_for(E):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-def _snapshot(env):
-    c = lambda t: t.detach().cpu().numpy().copy()
-    snap = {k: c(getattr(env, k)) for k in _FIELDS}
-    if env._roll is not None:
-        snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items() if k in _ROLL})
-    return snap
-
-
-def _assert_same_bytes(a, b, what=""):
-    assert sorted(a) == sorted(b)
-    for k in a:
-        assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
-
-
-def _single_steps(build, acts):
-    torch = _torch()
-    env = build()
-    acts_d = torch.from_numpy(acts).to(env.device)
-    snaps, done = [_snapshot(env)], []
-    for t in range(len(acts)):
-        env.step(acts_d[t])
-        snaps.append(_snapshot(env))
-        done.append(env.done.cpu().numpy().astype(bool).copy())
-    return env, snaps[1:], snaps[0], np.array(done)
-
-
-def _launches(build, acts, split, cuts, snaps, what=""):
-    torch = _torch()
-    from modelcrowdnav_amd import _hip
-    env = build()
-    acts_d = torch.from_numpy(acts).to(env.device)
-    _hip.set_tuning(rollout_fused=1, rollout_split=split)
-    for lo, hi in zip(cuts[:-1], cuts[1:]):
-        env.rollout(acts_d[lo:hi])
-        assert _hip.last_dispatch() == "env_rollout_quad_kernel" and _hip.last_rollout_form() == split
-        torch.cuda.synchronize()
-        _assert_same_bytes(_snapshot(env), snaps[hi - 1], "%s form %d cuts %s after step %d" % (what, split, cuts, hi - 1))
-
-
-def _every_cut(T):
-    """one launch, every two-launch cut, and T one-step launches"""
-    cuts = [(0, T)] + [(0, c, T) for c in range(1, T)]
-    if T > 2:
-        cuts.append(tuple(range(T + 1)))
-    return cuts
-
-
 def _all_lengths(build, acts, snaps, what):
     for T in LENGTHS:
-        for cuts in _every_cut(T):
-            _launches(build, acts, 2, cuts, snaps, what)
+        for cuts in every_cut(T):
+            launches_against(build, acts, 2, cuts, snaps, what)
         for split in (1, 0):
-            _launches(build, acts, split, (0, T), snaps, what)
+            launches_against(build, acts, split, (0, T), snaps, what)
 
 
 @pytest.mark.gpu
@@ -370,7 +312,7 @@ def test_line_table_equals_single_steps(E, kinematics, tuning):
         H.upload(env, st)
         env.attach_rollout(gamma=0.9, pool=None, fin_slots=2)
         return env
-    env, snaps, _, _ = _single_steps(build, acts)
+    env, snaps, _, _ = single_steps(build, acts)
     if kinematics == "holonomic":                              # (the replay's robot is holonomic; the humans never see it)
         H.assert_state_equal(H.download(env), _replay(E)["states"][-1], what="single steps against the oracle, E=%d" % E)
     else:
@@ -416,7 +358,7 @@ def test_restart_beside_a_3d_lp(E, kinematics, tuning):
         pool = S.scenario_pool(env.spec(), "test", range(_P), N, "circle_crossing")
         env.attach_rollout(gamma=0.9, pool=pool, case_stride=1, first_cases=(np.arange(E) + 1) % _P, fin_slots=2)
         return env
-    env, snaps, first, done = _single_steps(build, acts)
+    env, snaps, first, done = single_steps(build, acts)
     cfg = H.oracle_cfg_for(env)
     beside = False
     for t in range(3):
@@ -432,12 +374,6 @@ def test_restart_beside_a_3d_lp(E, kinematics, tuning):
 
 # ---------------------------------------------------------------------------------------------------------------------
 # no GPU: what the table costs, and that nobody else pays
-def _resource_rows(text):
-    return dict((name.strip(), tuple(int(v) for v in vals)) for name, *vals in
-                re.findall(r"^(\S.*?)\s+vgpr\s+(\d+) agpr\s+(\d+) sgpr\s+(\d+) scratch\s+(\d+) lds\s+(\d+) vspill (\d+)\s*$",
-                           text, re.M))
-
-
 WG4_LDS = 2560 + 3 * 64 * 16        # the hand-off arrays + three wavefronts' tables of 64 float4 slots
 
 
@@ -445,15 +381,9 @@ def test_line_table_kernel_resources():
     """Read from the built code objects: both env_rollout_wg4_kernel instantiations run without scratch in no more VGPRs
     than before the table (124 holonomic / 147 unicycle), their LDS is 5 632 B per workgroup, and every other kernel of
     the library has the registers, scratch and LDS recorded in profiles/r17_kernel_resources.txt."""
-    from modelcrowdnav_amd import _hip
-    assert os.path.exists(_hip.LIB_PATH)
-    assert os.path.exists(os.path.join(_ROOT, "modelcrowdnav_amd", "csrc", "env_rollout_quad.o")), \
-        "libmcn_hip.so is there but the objects it was linked from are not: rebuild (make -C modelcrowdnav_amd/csrc)"
-    out = subprocess.run([sys.executable, os.path.join(_ROOT, "tools", "kernel_resources.py")],
-                         capture_output=True, text=True, check=True).stdout
-    now = _resource_rows(out)
-    txt = open(os.path.join(_ROOT, "profiles", "r17_kernel_resources.txt")).read()
-    then = _resource_rows(txt[txt.index("# after, every kernel:"):])
+    now = kernel_resources()
+    txt = open(os.path.join(ROOT, "profiles", "r17_kernel_resources.txt")).read()
+    then = parse_resources(txt[txt.index("# after, every kernel:"):])
     assert len(then) > 150 and sorted(now) == sorted(then), sorted(set(now) ^ set(then))
     for name in sorted(then):
         vgpr, agpr, sgpr, scratch, lds, vspill = now[name]

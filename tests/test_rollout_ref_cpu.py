@@ -26,7 +26,7 @@ def test_replay_of_whole_episodes_equals_the_reference_explorer():
     rewards = [[[]] for _ in range(E)]                       # per env, per episode
     dist_sum = [0.0] * E                                     # explorer.py:88-90 over the env's steps, in step order
     for _ in range(400):
-        ax, ay = R.goal_seeking(st)
+        ax, ay = R.host_goal_seeking(st)
         out = rep.step(cfg, st, ax, ay)
         for e in range(E):
             rewards[e][-1].append(float(out["reward"][e]))

@@ -14,63 +14,24 @@ import pytest
 
 from tests import helpers as H
 from tests import ladder_states as L
+from tests.rollout_harness import assert_same_bytes, launch, launch_cuts, need_gpu, pool_env, random_actions, snapshot
 
 N = 5
-_FIELDS = ("hpos", "hvel", "hgoal", "hrad", "hvpref", "rpos", "rvel", "rgoal", "rtheta", "gtime", "human_times",
-           "step_rec", "human_act")
-_ROLL = ("state", "fin_return", "fin_time", "fin_info")
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
-
-
-def _rollout_env(E, kinematics="holonomic"):
-    from modelcrowdnav_amd.envs import scenarios as S
-    env = H.make_vec_env(E, N, robot_visible=False, kinematics=kinematics)
-    pool = S.scenario_pool(env.spec(), "test", range(64), N, "circle_crossing")
-    ids = np.arange(E) % 64
-    env.load_scenarios(pool[ids])
-    env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=(ids + 7) % 64, fin_slots=2)
-    return env
-
-
-def _snapshot(env):
-    c = lambda t: t.detach().cpu().numpy().copy()
-    snap = {k: c(getattr(env, k)) for k in _FIELDS}
-    snap.update({"roll_" + k: c(v) for k, v in env.rollout_buffers.items() if k in _ROLL})
-    return snap
-
-
-def _actions(kinematics, T, E, seed):
-    rng = np.random.RandomState(seed)
-    if kinematics == "unicycle":
-        return np.stack([rng.uniform(0, 1, (T, E)), rng.uniform(-np.pi / 4, np.pi / 4, (T, E))], -1)
-    sp, aa = rng.uniform(0, 1, (T, E)), rng.uniform(0, 2 * np.pi, (T, E))
-    return np.stack([sp * np.cos(aa), sp * np.sin(aa)], -1)
-
-
-def _assert_same_bytes(a, b, what=""):
-    for k in a:
-        assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), (what, k)
-
 
 _single_steps = {}
 
 
 def _single_step_reference(E, kinematics, T):
     """T mcn_env_step calls on the shared action sequence, computed once per configuration and left unchanged."""
-    torch = _torch()
+    torch = need_gpu()
     key = (E, kinematics)
     if key not in _single_steps:
-        b = _rollout_env(E, kinematics)
-        acts_d = torch.from_numpy(_actions(kinematics, T, E, 5)).to(b.device)
+        b = pool_env(E, N, kinematics=kinematics)
+        acts_d = torch.from_numpy(random_actions(kinematics, T, E, 5)).to(b.device)
         for t in range(T):
             b.step(acts_d[t])
         torch.cuda.synchronize()
-        _single_steps[key] = _snapshot(b)
+        _single_steps[key] = snapshot(b)
     return _single_steps[key]
 
 
@@ -81,19 +42,17 @@ def test_eight_lane_layout_equals_single_steps(E, kinematics, tuning):
     """Less than a workgroup, exactly one, a ragged second, a ragged third: every byte of state, step record, Explorer
     record and finished-episode records after launches of 30 + 1 + 79 steps equals 110 single steps; every env
     finishes, and so restarts from the pool, inside them."""
-    torch = _torch()
-    from modelcrowdnav_amd import _hip
+    torch = need_gpu()
     T = 110
     ref = _single_step_reference(E, kinematics, T)
     tuning(rollout_fused=1)
     tuning(rollout_split=2)
-    a = _rollout_env(E, kinematics)
-    acts_d = torch.from_numpy(_actions(kinematics, T, E, 5)).to(a.device)
+    a = pool_env(E, N, kinematics=kinematics)
+    acts_d = torch.from_numpy(random_actions(kinematics, T, E, 5)).to(a.device)
     for lo, hi in ((0, 30), (30, 31), (31, T)):
-        a.rollout(acts_d[lo:hi])
-        assert _hip.last_dispatch() == "env_rollout_quad_kernel" and _hip.last_rollout_form() == 2
+        launch(a, acts_d[lo:hi], 2)
     torch.cuda.synchronize()
-    _assert_same_bytes(_snapshot(a), ref)
+    assert_same_bytes(snapshot(a), ref)
     assert int(a.rollout_buffers["fin_count"].min().item()) >= 1
 
 
@@ -117,18 +76,15 @@ def _reduction_state():
 
 
 def _reduction_run(split, T):
-    torch = _torch()
-    from modelcrowdnav_amd import _hip
+    torch = need_gpu()
     st, ax = _reduction_state()
-    env = _rollout_env(_E)
+    env = pool_env(_E, N)
     H.upload(env, st)
     acts = np.zeros((T, _E, 2))
     acts[:, :, 0] = ax                                  # the velocity the constructions were laid out for
-    _hip.set_tuning(rollout_fused=1, rollout_split=split)
-    env.rollout(torch.from_numpy(acts).to(env.device))
-    assert _hip.last_dispatch() == "env_rollout_quad_kernel" and _hip.last_rollout_form() == split
+    launch_cuts(env, torch.from_numpy(acts).to(env.device), split, (0, T))
     torch.cuda.synchronize()
-    return env, _snapshot(env)
+    return env, snapshot(env)
 
 
 @pytest.mark.gpu
@@ -143,5 +99,5 @@ def test_reduction_order_is_not_seen(tuning):
     dmin, info = env1.dmin.cpu().numpy(), env1.info.cpu().numpy()
     assert dmin[_ALL_NAN] == np.inf and np.isfinite(dmin[_ONE_NAN]), dmin
     assert dmin[_TOUCH] == 0.0 and not np.signbit(dmin[_TOUCH]) and info[_TOUCH] == _hip.INFO_DANGER, (dmin, info)
-    _assert_same_bytes(one, _reduction_run(1, 1)[1], "T = 1")
-    _assert_same_bytes(_reduction_run(2, 3)[1], _reduction_run(1, 3)[1], "T = 3")
+    assert_same_bytes(one, _reduction_run(1, 1)[1], "T = 1")
+    assert_same_bytes(_reduction_run(2, 3)[1], _reduction_run(1, 3)[1], "T = 3")

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
 from tests import scenario_gen_ref as R  # noqa: E402
+from tests.rollout_harness import goal_seeking  # noqa: E402
 
 # Largest error of double cos / sin of the device math library (OCML) in ulps: the library implements the OpenCL C
 # math functions, whose specification (OpenCL C 3.0, 7.4 "Relative error as ULPs") allows double sin and cos 4 ulp.
@@ -114,14 +115,6 @@ def test_unplaced_cases_are_the_replays_capped_cases(name, over):
     assert np.array_equal(got.cpu().numpy(), want) and want.any() == e.dense
 
 
-def _goal_seeking(env, t):
-    """A state-only robot: +-0.6 along each axis by the sign of the remaining goal offset (0 inside a 0.2 band)."""
-    import torch
-    d = env.rgoal - env.rpos
-    v, z = torch.full_like(d, 0.6), torch.zeros_like(d)
-    return (torch.where(d > 0.2, v, z) - torch.where(d < -0.2, v, z)).contiguous()
-
-
 @pytest.mark.parametrize("rounds", [1, 2])
 @pytest.mark.parametrize("phase, counter", [("train", 37), ("val", 11)])
 def test_rollout_plays_the_case_ids_of_its_phase(phase, counter, rounds):
@@ -146,7 +139,7 @@ def test_rollout_plays_the_case_ids_of_its_phase(phase, counter, rounds):
     def action_fn(env_, t):
         if t == 0:
             first.extend(snap())
-        return _goal_seeking(env_, t)
+        return goal_seeking(env_, t)
 
     env.attach_rollout = lambda *a, **kw: bufs.append(attach(*a, **kw)) or bufs[0]
     ex = VecExplorer(env, env.robot, gamma=0.9, policy=object())

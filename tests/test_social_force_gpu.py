@@ -19,6 +19,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
+from tests.rollout_harness import assert_same_bytes, need_gpu, snapshot  # noqa: E402
 from tests import social_force_ref as R  # noqa: E402
 
 E = 251
@@ -27,12 +28,6 @@ DEFAULT = (4.0, 0.2, 2.0)
 PARAMS = {7: (2.5, 0.35, 1.5), 13: (1.0, 1.0, 0.5)}            # crowd sizes that run with other than the defaults
 NS = (1, 2, 5, 7, 10, 13, 32)
 STATE_FIELDS = H.STATE_FIELDS + ("rtheta",)
-
-
-def _torch():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch
 
 
 def _sf_env(E_, N, vis, kinematics="holonomic", params=DEFAULT):
@@ -101,7 +96,7 @@ def _bytes_equal(x, y, what):
 # ------------------------------------------------------------------------------------------ 1 the velocities
 @pytest.mark.parametrize("N", NS)
 def test_velocities_match_the_definition(N, tuning):
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     st = _state(N)
     feats = _features(st)
@@ -165,7 +160,7 @@ def _robot_actions(kin, st, seed):
 @pytest.mark.parametrize("count_hh", (1, 0))
 @pytest.mark.parametrize("kin", ("holonomic", "unicycle"))
 def test_everything_after_the_velocity_is_bitwise(kin, count_hh, tuning):
-    torch = _torch()
+    torch = need_gpu()
     infos, arrivals = set(), 0
     for N in (5, 10):
         for vis in (0, 1):
@@ -240,21 +235,11 @@ def _rollout_env(N, vis, null):
     return env
 
 
-def _same_bytes(a, b, what):
-    H.assert_state_equal(H.download(a), H.download(b), fields=STATE_FIELDS, what=what)
-    _bytes_equal(a.step_rec.cpu().numpy(), b.step_rec.cpu().numpy(), what + " step records")
-    _bytes_equal(a.human_act.cpu().numpy().reshape(E, -1), b.human_act.cpu().numpy().reshape(E, -1), what + " human_act")
-    for k in ("state", "fin_return", "fin_time", "fin_info"):
-        _bytes_equal(a.rollout_buffers[k].cpu().numpy().T if k != "state" else a.rollout_buffers[k].cpu().numpy(),
-                     b.rollout_buffers[k].cpu().numpy().T if k != "state" else b.rollout_buffers[k].cpu().numpy(),
-                     what + " " + k)
-
-
 @pytest.mark.parametrize("null", (None, "fin_return", "fin_time", "fin_info", "human_act"))
 @pytest.mark.parametrize("path", ("loop", "loop-run-time-N", "launches"))
 @pytest.mark.parametrize("N", (5, 10))
 def test_rollout_equals_single_steps(N, path, null, tuning):
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     if path == "launches":
         tuning(rollout_fused=0)
@@ -272,7 +257,9 @@ def test_rollout_equals_single_steps(N, path, null, tuning):
                 b.step(acts[t])
             assert _hip.last_dispatch() == "env_step_kernel"
             torch.cuda.synchronize()
-            _same_bytes(a, b, "N=%d vis=%d %s without %s after %d steps" % (N, vis, path, null, hi))
+            what = "N=%d vis=%d %s without %s after %d steps" % (N, vis, path, null, hi)
+            assert_same_bytes(snapshot(a), snapshot(b), what)
+            H.assert_bits_equal(a.rrad.cpu().numpy(), b.rrad.cpu().numpy(), what + " rrad")      # (in no snapshot)
         rec = a.rollout_buffers
         fin = rec["fin_count"].cpu().numpy()
         assert fin.max() >= 3 and (fin >= 1).all(), "episodes must end, restart from the pool and overflow the two slots"
@@ -287,7 +274,7 @@ def test_rollout_equals_single_steps(N, path, null, tuning):
 
 # ------------------------------------------------------------------------------------------ 4 symmetry
 def test_mirrored_pair_gets_exactly_negated_actions(tuning):
-    torch = _torch()
+    torch = need_gpu()
     rng = np.random.RandomState(3)
     st = H.random_state(rng, E, 2, randomize=True)
     for k in ("hpx", "hpy", "hvx", "hvy", "hgx", "hgy"):
@@ -310,7 +297,7 @@ def test_mirrored_pair_gets_exactly_negated_actions(tuning):
 
 # ------------------------------------------------------------------------------------------ 5 the public surface
 def test_vec_env_reset_step_rollout():
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import _hip
     n = 64
     a, b = _sf_env(n, 5, 1), _sf_env(n, 5, 1)
@@ -337,7 +324,7 @@ def test_vec_env_reset_step_rollout():
 
 
 def _sarl(query_env=False):
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.policy.sarl import SARL
     torch.manual_seed(11)
@@ -366,7 +353,7 @@ def _single_env(policy):
 def test_explorer_batched_equals_sequential():
     """Explorer.run_k_episodes(64, 'test') with a SARL robot among social-force humans: batched (VecExplorer) and
     batched = False give the same success / collision / timeout rates and navigation time."""
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.utils.explorer import Explorer
     res = []
     for batched in (True, False):
@@ -381,7 +368,7 @@ def test_explorer_batched_equals_sequential():
 
 
 def test_single_env_view_matches_the_batched_env():
-    torch = _torch()
+    torch = need_gpu()
     from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
     from modelcrowdnav_amd.envs.policy.socialforce import SocialForce
     from modelcrowdnav_amd.envs.utils.action import ActionXY
@@ -409,7 +396,7 @@ def test_single_env_view_matches_the_batched_env():
 def test_query_env_lookahead_is_the_non_mutating_step():
     """`query_env = true`: the humans' next states and the rewards the look-ahead is given are those of
     step(update = False), for three envs and every action of the table."""
-    torch = _torch()
+    torch = need_gpu()
     pol = _sarl(query_env=True)
     vec = _sf_env(3, 5, 1)
     vec.robot.set_policy(pol)
