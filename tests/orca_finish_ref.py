@@ -1,6 +1,8 @@
 """Host replay of mcn_orca_finish (include/mcn.h): CrowdSim.get_human_times (crowd_sim.py:219-258) over a batch, in plain
 numpy with the C oracle's ORCA solver (oracle.cport.orca_agent), operation for operation as the header states them.
 Also the scenes the CPU and GPU tests of the entry point share."""
+from fractions import Fraction
+
 import numpy as np
 
 from oracle import cport
@@ -10,12 +12,41 @@ f32, f64 = np.float32, np.float64
 STATE_KEYS = ("hpos", "hgoal", "hrad", "hvpref", "rpos", "rgoal", "rrad", "rvpref", "gtime", "human_times")
 
 
+EVENT_NAMES = ("arrival", "arrival_touch", "arrival_f64_only", "arrival_f32_only", "arrival_after_move",
+               "arrival_rad64_only", "pref_unit", "pref_ulp_above", "pref_zero", "neg_zero_pending", "odd_time_kept",
+               "odd_only_env", "clock_absorbed", "clock_rounded", "select_other_byte", "unselected_env")
+
+
+def _dist(p, g):
+    dx, dy = p[0] - g[0], p[1] - g[1]
+    return np.sqrt(dx * dx + dy * dy)
+
+
 def replay(state, sim_vel, select=None, max_steps=8000, time_step=0.25, neighbor_dist=10.0, max_neighbors=10,
-           time_horizon=5.0):
+           time_horizon=5.0, events=None):
     """state: dict of float64 arrays, hpos / hgoal [E,N,2], hrad / hvpref / human_times [E,N], rpos / rgoal [E,2],
     rrad / rvpref / gtime [E]; sim_vel [E,N+1,2] float32.  Nothing is modified.  Returns a dict: the four arrays the
     entry point writes (hpos, rpos, gtime, human_times), sim_vel, steps [E] int32 and traj, a list of E arrays
-    [steps[e], N+1, 2] float32 (positions after each simulated step)."""
+    [steps[e], N+1, 2] float32 (positions after each simulated step).
+    events: None, or a dict that receives counts of the float64 half's boundary events (EVENT_NAMES; a list of E dicts
+    under "per_env" as well), for coverage assertions; counting changes no result:
+      arrival             a first-arrival time was set
+      arrival_touch       a pending human at distance == radius exactly (strict <: not arrived)
+      arrival_f64_only / arrival_f32_only   on the first step of the call the test on the caller's float64 position and
+                          the test on float64(float32(position)) disagree (only the former / only the latter arrives)
+      arrival_after_move  not arrived by the position from before the step, but the position after it is inside
+      arrival_rad64_only  arrived by the float64 radius, not by float64(float32(radius))
+      pref_unit / pref_ulp_above / pref_zero   |goal - p64| == 1 (not normalised), == 1 + 2^-52, == 0
+      neg_zero_pending    a human_times entry of -0.0 at entry (it is == 0: pending)
+      odd_time_kept       a human_times entry that is NaN, negative, infinite or subnormal at entry of a selected env
+                          (it is != 0: set, and never written)
+      odd_only_env        a selected env that takes no step although no entry is a positive normal time
+      clock_absorbed / clock_rounded   gtime + time_step == gtime / is not the exact sum
+      select_other_byte / unselected_env   a select byte other than 0 and 1 / equal to 0"""
+    count = events is not None
+    if count:
+        events.update(dict.fromkeys(EVENT_NAMES, 0))
+        per_env = events["per_env"] = []
     out = {k: np.array(state[k], f64) for k in ("hpos", "rpos", "gtime", "human_times")}
     out["sim_vel"] = np.array(sim_vel, f32)
     E, N = out["human_times"].shape
@@ -23,8 +54,14 @@ def replay(state, sim_vel, select=None, max_steps=8000, time_step=0.25, neighbor
     out["traj"] = [np.zeros((0, N + 1, 2), f32) for _ in range(E)]
     dt32 = f32(time_step)
     for e in range(E):
+        ev = dict.fromkeys(EVENT_NAMES, 0)
+        if count:
+            per_env.append(ev)
         if select is not None and not select[e]:
+            ev["unselected_env"] += 1
             continue
+        if select is not None and int(select[e]) != 1:
+            ev["select_other_byte"] += 1
         p64 = np.concatenate([out["rpos"][e][None], out["hpos"][e]]).astype(f64)
         goal = np.concatenate([np.asarray(state["rgoal"], f64)[e][None], np.asarray(state["hgoal"], f64)[e]])
         rad64 = np.concatenate([np.asarray(state["rrad"], f64)[e:e + 1], np.asarray(state["hrad"], f64)[e]])
@@ -33,11 +70,20 @@ def replay(state, sim_vel, select=None, max_steps=8000, time_step=0.25, neighbor
         p32, vel = p64.astype(f32), out["sim_vel"][e].copy()
         times, t = out["human_times"][e].copy(), f64(out["gtime"][e])
         rows = []
+        if count:
+            odd = ~((times > 0) & np.isfinite(times) & (times >= np.finfo(f64).tiny)) & ~(times == 0)
+            ev["odd_time_kept"] += int(odd.sum())
+            ev["neg_zero_pending"] += int(((times == 0) & np.signbit(times)).sum())
+            ev["odd_only_env"] += int(np.all(times != 0) and bool(odd.all()))
         while not np.all(times != 0) and len(rows) < max_steps:
             pref = np.zeros((N + 1, 2), f32)
             for i in range(N + 1):
                 ex, ey = goal[i, 0] - p64[i, 0], goal[i, 1] - p64[i, 1]
                 n = np.sqrt(ex * ex + ey * ey)
+                if count:
+                    ev["pref_unit"] += int(n == 1)
+                    ev["pref_ulp_above"] += int(n == 1 + 2.0 ** -52)
+                    ev["pref_zero"] += int(n == 0)
                 if n > 1:
                     ex, ey = ex / n, ey / n
                 pref[i] = f32(ex), f32(ey)
@@ -49,10 +95,23 @@ def replay(state, sim_vel, select=None, max_steps=8000, time_step=0.25, neighbor
                                           time_horizon=time_horizon, time_step=dt32)
             vel = new.astype(f32)
             p32 = (p32 + (vel * dt32).astype(f32)).astype(f32)
+            if count:
+                ev["clock_absorbed"] += int(t + f64(time_step) == t)
+                ev["clock_rounded"] += int(Fraction(float(t)) + Fraction(float(time_step)) != Fraction(float(t + f64(time_step))))
             t = t + f64(time_step)
             for i in range(1, N + 1):
                 if times[i - 1] == 0:
                     dx, dy = p64[i, 0] - goal[i, 0], p64[i, 1] - goal[i, 1]
+                    if count:
+                        d, after = _dist(p64[i], goal[i]), _dist(p32[i].astype(f64), goal[i])
+                        ev["arrival"] += int(d < rad64[i])
+                        ev["arrival_touch"] += int(d == rad64[i])
+                        ev["arrival_after_move"] += int(not d < rad64[i] and after < rad64[i])
+                        ev["arrival_rad64_only"] += int(d < rad64[i] and not d < f64(rad32[i]))
+                        if not rows:
+                            d32 = _dist(p64[i].astype(f32).astype(f64), goal[i])
+                            ev["arrival_f64_only"] += int(d < rad64[i] and not d32 < rad64[i])
+                            ev["arrival_f32_only"] += int(d32 < rad64[i] and not d < rad64[i])
                     if np.sqrt(dx * dx + dy * dy) < rad64[i]:
                         times[i - 1] = t
             p64 = p32.astype(f64)
@@ -62,6 +121,10 @@ def replay(state, sim_vel, select=None, max_steps=8000, time_step=0.25, neighbor
             out["gtime"][e], out["human_times"][e], out["sim_vel"][e] = t, times, vel
             out["steps"][e] = len(rows)
             out["traj"][e] = np.stack(rows)
+    if count:
+        for ev in per_env:
+            for k, v in ev.items():
+                events[k] += v
     return out
 
 
