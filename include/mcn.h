@@ -47,7 +47,9 @@ enum { MCN_HUMANS_ORCA = 0,     /* crowd_sim/envs/policy/orca.py:82-132         
                                        * the model's three parameters; mcn_env_step / mcn_env_rollout reject this value) */
 enum { MCN_KIN_HOLONOMIC = 0, MCN_KIN_UNICYCLE = 1 };
 
-/* Scalar configuration: env.config [env]/[reward] + orca.py:60-66 + robot flags. */
+/* Scalar configuration: env.config [env]/[reward] + orca.py:60-66 + robot flags.  The orca_* fields belong to
+ * MCN_HUMANS_ORCA: with any other human_policy no kernel reads them (orca_max_neighbors is still range-checked), so
+ * they may hold anything, NaN included, and change no output. */
 typedef struct mcn_env_cfg {
     double time_step;                  /* env.config:3   */
     double time_limit;                 /* env.config:2   */

@@ -148,7 +148,10 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
 
     // ---- stage neighbour tiles in LDS ----
     const float fpx = (float)pos.x, fpy = (float)pos.y, fvx = (float)vel.x, fvy = (float)vel.y;
-    const float frad = (float)(attr.x + 0.01 + c.orca_safety_space);
+    // ORCA humans stage the padded radius their half-planes use; every other mode stages the plain one for the overlap
+    // pre-filter and reads no orca_* field of the cfg
+    float frad = (float)attr.x;
+    if constexpr (MODE == MCN_HUMANS_ORCA) frad = (float)(attr.x + 0.01 + c.orca_safety_space);
     if constexpr (kStageHumans) {
         sAgF[tid] = make_float4(fpx, fpy, fvx, fvy);
         sRadF[tid] = frad;
@@ -382,7 +385,11 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
             for (int j = h + 1; j < N; ++j) {
                 const float4 q = sAgF[gbase + j];
                 const float dxf = fpx - q.x, dyf = fpy - q.y;
-                const float gap = sqrtf(dxf * dxf + dyf * dyf) - ((float)attr.x + (sRadF[gbase + j] - 0.01f - (float)c.orca_safety_space));
+                float gap;
+                if constexpr (MODE == MCN_HUMANS_ORCA)      // the staged radius carries the ORCA padding
+                    gap = sqrtf(dxf * dxf + dyf * dyf) - ((float)attr.x + (sRadF[gbase + j] - 0.01f - (float)c.orca_safety_space));
+                else
+                    gap = sqrtf(dxf * dxf + dyf * dyf) - ((float)attr.x + sRadF[gbase + j]);
                 if (gap < -1e-3f) ++hh;
                 else if (gap < 1e-3f) borderline = true;
             }

@@ -1,12 +1,15 @@
 """The kernel paths the edge, ladder and accounting batteries run over: every decomposition of mcn_env_step, every path
 of mcn_env_rollout, what each must reach, and the four-wavefront form's battery under rolled env orders.  Tests of the
 oracle alone (no GPU) read the same tables."""
+import functools
+
 import numpy as np
 
 from tests import edge_states as ES
 from tests import helpers as H
 from tests import ladder_states as LS
 from tests.rollout_harness import assert_same_bytes, launch, need_gpu, snapshot
+from tests.rollout_ref import sf_velocities      # tests/social_force_ref.py on an oracle state
 
 STEP_KERNELS = ["auto", "lane-per-human", "lane-per-human-256", "deferred-lp3", "deferred-lp3-256", "run-time-N",
                 "run-time-N-256", "quad", "quad-split"]
@@ -145,3 +148,36 @@ def rolled_wg4_battery(build, take, st, acts, names, cuts, check_first, check_la
     for block in sorted(set(names)):
         slots = set().union(*(seen[i] for i in range(E) if names[i] == block))
         assert set(WG4_STRADDLERS) <= slots, (what, block, sorted(slots))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# social-force humans (mcn_env_step_sf / mcn_env_rollout_sf)
+SF_DEFAULT = (4.0, 0.2, 2.0)      # (strength A, range B, relaxation_rate k) as shipped
+# A = 0: every m = 0 * exp(..) is exactly 0, so exp -- the only inexact operation -- is multiplied away and the
+# restatement is bit-exact; k = 4 with dt = 0.25 gives a human at rest w = 0 + 4 * e * 0.25 = e exactly
+SF_INERT = (0.0, 0.2, 4.0)
+SF_COMPILED_NS = (5, 10)          # crowd sizes with compile-time-N step kernels besides the run-time-N ones
+SF_GENERIC_NS = (1, 2, 3, 7, 13, 32)
+SF_TOL = 8 * 2.0 ** -52           # of the restatement's magnitude M (tests/test_social_force_gpu.py, part 1)
+
+
+def sf_step_forms(N):
+    """(step_block, force_generic) of every env_step_kernel<.., MCN_HUMANS_SOCIALFORCE, ..> form that takes N humans."""
+    return [(b, g) for g in ((0, 1) if N in SF_COMPILED_NS else (0,)) for b in (64, 256)]
+
+
+@functools.lru_cache(maxsize=None)
+def sf_ladder_reference(N, visible, dd, params):
+    """The restatement's velocities on LS.ladder_batch(N, visible, dd), computed once per process; read-only."""
+    st = LS.ladder_batch(N, visible, dd)[0]
+    want, mag = sf_velocities(st, params, visible)
+    want.setflags(write=False); mag.setflags(write=False)
+    return want, mag
+
+
+def sf_oracle_step(cfg, st, ax, ay, params, visible, update=True):
+    """One host step of social-force humans: the restatement's velocities handed to the oracle's given-velocity step
+    (cfg.human_policy must be HUMANS_GIVEN).  Returns (the oracle's outputs, the velocities, their magnitudes)."""
+    from oracle import cport
+    want, mag = sf_velocities(st, params, visible, cfg.time_step)
+    return cport.env_step(cfg, st, ax, ay, update=update, given_v=want), want, mag

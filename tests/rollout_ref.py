@@ -311,18 +311,17 @@ def workload(name, N, mode):
     return _simulate(name, N, mode, min(ok, key=lambda e: abs(e - SHORT_MID)) + 1)
 
 
-def _simulate(name, N, mode, short_from, shift=None):
-    """The inputs and the replay of parameter set `name` for N humans, mode 'orca' (ORCA humans, overlap count, first
-    arrivals) or 'given' (velocities handed in, neither of the two).  Two envs in three walk to the goal by the exact
-    goal-seeking rule evaluated on the ORACLE's state -- every other one of them only after it has let the crowd cross
-    for the first 40 steps of the episode, so that goals are reached in crowds of 10 too; the third takes random dyadic
-    actions.  Every seeker also waits two more steps per episode it has finished (0, 2, .. 8, then again from 0), so that
-    an env that restarts the same case -- a pool of one -- does not repeat its episode byte for byte.  Given velocities
-    point at the human's goal, rounded to sixteenths, plus dyadic noise -- also computed from the oracle's state."""
+SF_PARAMS = (0.0, 0.2, 2.0)             # mode "sf": strength 0 -- every m = 0 * exp(..) is exactly 0, the replay bit-exact
+SF_SHIPPED = (4.0, 0.2, 2.0)            # the lock-step runs (LockStep): the device's own velocities go into the replay
+
+
+def _setup(name, N, mode, short_from, shift=None, visible=False):
+    """The pool, the contract, the replay, the oracle's state and cfg of parameter set `name`, and the set's random
+    stream (seeded by name, N and mode; the pool's start velocities are its first draws)."""
     from modelcrowdnav_amd.envs import scenarios as S
     s = SETS[name]
-    E, T, P = E_ACC, T_ACC, s["P"]
-    time_limit, speed = s.get("time_limit", 25.0), s.get("speed", 0.6)
+    E, P = E_ACC, s["P"]
+    time_limit = s.get("time_limit", 25.0)
     rng = np.random.RandomState(zlib.crc32(("%s/%d/%s" % (name, N, mode)).encode()))
     scen = S.scenario_pool(S.ScenarioSpec(), "test", range(P), N, "circle_crossing")
     if s["pool"] == "host":
@@ -338,8 +337,49 @@ def _simulate(name, N, mode, short_from, shift=None):
     first = (start + (s["shift"] if shift is None else shift)) % P
     rep = Replay(E, con, first_cases=first)
     st = initial_state(pool, start)
+    full = mode != "given"              # overlap count and first arrivals: all but the streaming kernel's lean step
     cfg = cport.default_cfg(time_limit=time_limit, human_policy=cport.HUMANS_ORCA if mode == "orca" else cport.HUMANS_GIVEN,
-                            count_hh=1 if mode == "orca" else 0, track_human_times=1 if mode == "orca" else 0)
+                            count_hh=1 if full else 0, track_human_times=1 if full else 0,
+                            robot_visible=1 if visible else 0)
+    return s, rng, scen, pool, con, first, rep, st, cfg
+
+
+def _robot_actions(s, st, rep, rng):
+    """[E, 2] actions of one step from the ORACLE's state and the replay's counters: _simulate's rule."""
+    E = st.E
+    role = (np.arange(E) + 2) % 3                  # (the last env, the one danger_short_from = E shortens, walks at once)
+    seeker = role != 2
+    late = role == 1                    # these stand still for the first `wait` steps of every episode
+    gx, gy = host_goal_seeking(st, s.get("speed", 0.6))
+    wait = np.where(late, s.get("wait", 40), 0) + 2 * (rep.rec["fin_count"] % 5)
+    hold = rep.rec["ep_steps"] < wait
+    gx, gy = np.where(hold, 0.0, gx), np.where(hold, 0.0, gy)
+    acts = np.zeros((E, 2))
+    acts[:, 0] = np.where(seeker, gx, rng.randint(-16, 17, E) / 16.0)
+    acts[:, 1] = np.where(seeker, gy, rng.randint(-16, 17, E) / 16.0)
+    return acts
+
+
+def sf_velocities(st, params, visible, dt=0.25):
+    """tests/social_force_ref.py on the oracle's state: ([E, N, 2] velocities, [E, N] magnitudes)."""
+    from tests import social_force_ref as SF
+    return SF.batch_velocities(np.stack([st.hpx, st.hpy], -1), np.stack([st.hvx, st.hvy], -1),
+                               np.stack([st.hgx, st.hgy], -1), st.hr, st.hvpref, params[0], params[1], params[2], dt,
+                               np.stack([st.rpx, st.rpy], -1) if visible else None, st.rr if visible else None)
+
+
+def _simulate(name, N, mode, short_from, shift=None):
+    """The inputs and the replay of parameter set `name` for N humans, mode 'orca' (ORCA humans, overlap count, first
+    arrivals), 'given' (velocities handed in, neither of the two) or 'sf' (social-force humans with SF_PARAMS: each
+    step's velocities are the restatement's on the oracle's state, handed to the oracle's given-velocity step with the
+    overlap count and first arrivals on).  Two envs in three walk to the goal by the exact
+    goal-seeking rule evaluated on the ORACLE's state -- every other one of them only after it has let the crowd cross
+    for the first 40 steps of the episode, so that goals are reached in crowds of 10 too; the third takes random dyadic
+    actions.  Every seeker also waits two more steps per episode it has finished (0, 2, .. 8, then again from 0), so that
+    an env that restarts the same case -- a pool of one -- does not repeat its episode byte for byte.  Given velocities
+    point at the human's goal, rounded to sixteenths, plus dyadic noise -- also computed from the oracle's state."""
+    s, rng, scen, pool, con, first, rep, st, cfg = _setup(name, N, mode, short_from, shift)
+    E, T = E_ACC, T_ACC
     w = Workload()
     w.name, w.N, w.mode, w.E, w.T, w.set, w.contract, w.cfg = name, N, mode, E, T, s, con, cfg
     w.scen, w.pool, w.first_cases, w.st0 = scen, pool, first, st.copy()
@@ -347,21 +387,15 @@ def _simulate(name, N, mode, short_from, shift=None):
     w.given = np.zeros((T, E, N, 2)) if mode == "given" else None
     w.recs = {k: [] for k in ("reward", "dmin", "done", "info", "hh_count")}
     w.human_act, w.snaps = {}, {}
-    role = (np.arange(E) + 2) % 3                  # (the last env, the one danger_short_from = E shortens, walks at once)
-    seeker = role != 2
-    late = role == 1                    # these stand still for the first `wait` steps of every episode
     for t in range(T):
-        gx, gy = host_goal_seeking(st, speed)
-        wait = np.where(late, s.get("wait", 40), 0) + 2 * (rep.rec["fin_count"] % 5)
-        hold = rep.rec["ep_steps"] < wait
-        gx, gy = np.where(hold, 0.0, gx), np.where(hold, 0.0, gy)
-        w.acts[t, :, 0] = np.where(seeker, gx, rng.randint(-16, 17, E) / 16.0)
-        w.acts[t, :, 1] = np.where(seeker, gy, rng.randint(-16, 17, E) / 16.0)
+        w.acts[t] = _robot_actions(s, st, rep, rng)
         gv = None
         if mode == "given":
             d = np.stack([st.hgx - st.hpx, st.hgy - st.hpy], -1)
             n = np.maximum(np.linalg.norm(d, axis=-1, keepdims=True), 1e-9)
             gv = w.given[t] = np.round(d / n * 12.0) / 16.0 + rng.randint(-3, 4, (E, N, 2)) / 16.0
+        elif mode == "sf":
+            gv = sf_velocities(st, SF_PARAMS, False)[0]
         out = rep.step(cfg, st, w.acts[t, :, 0].copy(), w.acts[t, :, 1].copy(), given_v=gv)
         for k in w.recs:
             w.recs[k].append(out[k].copy())
@@ -369,6 +403,12 @@ def _simulate(name, N, mode, short_from, shift=None):
             w.snaps[t + 1] = (st.copy(), rep.snapshot())
             w.human_act[t + 1] = out["human_act"].copy()
     w.recs = {k: np.stack(v) for k, v in w.recs.items()}
+    _close_events(w, rep)
+    return w
+
+
+def _close_events(w, rep):
+    con = rep.c
     w.events = dict(rep.events)
     w.last_danger = rep.last_danger.copy()
     # envs whose single slot would hold other bytes had it kept the FIRST episode (fin_slots == 1 only)
@@ -376,4 +416,59 @@ def _simulate(name, N, mode, short_from, shift=None):
         w.events["first_wins_differs"] = sum(1 for e, f in rep.first.items()
                                              if f != (rep.fin_return[0, e], rep.fin_time[0, e], int(rep.fin_info[0, e])))
     w.events["max_fin_count"] = int(rep.rec["fin_count"].max())
-    return w
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# social-force humans with the shipped parameters: the replay in lock step with the device
+
+# the boundary entries that only danger_short_from = "mid" / E can reach
+_MID_ONLY = ("long_side_counted", "boundary_gated", "below_boundary_counted")
+LOCKSTEP_SETS = ("explorer-first", "latest-wins")
+
+
+def lockstep_required(name):
+    return tuple(k for k in REQUIRED[name] if k not in _MID_ONLY)
+
+
+class LockStep(object):
+    """Parameter set `name` with social-force humans of SF_SHIPPED strength, one step at a time.  exp on the device may
+    differ from the host's by an ulp and 130 steps amplify that, so the host cannot run ahead: per step actions() gives
+    the robots' actions from the HOST state (_simulate's rule), restatement() the definition's velocities on it, and
+    advance() takes the velocities the humans actually chose (the device's, or the restatement's for a forecast) into
+    Replay.step as given velocities."""
+
+    def __init__(self, name, N, visible, params=SF_SHIPPED):
+        assert name in LOCKSTEP_SETS
+        (self.set, self.rng, self.scen, self.pool, self.contract, self.first_cases, self.rep, self.st,
+         self.cfg) = _setup(name, N, "sf-lockstep", SETS[name]["danger_short_from"], visible=visible)
+        self.name, self.N, self.E, self.T, self.visible, self.params = name, N, E_ACC, T_ACC, bool(visible), params
+        self.st0 = self.st.copy()
+        self.t = 0
+
+    def actions(self):
+        return _robot_actions(self.set, self.st, self.rep, self.rng)
+
+    def restatement(self):
+        return sf_velocities(self.st, self.params, self.visible)
+
+    def advance(self, acts, human_act):
+        out = self.rep.step(self.cfg, self.st, acts[:, 0].copy(), acts[:, 1].copy(),
+                            given_v=np.ascontiguousarray(human_act, np.float64))
+        self.t += 1
+        return out
+
+    def events(self):
+        w = Workload()
+        _close_events(w, self.rep)
+        return w.events
+
+
+@functools.lru_cache(maxsize=None)
+def lockstep_forecast(name, N, visible):
+    """The events of a LockStep run that takes the restatement's own velocities (libm's exp): what the device run, which
+    differs by ulps of exp only, is expected to reach."""
+    ls = LockStep(name, N, visible)
+    for _ in range(ls.T):
+        a = ls.actions()
+        ls.advance(a, ls.restatement()[0])
+    return ls.events()

@@ -17,6 +17,14 @@ The human's action is w.  Written from the definition, not from the kernel.
 import math
 
 
+def _exp(x):
+    """IEEE exp: +inf where the result overflows (math.exp raises there); NaN and -inf pass through math.exp."""
+    try:
+        return math.exp(x)
+    except OverflowError:
+        return math.inf
+
+
 def human_velocity(p, v, g, r, s, others, A, B, k, dt):
     """One human.  others: [(qx, qy, radius)] in the order they are added.  Returns ((wx, wy), M) with the magnitude
     M = |v| + dt * (k*(|e| + |v|) + sum_j m_ij) that an error bound of the result scales with."""
@@ -30,7 +38,7 @@ def human_velocity(p, v, g, r, s, others, A, B, k, dt):
         dx, dy = p[0] - qx, p[1] - qy
         dist = math.sqrt(dx * dx + dy * dy)
         if dist > 0:
-            m = A * math.exp((r + rj - dist) / B)
+            m = A * _exp((r + rj - dist) / B)
             ax = ax + m * (dx / dist)
             ay = ay + m * (dy / dist)
             msum += m

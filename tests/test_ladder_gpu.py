@@ -3,7 +3,8 @@ the swept test (touching, a point segment, u exactly 0 or 1, tied humans), the o
 touching (float32-rounded positions on the other side of touching included), the goal test at and within 1e-6 of the
 radius, the timeout rung at and one ulp below time_limit - 1, the rung precedences, first arrivals at exactly one radius,
 headings with a zero fmod remainder, and the look-ahead reward of mcn_sarl_predict, mcn_lstm_rl_predict and
-mcn_cadrl_predict.
+mcn_cadrl_predict.  The social-force instantiations (mcn_env_step_sf / mcn_env_rollout_sf) run the same batches: their
+velocity against tests/social_force_ref.py, everything after it against the oracle's given-velocity step.
 
 Each test replays its own inputs through the oracle and asserts that they reached the ladder events it claims
 (cport.ladder_counts); failures name the block of the first differing envs."""
@@ -15,8 +16,10 @@ pytestmark = pytest.mark.gpu
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
 from tests import ladder_states as LS  # noqa: E402
-from tests.kernel_paths import (ROLLOUT_PATHS, STEP_EVENTS, STEP_KERNELS, UNICYCLE_EVENTS, forced_form,  # noqa: E402
-                                ladder_configs, rolled_wg4_battery, select_step_kernel)
+from tests.kernel_paths import (ROLLOUT_PATHS, SF_COMPILED_NS, SF_DEFAULT, SF_GENERIC_NS, SF_INERT, SF_TOL,  # noqa: E402
+                                STEP_EVENTS, STEP_KERNELS, UNICYCLE_EVENTS, forced_form, ladder_configs,
+                                rolled_wg4_battery, select_step_kernel, sf_ladder_reference, sf_oracle_step,
+                                sf_step_forms)
 from tests.rollout_harness import assert_same_bytes, launch, need_gpu, snapshot  # noqa: E402
 
 LA_EVENTS = ("la_touch", "la_danger_edge", "la_reach_edge", "la_collision_after_min")
@@ -252,8 +255,158 @@ def test_rollout_on_ladder_batches_equals_single_steps_and_oracle(path, unicycle
     _assert_reached(total, events, path)
 
 
+# ------------------------------------------------------------------------------------------ social-force humans
+def _sf_env(N, visible, dd, count_hh, E, params):
+    env = H.make_vec_env(E, N, robot_visible=visible, **{"humans.policy": "socialforce"})
+    assert env.human_policy_name == "socialforce"
+    env._sf.strength, env._sf.range, env._sf.relaxation_rate = params
+    env.discomfort_dist = dd
+    env.count_hh = count_hh
+    return env
+
+
+def _sf_hold_velocities(got, want, mag, exact, names, what):
+    """human_act against the restatement: bitwise where it is exact (A = 0), else within SF_TOL * M.  Returns the
+    largest error / tolerance."""
+    if exact:
+        bad = H.bit_mismatch(got, want)
+        assert len(bad) == 0, (what, "human_act", len(bad), _where(names, bad))
+        return 0.0
+    assert np.isfinite(got).all() and np.isfinite(want).all(), what
+    tol = SF_TOL * mag[..., None]
+    err = np.abs(got - want)
+    bad = np.argwhere(err > tol)
+    assert len(bad) == 0, (what, "human_act", len(bad), _where(names, bad), float((err / np.maximum(tol, 1e-300)).max()))
+    return float(np.max(np.where(tol > 0, err / np.where(tol > 0, tol, 1), 0)))
+
+
+@pytest.mark.parametrize("update", [1, 0])
+@pytest.mark.parametrize("params", [SF_INERT, SF_DEFAULT], ids=["inert", "default"])
+def test_social_force_step_on_ladder_batches(params, update, tuning):
+    """env_step_kernel<.., MCN_HUMANS_SOCIALFORCE, HH 0 / 1> on the ladder batches: 5 and 10 humans at compile-time N
+    and force_generic, 1 .. 32 at run-time N, step_block 64 and 256.  The velocity against tests/social_force_ref.py;
+    everything after it bitwise against the oracle's given-velocity step.
+
+      inert    (A, B, k) = (0, 0.2, 4): every m = 0 * exp(..) is exactly 0, so the restatement is bit-exact and
+               human_act is held to it bitwise; the oracle is fed the restatement's velocities.  A human at rest gets
+               w = e exactly, so the first-arrival block ends exactly one radius from its goal (human_time_edge).
+      default  (4, 0.2, 2): human_act within 8 * 2^-52 * M of the restatement; the oracle is fed the device's
+               velocities.  (human_time_edge is not reached with these parameters: tests/test_social_force_cpu.py.)
+
+    As for the ORCA kernels the oracle counts human_time_edge only on a step that updates the state."""
+    torch = need_gpu()
+    from modelcrowdnav_amd import _hip
+    exact = params == SF_INERT
+    total, worst, runs = {}, 0.0, 0
+    for N, visible, dd, count_hh in ladder_configs(SF_COMPILED_NS + SF_GENERIC_NS, quad=False):
+        st, ax, ay, _, names = LS.ladder_batch(N, visible, dd)
+        want, mag = sf_ladder_reference(N, visible, dd, params)
+        env = _sf_env(N, visible, dd, count_hh, st.E, params)
+        act = torch.from_numpy(np.stack([ax, ay], -1)).to(env.device)
+        for block, generic in sf_step_forms(N):
+            tuning(step_block=block, force_generic=generic)
+            what = "social force %s N=%d visible=%d dd=%g count_hh=%d block=%d generic=%d update=%d" % (
+                "inert" if exact else "default", N, visible, dd, count_hh, block, generic, update)
+            H.upload(env, st)
+            env.human_act.fill_(float("nan"))
+            ob, reward, done, info = env.step(act, update=bool(update))
+            torch.cuda.synchronize()
+            assert _hip.last_dispatch() == "env_step_kernel", what
+            got = dict(reward=reward.cpu().numpy(), done=done.cpu().numpy(), info=info.cpu().numpy(),
+                       dmin=env.dmin.cpu().numpy(), hh_count=env.hh_count.cpu().numpy(),
+                       human_act=env.human_act.cpu().numpy())
+            if not update:
+                got.update(nobs_px=ob.pos[..., 0].cpu().numpy(), nobs_py=ob.pos[..., 1].cpu().numpy(),
+                           nobs_vx=ob.vel[..., 0].cpu().numpy(), nobs_vy=ob.vel[..., 1].cpu().numpy())
+            worst = max(worst, _sf_hold_velocities(got["human_act"], want, mag, exact, names, what))
+            ref_st = st.copy()
+            cport.ladder_counts(reset=True)
+            ref = cport.env_step(H.oracle_cfg_for(env, cport.HUMANS_GIVEN), ref_st, ax, ay, update=bool(update),
+                                 given_v=np.array(want) if exact else got["human_act"])
+            if (block, generic) == sf_step_forms(N)[0]:
+                _add(total)
+            for k in got:
+                bad = H.bit_mismatch(got[k], ref[k])
+                assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+            H.assert_state_equal(H.download(env), ref_st if update else st, fields=H.STATE_FIELDS, what=what)
+            runs += 1
+    cport.ladder_counts(reset=True)
+    events = [k for k in STEP_EVENTS if k != "human_time_edge" or (exact and update)]
+    _assert_reached(total, events, "social force")
+    print("social force %s update=%d: %d runs, largest error / tolerance %.4f, reached %s" % (
+        "inert" if exact else "default", update, runs, worst, {k: total[k] for k in events}))
+
+
+@pytest.mark.parametrize("N", SF_COMPILED_NS)
+def test_social_force_rollout_on_ladder_batches(N, tuning):
+    """mcn_env_rollout_sf with the inert parameters over 8 steps (3 + 5) == 8 mcn_env_step_sf calls, every byte, with
+    and without a scenario pool; the multi-step launches go out as env_step_loop_sf_kernel.  Without a pool also == the
+    host replay of 8 restatement + oracle steps (bit-exact: A = 0), and a one-step launch == the oracle's boundary
+    step."""
+    torch = need_gpu()
+    from modelcrowdnav_amd import _hip
+    from modelcrowdnav_amd.envs import scenarios as S
+    T, params = 8, SF_INERT
+    total = {}
+    for N_, visible, dd, count_hh in ladder_configs((N,), quad=False):
+        st, ax0, ay0, _, names = LS.ladder_batch(N, visible, dd)
+        E = st.E
+        rng = np.random.RandomState(N * 2 + visible)
+        ax = np.concatenate([ax0[None], rng.randint(0, 17, (T - 1, E)) / 16.0])
+        ay = np.concatenate([ay0[None], rng.randint(-4, 5, (T - 1, E)) / 16.0])
+        acts = torch.from_numpy(np.stack([ax, ay], -1))
+        what = "social force rollout N=%d visible=%d dd=%g count_hh=%d" % (N, visible, dd, count_hh)
+        for with_pool in (False, True):
+            a, b = (_sf_env(N, visible, dd, count_hh, E, params) for _ in range(2))
+            for env in (a, b):
+                H.upload(env, st)
+                if with_pool:
+                    pool = S.scenario_pool(env.spec(), "test", range(16), N, "circle_crossing")
+                    env.attach_rollout(gamma=0.9, pool=pool, case_stride=3, first_cases=np.arange(E) % 16, fin_slots=2)
+            acts_d = acts.to(a.device)
+            for lo, hi in ((0, 3), (3, T)):
+                a.rollout(acts_d[lo:hi])
+                assert _hip.last_dispatch() == "env_step_loop_sf_kernel", (what, _hip.last_dispatch())
+            for t in range(T):
+                b.step(acts_d[t])
+            assert _hip.last_dispatch() == "env_step_kernel"
+            torch.cuda.synchronize()
+            assert_same_bytes(snapshot(a), snapshot(b), (what, with_pool))
+            if with_pool:
+                assert int(a.rollout_buffers["fin_count"].sum().item()) > 0
+                continue
+            ref_st = st.copy()
+            cfg = H.oracle_cfg_for(a, cport.HUMANS_GIVEN)
+            cport.ladder_counts(reset=True)
+            for t in range(T):
+                ref, want, _ = sf_oracle_step(cfg, ref_st, ax[t], ay[t], params, visible)
+                if t == 0:
+                    _add(total)
+            cport.ladder_counts(reset=True)
+            H.assert_state_equal(H.download(a), ref_st, fields=H.STATE_FIELDS + ("rtheta",), what=what)
+            for k, v in (("reward", a.reward), ("done", a.done), ("info", a.info), ("dmin", a.dmin),
+                         ("hh_count", a.hh_count), ("human_act", a.human_act)):
+                bad = H.bit_mismatch(v.cpu().numpy(), want if k == "human_act" else ref[k])
+                assert len(bad) == 0, (what, k, len(bad), _where(names, bad))
+        c = _sf_env(N, visible, dd, count_hh, E, params)
+        H.upload(c, st)
+        c.rollout(acts.to(c.device)[:1])
+        torch.cuda.synchronize()
+        assert _hip.last_dispatch() == "env_step_kernel", (what, _hip.last_dispatch())
+        ref_st = st.copy()
+        ref, want, _ = sf_oracle_step(H.oracle_cfg_for(c, cport.HUMANS_GIVEN), ref_st, ax[0], ay[0], params, visible)
+        for k, v in (("reward", c.reward), ("done", c.done), ("info", c.info), ("dmin", c.dmin),
+                     ("hh_count", c.hh_count), ("human_act", c.human_act)):
+            bad = H.bit_mismatch(v.cpu().numpy(), want if k == "human_act" else ref[k])
+            assert len(bad) == 0, (what, "first step", k, len(bad), _where(names, bad))
+        H.assert_state_equal(H.download(c), ref_st, fields=H.STATE_FIELDS, what=what + " first step")
+    cport.ladder_counts(reset=True)
+    _assert_reached(total, STEP_EVENTS, "social force rollout")
+    print("social force rollout N=%d: the first step reached %s" % (N, {k: total[k] for k in STEP_EVENTS}))
+
+
 _LADDER_KEYS = ("reward", "done", "info", "dmin", "hh_count")
-_TRIG_FIELDS = ("rpx", "rpy", "rvx", "rvy", "hpx", "hpy", "hvx", "hvy", "human_times")
+_TRIG_FIELDS =("rpx", "rpy", "rvx", "rvy", "hpx", "hpy", "hvx", "hvy", "human_times")
 
 
 @pytest.mark.parametrize("unicycle", [False, True])

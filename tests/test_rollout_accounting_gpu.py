@@ -50,6 +50,31 @@ Which test catches which break (value-only changes of one body; none of them mov
   accounting done although `state` is NULL                      test_parts_off: sentinel bytes of every buffer
   split-wavefront hand-off (s_dn / s_case) one step late        quad-split, quad-rollout-split: state after a restart
   record not written back between launches                      rollout paths: 1 + 37 + 92 steps, compared after each
+
+The social-force instantiations (env_step_kernel<.., MCN_HUMANS_SOCIALFORCE, HH 1> at compile-time and run-time N, and
+env_step_loop_sf_kernel) share the source of that tail but are other template instantiations: HH_T 1 where ORCA has 2, no
+line slots in the LDS carve, and the loop restages its tiles around a restart.  They run the same replay twice over:
+
+  sf-step / sf-rollout paths    strength 0 (rollout_ref.SF_PARAMS): the restatement is bit-exact, so the host replay runs
+                                ahead as for ORCA humans and every set but latest-wins is compared as above
+  test_social_force_accounting_in_lock_step
+                                shipped strength: device exp may differ from the host's by an ulp, so the replay takes the
+                                device's own velocities step by step (held to the restatement within 8 * 2^-52 * M)
+
+  break in a social-force instantiation                         caught by
+  ------------------------------------------------------------  -----------------------------------------------------
+  any row of the table above                                    the same sets over the sf-step / sf-rollout paths;
+                                                                latest-wins' rows (one slot keeps the first episode,
+                                                                stride 0 on a pool of one) in lock step
+  loop kernel keeps a finished env's humans in its LDS tiles    sf-rollout-loop: the velocities of the step after a
+  (no restaging after the restart)                              restart (human_act, state) in every pool set
+  loop kernel reads step t's action row for step t + 1          sf-rollout-loop: step records after each launch
+  overlap count off in the HH 1 form, or on in the HH 0 form    hh_count of every step record (the replay counts)
+  first arrivals not cleared by a restart, or stamped with      human_times in the state at 1 / 38 / 130 steps
+  the clock before dt is added
+  compile-time-N form sums the others in another order than     human_act at the checkpoints, bitwise (strength 0 keeps
+  the run-time-N one                                            the sum exact: shown instead in lock step, where every
+                                                                form must reproduce the first form's velocities bitwise)
 """
 import numpy as np
 import pytest
@@ -58,7 +83,7 @@ pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
 from tests import rollout_ref as R  # noqa: E402
-from tests.kernel_paths import ROLLOUT_PATHS, STEP_KERNELS, forced_form, select_step_kernel  # noqa: E402
+from tests.kernel_paths import ROLLOUT_PATHS, SF_TOL, STEP_KERNELS, forced_form, select_step_kernel  # noqa: E402
 from tests.rollout_harness import launch, need_gpu  # noqa: E402
 
 STEP_DTYPE = np.dtype([("reward", "f8"), ("dmin", "f8"), ("done", "u1"), ("info", "u1"), ("reserved", "u2"),
@@ -71,15 +96,38 @@ GIVEN_STEP = [(ps, N) for N in (5, 10) for ps in (0, 1, 2)]
 ROLLOUT = [("quad-rollout", 5), ("quad-rollout-split", 5), ("quad-rollout-wg4", 5), ("step-loop", 7), ("lp3-defer", 7),
            ("lp3-defer", 10), ("unfused", 5), ("unfused", 10)]
 assert {p for p, _ in ROLLOUT} == set(ROLLOUT_PATHS) and all(N in ROLLOUT_PATHS[p][0] for p, N in ROLLOUT)
-PATHS = ([("step",) + c for c in ORCA_STEP] + [("given",) + c for c in GIVEN_STEP] + [("rollout",) + c for c in ROLLOUT])
+# social-force humans (mcn_env_step_sf / mcn_env_rollout_sf): the compile-time-N and force_generic instantiations at 5 and 10
+# humans, the run-time-N one at 7, each at both block sizes; the looped kernel and its launch-per-step fallback
+SF_FORMS = {"compiled-64": dict(step_block=64, force_generic=0), "compiled-256": dict(step_block=256, force_generic=0),
+            "generic-64": dict(step_block=64, force_generic=1), "generic-256": dict(step_block=256, force_generic=1),
+            "run-time-N-64": dict(step_block=64), "run-time-N-256": dict(step_block=256)}
+SF_STEP = ([(f, N) for N in (5, 10) for f in ("compiled-64", "compiled-256", "generic-64", "generic-256")] +
+           [("run-time-N-64", 7), ("run-time-N-256", 7)])
+SF_ROLLOUT = [(which, N) for N in (5, 10) for which in ("loop", "launches")]
+SF_PATHS = [("sf-step",) + c for c in SF_STEP] + [("sf-rollout",) + c for c in SF_ROLLOUT]
+# a zero-strength crowd on a pool of one case never collides, so latest-wins cannot reach its `collision` requirement
+# with the bit-exact parameters: that set runs in lock step with the shipped ones (below)
+SF_SETS = [name for name in R.SETS if name != "latest-wins"]
+PATHS = ([("step",) + c for c in ORCA_STEP] + [("given",) + c for c in GIVEN_STEP] + [("rollout",) + c for c in ROLLOUT] +
+         SF_PATHS)
 PATH_IDS = ["%s-%s-N%d" % p for p in PATHS]
 SPLITS = ((0, 1), (1, 38), (38, R.T_ACC))                   # the launches of the rollout paths: 1 + 37 + 92 steps
 assert tuple(b for _, b in SPLITS) == R.CHECKPOINTS
 
 
+def _mode(path):
+    return {"given": "given", "sf-step": "sf", "sf-rollout": "sf"}.get(path[0], "orca")
+
+
 def _env(w):
-    """A VecCrowdSim in the workload's initial state whose configuration is the one the replay's oracle ran with."""
-    env = H.make_vec_env(w.E, w.N)
+    """A VecCrowdSim in the workload's initial state whose configuration is the one the replay's oracle ran with (for
+    social-force humans: in every field but human_policy -- the oracle is handed their velocities)."""
+    if w.mode == "sf":
+        env = H.make_vec_env(w.E, w.N, **{"humans.policy": "socialforce"})
+        assert env.human_policy_name == "socialforce"
+        env._sf.strength, env._sf.range, env._sf.relaxation_rate = R.SF_PARAMS
+    else:
+        env = H.make_vec_env(w.E, w.N)
     env.time_limit = w.contract.time_limit
     if w.mode == "given":                         # what the streaming kernel takes (env_pair.hip)
         env.count_hh = env.track_human_times = env.export_human_actions = False
@@ -171,20 +219,25 @@ def _run(path, w, tuning, null=()):
     torch = need_gpu()
     from modelcrowdnav_amd import _hip
     kind, which, N = path
-    assert N == w.N and (kind == "given") == (w.mode == "given")
+    assert N == w.N and _mode(path) == w.mode
     what = "%s %s N=%d set %s%s" % (kind, which, N, w.name, " without %s" % "/".join(null) if null else "")
     if kind == "step":
         select_step_kernel(which, tuning)
     elif kind == "given":
         tuning(pair_stream=which)
+    elif kind == "sf-step":
+        tuning(**SF_FORMS[which])
+    elif kind == "sf-rollout":
+        tuning(**(dict(rollout_fused=0) if which == "launches" else {}))
     else:
         tuning(**ROLLOUT_PATHS[which][2])
     env = _env(w)
     _attach(env, w, null)
     acts = torch.from_numpy(w.acts).to(env.device)
-    if kind == "rollout":
+    if kind in ("rollout", "sf-rollout"):
         for a, b in SPLITS:
-            launch(env, acts[a:b], forced_form(which))      # a quad path: the forced form is the one that went out
+            # a quad path: the forced form is the one that went out
+            launch(env, acts[a:b], forced_form(which) if kind == "rollout" else None)
             _compare(env, w, b, what, null)
             _compare_step_recs(env.step_rec.cpu().numpy()[None], w, [b - 1], what)
         return _hip.last_dispatch()
@@ -201,6 +254,10 @@ def _run(path, w, tuning, null=()):
 
 def _expected_dispatch(path, w):
     kind, which, N = path
+    if kind == "sf-step":
+        return "env_step_kernel"
+    if kind == "sf-rollout":                      # (the last launch is 92 steps long)
+        return "env_step_loop_sf_kernel" if which == "loop" else "env_step_kernel"
     if kind == "given":
         # the streaming kernel keeps at most 128 table entries: one more and it must leave the step to env_step_kernel
         return "env_pair_kernel" if which and w.contract.disc_len <= 128 else "env_step_kernel"
@@ -211,13 +268,18 @@ def _expected_dispatch(path, w):
     return "env_step_quad_kernel" if which.startswith("quad") or (which == "auto" and N == 5) else "env_step_kernel"
 
 
-@pytest.mark.parametrize("path", PATHS, ids=PATH_IDS)
-@pytest.mark.parametrize("name", list(R.SETS))
+def _cases():
+    """(set, path): every set over every path; the social-force paths without latest-wins (SF_SETS)."""
+    return [pytest.param(name, path, id="%s-%s" % (name, PATH_IDS[i])) for name in R.SETS for i, path in enumerate(PATHS)
+            if name in SF_SETS or not path[0].startswith("sf")]
+
+
+@pytest.mark.parametrize("name,path", _cases())
 def test_accounting_matches_host_replay_bitwise(name, path, tuning):
     """One parameter set over one kernel path: the whole mcn_roll_rec, every fin_* slot (sentinels included), every step
     record and the env state with restarts, against the host replay.  The sets and what each pins: rollout_ref.SETS /
     REQUIRED.  table-128 / table-129: the streaming kernel runs with a 128-entry discount table and declines 129."""
-    w = R.workload(name, path[2], "given" if path[0] == "given" else "orca")
+    w = R.workload(name, path[2], _mode(path))
     R.check_events(name, w.events)
     ran = _run(path, w, tuning)
     assert ran == _expected_dispatch(path, w), (path, name, ran)
@@ -229,7 +291,7 @@ def test_parts_off(path, tuning):
     other two and the record are what they were (the replay's), the buffer that was left out keeps its sentinel.  Then a
     mcn_rollout with `state` NULL and no pool: state and step records are the oracle's (what roll = NULL gives) and no
     byte of any accounting buffer is written.  (All four bodies guard every store by its pointer -- read before run.)"""
-    mode = "given" if path[0] == "given" else "orca"
+    mode = _mode(path)
     w = R.workload("explorer-mid", path[2], mode)
     R.check_events(w.name, w.events)
     for part in ("fin_return", "fin_time", "fin_info"):
@@ -237,3 +299,84 @@ def test_parts_off(path, tuning):
     w = R.workload("no-pool", path[2], mode)
     R.check_events(w.name, w.events)
     _run(path, w, tuning, null=("state",))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# social-force humans with the shipped parameters: the replay in lock step with the device
+LOCKSTEP_FORMS = ((64, 0), (64, 1), (256, 0), (256, 1))          # (step_block, force_generic); the first sets the trace
+
+
+def _lockstep_env(ls, tuning, block, generic):
+    tuning(step_block=block, force_generic=generic)
+    env = H.make_vec_env(ls.E, ls.N, robot_visible=ls.visible, **{"humans.policy": "socialforce"})
+    assert env.human_policy_name == "socialforce"
+    env._sf.strength, env._sf.range, env._sf.relaxation_rate = ls.params
+    env.time_limit = ls.contract.time_limit
+    H.upload(env, ls.st0)
+    from oracle import cport
+    want = H.oracle_cfg_for(env, cport.HUMANS_GIVEN)
+    for name, _ in want._fields_:
+        assert getattr(want, name) == getattr(ls.cfg, name), "the replay's oracle runs with another %s" % name
+    w = R.Workload()                                  # what _attach reads of a workload
+    w.set, w.scen, w.pool, w.first_cases, w.contract = ls.set, ls.scen, ls.pool, ls.first_cases, ls.contract
+    _attach(env, w)
+    return env
+
+
+@pytest.mark.parametrize("visible", (False, True), ids=("invisible", "visible"))
+@pytest.mark.parametrize("N", (5, 10))
+@pytest.mark.parametrize("name", R.LOCKSTEP_SETS)
+def test_social_force_accounting_in_lock_step(name, N, visible, tuning):
+    """Shipped parameters (4, 0.2, 2), 130 steps of 251 envs.  Per step: the host computes the robots' actions from ITS
+    state (rollout_ref._simulate's rule) and uploads them; one mcn_env_step_sf; the device's human_act is held to the
+    restatement on the host state within 8 * 2^-52 * M and goes into Replay.step as given velocities; the step record is
+    compared bitwise; at rollout_ref.CHECKPOINTS the whole state, the mcn_roll_rec and the sentinel-filled fin_* arrays
+    too.  The first form (compile-time N, block 64) runs in lock step and leaves its human_act trace; force_generic and
+    block 256 must reproduce the trace, every step record and every checkpoint bitwise -- all forms perform the same IEEE
+    operations in the same order (contraction off), so a difference is a finding, not a tolerance to widen."""
+    torch = need_gpu()
+    from modelcrowdnav_amd import _hip
+    from tests.rollout_harness import assert_same_bytes, snapshot
+    ls = R.LockStep(name, N, visible)
+    w = R.Workload()
+    w.E, w.contract, w.snaps, w.human_act = ls.E, ls.contract, {}, {}
+    block, generic = LOCKSTEP_FORMS[0]
+    env = _lockstep_env(ls, tuning, block, generic)
+    what = "lock step %s N=%d visible=%d" % (name, N, visible)
+    acts, trace, recs, snaps, worst = [], [], [], {}, 0.0
+    for t in range(ls.T):
+        a = ls.actions()
+        want, mag = ls.restatement()
+        env.step(torch.from_numpy(a).to(env.device))
+        assert _hip.last_dispatch() == "env_step_kernel"
+        hact = env.human_act.cpu().numpy()
+        tol = SF_TOL * mag[..., None]
+        err = np.abs(hact - want)
+        assert np.isfinite(hact).all() and (err <= tol).all(), (what, "human_act at step", t, np.argwhere(~(err <= tol))[:4].tolist())
+        worst = max(worst, float(np.max(np.where(tol > 0, err / np.where(tol > 0, tol, 1), 0))))
+        out = ls.advance(a, hact)
+        rec = env.step_rec.cpu().numpy()
+        got = np.ascontiguousarray(rec).view(STEP_DTYPE).reshape(ls.E)
+        for f in ("reward", "dmin", "done", "info", "hh_count"):
+            bad = H.bit_mismatch(got[f], out[f])
+            assert len(bad) == 0, (what, "step record", f, "step", t, "envs", _first(bad))
+        acts.append(a); trace.append(hact); recs.append(rec)
+        if t + 1 in R.CHECKPOINTS:
+            w.snaps[t + 1] = (ls.st.copy(), ls.rep.snapshot())
+            w.human_act[t + 1] = hact
+            _compare(env, w, t + 1, what)
+            snaps[t + 1] = snapshot(env)
+    events = ls.events()
+    missing = [k for k in R.lockstep_required(name) if events.get(k, 0) == 0]
+    assert not missing, "%s: the replay never reached %s (%s)" % (what, missing, events)
+    print("%s: largest error / tolerance %.4f, events %s" % (what, worst, events))
+    acts_d = torch.from_numpy(np.stack(acts)).to(env.device)
+    for block, generic in LOCKSTEP_FORMS[1:]:
+        env = _lockstep_env(ls, tuning, block, generic)
+        for t in range(ls.T):
+            env.step(acts_d[t])
+            bad = H.bit_mismatch(env.human_act.cpu().numpy(), trace[t])
+            assert len(bad) == 0, (what, "block", block, "generic", generic, "human_act at step", t, _first(bad))
+            assert np.array_equal(env.step_rec.cpu().numpy().view(np.uint8), recs[t].view(np.uint8)), (what, block, generic, t)
+            if t + 1 in R.CHECKPOINTS:
+                assert_same_bytes(snapshot(env), snaps[t + 1], (what, block, generic, t + 1))

@@ -191,12 +191,17 @@ def test_restart_rewrites_the_env_and_nothing_else(with_velocities):
     assert rep.events["restart_moving"] == (1 if with_velocities else 0)
 
 
-@pytest.mark.parametrize("mode,N", [("orca", 5), ("orca", 7), ("orca", 10), ("given", 5), ("given", 10)])
+@pytest.mark.parametrize("mode,N", [("orca", 5), ("orca", 7), ("orca", 10), ("given", 5), ("given", 10), ("sf", 5), ("sf", 7),
+                                    ("sf", 10)])
 def test_gpu_workloads_reach_what_they_claim(mode, N):
     """Every parameter set of tests/test_rollout_accounting_gpu.py at every crowd size it runs: the replay passes
     through the events the set is there for (rollout_ref.REQUIRED), none of those it excludes, and the two table sizes
-    are the streaming kernel's limit and one more."""
+    are the streaming kernel's limit and one more.  Mode "sf" (social-force humans of strength 0) runs every set but
+    latest-wins: a zero-strength crowd on a pool of one case never collides, which that set requires; it is covered
+    with the shipped parameters in lock step (test_lock_step_forecast_reaches_its_events)."""
     for name in R.SETS:
+        if mode == "sf" and name == "latest-wins":
+            continue
         w = R.workload(name, N, mode)
         R.check_events(name, w.events)
         assert set(w.snaps) == set(R.CHECKPOINTS) and w.recs["done"].shape == (R.T_ACC, R.E_ACC)
@@ -207,5 +212,37 @@ def test_gpu_workloads_reach_what_they_claim(mode, N):
     for name in ("explorer-mid", "short-table", "table-128", "table-129"):      # the boundary falls inside an env group
         sf = R.workload(name, N, mode).contract.danger_short_from
         assert 2 <= sf - 1 < R.E_ACC - 1 and all((sf - 1) % g for g in R._group_sizes(N)), (name, sf)
+    if mode == "sf":
+        return
     # one slot: the kept record differs from the env's first episode, so "keeps the first" would show
     assert R.workload("latest-wins", N, mode).events["first_wins_differs"] >= 50
+
+
+def test_zero_strength_crowd_never_collides_on_a_pool_of_one():
+    """Why mode "sf" leaves latest-wins out: with strength 0 that set finishes reach and timeout episodes and not one
+    collision (5 humans)."""
+    ev = R._simulate("latest-wins", 5, "sf", 0).events
+    assert ev.get("collision", 0) == 0 and ev["reach"] > 100 and ev["timeout"] > 50, ev
+
+
+@pytest.mark.parametrize("visible", (False, True))
+@pytest.mark.parametrize("N", (5, 10))
+@pytest.mark.parametrize("name", R.LOCKSTEP_SETS)
+def test_lock_step_forecast_reaches_its_events(name, N, visible):
+    """tests/test_rollout_accounting_gpu.py::test_social_force_accounting_in_lock_step with the host's exp in place of the
+    device's (the two differ by ulps of exp; the dynamics are chaotic over 130 steps, so counts are forecasts, not
+    expectations): every required event of the set is reached with hundreds of occurrences to spare.  Seen here, N = 5 /
+    10, robot invisible / visible -- explorer-first: collisions 431 / 177 / 653 / 392, reach 78 / 167 / 53 / 91, timeouts
+    65 / 76 / 62 / 72, dropped 144 / 10 / 315 / 118, wraps 113 / 81 / 149 / 113; latest-wins: overwritten 336 / 84 / 607 /
+    256, first_wins_differs 84 / 84 / 100 / 88."""
+    ev = R.lockstep_forecast(name, N, visible)
+    missing = [k for k in R.lockstep_required(name) if ev.get(k, 0) == 0]
+    assert not missing, (name, N, visible, missing, ev)
+    assert set(R.lockstep_required(name)) >= set(R.REQUIRED[name]) - set(R._MID_ONLY)
+    for k in ("reach", "collision", "timeout"):
+        assert ev[k] >= 25, (k, ev)
+    if name == "latest-wins":
+        assert ev["overwritten"] >= 50 and ev["first_wins_differs"] >= 50, ev
+    else:
+        assert ev["dropped"] >= 5 and ev["wrap"] >= 40 and ev["danger_gated"] >= 400 and ev["danger_counted"] >= 200, ev
+

@@ -302,3 +302,131 @@ def test_default_parameters_sanity_run(n):
     assert pairs == 30 * 100 * n * (n - 1) // 2
     assert arrived >= 0.95 * 30 * n, (arrived, 30 * n)
     assert overlaps < 0.005 * pairs, (overlaps, pairs)
+
+
+# ----------------------------------------------------------------- the inputs of the GPU batteries reach their events
+def _ladder_events(params, Ns, update=True):
+    """What the restatement plus the oracle's given-velocity step reach on the ladder batches, as
+    tests/test_ladder_gpu.py::test_social_force_step_on_ladder_batches feeds them."""
+    from oracle import cport
+    from tests import kernel_paths as KP
+    from tests import ladder_states as LS
+    total = {}
+    for N, visible, dd, count_hh in KP.ladder_configs(Ns, quad=False):
+        st, ax, ay, _, names = LS.ladder_batch(N, visible, dd)
+        want, _ = KP.sf_ladder_reference(N, visible, dd, params)
+        cport.ladder_counts(reset=True)
+        cport.env_step(LS.cfg(visible, dd, count_hh, policy=cport.HUMANS_GIVEN), st, ax, ay, update=update,
+                       given_v=np.array(want))
+        for k, v in cport.ladder_counts(reset=True).items():
+            total[k] = total.get(k, 0) + v
+    return total
+
+
+def test_ladder_batches_reach_their_events_with_social_force_humans():
+    """inert parameters (0, 0.2, 4): every step event, the first arrival at exactly one radius included (a human at rest
+    gets w = e exactly); shipped parameters: every event but that one, which they never reach.  Also per crowd size of
+    the rollout test (5 and 10 humans alone)."""
+    from tests import kernel_paths as KP
+    total = _ladder_events(KP.SF_INERT, KP.SF_COMPILED_NS + KP.SF_GENERIC_NS)
+    assert all(total.get(k, 0) > 0 for k in KP.STEP_EVENTS), total
+    total = _ladder_events(KP.SF_INERT, (1, 2, 5, 10))
+    assert total["human_time_edge"] == 774, total["human_time_edge"]
+    for N in KP.SF_COMPILED_NS:
+        total = _ladder_events(KP.SF_INERT, (N,))
+        assert all(total.get(k, 0) > 0 for k in KP.STEP_EVENTS), (N, total)
+    total = _ladder_events(KP.SF_DEFAULT, KP.SF_COMPILED_NS + KP.SF_GENERIC_NS)
+    assert all(total.get(k, 0) > 0 for k in KP.STEP_EVENTS if k != "human_time_edge"), total
+    assert total.get("human_time_edge", 0) == 0, total
+    total = _ladder_events(KP.SF_INERT, KP.SF_COMPILED_NS + KP.SF_GENERIC_NS, update=False)
+    assert all(total.get(k, 0) > 0 for k in KP.STEP_EVENTS if k != "human_time_edge"), total
+
+
+def test_inert_parameters_make_the_restatement_exact():
+    """A = 0: the interaction terms are exactly 0 whatever exp returns, so the result does not depend on exp at all --
+    replacing it by a function that is off by a factor leaves every bit."""
+    from tests import kernel_paths as KP
+    from tests import ladder_states as LS
+    st = LS.ladder_batch(5, True, 0.25)[0]
+    want, _ = KP.sf_ladder_reference(5, True, 0.25, KP.SF_INERT)
+    real = R._exp
+    try:
+        R._exp = lambda x: 3.0 * real(x)
+        other, _ = KP.sf_velocities(st, KP.SF_INERT, True)
+    finally:
+        R._exp = real
+    assert other.tobytes() == np.array(want).tobytes()
+    # a human at rest with k = 4 and dt = 0.25 gets w = e exactly
+    w, _ = R.human_velocity((1.0, 2.0), (0.0, 0.0), (1.0, 2.5), 0.375, 0.5, [(1.25, 2.0, 0.3)], 0.0, 0.2, 4.0, 0.25)
+    assert w == (0.0, 0.5)
+
+
+def test_overlap_batches_overlap_well_inside_the_prefilter_margin():
+    """tests/sf_edge_states.py overlap_batch: the oracle counts exactly the constructed pairs, none within 0.04 of
+    touching (the float32 pre-filter's borderline band is 1e-3), every coordinate below 1024."""
+    from oracle import cport
+    from tests import sf_edge_states as SE
+    for N in (2, 5, 10, 13):
+        st, ax, ay, pairs = SE.overlap_batch(N)
+        ref = cport.env_step(cport.default_cfg(count_hh=1, human_policy=cport.HUMANS_GIVEN), st.copy(), ax, ay,
+                             update=False, given_v=np.zeros((st.E, N, 2)))
+        assert (ref["hh_count"] == pairs).all() and (pairs > 0).all()
+        g = SE.pair_gaps(st)[:, np.triu_indices(N, 1)[0], np.triu_indices(N, 1)[1]]
+        assert (np.abs(g) > 0.04).all() and (g < -0.04).any()
+        assert max(np.abs(st.hpx).max(), np.abs(st.hpy).max()) < 1024
+
+
+# events every (N, visible) batch of the edge battery must hold, by the robot's visibility and the crowd size
+_EDGE_ALWAYS = ("goal_tie", "goal_ulp_below", "goal_ulp_above", "on_goal", "vpref_zero", "neg_zero_e", "neg_zero_v",
+                "neg_zero_w", "w_tie", "w_ulp_above", "nonfinite_self", "nonfinite_w", "clipped")
+_EDGE_WITH_OTHERS = ("exp_subnormal", "exp_underflow", "exp_overflow", "nonfinite_other")
+
+
+@pytest.mark.parametrize("N", (1, 2, 5, 10, 13))
+def test_edge_batches_reach_their_events(N):
+    """tests/sf_edge_states.py: what tests/test_social_force_edges_gpu.py claims of its inputs, from an instrumented walk
+    through the definition over all parameter sets (N = 32 is built by the same code and left to the GPU test: its
+    walk alone takes several seconds of host Python)."""
+    from tests import kernel_paths as KP
+    from tests import sf_edge_states as SE
+    for visible in (0, 1):
+        st, ax, ay, names = SE.edge_batch(N, visible)
+        assert st.E == 11 * SE.BLOCK + SE.PAD and all(st.E % (64 // n) for n in SE.NS if n > 1)
+        total, per = {}, {}
+        for group, params in SE.PARAMS.items():
+            ev = SE.trace(st, params, visible)
+            per[group] = {k: int(v.sum()) for k, v in ev.items()}
+            for k, v in per[group].items():
+                total[k] = total.get(k, 0) + v
+        need = list(_EDGE_ALWAYS)
+        if N >= 2 or visible:
+            need += _EDGE_WITH_OTHERS
+        if N >= 2:
+            need += ["coincident_human", "all_coincident"]
+        if visible:
+            need += ["coincident_robot"]
+        need += ["no_term"] if (N == 1 and not visible) else []
+        need += ["robot_only"] if (N == 1 and visible) else []
+        missing = [k for k in need if total.get(k, 0) == 0]
+        assert not missing, (N, visible, missing, total)
+        # the exact |w| == v_pref tie and -0.0 results come from the set with A = 0 and k = 0; overflow from B = 2^-10
+        assert per["still"]["w_tie"] > 0 and per["still"]["w_ulp_above"] > 0 and per["still"]["neg_zero_w"] > 0
+        if N >= 2 or visible:
+            assert per["B-small"]["exp_overflow"] > 0 and per["B-tiny"]["exp_overflow"] > 0
+            assert per["default"]["exp_subnormal"] > 0 and per["default"]["exp_underflow"] > 0
+        # the unseen robot's twins differ in nothing but the robot's position
+        tw = [e for e, n in enumerate(names) if n == "nonfinite-robot"]
+        assert len(tw) == 16 and not np.isfinite(st.rpx[tw[8:]] + st.rpy[tw[8:]]).any()
+        assert (st.hpx[tw[8:]] == st.hpx[tw[:8]]).all() and (st.hvx[tw[8:]] == st.hvx[tw[:8]]).all()
+
+
+def test_restatement_overflow_is_inf_not_an_exception():
+    """exp beyond its range: m = inf; along an axis inf * 0 gives NaN in the other component, off the axes the clip's
+    inf / inf gives NaN in both."""
+    w, _ = R.human_velocity((0.0, 0.0), (0.0, 0.0), (1.0, 0.0), 0.375, 1.0, [(-1 / 32, 0.0, 0.375)], 4.0, 2.0 ** -10, 2.0, DT)
+    assert w[0] == math.inf and math.isnan(w[1])
+    w, _ = R.human_velocity((0.0, 0.0), (0.0, 0.0), (1.0, 0.0), 0.375, 1.0, [(-1 / 32, -1 / 32, 0.375)], 4.0, 2.0 ** -10, 2.0, DT)
+    assert math.isnan(w[0]) and math.isnan(w[1])
+    w, _ = R.human_velocity((0.0, 0.0), (0.0, 0.0), (1.0, 0.0), 0.375, 1.0, [(-1 / 32, 0.0, 0.375)], 0.0, 2.0 ** -10, 2.0, DT)
+    assert math.isnan(w[0]) and math.isnan(w[1])              # 0 * inf
+    assert R._exp(-math.inf) == 0.0 and math.isnan(R._exp(math.nan)) and R._exp(710.0) == math.inf
