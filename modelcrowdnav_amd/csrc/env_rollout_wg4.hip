@@ -23,7 +23,7 @@ namespace mcn {
 // The float64 wavefront OWNS every float64 value of the env: the robot, the clock, the records and the humans' position,
 // velocity, goal, radius, v_pref and human_times -- one human per lane, loaded in its prologue, integrated or restarted
 // from the pool by it, stored in its epilogue.  The ORCA wavefronts are float32 only: per step they read their human's
-// operands and their candidate's from LDS, run quad_orca_core (quad_common.hpp) and publish the new velocity as two
+// operands and their candidate's from LDS (what and when: below), run quad_orca_core (quad_common.hpp) and publish the new velocity as two
 // floats.  The four lanes of a quad would each repeat the float64 -> float32 conversions, the integrate and the restart
 // test; the float64 wavefront does them once per human and has the cycles to spare, and on a SIMD that holds two
 // wavefronts every instruction taken out of the ORCA stream is taken out of its neighbour's way too.
@@ -31,21 +31,41 @@ namespace mcn {
 // float64 -> ORCA, the new positions (the float64 wavefront integrates between the two).  Between the two all four
 // wavefronts wait for one serial chain, so only what depends on the new velocity is on it: read (rx, ry), two
 // conversions, the integrate, goal - pos, four conversions, one 16-byte write.  Everything else stays off it:
-//   * the velocity never leaves float32: the solve's velocity operands are the floats the ORCA wavefronts published
-//     (float32 -> float64 -> float32 gives the same bits back), read from s_res by owner and candidate alike;
+//   * the velocity never leaves float32: the solve's velocity operands are the floats the ORCA wavefronts produced
+//     (float32 -> float64 -> float32 gives the same bits back): the owner's are the (rx, ry) its quad still holds, the
+//     candidate's are read from s_res;
 //   * frad and the maximum speed change only on a restart and live in s_inv, written in the prologue and by restart lanes;
+//     the ORCA wavefronts keep them, and the candidate's frad, in registers from one restart step to the next;
 //   * what a restarted human publishes (position pack, start velocity, s_inv) is converted BEFORE hand-off 1, where the
 //     float64 wavefront would idle anyway, and stored between the hand-offs behind one wave-uniform branch;
 //   * the float64 wavefront's private arrays, its register update and the human_times test come after hand-off 2.
 // Each value is produced by the operation, on the operands, that the other forms use, so the same bits.
 //
-// s_res is double-buffered by step parity (parity 0 = the launch's first step): the ORCA wavefronts of step t write
-// buffer t & 1, the float64 wavefront reads (and a restart lane overwrites) buffer t & 1 between the hand-offs of step t,
-// and the top of step t + 1 reads buffer t & 1.  With one buffer a fast ORCA wavefront could publish step t + 1's
-// velocity while a slow one still reads step t's as its candidate's: no barrier lies between the two.  With two, the
-// next write to buffer t & 1 is step t + 2's, issued after hand-off 2 of step t + 1; its last readers are the tops of
-// step t + 1, whose values are consumed by a solve that ends before hand-off 1 of step t + 1: every reader has passed
-// two barriers since.  The prologue seeds buffer 1, which the top of step 0 reads.
+// The top of an ORCA wavefront's step reads only what hand-off 2 published, the two position packs.  Everything else the
+// solve needs is final at hand-off 1 and is fetched or kept: the candidate's velocity is read
+// BETWEEN the hand-offs, where the ORCA wavefronts wait for the float64 chain anyway -- except on a restart step, when a
+// restart lane overwrites its human's velocity and s_inv inside that very interval.  The float64 wavefront knows
+// any_restart when its ladder ends and stores it to s_flag[0] there; the ORCA wavefronts read it between the hand-offs,
+// make it a scalar, and on a restart step (and on step 0 of every launch, whose operands the prologue seeded) take the
+// SLOW PATH behind hand-off 2: own and candidate's velocity, (frad, ms) and the candidate's frad from LDS.  s_res is one
+// buffer, so those reads are fenced from the next solves' writes by a THIRD BARRIER, which all four wavefronts execute
+// on such steps and no other: the float64 wavefront branches on its own any_restart (and the prologue's second barrier
+// stands for step 0), the ORCA wavefronts on the flag it stored, so every wavefront counts the same barriers (after the
+// launch's last step the ORCA wavefronts execute it behind their loop, with nothing to read).
+// The three intervals of a step and who touches what in them (W = writes, R = reads; f64 = the float64 wavefront):
+//   A  hand-off 2 of the step before (or the prologue's barriers) -> hand-off 1: the solve
+//   B  hand-off 1 -> hand-off 2: the float64 chain
+//   C  restart steps only: hand-off 2 -> the third barrier (the head of the next step's interval A)
+//              A                                   B                                        C
+//   s_pack     R ORCA (top of step)                W f64 (every lane; restart lanes theirs)  R ORCA (it is their top of step)
+//   s_res      W ORCA (end of solve)               R f64, R ORCA (candidate), W f64 restart  R ORCA (own, candidate)
+//   s_inv      --                                  W f64 restart lanes                       R ORCA (own, candidate)
+//   s_flag     W f64 (behind its ladder)           R ORCA                                    --
+//   s_hpos/s_hrad  R f64 (pairs); W f64 (head of A: behind hand-off 2 / the third barrier)   --  (its own arrays)
+//   s_lines    W/R the owning ORCA wavefront       --                                        --
+// The candidate's velocity an ORCA wavefront reads in B of a restart step races with the restart lane's write; that value
+// is never used: the slow path overwrites it in C.  In C the ORCA wavefronts wait for
+// their reads before the third barrier, and the first write of s_res behind it is the end of the next solve.
 //
 // The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot integrate / restart and the epilogue
 // are the TWIN of env_rollout_quad_kernel's (env_rollout_quad.hip): a change to either is made to both.  The text is
@@ -81,11 +101,15 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
     // hand-off arrays, one slot per (env, human).  Written by the float64 wavefront between the step's two barriers:
     // s_pack = (px, py, prefx, prefy) of quad_orca_core's operands, every step; s_inv = (frad, maximum speed) and the
     // start velocity in s_res, restart lanes only.  Written by the ORCA wavefronts outside that window, read by the
-    // float64 one inside it and by the ORCA ones at the top of the next step: s_res, the human's new velocity, two
-    // buffers by step parity (see above).  s_hpos / s_hrad, the float64 position and radius the overlap pairs read from
-    // partner lanes, are the float64 wavefront's own: written after the second barrier, read in its next step.
+    // float64 one and (their candidate's) by the ORCA ones inside it, and by the ORCA ones' slow path behind it: s_res,
+    // the human's new velocity, one buffer (table above).  s_hpos / s_hrad, the float64 position and radius the overlap
+    // pairs read from partner lanes, are the float64 wavefront's own: written after the second barrier, read in its
+    // next step.
     __shared__ float4 s_pack[NQ];
-    __shared__ float2 s_res[2 * NQ], s_inv[NQ];
+    __shared__ float2 s_res[NQ], s_inv[NQ];
+    // word 0: some human of the workgroup restarts on this step (the float64 wavefront's any_restart).  The other words
+    // are the room the second velocity buffer had: the workgroup's LDS, and with it the CU's, stays what it was
+    __shared__ int s_flag[2 * NQ];
     __shared__ double2 s_hpos[NQ];
     __shared__ double s_hrad[NQ];
     // the ORCA wavefronts' sorted half-planes (quad_common.hpp: QuadTable): 64 slots each, private to the wavefront.  A lane
@@ -115,38 +139,51 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         const int ci = pop ? ge * NT + j : 0;
         const bool publish = pop && k == 0;
         const float inv_th = in_vgpr(1.0f / c.orca_time_horizon), inv_ts = in_vgpr(1.0f / (float)c.time_step);
-        // s_res slots the top of the step reads, as byte offsets (no shift per step): buffer 1 first
-        constexpr int RES_BUF = NQ * (int)sizeof(float2);
-        const int hi_b = hi * (int)sizeof(float2), ci_b = ci * (int)sizeof(float2);
-        int rd_h = hi_b + RES_BUF, rd_c = ci_b + RES_BUF;
-        const char *res_bytes = reinterpret_cast<const char *>(s_res);
-        const QuadTable lines = {s_lines + role * 64};
+        float4 *const tab = s_lines + role * 64;
+        // what a normal step keeps in registers: own velocity v, the candidate's cv, (frad, ms) and the candidate's frad
+        float vx = 0, vy = 0, cvx = 0, cvy = 0, frad = 0, ms = 0, orad = 0;
+        bool slow = true;                                        // wave-uniform: step 0 of a launch is a restart step
         __syncthreads();                                         // the float64 wavefront has seeded the packs
         STAMP(1);
 
         for (int t = 0; t < T; ++t) {
-            // own operands and the candidate's: positions published behind the step's second barrier, velocities by the
-            // last step's solves (buffer (t - 1) & 1; restart lanes overwritten), frad / ms since the last restart.  All
-            // six reads are issued before the first wait, one LDS round trip: the empty asm needs every value, and every
-            // use comes after it (left alone the compiler waits for the positions, starts on them and reads the rest then)
+            // behind hand-off 2: the positions, own and candidate's, on every step
             float4 P = s_pack[hi];
             float2 cp = *reinterpret_cast<const float2 *>(s_pack + ci);
-            float2 v = *reinterpret_cast<const float2 *>(res_bytes + rd_h), cv = *reinterpret_cast<const float2 *>(res_bytes + rd_c);
-            float2 fm = s_inv[hi];
-            float orad = s_inv[ci].x;                            // the candidate's own frad
-            asm volatile("" : "+v"(P.x), "+v"(P.y), "+v"(P.z), "+v"(P.w), "+v"(cp.x), "+v"(cp.y), "+v"(v.x), "+v"(v.y),
-                              "+v"(cv.x), "+v"(cv.y), "+v"(fm.x), "+v"(fm.y), "+v"(orad));
+            if (slow) {
+                // restart step (and step 0): every other operand from LDS too -- the velocities as the prologue or
+                // the last step's solves left them with restart lanes overwritten, frad / ms as the restart lanes left
+                // them.  Issued behind the two above, one LDS round trip for the six: the empty asm needs the last four,
+                // and LDS answers in order.  (The positions stay out of it: as its operands they would be copied into
+                // the registers the two paths share, six moves on every normal step.)  The barrier behind it keeps the
+                // solves' next write of s_res behind every wavefront's reads.
+                float2 v = s_res[hi], cv = s_res[ci];
+                float2 fm = s_inv[hi];
+                float od = s_inv[ci].x;                          // the candidate's own frad
+                asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(cv.x), "+v"(cv.y), "+v"(fm.x), "+v"(fm.y), "+v"(od));
+                __syncthreads();                                 // restart steps only: s_res has been read
+                vx = v.x; vy = v.y; cvx = cv.x; cvy = cv.y; frad = fm.x; ms = fm.y; orad = od;
+            }
             float rx, ry;
-            quad_orca_core(c, lane, k, cand_h && active, make_float4(P.x, P.y, v.x, v.y), make_float4(P.z, P.w, fm.x, fm.y),
-                           make_float4(cp.x, cp.y, cv.x, cv.y), orad, inv_th, inv_ts, rx, ry, lines);
-            if (publish) s_res[(t & 1) * NQ + hi] = make_float2(rx, ry);
-            // the next step reads the buffer this one wrote; its addresses are ready before the barriers
-            rd_h = in_vgpr(hi_b + (t & 1) * RES_BUF); rd_c = in_vgpr(ci_b + (t & 1) * RES_BUF);
+            quad_orca_core(c, lane, k, cand_h && active, make_float4(P.x, P.y, vx, vy), make_float4(P.z, P.w, frad, ms),
+                           make_float4(cp.x, cp.y, cvx, cvy), orad, inv_th, inv_ts, rx, ry, QuadTable{tab});
+            if (publish) s_res[hi] = make_float2(rx, ry);
             if (t < 20) STAMP(40 + t);
             __syncthreads();                                     // hand-off 1: the humans' new velocities
+            // between the hand-offs, where this wavefront waits for the float64 chain: the workgroup's restart flag and
+            // the candidate's new velocity, one LDS round trip; the own new velocity is (rx, ry), identical on the
+            // quad's lanes.  On a restart step the candidate's read races with the restart lane's overwrite and the quad's
+            // registers hold the old human's: nothing formed here is used then, the slow path re-reads it all.
+            int flag = s_flag[0];
+            float2 cv = s_res[ci];
+            asm volatile("" : "+v"(flag), "+v"(cv.x), "+v"(cv.y));      // waited for before the barrier
+            slow = __builtin_amdgcn_readfirstlane(flag) != 0;
+            vx = rx; vy = ry; cvx = cv.x; cvy = cv.y;
             __syncthreads();                                     // hand-off 2: the next step's positions
             if (t < 37) STAMP(2 + t);
         }
+        // the float64 wavefront executes the third barrier of the last step too (no test of the step count in its loop)
+        if (slow) __syncthreads();
     } else {
         // ---------------- float64 wavefront: lane 8 g + h = (env g, human h), h >= NT idle ----------------
         static_assert(EW * 8 == 64, "eight lanes per env fill the wavefront");
@@ -197,18 +234,18 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         const double k_discomfort = in_vgpr(c.discomfort_dist), k_factor = in_vgpr(c.discomfort_penalty_factor);
         const int k_stride = ro.case_stride, k_pool = ro.pool_size;
         const bool count_hh = c.count_hh != 0;
-        // the first step's operands: the loaded state goes through the hand-off arrays (velocity: buffer 1, the one the
-        // top of step 0 reads)
+        // the first step's operands: the loaded state goes through the hand-off arrays
         {
             float4 A, B;
             quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
             if (pop) {
-                s_pack[hs] = make_float4(A.x, A.y, B.x, B.y); s_res[NQ + hs] = make_float2(A.z, A.w);
+                s_pack[hs] = make_float4(A.x, A.y, B.x, B.y); s_res[hs] = make_float2(A.z, A.w);
                 s_inv[hs] = make_float2(B.z, B.w);
                 s_hpos[hs] = pos; s_hrad[hs] = rad;
             }
         }
         __syncthreads();
+        __syncthreads();                                         // step 0 is a restart step: the ORCA wavefronts have read s_res
         STAMP(1);
 
         for (int t = 0; t < T; ++t) {
@@ -297,6 +334,12 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
             else                                { rew = 0; dn = 0; inf = MCN_INFO_NOTHING; }
             o_rew = rew; o_dmin = dmin; o_dn = dn; o_inf = inf; o_hh = hh_sum;
             const double t_new = gtime + dt;
+            // the workgroup's restart flag as soon as the done flags are known: the store is long complete when this
+            // wavefront reaches hand-off 1 (issued there, the barrier's wait for it sat on the chain of every step on
+            // which this wavefront is the last to arrive: the unicycle robot's)
+            const bool restart = do_reset && dn;
+            const bool any_restart = __any(restart);             // roughly one workgroup-step in ten
+            s_flag[0] = any_restart ? 1 : 0;                     // (every lane the same word: no exec mask to set up)
 
             // ---- Explorer accounting: every lane of the env updates its copy; the stores are the lead lane's ----
             const int case_g = rs.next_case;
@@ -352,7 +395,6 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
             //      for the ORCA ones anyway (it knows the done flag first): the case is fetched straight into the state
             //      registers (nothing below reads the old one: the swept circle, the pairs and the ladder are done) and
             //      converted; between the hand-offs a restart lane only stores what it holds here ----
-            const bool restart = do_reset && dn;
             float4 n_pack = make_float4(0, 0, 0, 0);
             float2 n_fvel = make_float2(0, 0), n_inv = make_float2(0, 0);
             if (restart) {
@@ -377,12 +419,11 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 n_fvel = make_float2(in_vgpr(A.z), in_vgpr(A.w));
                 n_inv = make_float2(in_vgpr(B.z), in_vgpr(B.w));
             }
-            const bool any_restart = __any(restart);             // roughly one workgroup-step in ten
 
             if (t < 20) STAMP(40 + t);
             __syncthreads();                                     // hand-off 1: the humans' new velocities
             // ---- the chain every wavefront of the workgroup waits for: velocity -> position -> pack ----
-            float2 *vel_io = s_res + (t & 1) * NQ;
+            float2 *vel_io = s_res;
             {
                 const float2 r = vel_io[hs];
                 hax = (double)r.x; hay = (double)r.y;            // (restart lanes too: the epilogue's human_act)
@@ -395,6 +436,10 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 if (pop && restart) { s_pack[hs] = n_pack; vel_io[hs] = n_fvel; s_inv[hs] = n_inv; }
             }
             __syncthreads();                                     // hand-off 2: the next step's positions
+            // restart steps only: the ORCA wavefronts re-read every operand behind hand-off 2 and fence those reads from
+            // their solves' next write of s_res with one more barrier (after the last step: behind their loop); this
+            // wavefront takes part at once, before its own work, on its own copy of the flag they read
+            if (any_restart) __syncthreads();
             if (t < 37) STAMP(2 + t);
 
             // ---- off the chain: this wavefront's own arrays, the velocity register, the clock of the step just taken ----
