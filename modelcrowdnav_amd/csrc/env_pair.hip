@@ -26,15 +26,12 @@
 #include "../../include/mcn.h"
 #include "env_step_params.hpp"
 #include "env_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
-void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispatch()
 
 __device__ __forceinline__ long long d2ll(double v) { return __builtin_bit_cast(long long, v); }
 __device__ __forceinline__ double ll2d(long long v) { return __builtin_bit_cast(double, v); }
-
-// longest discount table the dispatcher accepts (longer ones stay on env_step_kernel)
-constexpr int kPairDiscMax = 128;
 
 // Non-temporal loads / stores for the per-human streams (positions, velocities, given velocities, radii: 3/4 of the
 // bytes, each touched exactly once per step).  Measured (round 3, MI355X, 5 humans, with Explorer record and pool
@@ -239,35 +236,20 @@ __global__ __launch_bounds__(256) void env_pair_kernel(const StepParams p)
 }
 
 template <int NT>
-static void launch_pair_one(const StepParams &p, hipStream_t stream)
+static void launch_pair_one(const StepParams &p, bool nontemporal, hipStream_t stream)
 {
     constexpr int G = 64 / NT;
     const long per_block = 4 * G;
     const int blocks = (int)((p.E + per_block - 1) / per_block);
-    // non-temporal per-human streams once one step's footprint (~(15 + 11 N) x 8 + 70 B per env) is well past the
-    // 256 MB memory-side cache (measured cross-over, 5 humans: 2^18 envs = 165 MB 27.9 vs 32 us without / with,
-    // 2^19 = 330 MB equal, 2^20 = 660 MB 126-142 vs 108-109); mcn_tuning.pair_stream 2 / 3 force it on / off
-    const double footprint = (double)p.E * ((15 + 11 * NT) * 8 + 70);
-    const bool nt = p.pair_stream == 2 || (p.pair_stream != 3 && footprint > 400e6);
-    if (nt) hipLaunchKernelGGL((env_pair_kernel<NT, true>), dim3(blocks), dim3(256), 0, stream, p);
-    else    hipLaunchKernelGGL((env_pair_kernel<NT, false>), dim3(blocks), dim3(256), 0, stream, p);
+    if (nontemporal) hipLaunchKernelGGL((env_pair_kernel<NT, true>), dim3(blocks), dim3(256), 0, stream, p);
+    else             hipLaunchKernelGGL((env_pair_kernel<NT, false>), dim3(blocks), dim3(256), 0, stream, p);
 }
 
-// Returns true when the streaming kernel handles this problem.
-bool launch_env_pair(const StepParams &p, hipStream_t stream)
+// env_dispatch.hpp: pair_applies() holds for p
+void launch_env_pair(const StepParams &p, bool nontemporal, hipStream_t stream)
 {
-    if (p.cfg.human_policy != MCN_HUMANS_GIVEN || !p.update || p.cfg.count_hh || p.cfg.robot_kinematics != MCN_KIN_HOLONOMIC)
-        return false;
-    if ((p.cfg.track_human_times && p.st.human_times) || p.out.human_act) return false;
-    if (p.has_roll && p.roll.state && p.roll.disc_len > kPairDiscMax) return false;
-    if (p.force_generic) return false;
-    switch (p.N) {
-        case 5:  launch_pair_one<5>(p, stream); break;
-        case 10: launch_pair_one<10>(p, stream); break;
-        default: return false;
-    }
-    note_dispatch("env_pair_kernel");
-    return true;
+    if (p.N == 5) launch_pair_one<5>(p, nontemporal, stream);
+    else          launch_pair_one<10>(p, nontemporal, stream);
 }
 
 }  // namespace mcn

@@ -7,12 +7,9 @@
 #include "quad_common.hpp"
 #include "env_step_params.hpp"
 #include "env_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
-void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispatch()
-void note_rollout_form(int form);                // mcn_api.hip: mcn_last_rollout_form()
-// env_rollout_wg4.hip: the four-wavefront form (5 humans, invisible robot), one workgroup per 8 envs
-void launch_env_rollout_wg4(const StepParams &p, int T, hipStream_t stream);
 
 // Diagnostic build only (make -C modelcrowdnav_amd/csrc stamp -> build_stamp/libmcn_hip.so, tools/fixed_cost.py):
 // lane 0 of every wavefront writes the 100 MHz real-time counter at kernel entry (slot 0), after the state load

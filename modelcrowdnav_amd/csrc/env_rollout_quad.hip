@@ -23,8 +23,6 @@
 namespace mcn {
 
 #ifdef MCN_DIAG
-int read_counts_wg4(void *dst, size_t bytes, int reset);      // env_rollout_wg4.hip
-int read_stamps_wg4(void *dst, size_t bytes);
 // the four-wavefront form keeps its own stamps and counts: read those of the form that went out last
 int read_counts(void *dst, size_t bytes, int reset, int form)
 {
@@ -362,56 +360,47 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64, SPLIT ? 3 : 1) void env_rollout_q
 }
 
 template <int NT, int VIS, bool UNI>
-static void launch_rollout_kin(const StepParams &p, int T, int blocks, hipStream_t stream)
+static void launch_rollout_kin(const StepParams &p, int form, int T, int blocks, hipStream_t stream)
 {
-    // quad_split = 2: the four-wavefront form where it is built (5 humans, invisible robot; env_rollout_wg4.hip); every
-    // other shape keeps the two-wavefront form
+    // form 2: the four-wavefront form, planned only where it is built (5 humans, invisible robot; env_rollout_wg4.hip)
     if constexpr (NT == 5 && VIS == 0) {
-        if (p.quad_split == 2) {
+        if (form == 2) {
             launch_env_rollout_wg4(p, T, stream);
-            note_rollout_form(2);
             return;
         }
     }
-    if (p.quad_split)
+    if (form)
         hipLaunchKernelGGL((env_rollout_quad_kernel<NT, VIS, UNI, true>), dim3(blocks), dim3(128), 0, stream, p, T);
     else
         hipLaunchKernelGGL((env_rollout_quad_kernel<NT, VIS, UNI, false>), dim3(blocks), dim3(64), 0, stream, p, T);
-    note_rollout_form(p.quad_split ? 1 : 0);
 }
 
 template <int NT, int VIS>
-static void launch_rollout_one(const StepParams &p, int T, hipStream_t stream)
+static void launch_rollout_one(const StepParams &p, int form, int T, hipStream_t stream)
 {
     constexpr int G = 64 / (4 * NT);
     const int blocks = (p.E + G - 1) / G;
     if (p.cfg.robot_kinematics == MCN_KIN_UNICYCLE)
-        launch_rollout_kin<NT, VIS, true>(p, T, blocks, stream);
+        launch_rollout_kin<NT, VIS, true>(p, form, T, blocks, stream);
     else
-        launch_rollout_kin<NT, VIS, false>(p, T, blocks, stream);
+        launch_rollout_kin<NT, VIS, false>(p, form, T, blocks, stream);
 }
 
-// Returns true when the fused T-step kernel handles this problem (ORCA humans, <= 4 neighbours each, update).
-bool launch_env_rollout_quad(const StepParams &p, int T, hipStream_t stream)
+// env_dispatch.hpp: quad_shape_applies() holds for p (ORCA humans, <= 4 neighbours each) and p.update is set
+void launch_env_rollout_quad(const StepParams &p, int form, int T, hipStream_t stream)
 {
-    if (p.cfg.human_policy != MCN_HUMANS_ORCA || p.cfg.orca_max_neighbors < 4 || !p.update) return false;
-    const int vis = p.cfg.robot_visible ? 1 : 0;
-    const int nc = p.N - 1 + vis;
-    if (nc > 4 || p.N < 1) return false;
-    switch (p.N * 2 + vis) {
-        case 2:  launch_rollout_one<1, 0>(p, T, stream); break;
-        case 3:  launch_rollout_one<1, 1>(p, T, stream); break;
-        case 4:  launch_rollout_one<2, 0>(p, T, stream); break;
-        case 5:  launch_rollout_one<2, 1>(p, T, stream); break;
-        case 6:  launch_rollout_one<3, 0>(p, T, stream); break;
-        case 7:  launch_rollout_one<3, 1>(p, T, stream); break;
-        case 8:  launch_rollout_one<4, 0>(p, T, stream); break;
-        case 9:  launch_rollout_one<4, 1>(p, T, stream); break;
-        case 10: launch_rollout_one<5, 0>(p, T, stream); break;
-        default: return false;
+    switch (p.N * 2 + (p.cfg.robot_visible ? 1 : 0)) {
+        case 2:  launch_rollout_one<1, 0>(p, form, T, stream); break;
+        case 3:  launch_rollout_one<1, 1>(p, form, T, stream); break;
+        case 4:  launch_rollout_one<2, 0>(p, form, T, stream); break;
+        case 5:  launch_rollout_one<2, 1>(p, form, T, stream); break;
+        case 6:  launch_rollout_one<3, 0>(p, form, T, stream); break;
+        case 7:  launch_rollout_one<3, 1>(p, form, T, stream); break;
+        case 8:  launch_rollout_one<4, 0>(p, form, T, stream); break;
+        case 9:  launch_rollout_one<4, 1>(p, form, T, stream); break;
+        case 10: launch_rollout_one<5, 0>(p, form, T, stream); break;
+        default: break;
     }
-    note_dispatch("env_rollout_quad_kernel");
-    return true;
 }
 
 }  // namespace mcn

@@ -29,9 +29,9 @@
 #include "env_common.hpp"
 #include "lp3_queue.hpp"
 #include "social_force.hpp"
+#include "launch.hpp"
 
 namespace mcn {
-void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispatch()
 
 // crowds up to this size pre-filter the human-human overlaps inside the ORCA candidate loop (squared distances, no
 // sqrt); larger ones keep the separate loop: the extra live values push their unrolled solver past 168 VGPRs
@@ -650,20 +650,18 @@ static void launch_one(const StepParams &p, int blocks, hipStream_t stream)
 {
     const size_t sm = step_smem_bytes(BLOCK, MODE != MCN_HUMANS_ORCA ? 0 : (NT ? NT / 2 : p.nl_cap),
                                       MODE == MCN_HUMANS_ORCA && NT > 0 && NT - 1 + VIS >= 5 && BLOCK == 64);
-    note_dispatch("env_step_kernel");
     hipLaunchKernelGGL((env_step_kernel<BLOCK, NT, VIS, MODE, HH_T>), dim3(blocks), dim3(BLOCK), sm, stream, p);
 }
 
+// the lane-per-human kernel: compile-time N (StepPlan.static_n: ORCA 1..10, social force 5 / 10) or the run-time-N body
 template <int BLOCK>
-static void dispatch(const StepParams &p, int blocks, hipStream_t stream)
+static void launch_lane(const StepParams &p, bool static_n, int blocks, hipStream_t stream)
 {
     const int vis = p.cfg.robot_visible ? 1 : 0;
     if (p.cfg.human_policy == MCN_HUMANS_ORCA) {
-        // register-resident ORCA specialisations for the crowd sizes the reference trains and tests on
-        // (human_num 5 / 10 in the configs, 5,7,9 in test_mul_env.py:31-33, 1..5 in the 'mixed' rule)
 #define MCN_CASE(NT_) case NT_: if (vis) launch_one<BLOCK, NT_, 1, MCN_HUMANS_ORCA, 2>(p, blocks, stream); \
                                else     launch_one<BLOCK, NT_, 0, MCN_HUMANS_ORCA, 2>(p, blocks, stream); return;
-        switch (p.force_generic ? 0 : p.N) {
+        switch (static_n ? p.N : 0) {
             MCN_CASE(1) MCN_CASE(2) MCN_CASE(3) MCN_CASE(4) MCN_CASE(5) MCN_CASE(6) MCN_CASE(7) MCN_CASE(8) MCN_CASE(9) MCN_CASE(10)
             default: break;
         }
@@ -675,8 +673,7 @@ static void dispatch(const StepParams &p, int blocks, hipStream_t stream)
     } else if (p.cfg.human_policy == MCN_HUMANS_SOCIALFORCE) {
 #define MCN_SF_CASE(NT_) if (p.cfg.count_hh) launch_one<BLOCK, NT_, 0, MCN_HUMANS_SOCIALFORCE, 1>(p, blocks, stream); \
                                   else                launch_one<BLOCK, NT_, 0, MCN_HUMANS_SOCIALFORCE, 0>(p, blocks, stream); return;
-        // compile-time N for the reference's crowd sizes: the loop over the others is unrolled (4 - 9 % per launch)
-        switch (p.force_generic ? 0 : p.N) {
+        switch (static_n ? p.N : 0) {
             case 5: MCN_SF_CASE(5)
             case 10: MCN_SF_CASE(10)
             default: break;
@@ -689,117 +686,54 @@ static void dispatch(const StepParams &p, int blocks, hipStream_t stream)
     }
 }
 
-// Small batches run one wavefront per workgroup so that the grid covers as many CUs as possible (crowds of 9-10: the
-// one-wavefront workgroups with the cooperative 3-D LP stay ahead longer -- 10 humans, 32 768 envs 63.6 vs 67.1 us,
-// 65 536 envs 105 vs 110, 2^18 envs 391 vs 307; 7 humans cross at ~24 k envs).  mcn_tuning.step_block overrides.
-static bool one_wave_batch(const StepParams &p, int waves_total, int nc)
+// env_dispatch.hpp: step_loop_applies() holds for p
+void launch_env_step_loop(const StepParams &p, int T, hipStream_t stream)
 {
-    return p.step_block > 0 ? p.step_block == 64 : waves_total <= (nc >= 8 ? 12288 : 4096);
-}
-
-// mcn_env_rollout for 6-10 ORCA humans (and 5 with a visible robot) in a latency-bound batch: one env_step_loop_kernel launch instead of T step
-// launches.  false = not applicable (the caller falls back to T launches).
-bool launch_env_step_loop(const StepParams &p, int T, hipStream_t stream)
-{
-    // (5 humans + a visible robot = 5 neighbours: one more than the quad-parallel rollout kernel takes)
-    const bool five_vis = p.N == 5 && p.cfg.robot_visible;
-    if (p.cfg.human_policy != MCN_HUMANS_ORCA || p.force_generic || !p.update || ((p.N < 6 || p.N > 10) && !five_vis)) return false;
-    if (p.lp3_defer > 0) return false;                                 // forced deferral: two kernels per step
-    const int G = 64 / p.N;
-    const int waves_total = (p.E + G - 1) / G;
-    const int nc = p.N - 1 + (p.cfg.robot_visible ? 1 : 0);
-    if (!one_wave_batch(p, waves_total, nc)) return false;             // launch_env_step's own rule
-    // The looped kernel holds 234-282 VGPRs (one wavefront per SIMD) against the step kernel's 160 (three): it wins while
-    // the batch leaves SIMDs idle anyway and loses once wavefronts queue up -- 10 humans: 4096 envs 28.9 -> 14.9 us per
-    // step, 16 384 envs (2731 wavefronts) 43.0 -> 41.3, 32 768 envs (5462) 64.2 -> 80.7.
-    if (p.step_block != 64 && waves_total > 3072) return false;
-    StepParams q = p;
-    q.lp3_defer = 0;
-    q.G = G;
-    const size_t sm = step_smem_bytes(64, p.N / 2, nc >= 5);
-    note_dispatch("env_step_loop_kernel");
+    const int waves_total = (int)lane_wavefronts(p);
+    const size_t sm = step_smem_bytes(64, p.N / 2, step_candidates(p) >= 5);
 #define MCN_LOOP_CASE(NT_) case NT_: \
-        if (p.cfg.robot_visible) hipLaunchKernelGGL((env_step_loop_kernel<NT_, 1>), dim3(waves_total), dim3(64), sm, stream, q, T); \
-        else                     hipLaunchKernelGGL((env_step_loop_kernel<NT_, 0>), dim3(waves_total), dim3(64), sm, stream, q, T); \
-        return true;
+        if (p.cfg.robot_visible) hipLaunchKernelGGL((env_step_loop_kernel<NT_, 1>), dim3(waves_total), dim3(64), sm, stream, p, T); \
+        else                     hipLaunchKernelGGL((env_step_loop_kernel<NT_, 0>), dim3(waves_total), dim3(64), sm, stream, p, T); \
+        break;
     switch (p.N) {
-        case 5: hipLaunchKernelGGL((env_step_loop_kernel<5, 1>), dim3(waves_total), dim3(64), sm, stream, q, T); return true;
+        case 5: hipLaunchKernelGGL((env_step_loop_kernel<5, 1>), dim3(waves_total), dim3(64), sm, stream, p, T); break;
         MCN_LOOP_CASE(6) MCN_LOOP_CASE(7) MCN_LOOP_CASE(8) MCN_LOOP_CASE(9) MCN_LOOP_CASE(10)
         default: break;
     }
 #undef MCN_LOOP_CASE
-    return false;
 }
 
-// mcn_env_rollout_sf in a latency-bound batch (launch_env_step's own one-wavefront rule): one env_step_loop_sf_kernel
-// launch instead of T step launches.  false = not applicable (the caller falls back to T launches).
-bool launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream)
+// env_dispatch.hpp: step_loop_sf_applies() holds for p
+void launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream)
 {
-    if (p.cfg.human_policy != MCN_HUMANS_SOCIALFORCE || !p.update) return false;
-    const int G = 64 / p.N;
-    const int waves_total = (p.E + G - 1) / G;
-    const int nc = p.N - 1 + (p.cfg.robot_visible ? 1 : 0);
-    if (!one_wave_batch(p, waves_total, nc)) return false;
-    StepParams q = p;
-    q.G = G;
+    const int waves_total = (int)lane_wavefronts(p);
     const size_t sm = step_smem_bytes(64, 0);
-    note_dispatch("env_step_loop_sf_kernel");
     // (run-time N only: the 5- / 10-human forms of the step kernel did not pass the adoption rule inside the loop)
-    if (p.cfg.count_hh) hipLaunchKernelGGL((env_step_loop_sf_kernel<1>), dim3(waves_total), dim3(64), sm, stream, q, T);
-    else                hipLaunchKernelGGL((env_step_loop_sf_kernel<0>), dim3(waves_total), dim3(64), sm, stream, q, T);
-    return true;
+    if (p.cfg.count_hh) hipLaunchKernelGGL((env_step_loop_sf_kernel<1>), dim3(waves_total), dim3(64), sm, stream, p, T);
+    else                hipLaunchKernelGGL((env_step_loop_sf_kernel<0>), dim3(waves_total), dim3(64), sm, stream, p, T);
 }
 
 // mcn_env_rollout_orca: one env_step_loop_orca_kernel launch for any batch and any 1 <= N <= MCN_MAX_HUMANS (ORCA or
-// linear humans, holonomic robot: validated by the caller).
-int launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream)
+// linear humans, holonomic robot: validated by the caller, whose p.nl_cap also covers the robot's solve).
+void launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream)
 {
-    StepParams q = p;
-    q.lp3_defer = 0;
-    q.update = 1;
-    q.G = 64 / p.N;
-    // line slots per lane: the larger of what a human's solve and the robot's solve (all N humans as candidates) can fill
-    const int rob_nl = cl.max_neighbors < p.N ? cl.max_neighbors : p.N;
-    q.nl_cap = p.nl_cap > rob_nl ? p.nl_cap : rob_nl;
-    const int waves_total = (p.E + q.G - 1) / q.G;
-    const size_t sm = step_smem_bytes(64, q.nl_cap);
-    note_dispatch("env_step_loop_orca_kernel");
+    const int waves_total = (int)lane_wavefronts(p);
+    const size_t sm = step_smem_bytes(64, p.nl_cap);
     if (p.cfg.human_policy == MCN_HUMANS_ORCA)
-        hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_ORCA>), dim3(waves_total), dim3(64), sm, stream, q, cl, T);
+        hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_ORCA>), dim3(waves_total), dim3(64), sm, stream, p, cl, T);
     else
-        hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_LINEAR>), dim3(waves_total), dim3(64), sm, stream, q, cl, T);
-    return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
+        hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_LINEAR>), dim3(waves_total), dim3(64), sm, stream, p, cl, T);
 }
 
-bool launch_env_step_quad(const StepParams &p, hipStream_t stream);      // env_step_quad.hip
-bool launch_env_pair(const StepParams &p, hipStream_t stream);           // env_pair.hip
-
-int launch_env_step(const StepParams &p_in, hipStream_t stream)
+// One single step as planned (env_dispatch.hpp: plan_env_step); p.lp3_defer already carries plan.lp3_defer.
+void launch_env_step(const StepParams &p, const StepPlan &plan, hipStream_t stream)
 {
-    StepParams p = p_in;
-    const int defer_policy = p.lp3_defer;
-    p.lp3_defer = 0;                                  // what the kernels see: 0 / 1
-    // <= 4 ORCA neighbours per human: quad-parallel kernel (env_step_quad.hip)
-    if (p.quad_max_envs > 0 && p.E <= p.quad_max_envs && launch_env_step_quad(p, stream))
-        return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
-    const int waves_total = (p.E + p.G - 1) / p.G;
-    // The compile-time-N ORCA kernels can park their 3-D LPs when the caller gave them a queue.  Measured on MI355X
-    // (round 3, circle crossing with pool restarts; step kernel alone / + the finish kernel vs solving in place):
-    // 10 humans 2^18 envs 344 -> 249 + 40 us, 32 768 envs 65 -> 65, 4096 envs 27 -> 31; 7 humans 2^18 envs 110 -> 122;
-    // 5 humans 2^20 envs 207 -> 205 + 20.  Only 0.9 / 1.8 / 3.7 % of the humans need the 3-D LP at 5 / 7 / 10 humans
-    // and the in-place code already skips every block no lane of the wavefront needs, so deferral pays only for the
-    // largest crowds in throughput-bound batches: automatic from 8 neighbours and 16 384 wavefronts.
-    const int nc = p.N - 1 + (p.cfg.robot_visible ? 1 : 0);
-    if (p.out.lp3_queue && p.cfg.human_policy == MCN_HUMANS_ORCA && !p.force_generic && p.N >= 2 && p.N <= 10 &&
-        nc >= 1 && nc <= kMaxLines && (defer_policy > 0 || (defer_policy < 0 && nc >= 8 && waves_total >= 16384)))
-        p.lp3_defer = 1;
-    // given velocities, large batch: the streaming form (env_pair.hip); mcn_tuning.pair_stream overrides
-    if ((p.pair_stream > 0 || (p.pair_stream < 0 && waves_total > 4096)) && launch_env_pair(p, stream))
-        return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
-    if (one_wave_batch(p, waves_total, nc)) dispatch<64>(p, waves_total, stream);
-    else                     dispatch<256>(p, (waves_total + 3) / 4, stream);
-    if (p.lp3_defer) launch_env_lp3(p, stream);
-    return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
+    if (plan.family == kStepQuad) return launch_env_step_quad(p, plan.quad_split, stream);
+    if (plan.family == kStepPair) return launch_env_pair(p, plan.pair_nontemporal, stream);
+    const int waves_total = (int)lane_wavefronts(p);
+    if (plan.block == 64) launch_lane<64>(p, plan.static_n, waves_total, stream);
+    else                  launch_lane<256>(p, plan.static_n, (waves_total + 3) / 4, stream);
+    if (plan.lp3_defer) launch_env_lp3(p, stream);
 }
 
 }  // namespace mcn

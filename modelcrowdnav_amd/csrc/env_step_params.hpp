@@ -5,6 +5,11 @@
 
 namespace mcn {
 
+// Limits that the kernels and the dispatch (env_dispatch.hpp) share; here because this header needs no HIP.
+constexpr int kMaxLines = 10;          // ORCA line slots per agent (orca_device.hpp)
+// longest discount table the dispatcher accepts for env_pair_kernel (longer ones stay on env_step_kernel)
+constexpr int kPairDiscMax = 128;
+
 struct StepParams {
     mcn_env_cfg cfg;
     mcn_env_state st;
@@ -14,13 +19,14 @@ struct StepParams {
     const double *given_v;
     int E, N, G, update, has_roll;
     int nl_cap;   // LDS line slots per lane
-    int quad_max_envs;   // use the quad-parallel kernel up to this batch size (0: never)
-    int force_generic;   // mcn_tuning.force_generic: run-time-N kernel even where a specialisation exists (tests, tuning)
+    // The unused_* members held host-only dispatch inputs (quad_max_envs, force_generic, quad_split, step_block,
+    // pair_stream) until the dispatch moved to env_dispatch.hpp.  No code reads or writes them; they stay as padding so
+    // that sizeof and the offset of every member a kernel reads, and with them the kernels' argument loads, are unchanged.
+    int unused_0, unused_1;
     int debug_noop;      // mcn_tuning.diag_noop, DIAGNOSTIC BUILD ONLY: kernels return at entry (launch-floor measurement)
-    int quad_split;      // quad kernel: ORCA and pairwise work on two cooperating wavefronts
-    int step_block;      // mcn_tuning.step_block: 64 / 256 lanes per workgroup in the lane-per-human kernels, -1 automatic
-    int lp3_defer;       // mcn_tuning.lp3_defer (-1 automatic); launch_env_step turns it into 0 / 1 for the kernel
-    int pair_stream;     // given-velocity step: streaming kernel of env_pair.hip (-1 automatic, 0 never, 1 where it applies)
+    int unused_2, unused_3;
+    int lp3_defer;       // 0 / 1 (StepPlan.lp3_defer): the compile-time-N ORCA kernels park their 3-D LPs in out.lp3_queue
+    int unused_4;
     // MCN_HUMANS_SOCIALFORCE only (mcn_env_step_sf / mcn_env_rollout_sf): A (m/s^2), B (m), k (1/s) of social_force.hpp
     double sf_strength, sf_range, sf_relaxation_rate;
 };

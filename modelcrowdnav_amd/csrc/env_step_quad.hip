@@ -23,9 +23,9 @@
 #include "quad_common.hpp"
 #include "env_step_params.hpp"
 #include "env_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
-void note_dispatch(const char *family);          // mcn_api.hip: mcn_last_dispatch()
 
 // SPLIT = true: the workgroup has two wavefronts working on the same G envs.  Wavefront 0 solves ORCA (float32),
 // wavefront 1 does the float64 swept-circle / overlap tests, the reward ladder and all per-env outputs AT THE
@@ -227,37 +227,31 @@ __global__ __launch_bounds__(SPLIT ? 128 : 64) void env_step_quad_kernel(const S
 }
 
 template <int NT, int VIS>
-static void launch_quad_one(const StepParams &p, hipStream_t stream)
+static void launch_quad_one(const StepParams &p, bool split, hipStream_t stream)
 {
     constexpr int G = 64 / (4 * NT);
     const int blocks = (p.E + G - 1) / G;
-    if (p.quad_split)
+    if (split)
         hipLaunchKernelGGL((env_step_quad_kernel<NT, VIS, true>), dim3(blocks), dim3(128), 0, stream, p);
     else
         hipLaunchKernelGGL((env_step_quad_kernel<NT, VIS, false>), dim3(blocks), dim3(64), 0, stream, p);
 }
 
-// Returns true when the quad kernel handles this problem (ORCA humans, <= 4 neighbours each).
-bool launch_env_step_quad(const StepParams &p, hipStream_t stream)
+// env_dispatch.hpp: quad_shape_applies() holds for p (ORCA humans, <= 4 neighbours each)
+void launch_env_step_quad(const StepParams &p, bool split, hipStream_t stream)
 {
-    if (p.cfg.human_policy != MCN_HUMANS_ORCA || p.cfg.orca_max_neighbors < 4) return false;
-    const int vis = p.cfg.robot_visible ? 1 : 0;
-    const int nc = p.N - 1 + vis;
-    if (nc > 4 || p.N < 1) return false;
-    switch (p.N * 2 + vis) {
-        case 2:  launch_quad_one<1, 0>(p, stream); break;
-        case 3:  launch_quad_one<1, 1>(p, stream); break;
-        case 4:  launch_quad_one<2, 0>(p, stream); break;
-        case 5:  launch_quad_one<2, 1>(p, stream); break;
-        case 6:  launch_quad_one<3, 0>(p, stream); break;
-        case 7:  launch_quad_one<3, 1>(p, stream); break;
-        case 8:  launch_quad_one<4, 0>(p, stream); break;
-        case 9:  launch_quad_one<4, 1>(p, stream); break;
-        case 10: launch_quad_one<5, 0>(p, stream); break;
-        default: return false;
+    switch (p.N * 2 + (p.cfg.robot_visible ? 1 : 0)) {
+        case 2:  launch_quad_one<1, 0>(p, split, stream); break;
+        case 3:  launch_quad_one<1, 1>(p, split, stream); break;
+        case 4:  launch_quad_one<2, 0>(p, split, stream); break;
+        case 5:  launch_quad_one<2, 1>(p, split, stream); break;
+        case 6:  launch_quad_one<3, 0>(p, split, stream); break;
+        case 7:  launch_quad_one<3, 1>(p, split, stream); break;
+        case 8:  launch_quad_one<4, 0>(p, split, stream); break;
+        case 9:  launch_quad_one<4, 1>(p, split, stream); break;
+        case 10: launch_quad_one<5, 0>(p, split, stream); break;
+        default: break;
     }
-    note_dispatch("env_step_quad_kernel");
-    return true;
 }
 
 }  // namespace mcn

@@ -23,12 +23,9 @@
 #include <stdint.h>
 #include "../../include/mcn.h"
 #include "lookahead_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
-
-int launch_sarl_argmax(const double *values, const double *rpos, const double *rgoal, const double *rrad, int E, int A,
-                       int32_t *best, double *best_val, const double *actions, double *action_out, double epsilon,
-                       unsigned long long seed, hipStream_t stream);       // sarl_value.hip
 
 namespace {
 

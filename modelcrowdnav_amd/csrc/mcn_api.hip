@@ -9,62 +9,9 @@
 #include "../../include/mcn.h"
 
 #include "env_step_params.hpp"
+#include "env_dispatch.hpp"
+#include "launch.hpp"
 #include "lp3_queue.hpp"
-
-namespace mcn {
-int launch_env_step(const StepParams &p, hipStream_t stream);
-bool launch_env_rollout_quad(const StepParams &p, int T, hipStream_t stream);
-bool launch_env_step_loop(const StepParams &p, int T, hipStream_t stream);
-bool launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream);
-int launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream);
-int launch_scenario_pool(const mcn_scenario_cfg &c, uint64_t seed, int64_t first_case, int P, int N, double *hpos,
-                         double *hgoal, double *hrad, double *hvpref, hipStream_t stream);
-struct SarlParams;
-long sarl_workspace_float4s(int E, int N, int A);
-int launch_mlp_world(const mcn_mlp_world_net *net, const double *hpos, const double *hvel, double *out_vel, int E, int N,
-                     hipStream_t stream);
-int launch_attn_world(const mcn_attn_world_net *net, const double *hpos, const double *hvel, const int32_t *hcount,
-                      void *workspace, double *out_vel, int E, int N, hipStream_t stream);
-long attn_world_workspace_float4s(int E, int N);
-int launch_sarl_c(const mcn_sarl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
-                  double gamma_pow, int kinematics, void *workspace, double *values, int32_t *best, double *best_val,
-                  float *attention, const double *next_hpos, const double *next_hvel, const double *reward_in,
-                  double *action_out, double epsilon, unsigned long long seed, int E, int N, const float *om_init,
-                  hipStream_t stream);
-int launch_sarl_om(const mcn_env_state *st, double dt, const double *next_hpos, const double *next_hvel,
-                   double cell_size, const float *w_om, const float *b_om, float *om, float *init, int E, int N,
-                   hipStream_t stream);
-int launch_lstm_rl(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
-                   double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val, int32_t *order,
-                   const double *next_hpos, const double *next_hvel, const double *reward_in, double *action_out,
-                   double epsilon, unsigned long long seed, int E, int N, hipStream_t stream);
-int launch_cadrl(const mcn_cadrl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
-                 double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val,
-                 const double *next_hpos, const double *next_hvel, const double *reward_in, double *action_out,
-                 double epsilon, unsigned long long seed, int E, int N, hipStream_t stream);
-int launch_lstm_rl_order(const double *hpos, const double *rpos, const int32_t *hcount, int32_t *order, int E, int N,
-                         hipStream_t stream);
-#ifdef MCN_DIAG
-int read_pool_clock(void *dst, size_t bytes);
-int read_sarl_phases(void *dst, size_t bytes, int reset);
-#endif
-int launch_sgan(const mcn_sgan_net *net, double *hist, int push_slot, int oldest, const double *cur_pos,
-                const float *noise, const int32_t *hcount, void *workspace, double *out_vel, float *out_rel,
-                double time_step, int E, int N, hipStream_t stream);
-int launch_sgan_predict(const mcn_sgan_net *net, const double *hist, int oldest, const float *noise, int K, int T,
-                        const int32_t *hcount, void *workspace, float *out_rel, double *out_pos, int E, int N,
-                        hipStream_t stream);
-int launch_orca_batch(const float *self, const float *others, const int32_t *n_other, float *out,
-                      int B, int M, float neighbor_dist, int max_neighbors, float time_horizon, float time_step,
-                      hipStream_t stream);
-int launch_orca_finish(const mcn_env_state &st, float *sim_vel, const uint8_t *select, int max_steps, int32_t *steps,
-                       float *traj, double time_step, float neighbor_dist, int max_neighbors, float time_horizon,
-                       int E, int N, hipStream_t stream);
-#ifdef MCN_DIAG
-int read_stamps(void *dst, size_t bytes, int form);
-int read_counts(void *dst, size_t bytes, int reset, int form);
-#endif
-}  // namespace mcn
 
 // Dispatch overrides (include/mcn.h: mcn_tuning).  The MCN_* environment variables are read ONCE, the first time a
 // launch needs them, as the initial values; after that only mcn_set_tuning changes them.  No getenv on the launch path.
@@ -139,13 +86,11 @@ int mcn_pack_x3(const float *wfrag, int32_t NT, int32_t KT, void *x3_out)
     return MCN_OK;
 }
 
-// mcn_last_dispatch(): the launch functions of the env kernels note which family they picked (per host thread).
+// mcn_last_dispatch(): the family of the plan the env entry points ran last (per host thread; env_dispatch.hpp: family_name)
 static thread_local const char *g_last_dispatch = "";
-namespace mcn { void note_dispatch(const char *family) { g_last_dispatch = family; } }
 const char *mcn_last_dispatch(void) { return g_last_dispatch; }
-// mcn_last_rollout_form(): set where env_rollout_quad.hip launches, so it names the kernel that really went out
+// mcn_last_rollout_form(): the form of mcn_env_rollout's last plan, -1 unless that was the fused quad rollout
 static thread_local int32_t g_last_rollout_form = -1;
-namespace mcn { void note_rollout_form(int form) { g_last_rollout_form = form; } }
 int32_t mcn_last_rollout_form(void) { return g_last_rollout_form; }
 
 int32_t mcn_abi_version(void) { return MCN_ABI_VERSION; }
@@ -171,10 +116,11 @@ int64_t mcn_sizeof(int32_t which)
     }
 }
 
-// Validates one env-step problem and fills the kernel argument block.  Shared by mcn_env_step / mcn_env_rollout and
-// their social-force twins: `social_force` says which family the caller is, and the cfg's policy must belong to it.
-static int fill_step_params(mcn::StepParams &p, const mcn_env_cfg *cfg, const mcn_env_state *st, const double *actions,
-                            const double *given_v, const mcn_env_out *out, const mcn_rollout *roll,
+// Validates one env-step problem and fills the kernel argument block; which kernel takes it is env_dispatch.hpp's to
+// say.  Shared by mcn_env_step / mcn_env_rollout and their social-force twins: `social_force` says which family the
+// caller is, and the cfg's policy must belong to it.  `tu`: the caller's snapshot of the tuning.
+static int fill_step_params(mcn::StepParams &p, const mcn_tuning &tu, const mcn_env_cfg *cfg, const mcn_env_state *st,
+                            const double *actions, const double *given_v, const mcn_env_out *out, const mcn_rollout *roll,
                             int32_t E, int32_t N, int32_t update, bool social_force = false, bool needs_actions = true)
 {
     if (!cfg || !st || !out || (needs_actions && !actions)) return MCN_EINVAL;
@@ -205,27 +151,38 @@ static int fill_step_params(mcn::StepParams &p, const mcn_env_cfg *cfg, const mc
     int nl = ncand < cfg->orca_max_neighbors ? ncand : cfg->orca_max_neighbors;
     if (cfg->human_policy != MCN_HUMANS_ORCA) nl = 0;
     p.nl_cap = nl;
-    // Small batches are latency-bound: use the quad-parallel kernel (env_step_quad.hip) while its 4x wider
-    // grid still fits the chip about twice over (measured cross-over on MI355X: ~2800 wavefronts, i.e.
-    // E <= 8192 at 5 humans); above that the lane-per-human kernel wins on throughput.  Inside the quad
-    // kernel, ORCA and the float64 pairwise work go to two cooperating wavefronts only while BOTH still get a
-    // SIMD of their own (grid <= 512 workgroups).  mcn_set_tuning overrides (tests, tuning).
-    const mcn_tuning tu = tuning();
-    p.force_generic = tu.force_generic > 0 ? 1 : 0;
-    p.pair_stream = tu.pair_stream;
-    p.step_block = tu.step_block;
-    p.lp3_defer = tu.lp3_defer;
 #ifdef MCN_DIAG
     p.debug_noop = tu.diag_noop;
 #endif
-    const int envs_per_wave = 64 / (4 * N);
-    const long quad_waves = envs_per_wave > 0 ? ((long)E + envs_per_wave - 1) / envs_per_wave : (1L << 40);
-    p.quad_max_envs = tu.quad_max_envs >= 0 ? tu.quad_max_envs : (quad_waves <= 2800 ? E : 0);
-    // two cooperating wavefronts per env group while the doubled grid still finds idle issue slots; re-measured in round 4
-    // (5 humans, us per step without / with: 1024 envs 5.87 / 5.37, 2048 6.28 / 6.10, 4096 = 1366 wavefronts 7.20 / 6.95,
-    //  5120 7.60 / 8.01, 6144 7.71 / 8.68): up to ~1400 wavefronts (round 3's rule stopped at 512)
-    p.quad_split = tu.quad_split >= 0 ? tu.quad_split : (quad_waves <= 1400 ? 1 : 0);
     return MCN_OK;
+}
+
+static int launched() { return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH; }
+
+// T single steps as planned, step t on actions[t][E][2] (mcn_env_step: T = 1)
+static int run_steps(mcn::StepParams &p, const mcn::StepPlan &plan, const double *actions, int32_t T, hipStream_t stream)
+{
+    g_last_dispatch = mcn::family_name(plan.family);
+    p.lp3_defer = plan.lp3_defer ? 1 : 0;
+    for (int32_t t = 0; t < T; ++t) {
+        p.actions = actions + (size_t)t * p.E * 2;
+        mcn::launch_env_step(p, plan, stream);
+        const int rc = launched();
+        if (rc != MCN_OK) return rc;
+    }
+    return MCN_OK;
+}
+
+static int run_rollout(mcn::StepParams &p, const mcn::RolloutPlan &plan, const double *actions, int32_t T, hipStream_t stream)
+{
+    switch (plan.family) {
+        case mcn::kRolloutQuad: mcn::launch_env_rollout_quad(p, plan.form, T, stream); break;
+        case mcn::kStepLoop:    mcn::launch_env_step_loop(p, T, stream); break;
+        case mcn::kStepLoopSf:  mcn::launch_env_step_loop_sf(p, T, stream); break;
+        default:                return run_steps(p, plan.step, actions, T, stream);
+    }
+    g_last_dispatch = mcn::family_name(plan.family);
+    return launched();
 }
 
 extern "C" {
@@ -270,60 +227,24 @@ int mcn_env_step(const mcn_env_cfg *cfg, const mcn_env_state *st, const double *
                  const double *given_v, const mcn_env_out *out, const mcn_rollout *roll,
                  int32_t E, int32_t N, int32_t update, void *stream)
 {
+    const mcn_tuning tu = tuning();
     mcn::StepParams p;
-    const int rc = fill_step_params(p, cfg, st, actions, given_v, out, roll, E, N, update);
+    const int rc = fill_step_params(p, tu, cfg, st, actions, given_v, out, roll, E, N, update);
     if (rc != MCN_OK) return rc;
-    return mcn::launch_env_step(p, (hipStream_t)stream);
+    return run_steps(p, mcn::plan_env_step(p, tu), actions, 1, (hipStream_t)stream);
 }
 
 int mcn_env_rollout(const mcn_env_cfg *cfg, const mcn_env_state *st, const double *actions, int32_t T,
                     const mcn_env_out *out, const mcn_rollout *roll, int32_t E, int32_t N, void *stream)
 {
     if (T <= 0) return MCN_EINVAL;
-    mcn::StepParams p;
-    const int rc = fill_step_params(p, cfg, st, actions, nullptr, out, roll, E, N, 1);
-    if (rc != MCN_OK) return rc;
-    // One launch with the env state held in registers for all T steps where the quad layout applies and beats T
-    // launches of the throughput kernel: measured cross-over on MI355X at ~45 k envs of 5 humans (19.2 vs 18.6 us per
-    // step at 49 152 envs, 13.9 vs 15.3 at 32 768), i.e. ~14 k env groups; below that the fused launch wins by up to
-    // 2.7x.  Two cooperating wavefronts per env group while the doubled grid still finds idle issue slots (measured:
-    // wins up to 1536 groups = 4608 envs, loses from 1707).  The four-wavefront form (rollout_split = 2: workgroups of 8
-    // envs; built for 5 humans and an invisible robot) costs what its fullest CU holds and is taken only where it was
-    // measured to win (profiles/r12_rollout_wg4.txt, T = 1000 and T = 20, us per step at T = 1000 against the better of
-    // the other two forms):
-    //   holonomic robot (95 VGPRs, up to 4 workgroups per CU resident: 1.86 / 2.32 / 2.78 us at 2 / 3 / 4 per CU):
-    //     128 .. 512 workgroups (1024 envs 1.49 against 1.72, 4096 envs 1.86 against 2.10) and 768 .. 1024 (6144 / 8192
-    //     envs: 2.32 / 2.78 against 3.29 / 3.33).  Not below: at 64 and 256 envs no form shares a CU and the two-wavefront
-    //     form's shorter chain wins (1.43 against 1.47 / 1.51).  Not in between: at 4608 envs = 576 workgroups a quarter
-    //     of the CUs hold three and it loses (2.30 against 2.13).
-    //   unicycle robot (129 VGPRs: 3 wavefronts per SIMD, so the fourth workgroup of a CU waits; the other forms' 153 /
-    //     168 VGPRs cost them more): 8 .. 1024 workgroups, every size measured from 64 envs (1.96 against 2.11) over
-    //     4096 (2.32 against 3.37) and 4608 (3.06 against 3.39) to 8192 (4.18 against 5.45).
-    // mcn_set_tuning (rollout_fused / rollout_split) overrides (tests, tuning).
     const mcn_tuning tu = tuning();
-    const int envs_per_wave = 64 / (4 * N) > 0 ? 64 / (4 * N) : 1;
-    const long waves = ((long)E + envs_per_wave - 1) / envs_per_wave;
-    const bool fused = tu.rollout_fused >= 0 ? tu.rollout_fused != 0 : waves <= 14000;
-    const int step_split = p.quad_split;              // the single-step kernel's own choice, for the T-launch path
-    const long wg4 = ((long)E + 7) / 8;
-    const bool wg4_wins = N == 5 && !cfg->robot_visible &&
-                          (cfg->robot_kinematics == MCN_KIN_UNICYCLE ? wg4 >= 8 && wg4 <= 1024
-                                                                     : (wg4 >= 128 && wg4 <= 512) || (wg4 >= 768 && wg4 <= 1024));
-    p.quad_split = tu.rollout_split >= 0 ? tu.rollout_split : wg4_wins ? 2 : (waves <= 1536 ? 1 : 0);
-    mcn::note_rollout_form(-1);
-    if (fused && !p.force_generic && mcn::launch_env_rollout_quad(p, T, (hipStream_t)stream))
-        return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
-    p.quad_split = step_split;
-    // 6-10 ORCA humans, latency-bound batch: the one-wavefront step kernel run T times inside one launch
-    // (env_step.hip: env_step_loop_kernel); rollout_fused = 0 keeps the T launches
-    if (tu.rollout_fused != 0 && T > 1 && mcn::launch_env_step_loop(p, T, (hipStream_t)stream))
-        return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
-    for (int32_t t = 0; t < T; ++t) {
-        p.actions = actions + (size_t)t * E * 2;
-        const int r = mcn::launch_env_step(p, (hipStream_t)stream);
-        if (r != MCN_OK) return r;
-    }
-    return MCN_OK;
+    mcn::StepParams p;
+    const int rc = fill_step_params(p, tu, cfg, st, actions, nullptr, out, roll, E, N, 1);
+    if (rc != MCN_OK) return rc;
+    const mcn::RolloutPlan plan = mcn::plan_env_rollout(p, T, tu);
+    g_last_rollout_form = plan.form;
+    return run_rollout(p, plan, actions, T, (hipStream_t)stream);
 }
 
 int mcn_env_rollout_orca(const mcn_env_cfg *cfg, const mcn_env_state *st, double robot_safety_space,
@@ -340,15 +261,20 @@ int mcn_env_rollout_orca(const mcn_env_cfg *cfg, const mcn_env_state *st, double
     if (cfg->human_policy != MCN_HUMANS_ORCA && cfg->human_policy != MCN_HUMANS_LINEAR) return MCN_EINVAL;
     if (!st->rvpref) return MCN_EINVAL;                                         // the robot's max speed
     mcn::StepParams p;
-    const int rc = fill_step_params(p, cfg, st, nullptr, nullptr, out, roll, E, N, 1, false, false);
+    const int rc = fill_step_params(p, tuning(), cfg, st, nullptr, nullptr, out, roll, E, N, 1, false, false);
     if (rc != MCN_OK) return rc;
+    // line slots per lane: the larger of what a human's solve and the robot's solve (all N humans as candidates) can fill
+    const int rob_nl = max_neighbors < N ? max_neighbors : N;
+    if (rob_nl > p.nl_cap) p.nl_cap = rob_nl;
     mcn::ClosedLoop cl;
     memset(&cl, 0, sizeof(cl));
     cl.safety_space = robot_safety_space;       // added after the 0.01, in the reference's order (orca.py:100,103)
     cl.neighbor_dist = neighbor_dist; cl.time_horizon = time_horizon; cl.max_neighbors = max_neighbors;
     cl.tr_robot = tr_robot; cl.tr_humans = tr_humans; cl.tr_hrad = tr_hrad; cl.tr_action = tr_action;
     cl.tr_rec = tr_rec; cl.tr_human_act = tr_human_act;
-    return mcn::launch_env_step_loop_orca(p, cl, T, (hipStream_t)stream);
+    g_last_dispatch = mcn::family_name(mcn::kStepLoopOrca);
+    mcn::launch_env_step_loop_orca(p, cl, T, (hipStream_t)stream);
+    return launched();
 }
 
 // the model's parameters (include/mcn.h): A >= 0, B > 0, k >= 0, all finite
@@ -363,11 +289,12 @@ int mcn_env_step_sf(const mcn_env_cfg *cfg, double strength, double range, doubl
                     const mcn_rollout *roll, int32_t E, int32_t N, int32_t update, void *stream)
 {
     if (!sf_params_ok(strength, range, relaxation_rate)) return MCN_EINVAL;
+    const mcn_tuning tu = tuning();
     mcn::StepParams p;
-    const int rc = fill_step_params(p, cfg, st, actions, nullptr, out, roll, E, N, update, true);
+    const int rc = fill_step_params(p, tu, cfg, st, actions, nullptr, out, roll, E, N, update, true);
     if (rc != MCN_OK) return rc;
     p.sf_strength = strength; p.sf_range = range; p.sf_relaxation_rate = relaxation_rate;
-    return mcn::launch_env_step(p, (hipStream_t)stream);
+    return run_steps(p, mcn::plan_env_step(p, tu), actions, 1, (hipStream_t)stream);
 }
 
 int mcn_env_rollout_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
@@ -375,20 +302,12 @@ int mcn_env_rollout_sf(const mcn_env_cfg *cfg, double strength, double range, do
                        const mcn_rollout *roll, int32_t E, int32_t N, void *stream)
 {
     if (T <= 0 || !sf_params_ok(strength, range, relaxation_rate)) return MCN_EINVAL;
+    const mcn_tuning tu = tuning();
     mcn::StepParams p;
-    const int rc = fill_step_params(p, cfg, st, actions, nullptr, out, roll, E, N, 1, true);
+    const int rc = fill_step_params(p, tu, cfg, st, actions, nullptr, out, roll, E, N, 1, true);
     if (rc != MCN_OK) return rc;
     p.sf_strength = strength; p.sf_range = range; p.sf_relaxation_rate = relaxation_rate;
-    // latency-bound batch: the one-wavefront step kernel run T times inside one launch (env_step.hip:
-    // env_step_loop_sf_kernel); rollout_fused = 0 keeps the T launches
-    if (tuning().rollout_fused != 0 && T > 1 && mcn::launch_env_step_loop_sf(p, T, (hipStream_t)stream))
-        return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
-    for (int32_t t = 0; t < T; ++t) {
-        p.actions = actions + (size_t)t * E * 2;
-        const int r = mcn::launch_env_step(p, (hipStream_t)stream);
-        if (r != MCN_OK) return r;
-    }
-    return MCN_OK;
+    return run_rollout(p, mcn::plan_env_rollout(p, T, tu), actions, T, (hipStream_t)stream);
 }
 
 int mcn_scenario_pool(const mcn_scenario_cfg *cfg, uint64_t seed, int64_t first_case, int32_t P, int32_t N,

@@ -9,6 +9,7 @@
 #include <stdint.h>
 #include "../../include/mcn.h"
 #include "orca_device.hpp"
+#include "launch.hpp"
 
 namespace mcn {
 

@@ -14,11 +14,11 @@
 // index lines at run time without spilling to scratch.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "env_step_params.hpp"      // kMaxLines
 
 namespace mcn {
 
 constexpr float kRvoEps = 1e-5f;
-constexpr int kMaxLines = 10;
 
 // Lines of one lane in LDS, strided by the block size.
 struct LdsLines {

@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include "../../include/mcn.h"
 #include "lookahead_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
 

@@ -39,6 +39,7 @@
 #include <string.h>
 #include "../../include/mcn.h"
 #include "lookahead_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
 
@@ -50,8 +51,6 @@ __device__ __forceinline__ void split_after(const f32x4 (&t)[NT], X3 (&o)[NB])
 #pragma unroll
     for (int m = 0; m < NB; ++m) o[m] = split8(t[2 * m], 2 * m + 1 < NT ? t[2 * m + 1] : z);
 }
-
-bool tuning_sarl_x3();              // mcn_api.hip: mcn_tuning.sarl_x3 (-1 / 1: use the x3 fragments when given, 0: never)
 
 // tiles of 16 features
 constexpr int T13 = 1, T150 = 10, T100 = 7, T50 = 4, T56 = 5 /* pooled 4 + self 1 */, T1 = 1;
@@ -494,7 +493,6 @@ int launch_sarl(SarlParams &p, int32_t *best, double *best_val, double *action_o
     return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
 }
 
-// the argmax / epsilon-greedy kernel above for the other look-ahead kernels (lstm_rl_value.hip)
 int launch_sarl_argmax(const double *values, const double *rpos, const double *rgoal, const double *rrad, int E, int A,
                        int32_t *best, double *best_val, const double *actions, double *action_out, double epsilon,
                        unsigned long long seed, hipStream_t stream)

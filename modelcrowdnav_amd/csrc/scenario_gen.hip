@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "../../include/mcn.h"
 #include "env_common.hpp"
+#include "launch.hpp"
 
 namespace mcn {
 

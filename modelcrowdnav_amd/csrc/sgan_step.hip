@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include "../../include/mcn.h"
 #include "mfma_chain.hpp"
+#include "launch.hpp"
 
 namespace mcn {
 
