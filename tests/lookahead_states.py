@@ -101,6 +101,29 @@ def tie_env(rng, st, e):
         _place(st, e, N // 2, dy, dx)
 
 
+def tie_state_eighth_grid(rng, E, N, kinematics="holonomic"):
+    """random_state with tie_env in every 3rd env (robot as drawn, offsets on eighths).  tests/test_lookahead_edges_gpu.py."""
+    st = H.random_state(rng, E, N, randomize=True)
+    for e in range(0, E, 3):
+        tie_env(rng, st, e)
+    if kinematics == "unicycle":
+        st.rtheta[:] = rng.uniform(-np.pi, np.pi, E)
+    return st
+
+
+def tie_state_quarter_grid(rng, E, N):
+    """random_state with exact distance ties in every 3rd env: the robot on a quarter grid, humans mirrored through it,
+    duplicated, and one on the robot.  N >= 4.  tests/test_lstm_rl_gpu.py."""
+    st = H.random_state(rng, E, N, randomize=True)
+    for e in range(0, E, 3):
+        st.rpx[e], st.rpy[e] = rng.randint(-8, 9, 2) * 0.25
+        st.hpx[e, 0], st.hpy[e, 0] = st.rpx[e] + 0.625, st.rpy[e] - 1.25
+        st.hpx[e, 1], st.hpy[e, 1] = st.rpx[e] - 0.625, st.rpy[e] + 1.25       # mirrored through the robot
+        st.hpx[e, 2], st.hpy[e, 2] = st.hpx[e, 0], st.hpy[e, 0]                 # duplicate
+        st.hpx[e, N - 1], st.hpy[e, N - 1] = st.rpx[e], st.rpy[e]               # on the robot
+    return st
+
+
 # the env kinds of order_batch; "mid" is slot N // 2, "end" slot N - 1
 ORDER_KINDS = ("ties", "near-tie", "inf", "inf-tie", "nan-first", "nan-mid", "nan-end", "nan-first-and-end",
                "all-nan", "nan-robot", "nonfinite-beyond-hcount", "random")

@@ -38,19 +38,14 @@ RUNS = [("il_freeze", dict(imitation_learning=True, add_sim=False, random_epi=Tr
 
 def _setup(g, name, E, n_world=5, hip_world=False):
     import torch
-    from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.envs import VecModelCrowdSim
-    from modelcrowdnav_amd.policy.sarl import SARL
     from modelcrowdnav_amd.policy.world_model import MlpWorld, VecMlpWorld, VecTorchWorld, vec_world
     from modelcrowdnav_amd.utils.memory import ReplayMemory
     from modelcrowdnav_amd.utils.datagen import VecDataGen
+    from tests.lookahead_harness import policy, weights
     dev = torch.device("cuda", 0)
     env = H.make_vec_env(E, 5, cls=VecModelCrowdSim)
-    pol = SARL()
-    pol.configure(configs.policy_config())
-    pol.kinematics = "holonomic"
-    pol.model.load_state_dict({k[3:].replace("__", "."): torch.from_numpy(g[k]) for k in g.files if k.startswith("w__")})
-    pol.set_device(dev); pol.set_phase("val"); pol.time_step = 0.25
+    pol = policy("sarl", weights(g, "w__"), phase="val")
     env.robot.set_policy(pol)
     pol.set_env(env)
     world = MlpWorld(n_world)

@@ -13,19 +13,10 @@ pytestmark = pytest.mark.gpu
 from tests import helpers as H  # noqa: E402
 
 
-def _load(model, g, pref):
-    import torch
-    model.load_state_dict({k[len(pref):].replace("__", "."): torch.from_numpy(g[k]) for k in g.files if k.startswith(pref)})
-
-
 def _sarl(g, pref, dev, phase):
-    from modelcrowdnav_amd import configs
-    from modelcrowdnav_amd.policy.sarl import SARL
-    p = SARL()
-    p.configure(configs.policy_config())
-    p.kinematics = "holonomic"
-    _load(p.model, g, pref)
-    p.set_device(dev); p.set_phase(phase); p.time_step = 0.25
+    from tests.lookahead_harness import policy, weights
+    p = policy("sarl", weights(g, pref), phase=phase)
+    assert p.device == dev
     p.multiagent_training = True
     return p
 

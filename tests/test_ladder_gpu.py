@@ -16,6 +16,7 @@ pytestmark = pytest.mark.gpu
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
 from tests import ladder_states as LS  # noqa: E402
+from tests import lookahead_harness as L  # noqa: E402
 from tests.kernel_paths import (ROLLOUT_PATHS, SF_COMPILED_NS, SF_DEFAULT, SF_GENERIC_NS, SF_INERT, SF_TOL,  # noqa: E402
                                 STEP_EVENTS, STEP_KERNELS, UNICYCLE_EVENTS, forced_form, ladder_configs,
                                 rolled_wg4_battery, select_step_kernel, sf_ladder_reference, sf_oracle_step,
@@ -456,27 +457,12 @@ def test_wg4_rollout_on_rolled_ladder_batch(unicycle, tuning):
                        (0, 3, 4, T), check_first, check_last, "rolled ladder batch unicycle=%d" % unicycle)
 
 
-def _sarl(seed=0, zero=True):
-    import torch
-    from tests.test_sarl_gpu import _policy
-    pol = _policy(seed=seed)
-    if zero:
-        # V == 0.0 exactly: every parameter zero except attention.4.bias = 1, so that every score is 1, the attention
-        # weights are uniform and mlp2 / mlp3 give 0.  (With that bias zero too every score is exactly 0 and the masked
-        # softmax of sarl.py:52-53 is 0 / 0: NaN in the reference and in the kernel.)
-        with torch.no_grad():
-            for p_ in pol.model.parameters():
-                p_.zero_()
-            pol.model.attention[4].bias.fill_(1.0)
+def _lookahead_rewards_on_ladder_batches(body, what):
+    """A zeroed network (lookahead_harness.zeroed: V == 0.0 exactly) on the look-ahead blocks, N = 1..10, 13 and 32 (all
+    three MAXN variants of the LSTM-RL order): every value is cport.lookahead_reward bit for bit; the argmax goes on at
+    |robot - goal| == rr and returns -1 inside."""
+    pol = L.zeroed(L.policy(body, seed=0), body)
     pol.build_action_space(1.0)
-    return pol
-
-
-def test_sarl_lookahead_rewards_on_ladder_batches():
-    """mcn_sarl_predict with a network whose V is exactly 0 (_sarl): values are exactly the look-ahead reward, bitwise against
-    cport.lookahead_reward on the look-ahead blocks, N = 1..10, 13 and 32; the argmax goes on at |robot - goal| == rr and
-    returns -1 inside."""
-    pol = _sarl()
     table = pol._action_table
     total = {}
     for N in list(range(1, 11)) + list(GENERIC_NS):
@@ -487,15 +473,21 @@ def test_sarl_lookahead_rewards_on_ladder_batches():
         cport.ladder_counts(reset=True)
         ref = cport.lookahead_reward(st, table, 0.25)
         _add(total)
-        bad = H.bit_mismatch(values.cpu().numpy(), ref)
-        assert len(bad) == 0, (N, len(bad), _where(names, bad))
-        best = best.cpu().numpy()
+        values = values.cpu().numpy()
+        bad = H.bit_mismatch(values, ref)
+        assert len(bad) == 0, (body, N, len(bad), _where(names, bad))
+        best, actions = best.cpu().numpy(), actions.cpu().numpy()
         for e, name in enumerate(names):
-            if name == "la-at-goal":
-                assert best[e] == -1, (N, e)
-            elif name == "la-at-goal-edge":
-                assert best[e] == int(np.argmax(ref[e])), (N, e, best[e])
-    _assert_reached(total, LA_EVENTS, "mcn_sarl_predict")
+            if name in ("la-at-goal", "la-at-goal-edge"):       # (values == ref bitwise: best is ref's first maximum)
+                L.check_choice(values[e], best[e], actions[e], ref[e], table, name == "la-at-goal", what=(N, e))
+    _assert_reached(total, LA_EVENTS, what)
+
+
+def test_sarl_lookahead_rewards_on_ladder_batches():
+    """mcn_sarl_predict with a network whose V is exactly 0: values are exactly the look-ahead reward, bitwise against
+    cport.lookahead_reward on the look-ahead blocks, N = 1..10, 13 and 32; the argmax goes on at |robot - goal| == rr and
+    returns -1 inside."""
+    _lookahead_rewards_on_ladder_batches("sarl", "mcn_sarl_predict")
 
 
 @pytest.mark.parametrize("N", GENERIC_NS)
@@ -503,22 +495,20 @@ def test_sarl_predict_above_ten_humans_against_torch_reference(N):
     """N = 13 and 32 (mcn_sarl_predict takes N <= MCN_MAX_HUMANS = 32): a trained-size random network against
     pyref.sarl_predict at the suite's 1e-5 bar, on a few envs of the look-ahead batch."""
     from oracle import pyref
-    from tests.test_sarl_gpu import TOL
-    pol = _sarl(seed=3, zero=False)
+    pol = L.policy("sarl", seed=3)
+    pol.build_action_space(1.0)
     table = pol._action_table
     st, names = LS.lookahead_batch(N, table)
     env = H.make_vec_env(st.E, N)
     H.upload(env, st)
     actions, best, values = pol.predict_batch(env, want_values=True)
     values = values.cpu().numpy()
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
+    w = L.cpu_weights(pol)
     for e in range(0, st.E, 19):
         if names[e] == "la-at-goal":
             continue
-        row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
-        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
-        ref, idx = pyref.sarl_predict(w, row, hum, table)
-        np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="N=%d env %d (%s)" % (N, e, names[e]))
+        ref, idx = pyref.sarl_predict(w, L.self_row(st, e), L.humans(st, e), table)
+        np.testing.assert_allclose(values[e], ref, rtol=0, atol=L.TOL, err_msg="N=%d env %d (%s)" % (N, e, names[e]))
 
 
 @pytest.mark.parametrize("body", ["lstm_rl", "cadrl"])
@@ -526,32 +516,4 @@ def test_lstm_rl_and_cadrl_lookahead_rewards_on_ladder_batches(body):
     """lstm_rl_value.hip's reward ladder, as test_sarl_lookahead_rewards_on_ladder_batches: with a zeroed network V is
     exactly 0 (LSTM-RL: every gate 1/2, the cell state and h stay 0), so every value is the look-ahead reward bit for
     bit, N = 1..10, 13 and 32 (all three MAXN variants of the order)."""
-    import torch
-    if body == "lstm_rl":
-        from tests.test_lstm_rl_gpu import _policy
-    else:
-        from tests.test_cadrl_gpu import _policy
-    pol = _policy(seed=0)
-    with torch.no_grad():
-        for p_ in pol.model.parameters():
-            p_.zero_()
-    pol.build_action_space(1.0)
-    table = pol._action_table
-    total = {}
-    for N in list(range(1, 11)) + list(GENERIC_NS):
-        st, names = LS.lookahead_batch(N, table)
-        env = H.make_vec_env(st.E, N)
-        H.upload(env, st)
-        actions, best, values = pol.predict_batch(env, want_values=True)
-        cport.ladder_counts(reset=True)
-        ref = cport.lookahead_reward(st, table, 0.25)
-        _add(total)
-        bad = H.bit_mismatch(values.cpu().numpy(), ref)
-        assert len(bad) == 0, (body, N, len(bad), _where(names, bad))
-        best = best.cpu().numpy()
-        for e, name in enumerate(names):
-            if name == "la-at-goal":
-                assert best[e] == -1, (N, e)
-            elif name == "la-at-goal-edge":
-                assert best[e] == int(np.argmax(ref[e])), (N, e, best[e])
-    _assert_reached(total, LA_EVENTS, "mcn_%s_predict" % body)
+    _lookahead_rewards_on_ladder_batches(body, "mcn_%s_predict" % body)

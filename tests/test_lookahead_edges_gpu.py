@@ -18,91 +18,41 @@ pytestmark = pytest.mark.gpu
 
 from oracle import cport  # noqa: E402
 from tests import helpers as H  # noqa: E402
+from tests import lookahead_harness as L  # noqa: E402
 from tests import lookahead_states as LS  # noqa: E402
 from tests import policy_ref as R  # noqa: E402
+from tests.lookahead_harness import TOL, cpu_model, humans, reached, self_row  # noqa: E402
+from tests.lookahead_states import tie_state_eighth_grid as _tie_state  # noqa: E402
 
-TOL = 1e-5
 BODIES = ("lstm_rl", "cadrl")
 SHAPE_NS = (1, 2, 3, 7, 8, 9, 15, 16, 17, 31, 32)
 
 
-def _policy(body, seed, kinematics="holonomic", speeds=None, rotations=None):
-    if body == "lstm_rl":
-        from tests.test_lstm_rl_gpu import _policy as make
-    else:
-        from tests.test_cadrl_gpu import _policy as make
-    pol = make(seed=seed, kinematics=kinematics)
-    if speeds is not None:
-        pol.speed_samples, pol.rotation_samples = speeds, rotations
-        pol.action_space = None
-    return pol
-
-
-def _self_row(st, e):
-    return [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, st.rtheta[e]]
-
-
-def _hum(st, e):
-    return np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
-
-
-def _reached(st, e):
-    return float(np.linalg.norm((st.rpy[e] - st.rgy[e], st.rpx[e] - st.rgx[e]))) < st.rr[e]
-
-
-def _cpu_model(pol):
-    return copy.deepcopy(pol.model).cpu().float()
-
-
-def _tie_state(rng, E, N, kinematics="holonomic"):
-    st = H.random_state(rng, E, N, randomize=True)
-    for e in range(0, E, 3):
-        LS.tie_env(rng, st, e)
-    if kinematics == "unicycle":
-        st.rtheta[:] = rng.uniform(-np.pi, np.pi, E)
-    return st
-
-
 def _run(pol, st, kinematics="holonomic", hcount=None):
-    """predict_batch on st (hcount: numpy int32 [E] or None) -> numpy (actions, best, values, order or None)."""
-    import torch
-    env = H.make_vec_env(st.E, st.N, kinematics=kinematics)
-    H.upload(env, st)
-    hc = None if hcount is None else torch.from_numpy(np.ascontiguousarray(hcount, np.int32)).cuda()
-    actions, best, values = pol.predict_batch(env, want_values=True, hcount=hc)
-    torch.cuda.synchronize()
-    out = [actions.cpu().numpy().copy(), best.cpu().numpy().copy(), values.cpu().numpy().copy(), None]
-    if hasattr(pol, "human_order"):
-        order = pol.last_order.cpu().numpy().copy()
-        assert np.array_equal(pol.human_order(env, hc).cpu().numpy(), order)
-        out[3] = order
-    return out, env
+    """predict_batch on st (hcount: numpy int32 [E] or None) -> numpy (actions, best, values, order or None), env."""
+    out = L.run_predict_batch(pol, st, kinematics, hcount)
+    return [out.actions, out.best, out.values, out.order], out.env
 
 
-def _check_env(body, model, pol, st, e, values, best, order, kinematics="holonomic", count=None):
-    """values (and best, order) of env e against torch float32 on the first `count` humans, sorted for LSTM-RL."""
+def _check_env(body, model, pol, st, e, out, kinematics="holonomic", count=None):
+    """values, best, the action (and order) of env e of out = (actions, best, values, order) against torch float32 on
+    the first `count` humans, sorted for LSTM-RL."""
+    actions, best, values, order = out
     n = st.N if count is None else int(count)
-    hum = _hum(st, e)
+    hum = humans(st, e)
     if body == "lstm_rl":
-        want = R.stable_desc_order(_self_row(st, e), hum, n)
+        want = R.stable_desc_order(self_row(st, e), hum, n)
         assert order[e].tolist() == want.tolist(), (e, order[e], want)
         hum = hum[want[:n]]
     else:
         hum = hum[:n]
-    ref = R.policy_values(model, body, _self_row(st, e), hum, pol._action_table, kinematics)
-    np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="env %d" % e)
-    if _reached(st, e):
-        assert best[e] == -1
-    elif best is not None:
-        assert best[e] == int(np.argmax(values[e]))
-        top2 = np.sort(ref)[-2:]
-        if len(ref) == 1 or top2[1] - top2[0] > 2 * TOL:
-            assert best[e] == int(np.argmax(ref)), e
+    ref = R.policy_values(model, body, self_row(st, e), hum, pol._action_table, kinematics)
+    L.check_choice(values[e], best[e], actions[e], ref, pol._action_table, reached(st, e), what="env %d" % e)
     return ref
 
 
 def _sample(rng, E, k=8):
-    return sorted(set([0, E - 1] + rng.choice(E, min(k, E), replace=False).tolist()))
+    return L.sample_envs(rng, E, k)
 
 
 # ------------------------------------------------------------------------------------------------- shapes
@@ -113,16 +63,17 @@ def test_human_counts_across_the_kernel_variants(body, N):
     makes E x 81 = 2997 pairs, not a multiple of 16."""
     rng = np.random.RandomState(400 + N)
     E = 37
-    pol = _policy(body, seed=N)
+    pol = L.policy(body, seed=N)
     st = _tie_state(rng, E, N)
-    (actions, best, values, order), _ = _run(pol, st)
+    out, _ = _run(pol, st)
+    actions, best, values, order = out
     assert values.shape == (E, 81)
-    model = _cpu_model(pol)
+    model = cpu_model(pol)
     for e in _sample(rng, E):
-        _check_env(body, model, pol, st, e, values, best, order)
+        _check_env(body, model, pol, st, e, out)
     if body == "lstm_rl":                   # every env's order, not only the sampled ones
         for e in range(E):
-            assert order[e].tolist() == R.stable_desc_order(_self_row(st, e), _hum(st, e)).tolist(), e
+            assert order[e].tolist() == R.stable_desc_order(self_row(st, e), humans(st, e)).tolist(), e
 
 
 @pytest.mark.parametrize("N", [1, 9, 32])
@@ -130,12 +81,12 @@ def test_human_counts_across_the_kernel_variants(body, N):
 def test_unicycle_human_counts(body, N):
     rng = np.random.RandomState(500 + N)
     E = 21
-    pol = _policy(body, seed=40 + N, kinematics="unicycle")
+    pol = L.policy(body, seed=40 + N, kinematics="unicycle")
     st = _tie_state(rng, E, N, "unicycle")
-    (actions, best, values, order), _ = _run(pol, st, "unicycle")
-    model = _cpu_model(pol)
+    out, _ = _run(pol, st, "unicycle")
+    model = cpu_model(pol)
     for e in _sample(rng, E, 6):
-        _check_env(body, model, pol, st, e, values, best, order, "unicycle")
+        _check_env(body, model, pol, st, e, out, "unicycle")
 
 
 @pytest.mark.parametrize("speeds,rotations,E", [(1, 1, 21), (1, 1, 1), (3, 8, 21), (7, 12, 21), (3, 8, 1333)])
@@ -146,20 +97,19 @@ def test_other_action_tables_and_batch_sizes(body, speeds, rotations, E):
     grid, so a workgroup takes a second group."""
     rng = np.random.RandomState(speeds * 100 + rotations + E)
     N = 5
-    pol = _policy(body, seed=6, speeds=speeds, rotations=rotations)
+    pol = L.with_action_grid(L.policy(body, seed=6), speeds, rotations)
     st = _tie_state(rng, E, N)
-    (actions, best, values, order), _ = _run(pol, st)
+    out, _ = _run(pol, st)
+    actions, best, values, order = out
     A = speeds * rotations + 1
     table = pol._action_table
     assert table.shape == (A, 2) and values.shape == (E, A)
     if E * A > 256 * 128:
         assert ((E * A + 15) // 16 + 7) // 8 > 256
-    model = _cpu_model(pol)
+    model = cpu_model(pol)
     sample = _sample(rng, E) + ([E - 2, E - 16, E - 17] if E > 32 else [])
     for e in sorted(set(sample)):
-        _check_env(body, model, pol, st, e, values, best, order)
-        if best[e] >= 0:
-            assert tuple(actions[e]) == tuple(table[best[e]])
+        _check_env(body, model, pol, st, e, out)
 
 
 # ------------------------------------------------------------------------------------------------- float64
@@ -189,12 +139,12 @@ def test_network_error_against_a_float64_evaluation(body, N, weights):
     import torch
     rng = np.random.RandomState(600 + N)
     E = 48
-    pol = _policy(body, seed=70 + N)
+    pol = L.policy(body, seed=70 + N)
     if weights == "saturating":
         _saturate(pol, body)
     st = H.random_state(rng, E, N, randomize=True)
     (actions, best, values, order), _ = _run(pol, st)
-    m32 = _cpu_model(pol)
+    m32 = cpu_model(pol)
     m64 = copy.deepcopy(m32).double()
     table = pol._action_table
     rew = cport.lookahead_reward(st, table, 0.25)
@@ -202,10 +152,10 @@ def test_network_error_against_a_float64_evaluation(body, N, weights):
     err_k = err_t = 0.0
     cmax = 0.0
     for e in range(0, E, 3):
-        hum = _hum(st, e)
+        hum = humans(st, e)
         if body == "lstm_rl":
-            hum = hum[R.stable_desc_order(_self_row(st, e), hum)]
-        xr, _ = R.rotated_rows(_self_row(st, e), hum, table, "holonomic")
+            hum = hum[R.stable_desc_order(self_row(st, e), hum)]
+        xr, _ = R.rotated_rows(self_row(st, e), hum, table, "holonomic")
         truth = R.network_value(m64, body, xr.double()).numpy()
         v32 = R.network_value(m32, body, xr).double().numpy()
         if body == "lstm_rl":
@@ -231,19 +181,20 @@ def test_human_order_edges(N):
     rng = np.random.RandomState(700 + N)
     st, hc, names = LS.order_batch(N)
     assert len(LS.fused_unfused_disagreements(st)) > 0
-    pol = _policy("lstm_rl", seed=12)
-    (actions, best, values, order), _ = _run(pol, st, hcount=hc)
+    pol = L.policy("lstm_rl", seed=12)
+    out, _ = _run(pol, st, hcount=hc)
+    actions, best, values, order = out
     bad = []
     for e in range(st.E):
-        want = R.stable_desc_order(_self_row(st, e), _hum(st, e), int(hc[e]))
+        want = R.stable_desc_order(self_row(st, e), humans(st, e), int(hc[e]))
         if order[e].tolist() != want.tolist():
             bad.append((names[e], e, order[e].tolist(), want.tolist()))
     assert not bad, bad[:4]
     # values where every visible human is finite: against torch
-    model = _cpu_model(pol)
-    fin = [e for e in range(st.E) if np.isfinite(_hum(st, e)[:hc[e], :2]).all() and np.isfinite(st.rpx[e] + st.rpy[e])]
+    model = cpu_model(pol)
+    fin = [e for e in range(st.E) if np.isfinite(humans(st, e)[:hc[e], :2]).all() and np.isfinite(st.rpx[e] + st.rpy[e])]
     for e in [fin[i] for i in sorted(set(rng.choice(len(fin), 8, replace=False)))]:
-        _check_env("lstm_rl", model, pol, st, e, values, best, order, count=hc[e])
+        _check_env("lstm_rl", model, pol, st, e, out, count=hc[e])
 
 
 # ------------------------------------------------------------------------------------------------- features
@@ -253,18 +204,18 @@ def test_feature_edges(body, kinematics):
     """dg == 0 after the chosen action (cr = 1, sr = 0; unicycle: f_theta = nth - atan2(0, 0)), a propagated human on
     the robot's next position (feature 11 through sqrt_f32's guard), still humans: every value against torch."""
     N = 5
-    pol = _policy(body, seed=81, kinematics=kinematics)
+    pol = L.policy(body, seed=81, kinematics=kinematics)
     pol.build_action_space(1.0)
     st, names, act = LS.feature_batch(N, pol._action_table, kinematics)
-    (actions, best, values, order), _ = _run(pol, st, kinematics)
-    model = _cpu_model(pol)
+    out, _ = _run(pol, st, kinematics)
+    model = cpu_model(pol)
     for e in range(st.E):
-        _check_env(body, model, pol, st, e, values, best, order, kinematics)
-        xr, rew = R.rotated_rows(_self_row(st, e), _hum(st, e), pol._action_table, kinematics)
+        _check_env(body, model, pol, st, e, out, kinematics)
+        xr, rew = R.rotated_rows(self_row(st, e), humans(st, e), pol._action_table, kinematics)
         a = int(act[e])
         if names[e] == "on-goal":                # the edge is reached: dg == 0 for the chosen action
             assert (xr[a, :, 0] == 0).all(), e
-            assert _reached(st, e) == (a == 0), e
+            assert reached(st, e) == (a == 0), e
         elif names[e].startswith("human-on-next"):
             assert (xr[a, :, 11] == 0).any() and rew[a] == -0.25, e
         elif names[e] == "still-humans":
@@ -276,20 +227,21 @@ def test_feature_edges(body, kinematics):
 def test_nonfinite_humans_beyond_hcount_stay_out(body):
     rng = np.random.RandomState(90)
     E, N = 40, 7
-    pol = _policy(body, seed=13)
+    pol = L.policy(body, seed=13)
     base = _tie_state(rng, E, N)
     hc = rng.randint(1, N, E).astype(np.int32)
     st = LS.nonfinite_beyond(base, hc)
     assert not np.isfinite(st.hpx).all()
-    (actions, best, values, order), _ = _run(pol, st, hcount=hc)
+    out, _ = _run(pol, st, hcount=hc)
+    actions, best, values, order = out
     assert np.isfinite(values).all()
     (_, _, clean, clean_order), _ = _run(pol, base, hcount=hc)
     assert np.array_equal(values, clean)
     if order is not None:
         assert np.array_equal(order, clean_order)
-    model = _cpu_model(pol)
+    model = cpu_model(pol)
     for e in _sample(rng, E):
-        _check_env(body, model, pol, st, e, values, best, order, count=hc[e])
+        _check_env(body, model, pol, st, e, out, count=hc[e])
 
 
 @pytest.mark.parametrize("body", BODIES)
@@ -297,7 +249,7 @@ def test_hcount_is_clamped_to_one_and_n(body):
     """hcount 0 (and negative) behaves as 1, hcount N + 3 as N -- bit for bit, order included."""
     rng = np.random.RandomState(91)
     E, N = 24, 6
-    pol = _policy(body, seed=14)
+    pol = L.policy(body, seed=14)
     st = _tie_state(rng, E, N)
     run = lambda hc: _run(pol, st, hcount=np.asarray(hc, np.int32))[0]
     lo = run(np.where(np.arange(E) % 2, 0, -5))
@@ -308,9 +260,9 @@ def test_hcount_is_clamped_to_one_and_n(body):
         assert H.bits_equal(a[2], b[2]) and np.array_equal(a[1], b[1])
         if a[3] is not None:
             assert np.array_equal(a[3], b[3])
-    model = _cpu_model(pol)
+    model = cpu_model(pol)
     for e in _sample(rng, E, 4):
-        _check_env(body, model, pol, st, e, lo[2], lo[1], lo[3], count=1)
+        _check_env(body, model, pol, st, e, lo, count=1)
     if lo[3] is not None:
         assert (lo[3] == np.arange(N)).all()
 
@@ -319,14 +271,15 @@ def test_hcount_is_clamped_to_one_and_n(body):
 def test_hcount_at_thirty_two_humans(body):
     rng = np.random.RandomState(92)
     E, N = 40, 32
-    pol = _policy(body, seed=15)
+    pol = L.policy(body, seed=15)
     st = _tie_state(rng, E, N)
     hc = rng.randint(1, N + 1, E).astype(np.int32)
     hc[:4] = (1, 31, 32, 17)
-    (actions, best, values, order), _ = _run(pol, st, hcount=hc)
-    model = _cpu_model(pol)
+    out, _ = _run(pol, st, hcount=hc)
+    order = out[3]
+    model = cpu_model(pol)
     if order is not None:
         for e in range(E):
-            assert order[e].tolist() == R.stable_desc_order(_self_row(st, e), _hum(st, e), int(hc[e])).tolist(), e
+            assert order[e].tolist() == R.stable_desc_order(self_row(st, e), humans(st, e), int(hc[e])).tolist(), e
     for e in sorted(set([0, 1, 2, 3] + _sample(rng, E, 6))):
-        _check_env(body, model, pol, st, e, values, best, order, count=hc[e])
+        _check_env(body, model, pol, st, e, out, count=hc[e])

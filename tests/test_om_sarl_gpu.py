@@ -23,48 +23,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
+from tests import lookahead_harness as L  # noqa: E402
 from tests import om_ref  # noqa: E402
+from tests.lookahead_harness import TOL, cpu_weights, humans, reached, self_row  # noqa: E402
 
-TOL = 1e-5
 VEL_TOL = 2.4e-7
 # H.random_state seeds of the 4096-env batches, picked once on the CPU: no pre-floor coordinate of the next states
 # within the edge band (the expected count per batch is ~1e-3)
 BATCH_SEED = {5: 245, 10: 250}
-
-
-def _weights(g, prefix="w0__"):
-    import torch
-    return {k[len(prefix):].replace("__", "."): torch.from_numpy(g[k]) for k in g.files if k.startswith(prefix)}
-
-
-def _policy(weights=None, seed=None, kinematics="holonomic", phase="test", **over):
-    import torch
-    from modelcrowdnav_amd import configs
-    from modelcrowdnav_amd.policy.sarl import SARL
-    if seed is not None:
-        torch.manual_seed(seed)
-    p = SARL()
-    p.configure(configs.policy_config(**dict({"sarl.with_om": "true"}, **over)))
-    p.kinematics = kinematics
-    if weights is not None:
-        p.model.load_state_dict(weights)
-    p.set_device(torch.device("cuda", 0))
-    p.set_phase(phase)
-    p.time_step = 0.25
-    return p
-
-
-def _cpu_weights(pol, dtype=None):
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
-    return w if dtype is None else {k: v.to(dtype) for k, v in w.items()}
-
-
-def _self_row(st, e):
-    return [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, st.rtheta[e]]
-
-
-def _hum(st, e):
-    return np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
 
 
 def _hum4(st):
@@ -73,10 +39,6 @@ def _hum4(st):
 
 def _next4(st, dt=0.25):
     return np.stack([st.hpx + st.hvx * dt, st.hpy + st.hvy * dt, st.hvx, st.hvy], -1)
-
-
-def _reached(st, e):
-    return float(np.linalg.norm((st.rpy[e] - st.rgy[e], st.rpx[e] - st.rgx[e]))) < st.rr[e]
 
 
 def _prepare(pol, hum, dt=0.0, hcount=None, nexts=None):
@@ -119,7 +81,7 @@ def test_maps_match_reference_fixture(golden_dir):
     """build_occupancy_maps (one E = 1 launch) and the batched prepare against the reference's maps, generic and
     constructed states; the batched launch gives the bits of the E = 1 launch for the same humans."""
     g = np.load(os.path.join(golden_dir, "g24_om_sarl.npz"))
-    pol = _policy()
+    pol = L.policy("om_sarl")
     left_out = 0
     for N in (2, 5, 10):
         hums, want = g["om_in_N%d" % N], g["om_out_N%d" % N]
@@ -144,7 +106,7 @@ def test_every_cell_edge_from_both_sides():
     """Others displaced across every inner edge and the outer boundary of both axes by +-1e-6 (eight orders above libm
     noise), a generic half-cell offset along the other axis; a human with a generic velocity direction and a still one.
     The exact cell on both sides: the comparison directions and cell = 4 iy + ix."""
-    pol = _policy()
+    pol = L.policy("om_sarl")
     cases, want = [], []
     for vel in ((0.53, -0.71), (0.0, 0.0)):
         th = np.arctan2(vel[1], vel[0])
@@ -177,7 +139,7 @@ def test_every_cell_edge_from_both_sides():
 
 
 def test_non_finite_coordinates_fall_into_no_cell():
-    pol = _policy()
+    pol = L.policy("om_sarl")
     base = np.array([[0.0, 0.0, 1.0, 0.0], [0.5, 0.5, 0.1, 0.2], [-0.5, 0.25, 0.3, -0.2]])
     assert om_ref.edge_margin(base) > om_ref.EDGE_BAND
     good = _prepare(pol, base[None])[0]
@@ -193,57 +155,35 @@ def test_non_finite_coordinates_fall_into_no_cell():
 # ------------------------------------------------------------------------------------------------ 2. E = 1 predict
 @pytest.mark.parametrize("kin", ["holonomic", "unicycle"])
 def test_predict_matches_reference_fixture(kin, golden_dir):
-    from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
     g = np.load(os.path.join(golden_dir, "g24_om_sarl.npz"))
-    pol = _policy(_weights(g), kinematics=kin)
-    compared = 0
-    for N in (2, 5, 10):
-        key = "pred_%s_N%d_" % (kin, N)
-        for s in range(g[key + "self"].shape[0]):
-            assert om_ref.edge_margin(om_ref.next_humans(g[key + "humans"][s][:, :4])) > om_ref.EDGE_BAND
-            me = FullState(*g[key + "self"][s].tolist())
-            js = JointState(me, [ObservableState(*row) for row in g[key + "humans"][s].tolist()])
-            act = pol.predict(js)
-            want_vals, want_act = g[key + "values"][s], g[key + "action"][s]
-            if np.isnan(want_vals[0]):
-                assert tuple(act) == (0, 0)
-                continue
-            got = np.array(pol.action_values)
-            np.testing.assert_allclose(got, want_vals, rtol=0, atol=TOL)
-            compared += 1
-            top2 = np.sort(want_vals)[-2:]
-            if top2[1] - top2[0] > 2 * TOL:
-                assert np.allclose(tuple(act), want_act, rtol=0, atol=0), (N, s)
+
+    def each(pol, g, key, s, N, compared):
+        if compared:
             assert pol.get_attention_weights().shape == (N,)
+        else:
+            assert om_ref.edge_margin(om_ref.next_humans(g[key + "humans"][s][:, :4])) > om_ref.EDGE_BAND
+    compared = L.check_fixture_predictions("om_sarl", g, (2, 5, 10), "pred_{kin}_N{N}_", kin, seeds=(0,), each=each)
     assert compared > 60
 
 
 def test_train_phase_epsilon_and_last_state_match_reference(golden_dir):
     """epsilon 0.5 on numpy's global stream; last_state = [rotate | maps of the CURRENT states], [N, 61]."""
     import torch
-    from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
     g = np.load(os.path.join(golden_dir, "g24_om_sarl.npz"))
-    pol = _policy(_weights(g), phase="train")
-    pol.set_epsilon(0.5)
-    np.random.seed(2400 + int(g["eps_seed"]))
     for s in range(g["eps_selfs"].shape[0]):
         assert om_ref.edge_margin(g["eps_humans"][s][:, :4]) > om_ref.EDGE_BAND
-        me = FullState(*g["eps_selfs"][s].tolist())
-        js = JointState(me, [ObservableState(*row) for row in g["eps_humans"][s].tolist()])
-        pol.action_values = None
-        act = pol.predict(js)
-        np.testing.assert_allclose([act.vx, act.vy], g["eps_actions"][s], rtol=0, atol=1e-12)
-        if int(g["eps_explored"][s]) != 2:
-            want = torch.from_numpy(g["eps_last_states"][s])
-            assert tuple(pol.last_state.shape) == (5, 61)
-            torch.testing.assert_close(pol.last_state.cpu(), want, rtol=2e-6, atol=2e-6)
-            assert torch.equal(pol.last_state.cpu()[:, 13::3], want[:, 13::3])
+
+    def each(pol, s, want):
+        assert tuple(pol.last_state.shape) == (5, 61)
+        assert torch.equal(pol.last_state.cpu()[:, 13::3], want[:, 13::3])
+    L.check_epsilon_fixture("om_sarl", g, 0, 2400 + int(g["eps_seed"]), reset_values=True, each=each,
+                            keeps_last_state=lambda s: int(g["eps_explored"][s]) != 2)
     assert set(g["eps_explored"].tolist()) >= {0, 1}
 
 
 def test_one_human_raises_value_error():
     from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
-    pol = _policy(seed=1)
+    pol = L.policy("om_sarl", seed=1)
     one = [ObservableState(1.0, 1.0, 0.1, 0.2, 0.3)]
     js = JointState(FullState(0, 0, 0, 0, 0.3, 0, 4, 1.0, 0.0), one)
     for call in (lambda: pol.predict(js), lambda: pol.transform(js), lambda: pol.build_occupancy_maps(one)):
@@ -260,10 +200,9 @@ def test_predict_batch_at_benchmark_size(N, x3):
     rows and the E = 1 path's values are the batch's bits for the same env."""
     import torch
     from modelcrowdnav_amd import _hip
-    from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
     rng = np.random.RandomState(BATCH_SEED[N])
     E = 4096
-    pol = _policy(seed=3)
+    pol = L.policy("om_sarl", seed=3)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
     assert int((om_ref.edge_margin_batch(_next4(st)) <= om_ref.EDGE_BAND).sum()) == 0
@@ -275,27 +214,18 @@ def test_predict_batch_at_benchmark_size(N, x3):
         values, best, actions = values.cpu().numpy().copy(), best.cpu().numpy().copy(), actions.cpu().numpy().copy()
         rows = pol.transform_batch(env).cpu()
         assert tuple(rows.shape) == (E, N, 61)
-        w, table = _cpu_weights(pol), pol._action_table
-        sample = sorted(set([0, 1, 15, 16, 17, 2047, 2048, E - 2, E - 1] + rng.choice(E, 58, replace=False).tolist()))
+        w, table = cpu_weights(pol), pol._action_table
+        sample = L.sample_envs(rng, E, 58, always=(1, 15, 16, 17, 2047, 2048, E - 2))
         assert len(sample) >= 64
         for e in sample:
-            if _reached(st, e):
-                assert best[e] == -1 and tuple(actions[e]) == (0.0, 0.0)
-            ref = om_ref.values(w, _self_row(st, e), _hum(st, e), table, "holonomic")
-            np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="env %d" % e)
-            if best[e] >= 0:
-                assert best[e] == int(np.argmax(values[e]))
-                top2 = np.sort(ref)[-2:]
-                if top2[1] - top2[0] > 2 * TOL:
-                    assert best[e] == int(np.argmax(ref))
+            ref = om_ref.values(w, self_row(st, e), humans(st, e), table, "holonomic")
+            L.check_choice(values[e], best[e], actions[e], ref, table, reached(st, e), what="env %d" % e)
         for e in sample[:10]:
-            me = FullState(*_self_row(st, e))
-            js = JointState(me, [ObservableState(*row) for row in _hum(st, e).tolist()])
             pol.last_state = None
             pol.set_phase("train"); pol.set_epsilon(0.0)
-            pol.predict(js)
+            pol.predict(L.joint_state(self_row(st, e), humans(st, e)))
             pol.set_phase("test")
-            if not _reached(st, e):
+            if not reached(st, e):
                 assert np.array_equal(np.array(pol.action_values), values[e]), e            # same bits
                 assert torch.equal(pol.last_state.cpu(), rows[e]), e
                 # current states, not next ones
@@ -312,9 +242,9 @@ def test_network_error_against_a_float64_evaluation(weights, golden_dir):
     N, E = 5, 256
     rng = np.random.RandomState(11)
     if weights == "g24":
-        pol = _policy(_weights(np.load(os.path.join(golden_dir, "g24_om_sarl.npz"))))
+        pol = L.policy("om_sarl", L.weights(np.load(os.path.join(golden_dir, "g24_om_sarl.npz")), "w0__"))
     else:
-        pol = _policy(seed=9)
+        pol = L.policy("om_sarl", seed=9)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
     assert int((om_ref.edge_margin_batch(_next4(st)) <= om_ref.EDGE_BAND).sum()) == 0
@@ -325,13 +255,13 @@ def test_network_error_against_a_float64_evaluation(weights, golden_dir):
             _, _, v = pol.predict_batch(env, want_values=True)
             got[name] = v.cpu().numpy().copy()
     assert not np.array_equal(got["x3"], got["f32_mfma"]), "the two layer forms should not be the same kernel"
-    w32, w64 = _cpu_weights(pol), _cpu_weights(pol, torch.float64)
+    w32, w64 = cpu_weights(pol), cpu_weights(pol, torch.float64)
     table, disc = pol._action_table, 0.9 ** 0.25
     err = dict(x3=0.0, f32_mfma=0.0, torch_f32=0.0)
     for e in range(0, E, 8):
-        if _reached(st, e):
+        if reached(st, e):
             continue
-        x, rew = om_ref.rows61(_self_row(st, e), _hum(st, e), table, "holonomic")
+        x, rew = om_ref.rows61(self_row(st, e), humans(st, e), table, "holonomic")
         rew = np.array(rew, np.float64)
         with torch.no_grad():
             from oracle import pyref
@@ -353,7 +283,7 @@ def test_hcount_masks_maps_and_humans():
     import torch
     rng = np.random.RandomState(7)
     E, N = 300, 6
-    pol = _policy(seed=5)
+    pol = L.policy("om_sarl", seed=5)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
     hcn = rng.randint(1, N + 1, E).astype(np.int32)
@@ -366,7 +296,7 @@ def test_hcount_masks_maps_and_humans():
     _, _, values = pol.predict_batch(env, want_values=True, hcount=hc)
     values = values.cpu().numpy().copy()
     om = pol._bufs["om"].cpu().numpy().copy()
-    w = _cpu_weights(pol)
+    w = cpu_weights(pol)
     for e in list(range(6)) + list(range(6, E, 7)):
         n = int(seen[e])
         want = om_ref.maps(_next4(st)[e], count=n)
@@ -374,14 +304,14 @@ def test_hcount_masks_maps_and_humans():
         assert not om[e, n:].any()
         if n == 1:
             assert not om[e].any()
-        if _reached(st, e):
+        if reached(st, e):
             continue
         if n >= 2:
-            ref = om_ref.values(w, _self_row(st, e), _hum(st, e)[:n], pol._action_table, "holonomic")
+            ref = om_ref.values(w, self_row(st, e), humans(st, e)[:n], pol._action_table, "holonomic")
         else:       # the reference has no answer for a lone human: the zero map is this build's rule (include/mcn.h)
             from tests import policy_ref as R
             from oracle import pyref
-            xr, rew = R.rotated_rows(_self_row(st, e), _hum(st, e)[:1], pol._action_table, "holonomic")
+            xr, rew = R.rotated_rows(self_row(st, e), humans(st, e)[:1], pol._action_table, "holonomic")
             x = torch.cat([xr, torch.zeros(xr.shape[0], 1, 48)], 2)
             with torch.no_grad():
                 ref = np.array(rew) + 0.9 ** 0.25 * pyref.sarl_forward(w, x)[0].double().numpy()
@@ -403,7 +333,7 @@ def test_query_env_builds_the_maps_from_the_envs_next_states():
     import torch
     rng = np.random.RandomState(31)
     E, N = 64, 5
-    pol = _policy(seed=9)
+    pol = L.policy("om_sarl", seed=9)
     pol.query_env = True
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
@@ -417,12 +347,12 @@ def test_query_env_builds_the_maps_from_the_envs_next_states():
     _, _, values = pol.predict_batch(env, want_values=True)
     values = values.cpu().numpy()
     om = pol._bufs["om"].cpu().numpy()
-    w = _cpu_weights(pol)
+    w = cpu_weights(pol)
     moved = 0
     for e in range(0, E, 3):
         _assert_maps(om[e], om_ref.maps(nexts[e]), "env %d" % e)
         moved += int(not np.array_equal(om_ref.maps(nexts[e]), om_ref.maps(_next4(st)[e])))
-        ref = om_ref.values(w, _self_row(st, e), _hum(st, e), pol._action_table, "holonomic", nexts=nexts[e],
+        ref = om_ref.values(w, self_row(st, e), humans(st, e), pol._action_table, "holonomic", nexts=nexts[e],
                             rewards=rew[e])
         np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL)
     assert moved > 0, "the env's next states should differ from constant-velocity ones somewhere"
@@ -437,49 +367,28 @@ def test_pair_counts(E, speeds, rotations, kin):
     import torch
     N = 4
     rng = np.random.RandomState(100 + E)
-    pol = _policy(seed=6, kinematics=kin)
+    pol = L.policy("om_sarl", seed=6, kinematics=kin)
     pol.speed_samples, pol.rotation_samples = speeds, rotations
     env = H.make_vec_env(E, N, kinematics=kin)
     st = H.random_state(rng, E, N, randomize=True)
     st.rtheta[:] = rng.uniform(-np.pi, np.pi, E) if kin == "unicycle" else 0.0
     assert int((om_ref.edge_margin_batch(_next4(st)) <= om_ref.EDGE_BAND).sum()) == 0
     H.upload(env, st)
-    _, best, values = pol.predict_batch(env, want_values=True)
-    values, best = values.cpu().numpy(), best.cpu().numpy()
+    actions, best, values = pol.predict_batch(env, want_values=True)
+    values, best, actions = values.cpu().numpy(), best.cpu().numpy(), actions.cpu().numpy()
     A = 1 + speeds * rotations
     assert values.shape == (E, A)
-    w = _cpu_weights(pol)
+    w = cpu_weights(pol)
     for e in (range(E) if E <= 37 else [0, 1, 2, 3, 4, E - 1] + list(range(5, E, 29))):
-        ref = om_ref.values(w, _self_row(st, e), _hum(st, e), pol._action_table, kin)
-        np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="env %d" % e)
-        if best[e] >= 0:
-            assert best[e] == int(np.argmax(values[e]))
+        ref = om_ref.values(w, self_row(st, e), humans(st, e), pol._action_table, kin)
+        L.check_choice(values[e], best[e], actions[e], ref, pol._action_table, reached(st, e), what="env %d" % e)
 
 
 # ------------------------------------------------------------------------------------------------ 8. callers
 def test_explorer_batched_equals_sequential():
     """Explorer.run_k_episodes(64, 'test') with an OM-SARL robot goes to the batched VecExplorer and reports what the
     sequential E = 1 loop reports."""
-    import torch
-    from modelcrowdnav_amd import configs
-    from modelcrowdnav_amd.envs import CrowdSim
-    from modelcrowdnav_amd.envs.utils.robot import Robot
-    from modelcrowdnav_amd.utils.explorer import Explorer
-    res = []
-    for batched in (True, False):
-        cfg = configs.env_config(**{"sim.human_num": 5})
-        env = CrowdSim()
-        env.configure(cfg)
-        robot = Robot(cfg, "robot")
-        robot.set_policy(_policy(seed=11))
-        env.set_robot(robot)
-        ex = Explorer(env, robot, torch.device("cuda", 0), gamma=0.9)
-        ex.batched = batched
-        res.append(ex.run_k_episodes(64, "test", returnNav=True))
-        assert ex.last_run_batched == batched
-    a, b = res
-    assert tuple(a[1:4]) == tuple(b[1:4]), (a, b)
-    assert abs(a[4] - b[4]) < 1e-9 and abs(a[0] - b[0]) < 1e-9, (a, b)
+    L.check_explorer_batched_equals_sequential("om_sarl")
 
 
 def test_update_memory_stores_61_wide_rows():
@@ -493,7 +402,7 @@ def test_update_memory_stores_61_wide_rows():
     E, N = 16, 5
     env = H.make_vec_env(E, N)
     env.track_human_times = False; env.export_human_actions = False
-    om_sarl = _policy(seed=0, phase="train")
+    om_sarl = L.policy("om_sarl", seed=0, phase="train")
     om_sarl.time_step = env.time_step
     mem = ReplayMemory(20000, device=dev)
     orca = policy_factory["orca"]()
@@ -512,33 +421,17 @@ def test_update_memory_stores_61_wide_rows():
 def test_trainer_step_changes_weights_and_next_predict_uses_them():
     """An optimizer step re-packs both halves of mlp1.0 (columns 0..12 and the map fragment + bias)."""
     import torch
-    from modelcrowdnav_amd.utils.memory import ReplayMemory
-    from modelcrowdnav_amd.utils.trainer import Trainer
-    rng = np.random.RandomState(17)
-    E, N = 128, 5
-    pol = _policy(seed=21)
-    env = H.make_vec_env(E, N)
-    st = H.random_state(rng, E, N, randomize=True)
-    assert int((om_ref.edge_margin_batch(_next4(st)) <= om_ref.EDGE_BAND).sum()) == 0
-    H.upload(env, st)
-    mem = ReplayMemory(1000, device=torch.device("cuda", 0))
-    rows = pol.transform_batch(env)
-    assert tuple(rows.shape) == (E, N, 61)
-    for e in range(E):
-        mem.push((rows[e], torch.tensor([rng.uniform(-1, 1)], dtype=torch.float32, device=rows.device)))
-    before = {k: v.clone() for k, v in pol.model.state_dict().items()}
-    _, _, v0 = pol.predict_batch(env, want_values=True)
-    v0 = v0.cpu().numpy().copy()
-    tr = Trainer(pol.model, mem, torch.device("cuda", 0), batch_size=32)
-    tr.set_learning_rate(0.01)
-    tr.optimize_batch(4)
-    after = pol.model.state_dict()
-    assert not torch.equal(before["mlp1.0.weight"][:, 13:], after["mlp1.0.weight"][:, 13:])
-    assert not torch.equal(before["mlp1.0.bias"], after["mlp1.0.bias"])
-    _, _, v1 = pol.predict_batch(env, want_values=True)
-    v1 = v1.cpu().numpy()
-    assert not np.array_equal(v0, v1)
-    w = _cpu_weights(pol)
-    for e in range(0, E, 16):
-        ref = om_ref.values(w, _self_row(st, e), _hum(st, e), pol._action_table, "holonomic")
-        np.testing.assert_allclose(v1[e], ref, rtol=0, atol=TOL)
+
+    def check_inputs(st, rows):
+        assert int((om_ref.edge_margin_batch(_next4(st)) <= om_ref.EDGE_BAND).sum()) == 0
+        assert tuple(rows.shape) == (st.E, st.N, 61)
+
+    def check_changed(before, after):
+        assert not torch.equal(before["mlp1.0.weight"][:, 13:], after["mlp1.0.weight"][:, 13:])
+        assert not torch.equal(before["mlp1.0.bias"], after["mlp1.0.bias"])
+
+    def reference(pol):
+        w = cpu_weights(pol)
+        return lambda st, e: om_ref.values(w, self_row(st, e), humans(st, e), pol._action_table, "holonomic")
+    L.check_trainer_step_is_seen("om_sarl", reference, randomize=True, check_inputs=check_inputs,
+                                 check_changed=check_changed)

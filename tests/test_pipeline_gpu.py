@@ -15,15 +15,14 @@ from tests import helpers as H  # noqa: E402
 
 def test_recorded_data_to_value_network(golden_dir, tmp_path):
     import torch
-    from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.envs import VecModelCrowdSim
-    from modelcrowdnav_amd.policy.sarl import SARL
     from modelcrowdnav_amd.policy.world_model import MlpWorld, VecMlpWorld, vec_world
     from modelcrowdnav_amd.utils import realdata
     from modelcrowdnav_amd.utils.datagen import VecDataGen
     from modelcrowdnav_amd.utils.memory import ReplayMemory
     from modelcrowdnav_amd.utils.trainer import Trainer
     from modelcrowdnav_amd.utils.trainer_sim import Trainer_Sim
+    from tests.lookahead_harness import policy
     dev = torch.device("cuda", 0)
     torch.manual_seed(0); random.seed(0)
     data = realdata.get_real_data(os.path.join(golden_dir, "g9_scenes.ndjson"), phase="test", stride=1, windows_size=12,
@@ -50,8 +49,8 @@ def test_recorded_data_to_value_network(golden_dir, tmp_path):
     assert l1 <= l0 and world.mse == l1
 
     env = H.make_vec_env(16, n_h - 1, cls=VecModelCrowdSim)
-    pol = SARL(); pol.configure(configs.policy_config()); pol.kinematics = "holonomic"
-    pol.set_device(dev); pol.set_phase("train"); pol.set_epsilon(0.1); pol.time_step = 0.25
+    pol = policy("sarl", phase="train")            # (no seed: the stream goes on from the world model's draws)
+    pol.set_epsilon(0.1)
     env.robot.set_policy(pol); pol.set_env(env)
     env.sim_world = vec_world(world.eval(), env)          # the HIP kernel (mcn_mlp_world_step)
     assert isinstance(env.sim_world, VecMlpWorld)

@@ -408,10 +408,9 @@ def test_model_crowd_sim_with_sgan_world(golden_dir):
     """BASELINE config 4 shape (reduced E): VecModelCrowdSim + VecSGANWorld + SARL robot; the env must move the
     humans exactly by the world model's velocities, and the E = 1 ModelCrowdSim view must agree with env 0."""
     import torch
-    from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.envs import VecModelCrowdSim
     from modelcrowdnav_amd.policy.world_model import VecSGANWorld, generator_from_arrays
-    from modelcrowdnav_amd.policy.sarl import SARL
+    from tests.lookahead_harness import policy
     dev = torch.device("cuda", 0)
     E, N = 64, 10
     env = H.make_vec_env(E, N, cls=VecModelCrowdSim)
@@ -421,9 +420,8 @@ def test_model_crowd_sim_with_sgan_world(golden_dir):
     world = VecSGANWorld(gen, E, N, dev, time_step=env.time_step, seed=0)
     world.init_constant_velocity(env.hpos, env.hvel)
     env.sim_world = world
-    torch.manual_seed(0)
-    pol = SARL(); pol.configure(configs.policy_config()); pol.kinematics = "holonomic"
-    pol.set_device(dev); pol.set_phase("test"); pol.time_step = env.time_step
+    pol = policy("sarl", seed=0)
+    pol.time_step = env.time_step
     for t in range(12):
         before = env.hpos.clone()
         actions, _ = pol.predict_batch(env)
@@ -485,18 +483,16 @@ def test_update_memory_value_targets(il):
     """Batched update_memory (imitation learning with the ORCA robot / RL with SARL and a target network)
     against the reference's per-episode formulae evaluated on the recorded traces."""
     import torch
-    from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
-    from modelcrowdnav_amd.policy.sarl import SARL
     from modelcrowdnav_amd.rollout import VecExplorer
     from modelcrowdnav_amd.utils.memory import ReplayMemory
+    from tests.lookahead_harness import policy
     dev = torch.device("cuda", 0)
     E, N, k = 16, 5, 16
     env = H.make_vec_env(E, N)
     env.track_human_times = False; env.export_human_actions = False
-    torch.manual_seed(0)
-    sarl = SARL(); sarl.configure(configs.policy_config()); sarl.kinematics = "holonomic"
-    sarl.set_device(dev); sarl.set_phase("train"); sarl.time_step = env.time_step
+    sarl = policy("sarl", seed=0, phase="train")
+    sarl.time_step = env.time_step
     mem = ReplayMemory(20000, device=dev)
     if il:
         orca = policy_factory["orca"]()

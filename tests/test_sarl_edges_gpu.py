@@ -11,7 +11,7 @@
 
 The reference everywhere is torch on the CPU (oracle/pyref through tests/sarl_states.reference): float32 for parity,
 float64 on the same float32 features as the yardstick.  Bar: 1e-5 absolute on values and attention weights
-(BASELINE.json north_star, TOL of tests/test_sarl_gpu.py).  Both variants of the kernel run every case: the bf16x3
+(BASELINE.json north_star, TOL of tests/lookahead_harness.py).  Both variants of the kernel run every case: the bf16x3
 layers (mcn_tuning.sarl_x3 = 1, the default) and the float32 MFMA layers (0)."""
 import numpy as np
 import pytest
@@ -19,80 +19,33 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from tests import helpers as H  # noqa: E402
+from tests import lookahead_harness as L  # noqa: E402
 from tests import sarl_states as S  # noqa: E402
+from tests.lookahead_harness import SENTINEL, TOL, run_lookahead as _run  # noqa: E402
 
-TOL = 1e-5
 X3 = pytest.mark.parametrize("x3", [1, 0], ids=["bf16x3", "f32mfma"])
-SENTINEL = 12345.0
 
 
 def _policy(w, kinematics="holonomic", table=None):
-    from tests.test_sarl_gpu import _policy as make
-    pol = make(weights=w)
-    pol.kinematics = kinematics
+    pol = L.policy("sarl", weights=w, kinematics=kinematics)
     pol.build_action_space(1.0)
-    if table is not None:
-        _set_table(pol, table)
-    return pol
+    return pol if table is None else L.with_table(pol, table)
 
 
-def _set_table(pol, table):
-    from modelcrowdnav_amd.envs.utils.action import ActionRot, ActionXY
-    make = ActionXY if pol.kinematics == "holonomic" else ActionRot
-    pol._action_table = np.ascontiguousarray(table, np.float64)
-    pol.action_space = [make(*row) for row in pol._action_table.tolist()]
-    pol._bufs = {}
-
-
-def _run(pol, st, x3, hcount=None, env_next=None, epsilon=0.0):
-    """One look-ahead of `pol` on the oracle EnvState st -> numpy dict (values [E,A], best, best_val, actions [E,2],
-    att [E,A,N]).  The launch is repeated on output buffers filled with a sentinel, so whatever the second launch does
-    not write shows."""
-    import torch
-    from modelcrowdnav_amd import _hip
-    env = H.make_vec_env(st.E, st.N, kinematics=pol.kinematics)
-    H.upload(env, st)
-    stt = env._st
-    if hcount is not None:
-        hc = torch.from_numpy(np.ascontiguousarray(hcount, np.int32)).to(env.device)
-        stt = _hip.EnvState.from_buffer_copy(env._st)
-        stt.hcount = _hip.ptr(hc)
-    nxt = None
-    if env_next is not None:
-        nxt = tuple(torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(env.device) for a in env_next)
-    pol._v_pref = 1.0
-    with _hip.tuned(sarl_x3=x3):
-        for rep in range(2):
-            values, best, best_val, att = pol._lookahead(stt, st.E, st.N, env.device, want_attention=True, env_next=nxt,
-                                                         epsilon=epsilon)
-            if rep == 0:
-                torch.cuda.synchronize()
-                values.fill_(SENTINEL); best_val.fill_(SENTINEL); att.fill_(SENTINEL)
-                best.fill_(-77); pol._bufs["action"].fill_(SENTINEL)
-        torch.cuda.synchronize()
-    out = dict(values=values, best=best, best_val=best_val, att=att, actions=pol._bufs["action"])
-    return {k: v.cpu().numpy().copy() for k, v in out.items()}
-
-
-def _check_argmax(out, e, table, reached=False):
-    """best / best_val / the action row of env e against the strict-'>' scan of the kernel's own values."""
-    idx, top = S.scan_argmax(out["values"][e])
-    if reached:
-        assert out["best"][e] == -1 and tuple(out["actions"][e]) == (0.0, 0.0), e
-        return
-    assert out["best"][e] == idx, (e, out["best"][e], idx)
-    H.assert_bits_equal(out["best_val"][e], top, "best_val of env %d" % e)
-    want = table[idx] if idx >= 0 else (0.0, 0.0)
-    assert tuple(out["actions"][e]) == tuple(want), (e, idx)
+def _check_argmax(out, e, table, reached=False, ref=None):
+    """best and the action row of env e by L.check_choice (against ref [A] too where given), best_val against the
+    strict-'>' scan of the kernel's own values."""
+    L.check_choice(out["values"][e], out["best"][e], out["actions"][e], ref, table, reached, what="env %d" % e)
+    if not reached:
+        H.assert_bits_equal(out["best_val"][e], S.scan_argmax(out["values"][e])[1], "best_val of env %d" % e)
 
 
 def _check_finite_env(out, ref, e, table, what="", att_tol=TOL):
-    np.testing.assert_allclose(out["values"][e], ref["values"], rtol=0, atol=TOL, err_msg="%s env %d" % (what, e))
     n = ref["att"].shape[1]
     np.testing.assert_allclose(out["att"][e][:, :n], ref["att"], rtol=0, atol=att_tol, err_msg="%s env %d attention" % (what, e))
     assert np.all(out["att"][e][:, n:] == 0.0), (what, e)
     assert np.all(np.abs(out["att"][e].sum(1) - 1.0) < TOL), (what, e)
-    _check_argmax(out, e, table)
+    _check_argmax(out, e, table, ref=ref["values"])
 
 
 def _check_nan_env(out, ref, e):
@@ -365,7 +318,7 @@ def test_more_than_one_round_of_the_persistent_grid(N, x3):
     assert np.isfinite(out["values"]).all() and np.abs(out["values"]).max() < 100
     assert (out["att"] != SENTINEL).all() and (out["best"] >= 0).all()
     rng = np.random.RandomState(N)
-    for e in sorted(set([0, 1, E - 3, E - 2, E - 1] + rng.choice(E, 6, replace=False).tolist())):
+    for e in L.sample_envs(rng, E, 6, always=(1, E - 3, E - 2)):
         _check_finite_env(out, S.reference(w, st, e, table), e, table, "E %d N %d" % (E, N))
 
 

@@ -13,85 +13,31 @@ pytestmark = pytest.mark.gpu
 
 from oracle import pyref  # noqa: E402
 from tests import helpers as H  # noqa: E402
-
-TOL = 1e-5
-
-
-def _policy(weights=None, seed=None):
-    import torch
-    from modelcrowdnav_amd import configs
-    from modelcrowdnav_amd.policy.sarl import SARL
-    if seed is not None:
-        torch.manual_seed(seed)
-    p = SARL()
-    p.configure(configs.policy_config())
-    p.kinematics = "holonomic"
-    if weights is not None:
-        p.model.load_state_dict(weights)
-    p.set_device(torch.device("cuda", 0))
-    p.set_phase("test")
-    p.time_step = 0.25
-    return p
-
-
-def _weights(g, prefix):
-    import torch
-    return {k[len(prefix):].replace("__", "."): torch.from_numpy(g[k]) for k in g.files if k.startswith(prefix)}
+from tests import lookahead_harness as L  # noqa: E402
+from tests.lookahead_harness import TOL, cpu_weights, humans, reached, self_row  # noqa: E402
 
 
 def test_predict_matches_reference_fixture(golden_dir):
     """SARL.predict(JointState) against action_values / chosen action recorded from the real reference."""
-    from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
     g = np.load(os.path.join(golden_dir, "g5_sarl.npz"))
-    for seed in (0, 1):
-        pol = _policy(_weights(g, "w%d__" % seed))
-        for N in (5, 10):
-            key = "pred%d_N%d_" % (seed, N)
-            for s in range(g[key + "self"].shape[0]):
-                me = FullState(*g[key + "self"][s].tolist())
-                hs = [ObservableState(*row) for row in g[key + "humans"][s].tolist()]
-                act = pol.predict(JointState(me, hs))
-                want_vals, want_act = g[key + "values"][s], g[key + "action"][s]
-                if np.isnan(want_vals[0]):
-                    assert tuple(act) == (0, 0)
-                    continue
-                got = np.array(pol.action_values)
-                np.testing.assert_allclose(got, want_vals, rtol=0, atol=TOL)
-                top2 = np.sort(want_vals)[-2:]
-                if top2[1] - top2[0] > 2 * TOL:
-                    assert tuple(act) == tuple(want_act), (seed, N, s)
+    L.check_fixture_predictions("sarl", g, (5, 10), "pred{seed}_N{N}_")
 
 
 @pytest.mark.parametrize("N", [5, 10, 1, 3])
 def test_predict_batch_matches_oracle(N):
     """predict_batch over a VecCrowdSim against the torch-fp32 restatement, env by env."""
-    import torch
     rng = np.random.RandomState(N)
     E = 37          # ragged vs the 16-pair wave tile
-    pol = _policy(seed=3)
-    env = H.make_vec_env(E, N)
+    pol = L.policy("sarl", seed=3)
     st = H.random_state(rng, E, N, randomize=True)
     st.rgx[0], st.rgy[0] = st.rpx[0] + 0.05, st.rpy[0] - 0.05        # env 0: robot already at its goal
-    H.upload(env, st)
-    actions, best, values = pol.predict_batch(env, want_values=True)
-    torch.cuda.synchronize()
-    values, best, actions = values.cpu().numpy(), best.cpu().numpy(), actions.cpu().numpy()
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
-    table = pol._action_table
-    assert best[0] == -1 and tuple(actions[0]) == (0.0, 0.0)
+    out = L.run_predict_batch(pol, st)
+    w, table = cpu_weights(pol), pol._action_table
+    assert out.best[0] == -1 and tuple(out.actions[0]) == (0.0, 0.0)
     for e in range(1, E, 3):
-        self_row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
-        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
-        ref, idx = pyref.sarl_predict(w, self_row, hum, table)
-        np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL)
-        top2 = np.sort(ref)[-2:]
-        reached = float(np.linalg.norm((st.rpy[e] - st.rgy[e], st.rpx[e] - st.rgx[e]))) < st.rr[e]
-        if reached:                       # policy.py:43-49 short cut: zero action, nothing evaluated
-            assert best[e] == -1 and tuple(actions[e]) == (0.0, 0.0)
-            continue
-        assert best[e] == int(np.argmax(values[e]))       # first-max-wins on the device's own values
-        if top2[1] - top2[0] > 2 * TOL:
-            assert best[e] == idx and tuple(actions[e]) == tuple(table[idx])
+        ref, idx = pyref.sarl_predict(w, self_row(st, e), humans(st, e), table)
+        # (a robot on its goal: policy.py:43-49 short cut, zero action)
+        L.check_choice(out.values[e], out.best[e], out.actions[e], ref, table, reached(st, e), what=e)
 
 
 @pytest.mark.parametrize("N", [5, 10])
@@ -99,35 +45,21 @@ def test_predict_batch_at_benchmark_size_matches_oracle(N):
     """The grids bench.py times (BASELINE configs 3 / 4: 4096 envs x 81 actions = 20 736 16-pair tiles, ten rounds
     of the resident workgroups): 64 sampled envs -- first, last, the tile-straddling ones and a random spread --
     against the torch-fp32 restatement (multi_human_rl.py:35-63, sarl.py:28-65)."""
-    import torch
     rng = np.random.RandomState(40 + N)
     E = 4096
-    pol = _policy(seed=3)
-    env = H.make_vec_env(E, N)
+    pol = L.policy("sarl", seed=3)
     st = H.random_state(rng, E, N, randomize=True)
-    H.upload(env, st)
-    actions, best, values = pol.predict_batch(env, want_values=True)
-    torch.cuda.synchronize()
-    values, best, actions = values.cpu().numpy(), best.cpu().numpy(), actions.cpu().numpy()
+    out = L.run_predict_batch(pol, st)
+    values, best, actions = out.values, out.best, out.actions
     assert values.shape == (E, 81) and np.isfinite(values).all()
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
-    table = pol._action_table
-    sample = sorted(set([0, 1, 15, 16, 2047, 2048, E - 2, E - 1] + rng.choice(E, 56, replace=False).tolist()))
+    w, table = cpu_weights(pol), pol._action_table
+    sample = L.sample_envs(rng, E, 56, always=(1, 15, 16, 2047, 2048, E - 2))
     worst = 0.0
     for e in sample:
-        row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
-        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
-        reached = float(np.linalg.norm((st.rpy[e] - st.rgy[e], st.rpx[e] - st.rgx[e]))) < st.rr[e]
-        if reached:
-            assert best[e] == -1 and tuple(actions[e]) == (0.0, 0.0)
-            continue
-        ref, idx = pyref.sarl_predict(w, row, hum, table)
-        np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL, err_msg="env %d" % e)
-        worst = max(worst, float(np.abs(values[e] - ref).max()))
-        assert best[e] == int(np.argmax(values[e]))
-        top2 = np.sort(ref)[-2:]
-        if top2[1] - top2[0] > 2 * TOL:
-            assert best[e] == idx and tuple(actions[e]) == tuple(table[idx])
+        ref, idx = pyref.sarl_predict(w, self_row(st, e), humans(st, e), table)
+        L.check_choice(values[e], best[e], actions[e], ref, table, reached(st, e), what="env %d" % e)
+        if not reached(st, e):
+            worst = max(worst, float(np.abs(values[e] - ref).max()))
     # every env's action is the table row of its own argmax (the whole batch, not only the sample)
     moving = best >= 0
     assert np.array_equal(best[moving], np.argmax(values[moving], 1))
@@ -142,7 +74,7 @@ def test_epsilon_greedy_in_train_phase():
     import torch
     rng = np.random.RandomState(12)
     E, N = 2048, 5
-    pol = _policy(seed=3)
+    pol = L.policy("sarl", seed=3)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N)
     st.rgx[0], st.rgy[0] = st.rpx[0] + 0.05, st.rpy[0] - 0.05        # env 0: robot already at its goal
@@ -191,11 +123,7 @@ def test_rewards_are_float64_exact():
     from oracle import cport
     rng = np.random.RandomState(9)
     E, N = 200, 5
-    pol = _policy(seed=0)
-    with torch.no_grad():
-        for p_ in pol.model.parameters():
-            p_.zero_()
-        pol.model.attention[4].bias.fill_(1.0)
+    pol = L.zeroed(L.policy("sarl", seed=0), "sarl")
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, crowded_frac=0.6)
     H.upload(env, st)
@@ -212,29 +140,18 @@ def test_other_action_space_sizes(speeds, rotations):
     import torch
     rng = np.random.RandomState(speeds * 100 + rotations)
     E, N = 21, 5
-    pol = _policy(seed=6)
-    pol.speed_samples, pol.rotation_samples = speeds, rotations
-    pol.action_space = None
-    env = H.make_vec_env(E, N)
+    pol = L.with_action_grid(L.policy("sarl", seed=6), speeds, rotations)
     st = H.random_state(rng, E, N, randomize=True)
-    H.upload(env, st)
-    actions, best, values = pol.predict_batch(env, want_values=True)
-    values, best, actions = values.cpu().numpy(), best.cpu().numpy(), actions.cpu().numpy()
+    out = L.run_predict_batch(pol, st)
     table = pol._action_table
     A = speeds * rotations + 1
-    assert table.shape == (A, 2) and values.shape == (E, A)
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
+    assert table.shape == (A, 2) and out.values.shape == (E, A)
+    w = cpu_weights(pol)
     for e in range(0, E, 3):
-        row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
-        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
-        if np.hypot(row[5] - row[0], row[6] - row[1]) < row[4]:
-            assert best[e] == -1 and tuple(actions[e]) == (0.0, 0.0)
-            continue
-        ref, idx = pyref.sarl_predict(w, row, hum, table)
-        np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL)
-        top2 = np.sort(ref)[-2:]
-        if A == 2 or top2[1] - top2[0] > 2 * TOL:
-            assert best[e] == idx and tuple(actions[e]) == tuple(table[idx])
+        ref, idx = pyref.sarl_predict(w, self_row(st, e), humans(st, e), table)
+        L.check_choice(out.values[e], out.best[e], out.actions[e], ref, table, reached(st, e), what=e)
+        if A == 2 and not reached(st, e):          # two rows: the reference's choice whatever the gap
+            assert out.best[e] == idx and tuple(out.actions[e]) == tuple(table[idx])
 
 
 def test_unicycle_lookahead_matches_oracle():
@@ -242,9 +159,7 @@ def test_unicycle_lookahead_matches_oracle():
     import torch
     rng = np.random.RandomState(21)
     E, N = 24, 5
-    pol = _policy(seed=5)
-    pol.kinematics = "unicycle"
-    pol.action_space = None
+    pol = L.policy("sarl", seed=5, kinematics="unicycle")
     env = H.make_vec_env(E, N, kinematics="unicycle")
     st = H.random_state(rng, E, N)
     st.rtheta[:] = rng.uniform(-3, 3, E)
@@ -253,11 +168,9 @@ def test_unicycle_lookahead_matches_oracle():
     values = values.cpu().numpy()
     table = pol._action_table
     assert table.shape == (81, 2) and table[1, 1] == -np.pi / 4          # (speed, rotation) rows
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
+    w = cpu_weights(pol)
     for e in range(0, E, 4):
-        row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, st.rtheta[e]]
-        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)
-        ref, idx = pyref.sarl_predict(w, row, hum, table, kinematics="unicycle")
+        ref, idx = pyref.sarl_predict(w, self_row(st, e), humans(st, e), table, kinematics="unicycle")
         np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL)
 
 
@@ -268,9 +181,7 @@ def test_unicycle_predict_matches_reference_fixture(N, golden_dir):
     (v, r) action wherever its top two values are further apart than that, (0, 0) where the robot stands on its goal."""
     import torch
     g = np.load(os.path.join(golden_dir, "g17_sarl_unicycle.npz"))
-    pol = _policy(_weights(g, "w__"))
-    pol.kinematics = "unicycle"
-    pol.action_space = None
+    pol = L.policy("sarl", L.weights(g, "w__"), kinematics="unicycle")
     me, hum = g["N%d_self" % N], g["N%d_humans" % N]
     E = me.shape[0]
     env = H.make_vec_env(E, N, kinematics="unicycle")
@@ -280,15 +191,16 @@ def test_unicycle_predict_matches_reference_fixture(N, golden_dir):
     st.hpx[:], st.hpy[:], st.hvx[:], st.hvy[:], st.hr[:] = (hum[:, :, c] for c in range(5))
     H.upload(env, st)
     actions, best, values = pol.predict_batch(env, want_values=True)
-    values, actions = values.cpu().numpy(), actions.cpu().numpy()
+    values, best, actions = values.cpu().numpy(), best.cpu().numpy(), actions.cpu().numpy()
     assert np.array_equal(pol._action_table, g["table"])
     checked = 0
     for e in range(E):
         want = g["N%d_values" % N][e]
-        if np.isnan(want[0]):
-            assert tuple(actions[e]) == (0.0, 0.0)
+        if np.isnan(want[0]):                 # the reference returned early: the robot stands on its goal
+            assert reached(st, e)
+            L.check_choice(values[e], best[e], actions[e], None, g["table"], True, what=e)
             continue
-        np.testing.assert_allclose(values[e], want, rtol=0, atol=TOL)
+        L.check_choice(values[e], best[e], actions[e], want, g["table"], reached(st, e), what=e)
         top2 = np.sort(want)[-2:]
         if top2[1] - top2[0] > 2 * TOL:
             assert tuple(actions[e]) == tuple(g["N%d_action" % N][e]), e
@@ -296,11 +208,9 @@ def test_unicycle_predict_matches_reference_fixture(N, golden_dir):
     assert checked > 25
     # the E = 1 surface on the same states: get_attention_weights() is what the reference's model holds after predict()
     # -- the weights of the last candidate action (sarl.py:56,88-89), unchanged where predict() returned early
-    from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
     prev = None
     for e in range(0, E, 2):
-        js = JointState(FullState(*me[e].tolist()), [ObservableState(*row) for row in hum[e].tolist()])
-        act = pol.predict(js)
+        act = pol.predict(L.joint_state(me[e], hum[e]))
         want = g["N%d_attention" % N][e]
         if np.isnan(g["N%d_values" % N][e][0]):
             assert tuple(act) == (0, 0)
@@ -317,19 +227,17 @@ def test_e1_epsilon_greedy_follows_numpys_stream_like_the_reference(golden_dir):
     draw where the robot stands on its goal (:22-23), `last_state` = transform(state) kept in the train phase only
     (:60-61).  The E = 1 predict() consumes numpy's global stream the same way: same explored calls, same random
     rows, same greedy actions, same stored states."""
-    import torch
-    from modelcrowdnav_amd.envs.utils.state import FullState, ObservableState, JointState
     g = np.load(os.path.join(golden_dir, "g21_epsilon.npz"))
-    pol = _policy(_weights(np.load(os.path.join(golden_dir, "g17_sarl_unicycle.npz")), "w__"))
+    pol = L.policy("sarl", L.weights(np.load(os.path.join(golden_dir, "g17_sarl_unicycle.npz")), "w__"))
     pol.set_phase("train")
     with pytest.raises(AttributeError):
-        pol.predict(JointState(FullState(*g["selfs"][0].tolist()), [ObservableState(*r) for r in g["humans"][0].tolist()]))
+        pol.predict(L.joint_state(g["selfs"][0], g["humans"][0]))
     pol.set_epsilon(0.5)
     np.random.seed(2100)
     kinds = np.bincount(g["explored"], minlength=3)
     assert kinds.min() >= 5
     for s in range(g["selfs"].shape[0]):
-        js = JointState(FullState(*g["selfs"][s].tolist()), [ObservableState(*r) for r in g["humans"][s].tolist()])
+        js = L.joint_state(g["selfs"][s], g["humans"][s])
         pol.action_values = None
         act = pol.predict(js)
         kind = int(g["explored"][s])
@@ -344,7 +252,7 @@ def test_e1_epsilon_greedy_follows_numpys_stream_like_the_reference(golden_dir):
             np.testing.assert_allclose(pol.last_state.cpu().numpy(), g["last_states"][s], rtol=2e-6, atol=2e-6)
     pol.set_phase("test")
     pol.last_state = None
-    pol.predict(JointState(FullState(*g["selfs"][0].tolist()), [ObservableState(*r) for r in g["humans"][0].tolist()]))
+    pol.predict(L.joint_state(g["selfs"][0], g["humans"][0]))
     assert pol.last_state is None                       # only the train phase keeps it
 
 
@@ -355,7 +263,7 @@ def test_per_env_pedestrian_counts():
     import torch
     rng = np.random.RandomState(17)
     E, N = 41, 7
-    pol = _policy(seed=4)
+    pol = L.policy("sarl", seed=4)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
     H.upload(env, st)
@@ -366,22 +274,17 @@ def test_per_env_pedestrian_counts():
     values, best = values.cpu().numpy().copy(), best.cpu().numpy().copy()
     full = pol.predict_batch(env, want_values=True)[2].cpu().numpy()
     assert np.array_equal(values[0], full[0])                         # hcount == N is the unmasked path
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
+    w = cpu_weights(pol)
     table = pol._action_table
     for e in range(0, E, 2):
-        n = int(counts[e])
-        row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
-        hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)[:n]
-        ref, idx = pyref.sarl_predict(w, row, hum, table)
+        ref, idx = pyref.sarl_predict(w, self_row(st, e), humans(st, e)[:int(counts[e])], table)
         np.testing.assert_allclose(values[e], ref, rtol=0, atol=TOL)
     # garbage in the absent slots must not leak in
     env.hpos[:, 3:] = 1e6; env.hvel[:, 3:] = -7.0
     hc3 = torch.full((E,), 3, dtype=torch.int32, device=env.device)
     v3 = pol.predict_batch(env, want_values=True, hcount=hc3)[2].cpu().numpy()
-    e = 5
-    row = [st.rpx[e], st.rpy[e], st.rvx[e], st.rvy[e], st.rr[e], st.rgx[e], st.rgy[e], 1.0, 0.0]
-    hum = np.stack([st.hpx[e], st.hpy[e], st.hvx[e], st.hvy[e], st.hr[e]], 1)[:3]
-    np.testing.assert_allclose(v3[e], pyref.sarl_predict(w, row, hum, table)[0], rtol=0, atol=TOL)
+    ref = pyref.sarl_predict(w, self_row(st, 5), humans(st, 5)[:3], table)[0]
+    np.testing.assert_allclose(v3[5], ref, rtol=0, atol=TOL)
     with pytest.raises(ValueError):
         pol.predict_batch(env, hcount=hc.long())
 
@@ -397,7 +300,7 @@ def test_bf16x3_layers_agree_with_the_float32_mfma_layers(N):
     from modelcrowdnav_amd import _hip
     rng = np.random.RandomState(70 + N)
     E = 1024
-    pol = _policy(seed=5)
+    pol = L.policy("sarl", seed=5)
     env = H.make_vec_env(E, N)
     H.upload(env, H.random_state(rng, E, N, randomize=True))
     with _hip.tuned(sarl_x3=1):
@@ -430,9 +333,9 @@ def test_network_error_against_a_float64_evaluation(weights, golden_dir):
     rng = np.random.RandomState(11)
     if weights == "g17":
         g = np.load(os.path.join(golden_dir, "g17_sarl_unicycle.npz"))
-        pol = _policy(weights=_weights(g, "w__"))
+        pol = L.policy("sarl", L.weights(g, "w__"))
     else:
-        pol = _policy(seed=9)
+        pol = L.policy("sarl", seed=9)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
     H.upload(env, st)
@@ -442,13 +345,11 @@ def test_network_error_against_a_float64_evaluation(weights, golden_dir):
     with _hip.tuned(sarl_x3=0):
         _, _, v_f32 = pol.predict_batch(env, want_values=True)
         v_f32 = v_f32.cpu().numpy().copy()
-    w32 = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
-    w64 = {k: v.double() for k, v in w32.items()}
+    w32, w64 = cpu_weights(pol), cpu_weights(pol, torch.float64)
     table, dt = pol._action_table, 0.25
     err = dict(x3=0.0, f32_mfma=0.0, torch_f32=0.0)
     for e in range(0, E, 8):
-        reached = float(np.linalg.norm((st.rpy[e] - st.rgy[e], st.rpx[e] - st.rgx[e]))) < st.rr[e]
-        if reached:
+        if reached(st, e):
             continue
         nxt = np.stack([st.hpx[e] + st.hvx[e] * dt, st.hpy[e] + st.hvy[e] * dt, st.hvx[e], st.hvy[e], st.hr[e]], 1)
         rows = np.zeros((len(table), N, 14))
@@ -480,7 +381,7 @@ def test_benchmark_grid_every_pair_against_the_torch_reference(N):
     import torch
     rng = np.random.RandomState(90 + N)
     E, dt, gamma = 4096, 0.25, 0.9
-    pol = _policy(seed=4)
+    pol = L.policy("sarl", seed=4)
     env = H.make_vec_env(E, N)
     st = H.random_state(rng, E, N, randomize=True)
     H.upload(env, st)
@@ -489,7 +390,7 @@ def test_benchmark_grid_every_pair_against_the_torch_reference(N):
     values, best = values.cpu().numpy(), best.cpu().numpy()
     table = np.asarray(pol._action_table, np.float64)
     A = len(table)
-    w = {k: v.detach().cpu() for k, v in pol.model.state_dict().items()}
+    w = cpu_weights(pol)
     # propagate (float64), one row per (env, action, human)
     npx = st.rpx[:, None] + table[None, :, 0] * dt; npy = st.rpy[:, None] + table[None, :, 1] * dt          # [E, A]
     hx, hy = st.hpx + st.hvx * dt, st.hpy + st.hvy * dt                                                      # [E, N]

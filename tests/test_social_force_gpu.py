@@ -324,16 +324,10 @@ def test_vec_env_reset_step_rollout():
 
 
 def _sarl(query_env=False):
-    torch = need_gpu()
-    from modelcrowdnav_amd import configs
-    from modelcrowdnav_amd.policy.sarl import SARL
-    torch.manual_seed(11)
-    p = SARL()
-    p.configure(configs.policy_config(**({"action_space.query_env": "true"} if query_env else {})))
-    p.kinematics = "holonomic"
-    p.set_device(torch.device("cuda", 0))
-    p.set_phase("test")
-    p.time_step = DT
+    need_gpu()
+    from tests.lookahead_harness import policy
+    p = policy("sarl", seed=11, **({"action_space.query_env": "true"} if query_env else {}))
+    assert p.time_step == DT
     return p
 
 

@@ -14,20 +14,18 @@ from tests import helpers as H  # noqa: E402
 
 def test_imitation_then_reinforcement_learning_loop():
     import torch
-    from modelcrowdnav_amd import configs
     from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
-    from modelcrowdnav_amd.policy.sarl import SARL
     from modelcrowdnav_amd.rollout import VecExplorer
     from modelcrowdnav_amd.utils.memory import ReplayMemory
     from modelcrowdnav_amd.utils.trainer import Trainer
+    from tests.lookahead_harness import policy
     dev = torch.device("cuda", 0)
     E, N = 256, 5
     env = H.make_vec_env(E, N)
     env.track_human_times = False; env.export_human_actions = False
-    torch.manual_seed(0)
-    sarl = SARL(); sarl.configure(configs.policy_config()); sarl.kinematics = "holonomic"
+    sarl = policy("sarl", seed=0, phase="train")
     sarl.multiagent_training = True
-    sarl.set_device(dev); sarl.set_phase("train"); sarl.time_step = env.time_step
+    sarl.time_step = env.time_step
     model = sarl.get_model()
     memory = ReplayMemory(100000, device=dev)
     trainer = Trainer(model, memory, dev, 100)

@@ -61,8 +61,8 @@ def _sgan_case():
 def _policy_case(kind):
     import torch
     from tests import helpers as H
-    make = {"sarl": "tests.test_sarl_gpu", "cadrl": "tests.test_cadrl_gpu", "lstm_rl": "tests.test_lstm_rl_gpu"}[kind]
-    make = __import__(make, fromlist=["_policy"])._policy
+    from tests.lookahead_harness import policy
+    make = lambda **kw: policy(kind, **kw)
     pol = make(seed=4)
     E, N = 23, 5
     env = H.make_vec_env(E, N)
