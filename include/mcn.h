@@ -529,6 +529,49 @@ int mcn_cadrl_predict(const mcn_cadrl_net *net, const mcn_env_state *st, const d
                       double *action_out, double epsilon, uint64_t seed, int32_t E, int32_t N, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SARL value-network training step (crowd_nav/utils/trainer.py:64-82 on crowd_nav/policy/sarl.py:28-65).
+ * ---------------------------------------------------------------------------------------------- */
+
+/*
+ * The network is the shipped SARL ValueNetwork with the global state on: input_dim 13 (SARL) or 61 (OM-SARL),
+ * self_state_dim 6, mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-1.  Parameters, gradient and
+ * momentum are each ONE flat float32 device buffer in state_dict order -- mlp1.0.weight, mlp1.0.bias, mlp1.2.*, mlp2.0.*,
+ * mlp2.2.*, attention.0.*, attention.2.*, attention.4.*, mlp3.0.*, mlp3.2.*, mlp3.4.*, mlp3.6.* -- every weight row-major
+ * [out][in] as torch stores it: mcn_sarl_train_param_count floats, 96502 for input_dim 13 and 103702 for 61, -1 for any
+ * other input_dim.
+ */
+int64_t mcn_sarl_train_param_count(int32_t input_dim);
+int64_t mcn_sarl_train_workspace_bytes(int32_t B, int32_t N, int32_t input_dim);    /* 0 for arguments the step refuses */
+
+/*
+ * mcn_sarl_loss_grad -- loss = mean_b (V(states[rows[b]]) - values[rows[b]])^2 over a mini-batch of B states and its
+ * gradient by every parameter, with the semantics of torch autograd on ValueNetwork.forward in float32: the softmax is
+ * the un-stabilised exp(s) (s != 0) / sum with the mask a constant, ReLU passes gradient where its output is > 0, and
+ * where torch gives NaN (a state whose scores are all exactly 0 is 0 / 0) so does this.
+ * states: [rows of the memory][N][input_dim] float, values: [rows of the memory] float, both device.  rows: [B] int64
+ * device, the memory row of each state of the batch, or NULL for rows 0 .. B-1.  The kernel TRUSTS the row indices:
+ * the caller checks them against the number of rows the memory holds before it uploads them.
+ * workspace: mcn_sarl_train_workspace_bytes(B, N, input_dim) device bytes, 8-byte aligned; grad: [param_count] float
+ * device out; loss: [1] float device out.  Two launches on `stream` (per-workgroup partial gradients, then their sum in
+ * workgroup order): no atomics, so the same inputs give the same bits.  The forward pass and the sums over the batch run
+ * in float64, the backward pass in float32: loss and grad are within float32 rounding of float64 autograd's, and the
+ * gradient of attention.4.bias, which the softmax makes 0, is returned as exactly 0 (or NaN).
+ * MCN_EINVAL before any launch: a NULL params / states / values / workspace / grad / loss, B < 1, N outside
+ * 1 .. MCN_MAX_HUMANS, an input_dim other than 13 / 61.
+ */
+int mcn_sarl_loss_grad(const float *params, int32_t input_dim, const float *states, const float *values,
+                       const int64_t *rows, int32_t B, int32_t N, void *workspace, float *grad, float *loss, void *stream);
+
+/*
+ * mcn_sgd_momentum_step -- torch.optim.SGD(momentum) without dampening, weight decay or Nesterov over flat float32
+ * device buffers of `count` elements: buf = momentum buf + grad, p = p - lr buf (the latter one fused multiply-add, as
+ * torch's p.add_(buf, alpha=-lr)).  A zero buf makes it torch's first step.  One launch on `stream`.
+ * MCN_EINVAL before any launch: a NULL pointer, count < 1, an lr or momentum that is not finite.
+ */
+int mcn_sgd_momentum_step(float *params, float *momentum_buf, const float *grad, int64_t count, float lr, float momentum,
+                          void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Social-GAN one-step world model (crowd_nav/policy/world_model.py:134-268, sgan/models.py:501-553).
  * ---------------------------------------------------------------------------------------------- */
 

@@ -60,6 +60,15 @@ int launch_sarl_om(const mcn_env_state *st, double dt, const double *next_hpos, 
                    double cell_size, const float *w_om, const float *b_om, float *om, float *init, int E, int N,
                    hipStream_t stream);
 
+// sarl_train.hip
+long sarl_train_param_count(int input_dim);                          // -1 unless input_dim is 13 or 61
+long sarl_train_workspace_floats(int B, int N, int input_dim);
+int launch_sarl_loss_grad(const float *params, int input_dim, const float *states, const float *values,
+                          const int64_t *rows, int B, int N, void *workspace, float *grad, float *loss,
+                          hipStream_t stream);
+int launch_sgd_momentum(float *params, float *momentum_buf, const float *grad, int64_t count, float lr, float momentum,
+                        hipStream_t stream);
+
 // lstm_rl_value.hip
 int launch_lstm_rl(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                    double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val, int32_t *order,

@@ -526,6 +526,30 @@ int mcn_cadrl_predict(const mcn_cadrl_net *net, const mcn_env_state *st, const d
                              next_hvel, rewards, action_out, epsilon, (unsigned long long)seed, E, N, (hipStream_t)stream);
 }
 
+int64_t mcn_sarl_train_param_count(int32_t input_dim) { return (int64_t)mcn::sarl_train_param_count(input_dim); }
+
+int64_t mcn_sarl_train_workspace_bytes(int32_t B, int32_t N, int32_t input_dim)
+{
+    if (B <= 0 || N <= 0 || N > MCN_MAX_HUMANS || mcn::sarl_train_param_count(input_dim) < 0) return 0;
+    return (int64_t)mcn::sarl_train_workspace_floats(B, N, input_dim) * 4;
+}
+
+int mcn_sarl_loss_grad(const float *params, int32_t input_dim, const float *states, const float *values,
+                       const int64_t *rows, int32_t B, int32_t N, void *workspace, float *grad, float *loss, void *stream)
+{
+    if (!params || !states || !values || !workspace || !grad || !loss) return MCN_EINVAL;
+    if (B < 1 || N < 1 || N > MCN_MAX_HUMANS || (input_dim != 13 && input_dim != 61)) return MCN_EINVAL;
+    return mcn::launch_sarl_loss_grad(params, input_dim, states, values, rows, B, N, workspace, grad, loss,
+                                      (hipStream_t)stream);
+}
+
+int mcn_sgd_momentum_step(float *params, float *momentum_buf, const float *grad, int64_t count, float lr, float momentum,
+                          void *stream)
+{
+    if (!params || !momentum_buf || !grad || count < 1 || !isfinite(lr) || !isfinite(momentum)) return MCN_EINVAL;
+    return mcn::launch_sgd_momentum(params, momentum_buf, grad, count, lr, momentum, (hipStream_t)stream);
+}
+
 int mcn_mlp_world_step(const mcn_mlp_world_net *net, const double *hpos, const double *hvel, double *out_vel,
                        int32_t E, int32_t N, void *stream)
 {

@@ -11,7 +11,13 @@ permutation: every rank issues the same number of collectives, every batch is fu
 
 The arithmetic (one SGD-momentum step of the MSE loss) is pinned against the reference's own Trainer by
 tests/golden/g10_trainer.npz (tests/test_training_cpu.py).
+
+`Trainer(..., fused=True)` (opt-in; `Trainer.fused_default` for drop-in users) replaces autograd and the torch optimizer
+by the HIP training step of csrc/sarl_train.hip: per mini-batch three launches (loss and per-workgroup gradients, their
+sum, SGD-momentum) on flat parameter / gradient / momentum buffers, the row indices of all batches of a call uploaded
+once and the losses read back once.  It draws the same batches from the same generator as the torch path.
 """
+import ctypes as C
 import logging
 
 import torch
@@ -21,7 +27,9 @@ import torch.optim as optim
 
 
 class Trainer(object):
-    def __init__(self, model, memory, device, batch_size):
+    fused_default = False        # what `fused=None` means; a drop-in user may flip it
+
+    def __init__(self, model, memory, device, batch_size, fused=None):
         self.model = model
         self.device = device
         self.criterion = nn.MSELoss().to(device)
@@ -31,10 +39,17 @@ class Trainer(object):
         self.optimizer = None
         self._flat = None
         self._gen = torch.Generator()
+        self.fused = bool(Trainer.fused_default if fused is None else fused)
+        self._fz = None                  # fused path: flat params / grad / momentum, workspace
+        self.last_rows = None            # fused path: the memory rows of each mini-batch of the latest call (host)
+        if self.fused:
+            self._fused_check()
 
     def set_learning_rate(self, learning_rate):
         logging.info("Current learning rate: %f", learning_rate)
         self.optimizer = optim.SGD(self.model.parameters(), lr=learning_rate, momentum=0.9)
+        if self._fz is not None:
+            self._fz["mom"].zero_()      # the reference makes a new optimizer here: the momentum starts over
 
     # ------------------------------------------------------------------ data parallel helpers
     @staticmethod
@@ -99,6 +114,155 @@ class Trainer(object):
         self.optimizer.step()
         return loss.data.item()
 
+    # ------------------------------------------------------------------ fused HIP step (csrc/sarl_train.hip)
+    def _fused_layout(self):
+        """[(state_dict key, offset, shape)] of the flat buffers, and their length: state_dict order, each tensor in
+        torch's own row-major layout (include/mcn.h: mcn_sarl_train_param_count)."""
+        table, off = [], 0
+        for k, v in self.model.state_dict().items():
+            table.append((k, off, tuple(v.shape)))
+            off += v.numel()
+        return table, off
+
+    def _fused_check(self):
+        """ValueError for what the fused step is not built for.  The memory is looked at again at every call: rows
+        arrive after the trainer is made."""
+        from .. import _hip
+        from ..policy.sarl import ValueNetwork
+        m = self.model
+        why = None
+        if not isinstance(m, ValueNetwork) or not m.with_global_state or m.self_state_dim != 6:
+            why = "it is not a SARL ValueNetwork with the global state and a 6-wide self state"
+        else:
+            sd = m.state_dict()
+            D = sd["mlp1.0.weight"].shape[1] if "mlp1.0.weight" in sd else -1
+            expect = {"mlp1.0": (150, D), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
+                      "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
+                      "mlp3.0": (150, 56), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (1, 100)}
+            keys = [k + s for k in expect for s in (".weight", ".bias")]
+            if list(sd.keys()) != keys or D not in (13, 61):
+                why = "its layers are not the shipped ones (policy.config:44-50, input_dim 13 or 61)"
+            else:
+                for k, shp in expect.items():
+                    if tuple(sd[k + ".weight"].shape) != shp or tuple(sd[k + ".bias"].shape) != shp[:1]:
+                        why = "%s.weight is %s, expected %s" % (k, tuple(sd[k + ".weight"].shape), shp)
+                        break
+                if why is None and any(v.dtype != torch.float32 for v in sd.values()):
+                    why = "its parameters are not float32"
+                if why is None and self._fused_layout()[1] != int(_hip.lib.mcn_sarl_train_param_count(D)):
+                    why = "its parameter count is not mcn_sarl_train_param_count(%d)" % D
+        if why is not None:
+            raise ValueError("Trainer(fused=True): sarl_train.hip is built for the shipped SARL value network; this model "
+                             "cannot be trained by it: " + why)
+        self._fused_check_memory()
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise ValueError("Trainer(fused=True) runs HIP kernels: the trainer's device is %s, not a GPU" % (dev,))
+
+    def _fused_check_memory(self):
+        mem = self.memory
+        if getattr(mem, "_odd", None):
+            raise ValueError("Trainer(fused=True): the memory holds %d _odd rows (states of another human count than its "
+                             "tensor store), which the fused step cannot gather" % len(mem._odd))
+        st = getattr(mem, "_states", None)
+        if st is not None:
+            dev = torch.device(self.device)
+            same = st.device.type == dev.type and (dev.type != "cuda" or st.device.index ==
+                                                   (torch.cuda.current_device() if dev.index is None else dev.index))
+            if not same:
+                raise ValueError("Trainer(fused=True): the memory lives on %s, the trainer on %s; the fused step gathers "
+                                 "its batches on the device (ReplayMemory(capacity, device=...))" % (st.device, dev))
+
+    def _fused_run(self, batches):
+        """One fused training step per entry of `batches` (1-D int64 host tensors of memory rows); returns the list of
+        their float32 losses as Python floats, read back with one copy after the last step."""
+        from .. import _hip
+        self._fused_check()
+        n = len(self.memory)
+        if n < 1 or any(b.numel() < 1 for b in batches):
+            raise ValueError("Trainer(fused=True): the memory holds no rows to train on")
+        self.last_rows = batches
+        rows = torch.cat(batches)
+        if int(rows.min()) < 0 or int(rows.max()) >= n:          # the kernel trusts the rows: checked here, on the host
+            raise IndexError("Trainer(fused=True): a batch names memory row %d; the memory holds %d rows" %
+                             (int(rows.max()) if int(rows.max()) >= n else int(rows.min()), n))
+        dev = self.memory._states.device
+        params = [p for _, p in self.model.named_parameters()]
+        if any(p.device != dev for p in params):
+            raise ValueError("Trainer(fused=True): the model lives on %s, the memory on %s" % (params[0].device, dev))
+        states, values = self.memory._states, self.memory._values
+        N, D = int(states.shape[1]), int(states.shape[2])
+        table, count = self._fused_layout()
+        if states.dim() != 3 or D != table[0][2][1] or not 1 <= N <= _hip.MAX_HUMANS:
+            raise ValueError("Trainer(fused=True): memory states are %s, the model takes [N <= %d][%d]" %
+                             (tuple(states.shape[1:]), _hip.MAX_HUMANS, table[0][2][1]))
+        z = self._fz
+        if z is None or z["params"].numel() != count or z["params"].device != dev:
+            z = self._fz = {k: torch.zeros(count, dtype=torch.float32, device=dev) for k in ("params", "grad", "mom")}
+            z["ws"] = None
+        self._flat = z["grad"]                                   # data parallel: the flat gradient is the bucket
+        need = max(int(_hip.lib.mcn_sarl_train_workspace_bytes(int(b.numel()), N, D)) for b in batches)
+        if z["ws"] is None or z["ws"].numel() < need:
+            z["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        group = self.optimizer.param_groups[0]
+        lr, momentum = float(group["lr"]), float(group["momentum"])
+        grouped, world = self._grouped(), self._world()
+        with torch.no_grad():
+            # load_state_dict / sync_weights since the last call are honoured: the module is the master copy
+            torch.cat([p.detach().reshape(-1) for p in params], out=z["params"])
+            rows_dev = rows.to(dev)
+            losses = torch.empty(len(batches), dtype=torch.float32, device=dev)
+            stream = _hip.stream_ptr(dev)
+            at = 0
+            for s, b in enumerate(batches):
+                B = int(b.numel())
+                _hip.check(_hip.lib.mcn_sarl_loss_grad(
+                    _hip.ptr(z["params"]), D, _hip.ptr(states), _hip.ptr(values), C.c_void_p(rows_dev.data_ptr() + 8 * at),
+                    B, N, _hip.ptr(z["ws"]), _hip.ptr(z["grad"]), C.c_void_p(losses.data_ptr() + 4 * s), stream),
+                    "mcn_sarl_loss_grad")
+                at += B
+                if grouped:
+                    self._collective(dist.all_reduce, z["grad"])          # one bucket, one collective
+                    if world > 1:
+                        z["grad"].div_(world)
+                _hip.check(_hip.lib.mcn_sgd_momentum_step(_hip.ptr(z["params"]), _hip.ptr(z["mom"]), _hip.ptr(z["grad"]),
+                                                          count, lr, momentum, stream), "mcn_sgd_momentum_step")
+            # p.copy_ (not p.data): the version counters move, so packed HIP weights of the model are re-made
+            for p, (_, off, _shape) in zip(params, table):
+                p.copy_(z["params"][off:off + p.numel()].view_as(p))
+            return losses.cpu().tolist()
+
+    def _fused_epoch(self, num_epochs, perms):
+        n = len(self.memory)
+        multi = self._world() > 1
+        batches, per_epoch = [], []
+        for ep in range(num_epochs):
+            perm = torch.randperm(n, generator=self._gen) if perms is None else torch.as_tensor(perms[ep], dtype=torch.long)
+            steps = self._agreed_steps(n)
+            for b in range(steps):
+                lo = b * self.batch_size
+                batches.append(perm[(lo + torch.arange(self.batch_size)) % n] if multi else perm[lo:lo + self.batch_size])
+            per_epoch.append(steps)
+        losses = self._fused_run(batches) if batches else []
+        average_epoch_loss, at = 0, 0
+        for steps in per_epoch:
+            epoch_loss = 0
+            for v in losses[at:at + steps]:
+                epoch_loss += v
+            at += steps
+            average_epoch_loss = epoch_loss / n
+        return average_epoch_loss
+
+    def _fused_batch(self, num_batches):
+        n = len(self.memory)
+        batches = [torch.randperm(n, generator=self._gen)[:min(self.batch_size, n)] for _ in range(num_batches)]
+        losses = 0
+        for v in (self._fused_run(batches) if batches else []):
+            losses += v
+        average_loss = losses / num_batches
+        logging.debug("Average loss : %.2E", average_loss)
+        return average_loss
+
     # ------------------------------------------------------------------ reference surface
     def _agreed_steps(self, n_local):
         """Mini-batches per epoch: the local count, or with several ranks the largest count of any rank."""
@@ -116,6 +280,8 @@ class Trainer(object):
         reference's DataLoader draws them from torch's global generator."""
         if self.optimizer is None:
             raise ValueError("Learning rate is not set!")
+        if self.fused:
+            return self._fused_epoch(num_epochs, perms)
         average_epoch_loss = 0
         n = len(self.memory)
         multi = self._world() > 1
@@ -139,6 +305,8 @@ class Trainer(object):
         """trainer.py:64-82: num_batches independent random mini-batches; returns the mean loss."""
         if self.optimizer is None:
             raise ValueError("Learning rate is not set!")
+        if self.fused:
+            return self._fused_batch(num_batches)
         losses = 0
         for _ in range(num_batches):
             inputs, values = self.memory.sample(self.batch_size, self._gen)

@@ -1,0 +1,187 @@
+"""CPU: the host side of the fused SARL training step (csrc/sarl_train.hip; include/mcn.h: mcn_sarl_train_param_count,
+mcn_sarl_train_workspace_bytes, mcn_sarl_loss_grad, mcn_sgd_momentum_step; utils/trainer.py: Trainer(fused=True)) -- the
+flat layout, the sizes, the argument validation (before any launch) and the refusals of the Python path.  The kernels
+themselves are tested on the device by tests/test_fused_trainer_gpu.py."""
+import os
+import subprocess
+import sys
+
+import pytest
+import torch
+
+from tests import trainer_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _sarl_model(with_om=False):
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.policy.sarl import SARL
+    torch.manual_seed(0)
+    p = SARL()
+    p.configure(configs.policy_config(**({"sarl.with_om": "true"} if with_om else {})))
+    return p.model
+
+
+def test_param_count_is_the_configured_models():
+    from modelcrowdnav_amd import _hip
+    n13 = sum(p.numel() for p in _sarl_model().parameters())
+    n61 = sum(p.numel() for p in _sarl_model(with_om=True).parameters())
+    assert _hip.lib.mcn_sarl_train_param_count(13) == 96502 == n13
+    assert _hip.lib.mcn_sarl_train_param_count(61) == 103702 == n61
+    assert _hip.lib.mcn_sarl_train_param_count(12) == -1 and _hip.lib.mcn_sarl_train_param_count(0) == -1
+
+
+@pytest.mark.parametrize("input_dim", [13, 61])
+def test_flat_layout_is_state_dict_order(input_dim):
+    """The hand-written (name, offset, shape) table of tests/trainer_ref.py against the layout the Trainer uses and
+    against the module's own state_dict."""
+    from modelcrowdnav_amd import _hip
+    from modelcrowdnav_amd.utils.memory import ReplayMemory
+    from modelcrowdnav_amd.utils.trainer import Trainer
+    model = R.value_network(input_dim, seed=0)
+    table, total = R.layout(input_dim)
+    assert total == _hip.lib.mcn_sarl_train_param_count(input_dim)
+    assert [(k, tuple(v.shape)) for k, v in model.state_dict().items()] == [(k, shp) for k, _, shp in table]
+    assert [k for k, _ in model.named_parameters()] == [k for k, _, _ in table]
+    tr = Trainer(model, ReplayMemory(4), torch.device("cpu"), 2)          # not fused: only its layout is asked for
+    assert tr._fused_layout() == (table, total)
+    numel = {k: v.numel() for k, v in model.state_dict().items()}
+    assert table[0][1] == 0 and all(b[1] == a[1] + numel[a[0]] for a, b in zip(table[:-1], table[1:]))
+
+
+def test_workspace_grows_with_the_batch():
+    from modelcrowdnav_amd import _hip
+    for D in (13, 61):
+        for N in (1, 2, 5, 10, 32):
+            sizes = [_hip.lib.mcn_sarl_train_workspace_bytes(B, N, D) for B in range(1, 130)]
+            assert sizes[0] >= 4 * (_hip.lib.mcn_sarl_train_param_count(D) + 1)
+            assert all(b >= a > 0 for a, b in zip(sizes[:-1], sizes[1:])), (D, N)
+    assert _hip.lib.mcn_sarl_train_workspace_bytes(0, 5, 13) == 0
+    assert _hip.lib.mcn_sarl_train_workspace_bytes(4, 33, 13) == 0
+    assert _hip.lib.mcn_sarl_train_workspace_bytes(4, 5, 14) == 0
+
+
+_VALIDATION = r"""
+import ctypes as C
+from modelcrowdnav_amd import _hip
+lib = _hip.lib
+fake = C.c_void_p(0x1000)                     # never dereferenced: validation fails first
+inf, nan = float("inf"), float("nan")
+
+
+def grad(params=fake, D=13, states=fake, values=fake, rows=fake, B=4, N=5, ws=fake, g=fake, loss=fake):
+    return lib.mcn_sarl_loss_grad(params, D, states, values, rows, B, N, ws, g, loss, None)
+
+
+def sgd(p=fake, buf=fake, g=fake, count=100, lr=0.01, momentum=0.9):
+    return lib.mcn_sgd_momentum_step(p, buf, g, count, lr, momentum, None)
+
+
+# the acceptable calls get past validation and, with no device in sight, fail at the launch: each MCN_EINVAL below comes
+# from the one argument that was changed (made only once the runtime itself confirms that it sees no device)
+count = C.c_int(-1)
+err = C.CDLL("libamdhip64.so").hipGetDeviceCount(C.byref(count))
+if err != 0 or count.value <= 0:
+    assert grad() == _hip.MCN_ELAUNCH
+    assert grad(rows=None) == _hip.MCN_ELAUNCH, "rows = NULL means rows 0 .. B-1"
+    assert grad(D=61, N=32, B=1) == _hip.MCN_ELAUNCH
+    assert sgd() == _hip.MCN_ELAUNCH and sgd(lr=0.0, momentum=0.0, count=1) == _hip.MCN_ELAUNCH
+    print("POSITIVE_CONTROL_OK")
+bad_grad = {
+    "params = NULL": dict(params=None), "states = NULL": dict(states=None), "values = NULL": dict(values=None),
+    "workspace = NULL": dict(ws=None), "grad = NULL": dict(g=None), "loss = NULL": dict(loss=None),
+    "B = 0": dict(B=0), "B = -1": dict(B=-1), "N = 0": dict(N=0), "N = -3": dict(N=-3),
+    "N = MCN_MAX_HUMANS + 1": dict(N=_hip.MAX_HUMANS + 1),
+    "input_dim = 12": dict(D=12), "input_dim = 0": dict(D=0), "input_dim = 14": dict(D=14), "input_dim = 60": dict(D=60),
+}
+for what, kw in bad_grad.items():
+    assert grad(**kw) == _hip.MCN_EINVAL, what
+bad_sgd = {
+    "params = NULL": dict(p=None), "momentum_buf = NULL": dict(buf=None), "grad = NULL": dict(g=None),
+    "count = 0": dict(count=0), "count = -5": dict(count=-5),
+    "lr = inf": dict(lr=inf), "lr = -inf": dict(lr=-inf), "lr = nan": dict(lr=nan),
+    "momentum = inf": dict(momentum=inf), "momentum = nan": dict(momentum=nan),
+}
+for what, kw in bad_sgd.items():
+    assert sgd(**kw) == _hip.MCN_EINVAL, what
+print("TRAIN_VALIDATION_OK")
+"""
+
+
+def test_training_entry_points_validate_on_host():
+    """Every MCN_EINVAL case of mcn_sarl_loss_grad and mcn_sgd_momentum_step.  The pointers are fakes, so a check that
+    went missing would launch a kernel on them: the calls are made in a fresh child process that sees NO device, where
+    such a launch fails with MCN_ELAUNCH instead of faulting a GPU that others share."""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", ROCR_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1",
+               PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    res = subprocess.run([sys.executable, "-c", _VALIDATION], env=env, cwd=ROOT, capture_output=True, text=True,
+                         timeout=300)
+    assert res.returncode == 0 and "TRAIN_VALIDATION_OK" in res.stdout, (res.returncode, res.stdout[-2000:], res.stderr[-2000:])
+    assert "POSITIVE_CONTROL_OK" in res.stdout, "the child process still saw a device: %s" % res.stdout[-500:]
+
+
+def _memory(N=5, D=13, rows=8):
+    from modelcrowdnav_amd.utils.memory import ReplayMemory
+    s, v = R.states_and_values(rows, N, D, seed=3)
+    mem = ReplayMemory(32)
+    mem.push_batch(s, v)
+    return mem
+
+
+def test_fused_trainer_refuses_what_it_is_not_built_for():
+    from modelcrowdnav_amd.policy.sarl import ValueNetwork
+    from modelcrowdnav_amd.utils.trainer import Trainer
+    cpu = torch.device("cpu")
+    assert Trainer.fused_default is False
+    # another architecture: a narrower mlp2, and a module that is no ValueNetwork at all
+    narrow = ValueNetwork(13, 6, [150, 100], [100, 40], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4)
+    with pytest.raises(ValueError, match="shipped SARL value network"):
+        Trainer(narrow, _memory(), cpu, 4, fused=True)
+    with pytest.raises(ValueError, match="shipped SARL value network"):
+        Trainer(torch.nn.Linear(13, 1), _memory(), cpu, 4, fused=True)
+    with pytest.raises(ValueError, match="shipped SARL value network"):
+        Trainer(ValueNetwork(14, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4), _memory(D=14),
+                cpu, 4, fused=True)
+    # a memory with a row of another human count
+    model = R.value_network(13, seed=0)
+    odd = _memory()
+    odd.push((torch.zeros(3, 13), torch.zeros(1)))
+    assert odd._odd
+    with pytest.raises(ValueError, match="_odd"):
+        Trainer(model, odd, cpu, 4, fused=True)
+    # the shipped model and a clean memory, but no GPU to run on
+    with pytest.raises(ValueError, match="not a GPU"):
+        Trainer(model, _memory(), cpu, 4, fused=True)
+    # the class default is what fused=None reads
+    Trainer.fused_default = True
+    try:
+        with pytest.raises(ValueError, match="shipped SARL value network"):
+            Trainer(narrow, _memory(), cpu, 4)
+        assert Trainer(narrow, _memory(), cpu, 4, fused=False).fused is False
+    finally:
+        Trainer.fused_default = False
+
+
+def test_unfused_trainer_is_unaffected():
+    """fused=False (and the default) takes the torch path whatever the model and the memory are: the refusals above are
+    the fused path's alone, and two default trainers from the same seed still walk the same weights."""
+    from modelcrowdnav_amd.policy.sarl import ValueNetwork
+    from modelcrowdnav_amd.utils.trainer import Trainer
+    cpu = torch.device("cpu")
+    out = []
+    for kw in ({}, {"fused": False}, {"fused": None}):
+        torch.manual_seed(4)
+        narrow = ValueNetwork(13, 6, [150, 100], [100, 40], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4)
+        mem = _memory()
+        mem.push((torch.zeros(3, 13), torch.zeros(1)))              # an _odd row: the torch path trains on its zero slot
+        tr = Trainer(narrow, mem, cpu, 4, **kw)
+        assert tr.fused is False and tr._fz is None
+        tr._gen.manual_seed(9)
+        tr.set_learning_rate(0.01)
+        losses = [tr.optimize_batch(2), tr.optimize_epoch(1)]
+        assert tr._fz is None and tr.last_rows is None
+        out.append((losses, [p.detach().clone() for p in narrow.parameters()]))
+    for losses, params in out[1:]:
+        assert losses == out[0][0]
+        assert all(torch.equal(a, b) for a, b in zip(params, out[0][1]))

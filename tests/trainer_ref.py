@@ -1,0 +1,106 @@
+"""Float64 yardstick of the value-network training step: the SAME ValueNetwork module (policy/sarl.py) in
+torch.float64 with torch autograd on the CPU -- MSE loss, the gradient as one flat vector in state_dict order, and k
+SGD-momentum steps on given batches by torch's own rule (buf = momentum buf + grad with the first buf = grad,
+p = p - lr buf), written out in float64 tensor ops.  Every tolerance of tests/test_fused_trainer_gpu.py is measured
+against this; nothing here touches a GPU or the HIP library's kernels."""
+import copy
+
+import numpy as np
+import torch
+
+SHIPPED = dict(mlp1=[150, 100], mlp2=[100, 50], mlp3=[150, 100, 100, 1], attention=[100, 100, 1])
+
+
+def value_network(input_dim, seed):
+    """A shipped-dimension SARL ValueNetwork (input_dim 13, or 61 for OM-SARL) with torch's default initialisation
+    under `seed`, float32 on the CPU."""
+    from modelcrowdnav_amd.policy.sarl import ValueNetwork
+    torch.manual_seed(seed)
+    return ValueNetwork(input_dim, 6, SHIPPED["mlp1"], SHIPPED["mlp2"], SHIPPED["mlp3"], SHIPPED["attention"], True, 1.0, 4)
+
+
+def layout(input_dim):
+    """[(state_dict key, offset, shape)] of the flat parameter / gradient / momentum buffers, written out by hand:
+    state_dict order, each tensor row-major as torch stores it."""
+    dims = [("mlp1.0", input_dim, 150), ("mlp1.2", 150, 100), ("mlp2.0", 100, 100), ("mlp2.2", 100, 50),
+            ("attention.0", 200, 100), ("attention.2", 100, 100), ("attention.4", 100, 1),
+            ("mlp3.0", 56, 150), ("mlp3.2", 150, 100), ("mlp3.4", 100, 100), ("mlp3.6", 100, 1)]
+    table, off = [], 0
+    for name, fan_in, fan_out in dims:
+        table.append((name + ".weight", off, (fan_out, fan_in)))
+        off += fan_in * fan_out
+        table.append((name + ".bias", off, (fan_out,)))
+        off += fan_out
+    return table, off
+
+
+def states_and_values(rows, N, input_dim, seed):
+    """`rows` memory rows: randn states [rows, N, input_dim] whose robot columns (the first six) are shared by the
+    humans of a row, as in a rotated joint state, and randn values [rows, 1].  float32."""
+    g = torch.Generator().manual_seed(seed)
+    s = torch.randn(rows, N, input_dim, generator=g)
+    s[:, :, :6] = s[:, :1, :6]
+    return s, torch.randn(rows, 1, generator=g)
+
+
+def as64(model):
+    m = copy.deepcopy(model).cpu().double()
+    for p in m.parameters():
+        p.grad = None
+    return m
+
+
+def flat(tensors):
+    return np.concatenate([t.detach().cpu().numpy().reshape(-1) for t in tensors])
+
+
+def loss_and_grad(model, states, values):
+    """torch autograd on `model` as it is (its dtype and device): (loss as a Python float of the model's precision,
+    flat gradient as a numpy array in state_dict order)."""
+    for p in model.parameters():
+        p.grad = None
+    loss = torch.nn.functional.mse_loss(model(states), values)
+    loss.backward()
+    return loss.detach().cpu().item(), flat([p.grad for p in model.parameters()])
+
+
+def loss_and_grad64(model, states, values):
+    """The yardstick: loss and flat gradient of the float32 `model` on float32 (states [B,N,D], values [B,1]), every
+    operation in float64."""
+    return loss_and_grad(as64(model), states.detach().cpu().double(), values.detach().cpu().double())
+
+
+def sgd64(model, states, values, batches, lr, momentum=0.9, buf=None):
+    """k = len(batches) SGD-momentum steps in float64 from the float32 `model`'s weights: step s trains on the memory
+    rows batches[s].  Returns (losses [k], trained float64 module, momentum buffers)."""
+    m = as64(model)
+    s64, v64 = states.detach().cpu().double(), values.detach().cpu().double().reshape(-1, 1)
+    losses = []
+    for rows in batches:
+        rows = torch.as_tensor(np.asarray(rows), dtype=torch.long)
+        for p in m.parameters():
+            p.grad = None
+        loss = torch.nn.functional.mse_loss(m(s64[rows]), v64[rows])
+        loss.backward()
+        losses.append(loss.item())
+        with torch.no_grad():
+            grads = [p.grad.clone() for p in m.parameters()]
+            buf = grads if buf is None else [momentum * b + g for b, g in zip(buf, grads)]
+            for p, b in zip(m.parameters(), buf):
+                p.sub_(lr * b)
+    return losses, m, buf
+
+
+def tensor_errors(got_flat, want_flat, input_dim):
+    """{state_dict key: (max |got - want|, max |want|)} over the tensors of the flat layout: numerator and denominator
+    of the relative error max |got - want| / max |want|, kept apart because a tensor's float64 gradient can be exactly
+    0 (one human: the softmax weight is 1 whatever the score, so attention gets no gradient), where the quotient is
+    0 / 0 or x / 0.  Two errors against the same `want` compare by their numerators."""
+    table, total = layout(input_dim)
+    assert got_flat.shape == want_flat.shape == (total,)
+    out = {}
+    for name, off, shape in table:
+        n = int(np.prod(shape))
+        g, w = got_flat[off:off + n].astype(np.float64), want_flat[off:off + n].astype(np.float64)
+        out[name] = (float(np.abs(g - w).max()), float(np.abs(w).max()))
+    return out

@@ -6,6 +6,7 @@ human-policy modes, measured with HIP events around a hipGraph of back-to-back l
     python tools/kbench.py --sgan-predict --sizes 4096 --humans 10,5 --samples 1,20 --steps 8,12
     python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
     python tools/kbench.py --finish [--humans 5,10] [--sizes 4096]   (mcn_orca_finish vs one mcn_orca_batch launch per step)
+    python tools/kbench.py --trainer [--humans 5,10]   (Trainer.optimize_batch(100): fused HIP step vs torch autograd)
 """
 import argparse
 import os
@@ -108,7 +109,14 @@ def main():
     ap.add_argument("--closed-loop", action="store_true",
                     help="time one 128-step mcn_env_rollout_orca launch (with and without traces) at --sizes x --humans "
                          "against 128 x (ORCA.predict_batch + env.step) and against the per-step Explorer loop body")
+    ap.add_argument("--trainer", action="store_true",
+                    help="time Trainer.optimize_batch(100) at batch 100 x --humans: fused HIP step (fused=True) against "
+                         "the torch path, five alternating repeats")
     a = ap.parse_args()
+    if a.trainer:
+        for N in [int(x) for x in str(a.humans).split(",")]:
+            trainer_bench(N)
+        return
     if a.closed_loop:
         for N in [int(x) for x in str(a.humans).split(",")]:
             for E in [int(x) for x in a.sizes.split(",")]:
@@ -194,6 +202,50 @@ def main():
         del env
 
 
+
+
+def trainer_bench(N, batch=100, num_batches=100, rows=20000, reps=5):
+    """Wall time of one Trainer.optimize_batch(num_batches) call -- what train.py makes after every episode -- with the
+    fused HIP step and with torch autograd + optim.SGD, on the same seeded SARL network and device memory.  The two
+    paths alternate within one process (fused, torch, fused, ...) so that clock and cache state drift hits both; one
+    untimed call of each first.  The call ends with its own device-to-host copy of the losses, so host time is device
+    time plus launch overhead: that overhead is what the fused step is about."""
+    import copy
+    import time
+    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd.policy.sarl import SARL
+    from modelcrowdnav_amd.utils.memory import ReplayMemory
+    from modelcrowdnav_amd.utils.trainer import Trainer
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    pol = SARL()
+    pol.configure(configs.policy_config())
+    g = torch.Generator().manual_seed(1)
+    states = torch.randn(rows, N, 13, generator=g)
+    states[:, :, :6] = states[:, :1, :6]
+    values = torch.tanh(states[:, :, 6].mean(1))
+    mem = ReplayMemory(rows, device=dev)
+    mem.push_batch(states.to(dev), values.to(dev))
+    trainers = {}
+    for name, fused in (("fused", True), ("torch", False)):
+        tr = Trainer(copy.deepcopy(pol.model).to(dev), mem, dev, batch, fused=fused)
+        tr._gen.manual_seed(2)
+        tr.set_learning_rate(0.001)
+        tr.optimize_batch(num_batches)                       # untimed: allocations, module load, first-launch costs
+        trainers[name] = tr
+    times = {"fused": [], "torch": []}
+    for _ in range(reps):
+        for name in ("fused", "torch"):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            trainers[name].optimize_batch(num_batches)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+    for name in ("fused", "torch"):
+        t = np.asarray(times[name])
+        print("trainer N=%d batch=%d optimize_batch(%d) %-5s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats; %.1f us / step)"
+              % (N, batch, num_batches, name, np.median(t), t.min(), t.max(), reps, np.median(t) * 1e3 / num_batches))
+    print("trainer N=%d: torch / fused = %.2f (medians)" % (N, np.median(times["torch"]) / np.median(times["fused"])))
 
 
 def closed_loop_bench(E, N, T=128, reps=5):
