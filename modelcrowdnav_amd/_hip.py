@@ -305,6 +305,22 @@ def ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def env_state_of(obj):
+    """EnvState of an object that holds the state tensors as attributes named like the struct's fields (a VecCrowdSim,
+    a shadow view of one); a missing or None attribute -- `hcount` of a plain env -- is a null pointer."""
+    return EnvState(*[ptr(getattr(obj, k, None)) for k, _ in EnvState._fields_])
+
+
+def with_hcount(st, hcount):
+    """The EnvState `st` showing only the first hcount[e] pedestrians of env e ([E] int32 device tensor): a copy with
+    that pointer; `st` itself for None."""
+    if hcount is None:
+        return st
+    st = EnvState.from_buffer_copy(st)
+    st.hcount = ptr(hcount)
+    return st
+
+
 def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 

@@ -49,3 +49,15 @@ def pack_linear(W, b, kmap, omap, dev, bias=True, host=False, what="mcn_pack_lin
                                         KT, om, NT, wf.ctypes.data_as(fp), bf.ctypes.data_as(fp) if bias else None), what)
     out = (torch.from_numpy(wf).to(dev), torch.from_numpy(bf).to(dev) if bias else None)
     return out + (wf,) if host else out
+
+
+def pack_layers(net, plan, dev):
+    """A network of Linear layers into the ctypes struct `net`: plan rows (name, weight, bias, kmap, omap) go through
+    pack_linear into the fields w_<name> / b_<name>.  Returns (net, [device tensors kept alive])."""
+    keep = []
+    for name, W, b, kmap, omap in plan:
+        dw, db = pack_linear(W, b, kmap, omap, dev)
+        keep += [dw, db]
+        setattr(net, "w_" + name, dw.data_ptr())
+        setattr(net, "b_" + name, db.data_ptr())
+    return net, keep

@@ -137,9 +137,7 @@ class VecCrowdSim(object):
         self.human_act = z(E, N, 2)
         self.nobs_pos, self.nobs_vel = z(E, N, 2), z(E, N, 2)
         self._alloc_N = N
-        self._st = _hip.EnvState(*[_hip.ptr(t) for t in (self.hpos, self.hvel, self.hgoal, self.hrad, self.hvpref,
-                                                         self.rpos, self.rvel, self.rgoal, self.rrad, self.rvpref,
-                                                         self.rtheta, self.gtime, self.human_times)])
+        self._st = _hip.env_state_of(self)
         # work queue of the deferred 3-D LP (mcn.h: mcn_env_out.lp3_queue): zero-filled once, then the kernels' own
         # (the library parks 3-D LPs only for crowds of >= 8 ORCA neighbours in batches of >= 16 384 wavefronts, or when
         #  mcn_tuning.lp3_defer forces it: small queues are always provided, large ones only where they will be used)
@@ -285,6 +283,14 @@ class VecCrowdSim(object):
     def observation(self):
         return ObsBatch(self.hpos, self.hvel, self.hrad)
 
+    def _env_call(self, name, human_policy, social_force, *args):
+        """The C entry `name` on this env's configuration, or its social-force form `name`_sf, which takes the model's
+        strength / range / relaxation_rate right after the configuration."""
+        if social_force:
+            name, sf = name + "_sf", self._sf
+            args = (sf.strength, sf.range, sf.relaxation_rate) + args
+        _hip.check(getattr(_hip.lib, name)(self._cfg_struct(human_policy), *args), name)
+
     def step(self, actions, update=True, given_v=None):
         """crowd_sim.py:331-434 for every env: one mcn_env_step (social-force humans: mcn_env_step_sf) launch, no host sync.
 
@@ -302,18 +308,12 @@ class VecCrowdSim(object):
                 given_v = given_v.to(self.device, torch.float64).contiguous()
             if tuple(given_v.shape) != (E, N, 2):
                 raise ValueError("given_v must be [E,N,2]")
-        cfg = self._cfg_struct(policy)
         out = self._out if self.export_human_actions else self._out_lean
         roll = self._roll if (self._roll is not None and update) else None
-        if policy is None and self.human_policy_name == "socialforce":
-            sf = self._sf
-            rc = _hip.lib.mcn_env_step_sf(cfg, sf.strength, sf.range, sf.relaxation_rate, self._st, _hip.ptr(actions),
-                                          out, roll, E, N, 1 if update else 0, _hip.stream_ptr(self.device))
-            _hip.check(rc, "mcn_env_step_sf")
-        else:
-            rc = _hip.lib.mcn_env_step(cfg, self._st, _hip.ptr(actions), _hip.ptr(given_v), out, roll,
-                                       E, N, 1 if update else 0, _hip.stream_ptr(self.device))
-            _hip.check(rc, "mcn_env_step")
+        social_force = policy is None and self.human_policy_name == "socialforce"     # that entry takes no given_v
+        self._env_call("mcn_env_step", policy, social_force, self._st, _hip.ptr(actions),
+                       *(() if social_force else (_hip.ptr(given_v),)), out, roll, E, N, 1 if update else 0,
+                       _hip.stream_ptr(self.device))
         if update:
             ob = self.observation()
         else:
@@ -332,16 +332,8 @@ class VecCrowdSim(object):
         if actions.dtype != torch.float64 or not actions.is_contiguous() or actions.device != self.device:
             actions = actions.to(self.device, torch.float64).contiguous()
         out = self._out if self.export_human_actions else self._out_lean
-        if self.human_policy_name == "socialforce":
-            sf = self._sf
-            rc = _hip.lib.mcn_env_rollout_sf(self._cfg_struct(None), sf.strength, sf.range, sf.relaxation_rate, self._st,
-                                             _hip.ptr(actions), int(actions.shape[0]), out, self._roll, E, N,
-                                             _hip.stream_ptr(self.device))
-            _hip.check(rc, "mcn_env_rollout_sf")
-        else:
-            rc = _hip.lib.mcn_env_rollout(self._cfg_struct(None), self._st, _hip.ptr(actions), int(actions.shape[0]),
-                                          out, self._roll, E, N, _hip.stream_ptr(self.device))
-            _hip.check(rc, "mcn_env_rollout")
+        self._env_call("mcn_env_rollout", None, self.human_policy_name == "socialforce", self._st, _hip.ptr(actions),
+                       int(actions.shape[0]), out, self._roll, E, N, _hip.stream_ptr(self.device))
         return self.observation(), self.reward, self.done, self.info
 
     def rollout_orca(self, policy, T, trace=False):

@@ -52,7 +52,9 @@ import logging
 import torch
 
 from .. import _hip
-from .._pack import ident as _ident, natural as _natural, pack_linear
+from types import SimpleNamespace
+
+from .._pack import ident as _ident, natural as _natural, pack_layers
 from ..envs.policy.policy import Policy
 from ..envs.utils.action import ActionRot, ActionXY
 from ..envs.utils.state import FullState, ObservableState
@@ -105,13 +107,8 @@ def pack_cadrl_network(model, dev):
             ("l1", "value_network.2", _ident(150, 10), _ident(100, 7)),
             ("l2", "value_network.4", _ident(100, 7), _ident(100, 7)),
             ("l3", "value_network.6", _ident(100, 7), _ident(1, 1))]
-    net, keep = _hip.CadrlNet(), []
-    for name, key, kmap, omap in plan:
-        dw, db = pack_linear(sd[key + ".weight"], sd[key + ".bias"], kmap, omap, dev)
-        keep += [dw, db]
-        setattr(net, "w_" + name, dw.data_ptr())
-        setattr(net, "b_" + name, db.data_ptr())
-    return net, keep
+    return pack_layers(_hip.CadrlNet(), [(name, sd[key + ".weight"], sd[key + ".bias"], kmap, omap)
+                                         for name, key, kmap, omap in plan], dev)
 
 
 class CADRL(Policy):
@@ -142,7 +139,8 @@ class CADRL(Policy):
         self.human_state_dim = 7
         self.joint_state_dim = self.self_state_dim + self.human_state_dim
         self._action_table = None
-        self._frags = None        # packed MFMA operand fragments (device) + the weight stamp they were packed at
+        self._table_dev = None    # (host table, device, its device copy): _table()
+        self._frags = None       # packed MFMA operand fragments (device) + the weight stamp they were packed at
         self._ws = None
         self._bufs = {}
 
@@ -215,8 +213,9 @@ class CADRL(Policy):
 
     # ------------------------------------------------------------------ reference surface (E = 1)
     def predict(self, state):
-        """cadrl.py:131-178: the minimum over the humans of the value network, maximised over the action table; one
-        mcn_cadrl_predict launch.  Returns None when every value is NaN (the reference's `max_action = None`)."""
+        """cadrl.py:131-178 = multi_human_rl.py:14-63 around the look-ahead, in the reference's order: attribute
+        checks, the reach-destination short cut, the action space, ONE draw from numpy's global stream (unconditional),
+        the epsilon test or `_greedy_action` (one look-ahead launch), then `last_state` in phase 'train'."""
         if self.phase is None or self.device is None:
             raise AttributeError("Phase, device attributes have to be set!")
         if self.phase == "train" and self.epsilon is None:
@@ -229,49 +228,52 @@ class CADRL(Policy):
         if self.phase == "train" and probability < self.epsilon:
             max_action = self.action_space[np.random.choice(len(self.action_space))]
         else:
-            values = self._predict_one(state)
-            self.action_values = values.tolist()
-            idx = -1
-            for i, v in enumerate(self.action_values):            # strict '>' from -inf: NaN never wins
-                if v > (self.action_values[idx] if idx >= 0 else float("-inf")):
-                    idx = i
-            max_action = self.action_space[idx] if idx >= 0 else None
+            max_action = self._greedy_action(state)
         if self.phase == "train":
             self.last_state = self.transform(state)
         return max_action
 
-    def _predict_one(self, state, order_out=None):
-        """The E = 1 look-ahead of `state` (host JointState): values [A] (numpy float64)."""
+    def _greedy_action(self, state):
+        """The minimum over the humans of the value network, maximised over the action table; one mcn_cadrl_predict
+        launch.  None when every value is NaN (the reference's `max_action = None`)."""
+        st, _stage, N, dev = self._stage_joint_state(state)
+        values, _, _, _ = self._lookahead(st, 1, N, dev, env_next=self._env_next_of_host_env())
+        self.action_values = values[0].cpu().numpy().tolist()
+        idx = -1
+        for i, v in enumerate(self.action_values):            # strict '>' from -inf: NaN never wins
+            if v > (self.action_values[idx] if idx >= 0 else float("-inf")):
+                idx = i
+        return self.action_space[idx] if idx >= 0 else None
+
+    def _stage_joint_state(self, state):
+        """A host JointState as the E = 1 env state of a look-ahead: (EnvState, the staged device tensor its pointers
+        point into -- keep it until the launch is issued --, N, device).  One host row, one host-to-device copy; the
+        state arrays are views of it (16-byte aligned: pairs first)."""
         me, humans = state.self_state, state.human_states
-        dev = self._gpu_device()
-        N = len(humans)
-        # one host row, one host-to-device copy; the state arrays are views of it (16-byte aligned: pairs first)
+        dev, N = self._gpu_device(), len(humans)
         row = [c for h in humans for c in (h.px, h.py)] + [c for h in humans for c in (h.vx, h.vy)] + \
               [me.px, me.py, me.vx, me.vy, me.gx, me.gy] + [h.radius for h in humans] + [me.radius, me.v_pref, me.theta]
         stage = torch.tensor(row, dtype=torch.float64).to(dev)
         names = ("hpos", "hvel", "rpos", "rvel", "rgoal", "hrad", "rrad", "rvpref", "rtheta")
         sizes = (2 * N, 2 * N, 2, 2, 2, N, 1, 1, 1)
-        shapes = ((N, 2), (N, 2), (1, 2), (1, 2), (1, 2), (N,), (1,), (1,), (1,))
-        bufs = {k: piece.view(shp) for k, piece, shp in zip(names, torch.split(stage, sizes), shapes)}
-        st = _hip.EnvState()
-        for k, v in bufs.items():
-            setattr(st, k, _hip.ptr(v))
         self._v_pref = me.v_pref
-        env_next = None
-        if self.query_env:
-            venv = self.env.__dict__.get("_vec") if hasattr(self.env, "__dict__") else None
-            if venv is None:
-                raise AttributeError("query_env needs set_env(CrowdSim)")
-            self.env._push_host_state()
-            env_next = self._query_env(venv)
-        values, _, _, _ = self._lookahead(st, 1, N, dev, env_next=env_next)
-        return values[0].cpu().numpy()
+        return _hip.env_state_of(SimpleNamespace(**dict(zip(names, torch.split(stage, sizes))))), stage, N, dev
+
+    def _env_next_of_host_env(self):
+        """`query_env` at E = 1: the reference asks its env (whose internal state is the current one) once per action;
+        here the E = 1 view's batched env answers for the whole table at once (`_query_env`).  None without query_env."""
+        if not self.query_env:
+            return None
+        venv = self.env.__dict__.get("_vec") if hasattr(self.env, "__dict__") else None
+        if venv is None:
+            raise AttributeError("query_env needs set_env(CrowdSim)")
+        self.env._push_host_state()
+        return self._query_env(venv)
 
     def _pack(self, dev):
         return pack_cadrl_network(self.model, dev)
 
-    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
-        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, npos, nvel, rew, epsilon, seed, want_attention):
         rc = _hip.lib.mcn_cadrl_predict(C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin,
                                         _hip.ptr(b["values"]), _hip.ptr(b["best"]), _hip.ptr(b["best_val"]),
                                         _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew), _hip.ptr(b["action"]),
@@ -322,7 +324,7 @@ class CADRL(Policy):
                 "best": torch.empty(E, dtype=torch.int32, device=dev),
                 "best_val": torch.empty(E, dtype=torch.float64, device=dev),
                 "action": torch.empty(E, 2, dtype=torch.float64, device=dev),
-                "table": torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev),
+                "table": self._table(dev),
                 "att": None,
             }
         b = self._bufs
@@ -335,8 +337,16 @@ class CADRL(Policy):
         # a fresh 63-bit seed per call from torch's host generator (no device launch): torch.manual_seed() makes
         # training rollouts reproducible
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if epsilon > 0 else 0
-        self._launch(net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention)
+        self._launch(net, st, b, A, E, N, dev, kin, gamma_pow, npos, nvel, rew, epsilon, seed, want_attention)
         return b["values"], b["best"], b["best_val"], b["att"]
+
+    def _table(self, dev):
+        """The action table on `dev`: uploaded once per table and device."""
+        c = self._table_dev
+        if c is None or c[0] is not self._action_table or c[1] != dev:
+            c = self._table_dev = (self._action_table, dev,
+                                   torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev))
+        return c[2]
 
     def _query_env(self, venv):
         """`query_env = true` (multi_human_rl.py:37-38): what `env.onestep_lookahead(action)` returns for every action
@@ -347,19 +357,14 @@ class CADRL(Policy):
         Returns (next_hpos [E,N,2], next_hvel [E,N,2], rewards [E,A])."""
         E, N, dev = venv.num_envs, venv._alloc_N, venv.device
         A = len(self.action_space)
-        table = self._bufs["table"] if self._bufs.get("table") is not None else \
-            torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev)
         ob, _, _, _ = venv.onestep_lookahead(torch.zeros(E, 2, dtype=torch.float64, device=dev))
         npos, nvel = ob.pos.clone(), ob.vel.clone()
         rep = lambda t: t.repeat_interleave(A, 0).contiguous()
         x = dict(hpos=rep(venv.hpos), hvel=rep(venv.hvel), hrad=rep(venv.hrad), rpos=rep(venv.rpos), rvel=rep(venv.rvel),
                  rgoal=rep(venv.rgoal), rrad=rep(venv.rrad), rvpref=rep(venv.rvpref), rtheta=rep(venv.rtheta),
                  gtime=rep(venv.gtime))
-        st = _hip.EnvState()
-        for k, v in x.items():
-            setattr(st, k, _hip.ptr(v))
-        st.hgoal, st.hvpref = _hip.ptr(x["hpos"]), _hip.ptr(x["hrad"])      # not read with given velocities
-        acts = table.repeat(E, 1).contiguous()
+        st = _hip.env_state_of(SimpleNamespace(hgoal=x["hpos"], hvpref=x["hrad"], **x))  # not read with given velocities
+        acts = self._table(dev).repeat(E, 1).contiguous()
         given = rep(nvel)
         rec = torch.zeros(E * A, 3, dtype=torch.float64, device=dev)
         out = _hip.EnvOut(_hip.ptr(rec), None, None, None)
@@ -385,18 +390,14 @@ class CADRL(Policy):
             self.build_action_space(float(env.robot.v_pref))
         dev = env.device
         self._v_pref = float(env.robot.v_pref)
-        st = env._st
-        if hcount is not None:
-            if hcount.dtype != torch.int32 or not hcount.is_contiguous() or hcount.numel() != env.num_envs:
-                raise ValueError("hcount must be a contiguous int32 tensor with one entry per env")
-            st = _hip.EnvState.from_buffer_copy(env._st)
-            st.hcount = _hip.ptr(hcount)
+        if hcount is not None and (hcount.dtype != torch.int32 or not hcount.is_contiguous() or
+                                   hcount.numel() != env.num_envs):
+            raise ValueError("hcount must be a contiguous int32 tensor with one entry per env")
+        st = _hip.with_hcount(env._st, hcount)
         env_next = None
         if self.query_env:
             if hcount is not None:
                 raise NotImplementedError("query_env with per-env pedestrian counts")
-            if self._bufs.get("table") is None:
-                self._bufs["table"] = torch.from_numpy(np.ascontiguousarray(self._action_table)).to(dev)
             env_next = self._query_env(env)
         eps = float(getattr(self, "epsilon", 0) or 0) if self.phase == "train" else 0.0
         # epsilon-greedy happens inside the look-ahead's argmax kernel (one draw per env per step from a counter-based

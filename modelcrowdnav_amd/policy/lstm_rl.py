@@ -15,7 +15,8 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
-from .cadrl import _ident, _natural, _state_arrays, mlp, pack_linear
+from .._pack import ident as _ident, natural as _natural, pack_layers
+from .cadrl import _state_arrays, mlp
 from .multi_human_rl import MultiHumanRL
 
 
@@ -69,13 +70,7 @@ def pack_lstm_rl_network(model, dev):
             ("m1", sd["mlp.2.weight"], sd["mlp.2.bias"], _ident(150, 10), _ident(100, 7)),
             ("m2", sd["mlp.4.weight"], sd["mlp.4.bias"], _ident(100, 7), _ident(100, 7)),
             ("m3", sd["mlp.6.weight"], sd["mlp.6.bias"], _ident(100, 7), _ident(1, 1))]
-    net, keep = _hip.LstmRLNet(), []
-    for name, W, b, kmap, omap in plan:
-        dw, db = pack_linear(W, b, kmap, omap, dev)
-        keep += [dw, db]
-        setattr(net, "w_" + name, dw.data_ptr())
-        setattr(net, "b_" + name, db.data_ptr())
-    return net, keep
+    return pack_layers(_hip.LstmRLNet(), plan, dev)
 
 
 def sort_humans(state):
@@ -117,10 +112,9 @@ class LstmRL(MultiHumanRL):
     def _pack(self, dev):
         return pack_lstm_rl_network(self.model, dev)
 
-    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, npos, nvel, rew, epsilon, seed, want_attention):
         if b.get("order") is None:
             b["order"] = torch.empty(E, N, dtype=torch.int32, device=dev)
-        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
         rc = _hip.lib.mcn_lstm_rl_predict(C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow,
                                           kin, _hip.ptr(b["values"]), _hip.ptr(b["best"]), _hip.ptr(b["best_val"]),
                                           _hip.ptr(b["order"]), _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew),
@@ -132,13 +126,9 @@ class LstmRL(MultiHumanRL):
         the order the look-ahead kernel uses without query_env).  hcount: as predict_batch (slots >= hcount[e] keep
         their index)."""
         E, N = env.num_envs, env._alloc_N
-        st = env._st
-        if hcount is not None:
-            st = _hip.EnvState.from_buffer_copy(env._st)
-            st.hcount = _hip.ptr(hcount)
         order = torch.empty(E, N, dtype=torch.int32, device=env.device)
-        _hip.check(_hip.lib.mcn_lstm_rl_order(st, _hip.ptr(order), E, N, _hip.stream_ptr(env.device)),
-                   "mcn_lstm_rl_order")
+        _hip.check(_hip.lib.mcn_lstm_rl_order(_hip.with_hcount(env._st, hcount), _hip.ptr(order), E, N,
+                                              _hip.stream_ptr(env.device)), "mcn_lstm_rl_order")
         return order
 
     def transform_batch(self, env):

@@ -13,7 +13,6 @@ import torch
 
 from .. import _hip
 from .cadrl import CADRL
-from ..envs.utils.action import ActionRot, ActionXY
 
 
 OM_CELL_NUM, OM_CHANNELS = 4, 3           # the [om] geometry sarl_om.hip is built for (policy.config); any cell_size
@@ -29,67 +28,31 @@ class MultiHumanRL(CADRL):
     def _pack(self, dev):
         raise NotImplementedError
 
-    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, npos, nvel, rew, epsilon, seed, want_attention):
         raise NotImplementedError
 
     # ------------------------------------------------------------------ reference surface (E = 1)
-    def predict(self, state):
-        if self.phase is None or self.device is None:
-            raise AttributeError("Phase, device attributes have to be set!")
-        if self.phase == "train" and self.epsilon is None:
-            raise AttributeError("Epsilon attribute has to be set in training phase")
-        zero = ActionXY(0, 0) if self.kinematics == "holonomic" else ActionRot(0, 0)
-        if self.reach_destination(state):
-            return zero
-        me, humans = state.self_state, state.human_states
-        if self.action_space is None:
-            self.build_action_space(me.v_pref)
-        probability = np.random.random()                       # drawn unconditionally, as the reference does
-        if self.phase == "train" and probability < self.epsilon:
-            max_action = self.action_space[np.random.choice(len(self.action_space))]
-        else:
-            N = len(humans)
-            if self.with_om:
-                self._om_needs_others(N)
-            dev = self._gpu_device()
-            # one host row, one host-to-device copy; the state arrays are views of it (16-byte aligned: pairs first)
-            row = [c for h in humans for c in (h.px, h.py)] + [c for h in humans for c in (h.vx, h.vy)] + \
-                  [me.px, me.py, me.vx, me.vy, me.gx, me.gy] + [h.radius for h in humans] + [me.radius, me.v_pref, me.theta]
-            stage = torch.tensor(row, dtype=torch.float64).to(dev)
-            names = ("hpos", "hvel", "rpos", "rvel", "rgoal", "hrad", "rrad", "rvpref", "rtheta")
-            sizes = (2 * N, 2 * N, 2, 2, 2, N, 1, 1, 1)
-            shapes = ((N, 2), (N, 2), (1, 2), (1, 2), (1, 2), (N,), (1,), (1,), (1,))
-            bufs = {k: piece.view(shp) for k, piece, shp in zip(names, torch.split(stage, sizes), shapes)}
-            st = _hip.EnvState()
-            for k, v in bufs.items():
-                setattr(st, k, _hip.ptr(v))
-            self._v_pref = me.v_pref
-            env_next = None
-            if self.query_env:
-                # the reference asks its env (whose internal state is the current one) 81 times; here the E = 1 view's
-                # batched env answers for the whole table at once
-                venv = self.env.__dict__.get("_vec") if hasattr(self.env, "__dict__") else None
-                if venv is None:
-                    raise AttributeError("query_env needs set_env(CrowdSim)")
-                self.env._push_host_state()
-                env_next = self._query_env(venv)
-            values, best, _, att = self._lookahead(st, 1, N, dev, want_attention=self._attention, env_next=env_next)
-            vals = values[0].cpu().numpy()
-            self.action_values = vals.tolist()
-            idx = int(best.item())
-            if self._attention:
-                # the reference's model keeps the weights of its LAST forward, i.e. of the last candidate action
-                # (sarl.py:56,88-89), and that is what env.step stores per step; the chosen action's are kept beside them
-                a_host = att[0].cpu().numpy()
-                self._last_attention = a_host[-1].copy()
-                self.chosen_attention_weights = a_host[max(idx, 0)].copy()
-            if idx < 0 or not np.isfinite(vals[idx]):
-                # every value NaN <=> `value > max_value` never fired in the reference loop
-                raise ValueError("Value network is not well trained. ")
-            max_action = self.action_space[idx]
-        if self.phase == "train":
-            self.last_state = self.transform(state)
-        return max_action
+    def _greedy_action(self, state):
+        """multi_human_rl.py:31-57 as one look-ahead launch (`predict` itself is CADRL's): `action_values`, the
+        attention weights, and the ValueError on an all-NaN network."""
+        if self.with_om:
+            self._om_needs_others(len(state.human_states))
+        st, _stage, N, dev = self._stage_joint_state(state)
+        values, best, _, att = self._lookahead(st, 1, N, dev, want_attention=self._attention,
+                                               env_next=self._env_next_of_host_env())
+        vals = values[0].cpu().numpy()
+        self.action_values = vals.tolist()
+        idx = int(best.item())
+        if self._attention:
+            # the reference's model keeps the weights of its LAST forward, i.e. of the last candidate action
+            # (sarl.py:56,88-89), and that is what env.step stores per step; the chosen action's are kept beside them
+            a_host = att[0].cpu().numpy()
+            self._last_attention = a_host[-1].copy()
+            self.chosen_attention_weights = a_host[max(idx, 0)].copy()
+        if idx < 0 or not np.isfinite(vals[idx]):
+            # every value NaN <=> `value > max_value` never fired in the reference loop
+            raise ValueError("Value network is not well trained. ")
+        return self.action_space[idx]
 
     def transform(self, state):
         """multi_human_rl.py:90-104: [N,13] rotated rows (float32) for the replay memory."""
@@ -111,10 +74,7 @@ class MultiHumanRL(CADRL):
         rows = self.rotate(rows).view(E, N, 13)
         if self.with_om:
             # maps of the current states; env.hcount, when the env keeps one, masks as in the look-ahead
-            st, hcount = env._st, getattr(env, "hcount", None)
-            if hcount is not None:
-                st = _hip.EnvState.from_buffer_copy(env._st)
-                st.hcount = _hip.ptr(hcount)
+            st = _hip.with_hcount(env._st, getattr(env, "hcount", None))
             om = torch.empty(E, N, OM_WIDTH, dtype=f, device=env.device)
             self._om_prepare(st, 0.0, None, None, om, E, N, env.device)
             rows = torch.cat([rows, om.to(rows.device)], 2)

@@ -92,15 +92,20 @@ class _SarlNet(C.Structure):
 _hip.check_mirrors({_hip.SIZEOF_SARL_NET: _SarlNet, _hip.SIZEOF_SARL_X3: _SarlX3})
 
 
+def shipped_shapes(input_dim):
+    """Weight shapes of the shipped SARL value network (policy.config:44-50) by state_dict key prefix, in state_dict
+    order: what sarl_value.hip and sarl_train.hip are built for (input_dim 13, or 61 with occupancy maps)."""
+    return {"mlp1.0": (150, input_dim), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
+            "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
+            "mlp3.0": (150, 56), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (1, 100)}
+
+
 def pack_value_network(model, dev, with_om=False):
     """state_dict -> (ctypes mcn_sarl_net, [device tensors kept alive]).  with_om: mlp1.0.weight is (150, 61); its
     columns 0..12 go into `m1a` as for SARL, columns 13..60 and the bias into the fragments of mcn_sarl_om_prepare
     (net.om_w / net.om_b, attributes of the ctypes object beside the C fields)."""
     sd = {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in model.state_dict().items()}
-    expect = {"mlp1.0": (150, 13 + (OM_WIDTH if with_om else 0)), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
-              "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
-              "mlp3.0": (150, 56), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (1, 100)}
-    for k, shp in expect.items():
+    for k, shp in shipped_shapes(13 + (OM_WIDTH if with_om else 0)).items():
         if tuple(sd[k + ".weight"].shape) != shp:
             raise ValueError("sarl_value.hip is built for the shipped SARL dimensions (policy.config:44-50); "
                              "%s.weight is %s, expected %s" % (k, sd[k + ".weight"].shape, shp))
@@ -165,8 +170,7 @@ class SARL(MultiHumanRL):
     def _workspace_bytes(self, E, N, A):
         return _hip.lib.mcn_sarl_workspace_bytes(E, N, A)
 
-    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, env_next, epsilon, seed, want_attention):
-        npos, nvel, rew = env_next if env_next is not None else (None, None, None)
+    def _launch(self, net, st, b, A, E, N, dev, kin, gamma_pow, npos, nvel, rew, epsilon, seed, want_attention):
         head = (C.byref(net), st, _hip.ptr(b["table"]), A, float(self.time_step), gamma_pow, kin, _hip.ptr(b["ws"]),
                 _hip.ptr(b["values"]), _hip.ptr(b["best"]), _hip.ptr(b["best_val"]),
                 _hip.ptr(b["att"]) if want_attention else None, _hip.ptr(npos), _hip.ptr(nvel), _hip.ptr(rew),

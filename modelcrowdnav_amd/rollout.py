@@ -9,9 +9,14 @@ there is one policy launch and one env launch, no host synchronisation; discount
 (explorer.py:124), outcomes, navigation times and the "too close" statistics (:88-90) are accumulated
 in-kernel.  With several ranks, envs are sharded by global env id and the records are combined by ONE
 all_gather (dist.gather_records).
+
+`run_k_episodes` reads top to bottom: `episode_plan` (which case sits in which pool row, host arithmetic only),
+attach, one of three drivers (closed-loop ORCA launch, `action_seq` launch, per-step loop -- each returns the steps
+taken and one trace dict of stacked [T,E,...] tensors), `_push_memory`, `_emit_collected`, `summarize_episodes`, detach.
 """
 import logging
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -23,6 +28,80 @@ from .envs import scenarios as S
 
 def average(xs):
     return sum(xs) / len(xs) if xs else 0
+
+
+def summarize_episodes(returns, infos, times, k, time_limit, returnRate=True, returnNav=False, phase=None, stay=False,
+                       episode=None, print_failure=False, danger=None, time_step=None):
+    """The end of every run_k_episodes (explorer.py:126-151; datagen.py:505-518 is the same arithmetic): per-episode
+    discounted returns, final info codes (_hip.INFO_*) and times -> (result, stats).  `result` is the reference's return
+    tuple: (average return, success, collision, timeout[, average navigation time]), rates when returnRate else counts
+    (returnNav is only honoured together with returnRate).  `stats` holds the counts and avg_nav_time, the mean time
+    of the successful episodes or `time_limit` when there is none.
+    Logging, in the reference's order (nothing without `phase`): the phase line unless `stay`; for phase val / test
+    the danger line, from `danger` = (steps whose info was Danger, sum of their min_dist) over sum(times) / time_step
+    steps; with print_failure the two failure-case lines."""
+    success = sum(1 for c in infos if c == _hip.INFO_REACHGOAL)
+    collision = sum(1 for c in infos if c == _hip.INFO_COLLISION)
+    timeout = sum(1 for c in infos if c == _hip.INFO_TIMEOUT)
+    assert success + collision + timeout == k
+    success_times = [t for t, c in zip(times, infos) if c == _hip.INFO_REACHGOAL]
+    avg_nav_time = sum(success_times) / len(success_times) if success_times else time_limit
+    if phase is not None and not stay:                                      # explorer.py:132
+        extra = "" if episode is None else "in episode {} ".format(episode)
+        logging.info("%-5s %shas success rate: %.2f, collision rate: %.2f, nav time: %.2f, total reward: %.4f",
+                     phase.upper(), extra, success / k, collision / k, avg_nav_time, average(returns))
+    if phase in ("val", "test"):                                            # explorer.py:88-90,138-141
+        too_close, dist_sum = danger
+        logging.info("Frequency of being in danger: %.2f and average min separate distance in danger: %.2f",
+                     too_close / (sum(times) / time_step), dist_sum / too_close if too_close else 0.0)
+    if phase is not None and print_failure:
+        logging.info("Collision cases: %s", " ".join(str(i) for i, c in enumerate(infos) if c == _hip.INFO_COLLISION))
+        logging.info("Timeout cases: %s", " ".join(str(i) for i, c in enumerate(infos) if c == _hip.INFO_TIMEOUT))
+    stats = dict(success=success, collision=collision, timeout=timeout, avg_nav_time=avg_nav_time)
+    if not returnRate:
+        return (average(returns), success, collision, k - success - collision), stats
+    rates = (average(returns), success / k, collision / k, (k - success - collision) / k)
+    return (rates + (avg_nav_time,) if returnNav else rates), stats
+
+
+def episode_plan(first, size, k, E_total, lo, E_local, test_case=None, contiguous_pool=False):
+    """Which case every env plays in every round, as pool rows -- pure host arithmetic, no device, no env.
+    Global episode g < k is case (first + g) % size (or `test_case`, explorer.py:54) and runs in global env g % E_total
+    as that env's round g // E_total; this rank holds the E_local envs from global env `lo` on.  The pool has one row
+    per distinct case in increasing case order; contiguous_pool (the device generator makes a case range) instead has
+    row c - uniq[0] for case c.  The kernel's rule (include/mcn.h, mcn_rollout): round 0 is the loaded row mine[:, 0];
+    every restart takes the env's next_case and advances it by `stride` modulo `pool_size`.
+
+    Returns a namespace: rounds, cases (rounds * E_total of them), uniq, mine [E_local, rounds], pool_size, stride,
+    next_case [E_local], n_full (local envs whose last round is one of the k episodes), danger_short_from (what
+    attach_rollout takes for it), fin_slots."""
+    rounds = -(-k // E_total)                               # episodes per env (ceil)
+    M = rounds * E_total
+    cases = [test_case] * M if test_case is not None else [(first + i) % size for i in range(M)]
+    uniq = sorted(set(cases))
+    if contiguous_pool:
+        pool_size, slot_of = uniq[-1] - uniq[0] + 1, {c: c - uniq[0] for c in uniq}
+    else:
+        pool_size, slot_of = len(uniq), {c: j for j, c in enumerate(uniq)}
+    # env e of this rank plays global episodes (lo + e) + r * E_total, r = 0..rounds-1
+    mine = np.array([[slot_of[cases[(lo + e) + r * E_total]] for r in range(rounds)] for e in range(E_local)],
+                    np.int64).reshape(E_local, rounds)
+    # The row step between rounds is one constant.  M <= size: the M cases are distinct and form a cyclic interval,
+    # so a case's rank among them is a rotation of its episode number i, and i + E_total moves the row by E_total mod
+    # M (= pool_size; a contiguous pool that wraps spans all `size` cases and its row is the case itself).  M > size:
+    # every case occurs, the row is the case, the step is E_total mod size.  test_case: one row, step 0.
+    steps = np.diff(mine, axis=1) % pool_size
+    stride = int(steps.flat[0]) if steps.size else 0
+    assert (steps == stride).all(), "pool rows do not advance by a constant stride"
+    # at least two finished-episode slots: with one the kernel keeps the LATEST episode of an env (mcn.h), and an env
+    # that finishes early keeps replaying its case until the slowest env is done -- with a stochastic robot
+    # (epsilon-greedy, random action_fn) the record would then describe the last repeat instead of the first run.
+    # The "too close" counters cover exactly the k episodes: env g (global) plays `rounds` of them if
+    # (rounds - 1) * E_total + g < k, else one fewer
+    n_full = min(max(k - (rounds - 1) * E_total - lo, 0), E_local)
+    return SimpleNamespace(rounds=rounds, cases=cases, uniq=uniq, mine=mine, pool_size=pool_size, stride=stride,
+                           next_case=mine[:, 1] if rounds > 1 else mine[:, 0], n_full=n_full,
+                           danger_short_from=0 if n_full == E_local else n_full + 1, fin_slots=max(rounds, 2))
 
 
 def value_targets(states, rewards, dones, infos, imitation_learning, gamma_bar, target_model=None, device=None,
@@ -64,7 +143,6 @@ def trace_env_view(tr, rrad, rgoal, rvpref):
     """The [T, E] states of a closed-loop trace (VecCrowdSim.rollout_orca) as ONE batch of T * E envs: an object with
     the attributes a policy's `transform_batch` reads from a VecCrowdSim.  rrad / rgoal / rvpref ([E] / [E,2] / [E]) are
     the robot fields no step changes (a pool restart puts the robot back at the same goal)."""
-    from types import SimpleNamespace
     T, E, N = tr["hrad"].shape
     rob, hum = tr["robot"].reshape(T * E, 5), tr["humans"].reshape(T * E, N, 4)
     const = lambda x: x.unsqueeze(0).expand(T, *x.shape).reshape(T * E, *x.shape[1:])
@@ -116,9 +194,10 @@ class VecExplorer(object):
         return value_targets(states, rewards, dones, infos, imitation_learning, gbar, self.target_model, self.device,
                              return_index=True)
 
-    def _emit_collected(self, cur, ob, rew, done, info, dmin, k, rounds, E_total, update_raw_ob, cache_dir):
-        """Split the recorded [T,E,...] traces at the dones and hand the k episodes out in the reference's order
+    def _emit_collected(self, trace, k, rounds, E_total, update_raw_ob, cache_dir):
+        """Split the recorded [T,E,...] trace at the dones and hand the k episodes out in the reference's order
         (episode g = round * E + env): raw_memory rows, world-model pairs, SGAN cache files."""
+        cur, ob, rew, done, info, dmin = (trace[f].cpu().numpy() for f in ("cur", "ob", "reward", "done", "info", "dmin"))
         T, E = done.shape
         bounds = []
         for e in range(E):
@@ -166,11 +245,122 @@ class VecExplorer(object):
             return False
         return transformer is None or rows_from_trace_ok(transformer, env)
 
-    def _actions(self, step_actions):
-        if step_actions is not None:
-            return step_actions
-        a, _ = self.policy.predict_batch(self.env)
-        return a
+    # ------------------------------------------------------------------ the three drivers
+    # Each advances the env until every env has finished `rounds` episodes or `limit` steps are taken and returns
+    # (steps taken, trace): one dict of stacked [T,E,...] tensors, None when nothing was asked for.  With a
+    # `transformer` it holds the memory fields rows, reward, done, info; with `collect` the collection fields cur
+    # (humans [px,py,vx,vy] before the step), ob (humans [px,py,vx,vy,radius] after it), reward, done, info, dmin.
+    def _all_finished(self, rounds):
+        return int(self.env.rollout_buffers["fin_count"].min().item()) >= rounds
+
+    def _drive_chunks(self, launch, limit, rounds):
+        """`launch(t, n)` for chunks of at most 128 steps (a launch's time is set by its slowest env group)."""
+        t = 0
+        while t < limit:
+            n = min(128, limit - t)
+            launch(t, n)
+            t += n
+            if self._all_finished(rounds):
+                break
+        return t
+
+    def _drive_closed_loop(self, limit, rounds, transformer, collect):
+        """The ORCA robot's solve and the env step, up to 128 steps per launch (VecCrowdSim.rollout_orca); the trace
+        fields are the per-step driver's arithmetic over the launch's trace at once."""
+        env, chunks = self.env, []
+
+        def launch(t, n):
+            tr = env.rollout_orca(self.policy, n, trace=transformer is not None or collect)
+            if collect:
+                tr["hrad_after"] = torch.cat([tr["hrad"][1:], env.hrad.unsqueeze(0)])      # radii after each step
+            if tr is not None:
+                chunks.append(tr)
+        steps = self._drive_chunks(launch, limit, rounds)
+        if not chunks:
+            return steps, None
+        tr = {f: torch.cat([c[f] for c in chunks]) for f in chunks[0]}
+        trace = dict(reward=tr["reward"], done=tr["done"].bool(), info=tr["info"])
+        if transformer is not None:
+            trace["rows"] = trace_state_rows(transformer, tr, env.rrad, env.rgoal, env.rvpref)
+        if collect:
+            trace.update(cur=tr["humans"], dmin=tr["dmin"],
+                         ob=torch.cat([tr["humans"][..., 0:2] + tr["human_act"] * env.time_step, tr["human_act"],
+                                       tr["hrad_after"].unsqueeze(3)], 3))
+        return steps, trace
+
+    def _drive_action_seq(self, action_seq, limit, rounds):
+        """A robot whose actions are known up front: 128 steps per mcn_env_rollout launch, nothing recorded."""
+        limit = min(limit, int(action_seq.shape[0]))
+        return self._drive_chunks(lambda t, n: self.env.rollout(action_seq[t:t + n]), limit, rounds), None
+
+    def _drive_per_step(self, limit, rounds, transformer, collect, action_fn, stay):
+        """One policy launch (or `action_fn(env, t)`, or the zero action of `stay`) and one env launch per step."""
+        env = self.env
+        fields = (["rows"] if transformer is not None else []) + (["cur", "ob", "dmin"] if collect else [])
+        rec = {f: [] for f in fields + ["reward", "done", "info"]} if fields else {}
+        t = 0
+        while t < limit:
+            if transformer is not None:
+                rec["rows"].append(transformer.transform_batch(env))           # the state the action is chosen in
+            if stay:
+                a = torch.zeros(env.num_envs, 2, dtype=torch.float64, device=env.device)
+            else:
+                a = action_fn(env, t) if action_fn is not None else self.policy.predict_batch(env)[0]
+            if collect:
+                prev_pos = env.hpos.clone()
+                rec["cur"].append(torch.cat([prev_pos, env.hvel], 2))
+            env.step(a)
+            if collect:
+                # the observation the reference's step() returns, also for envs that finished and were restarted
+                # in-kernel: humans moved by the velocity they chose (same two roundings as the kernel's integrate)
+                pos = prev_pos + env.human_act * env.time_step
+                rec["ob"].append(torch.cat([pos, env.human_act, env.hrad.unsqueeze(2)], 2))
+                rec["dmin"].append(env.dmin.clone())
+            if rec:
+                rec["reward"].append(env.reward.clone()); rec["done"].append(env.done.bool())
+                rec["info"].append(env.info.clone())
+            t += 1
+            if t % 32 == 0 and self._all_finished(rounds):
+                break
+        return t, ({f: torch.stack(v) for f, v in rec.items()} if rec and t else None)
+
+    def _push_memory(self, trace, k, rounds, E_total, lo, imitation_learning):
+        """Value targets of the trace's k episodes into the memory, in the reference's push order."""
+        dones = trace["done"]
+        # only the first `rounds` episodes of each env are the k requested ones: cut each env's trace there
+        order = torch.cumsum(dones.long(), 0) - dones.long()          # episode number each step belongs to
+        valid = order < rounds
+        gidx = (order * E_total + lo + torch.arange(dones.shape[1], device=dones.device).unsqueeze(0))
+        valid &= gidx < k
+        s, v, idx = self._value_targets(trace["rows"], trace["reward"], dones & valid, trace["info"], imitation_learning)
+        # the reference pushes episode by episode (explorer.py:107-110): rows go to the memory in global episode
+        # order (episode g = round * E_total + env), time order inside an episode -- a stable sort of the
+        # (env, time)-ordered rows by their episode number
+        ep_of_row = gidx.t().reshape(-1)[idx]
+        perm = torch.argsort(ep_of_row, stable=True)
+        s, v = s[perm], v[perm]
+        if hasattr(self.memory, "push_batch"):
+            self.memory.push_batch(s, v)
+        else:                                                         # any object with the reference's push()
+            for row_s, row_v in zip(s, v):
+                self.memory.push((row_s, row_v.reshape(1).to(self.device)))
+
+    def _load_cases(self, plan, phase, n, rule, device_scenarios):
+        """Build the plan's pool (host scenarios, or on the device from the seed `device_scenarios`) and put every
+        env on its round-0 row; returns the pool attach_rollout takes."""
+        env = self.env
+        if device_scenarios is None:
+            pool = S.scenario_pool(env.spec(), phase, plan.uniq, n, rule)
+            env.load_scenarios(pool[plan.mine[:, 0]])
+            return pool
+        if rule not in ("circle_crossing", "square_crossing"):
+            raise NotImplementedError("device scenarios: circle_crossing / square_crossing only")
+        # case ids keyed like the reference's seeds: offset(phase) + case (crowd_sim.py:270-272)
+        offset = {"train": env.case_capacity["val"] + env.case_capacity["test"], "val": 0,
+                  "test": env.case_capacity["val"]}[phase]
+        pool = env.device_pool(device_scenarios, offset + plan.uniq[0], plan.pool_size, n, rule)
+        env.load_device_scenarios(pool, plan.mine[:, 0])
+        return pool
 
     def run_k_episodes(self, k, phase, update_memory=False, imitation_learning=False, episode=None,
                        print_failure=False, returnRate=True, returnNav=False, action_fn=None, max_steps=None,
@@ -204,161 +394,45 @@ class VecExplorer(object):
         if hasattr(self.policy, "set_phase"):
             self.policy.set_phase(phase)
         n, rule = env._phase_rule(phase)
-        first = env.case_counter[phase]
-        size = env.case_size[phase]
-        rounds = -(-k // E_total)                               # episodes per env (ceil)
-        cases = [(first + i) % size for i in range(rounds * E_total)]
-        if test_case is not None:
-            if device_scenarios is not None:
-                raise NotImplementedError("test_case with device scenarios")
-            cases = [test_case] * (rounds * E_total)
-        uniq = sorted(set(cases))
-        if device_scenarios is None:
-            pool = S.scenario_pool(env.spec(), phase, uniq, n, rule)
-            slot_of = {c: j for j, c in enumerate(uniq)}
-        else:
-            if rule not in ("circle_crossing", "square_crossing"):
-                raise NotImplementedError("device scenarios: circle_crossing / square_crossing only")
-            # case ids keyed like the reference's seeds: offset(phase) + case (crowd_sim.py:270-272)
-            offset = {"train": env.case_capacity["val"] + env.case_capacity["test"], "val": 0,
-                      "test": env.case_capacity["val"]}[phase]
-            pool = env.device_pool(device_scenarios, offset + uniq[0], uniq[-1] - uniq[0] + 1, n, rule)
-            slot_of = {c: c - uniq[0] for c in uniq}
-        # env e of this rank plays global episodes (lo + e) + r * E_total, r = 0..rounds-1
-        mine = np.array([[slot_of[cases[(lo + e) + r * E_total]] for r in range(rounds)] for e in range(E_local)])
-        if device_scenarios is None:
-            env.load_scenarios(pool[mine[:, 0]])
-        else:
-            env.load_device_scenarios(pool, mine[:, 0])
-        stride = 0
-        if rounds > 1:
-            # pool slots advance by a constant stride when cases are consecutive (the usual situation)
-            n_pool = len(uniq) if device_scenarios is None else uniq[-1] - uniq[0] + 1
-            d = (mine[:, 1] - mine[:, 0]) % n_pool
-            if not np.all(d == d[0]) or any(np.any((mine[:, r + 1] - mine[:, r]) % n_pool != d[0])
-                                            for r in range(rounds - 1)):
-                # the case list wraps unevenly (e.g. the counter starts near case_size): lay the pool out in episode
-                # order instead, one row per global episode -- then every env advances by exactly E_total rows
-                if device_scenarios is not None:
-                    raise NotImplementedError("device scenarios with a case list that wraps unevenly")
-                pool = pool[[slot_of[c] for c in cases]]
-                mine = np.array([[(lo + e) + r * E_total for r in range(rounds)] for e in range(E_local)])
-                d = np.array([E_total % (rounds * E_total)])
-            stride = int(d[0])
-        # at least two finished-episode slots: with one the kernel keeps the LATEST episode of an env (mcn.h), and an env
-        # that finishes early keeps replaying its case until the slowest env is done -- with a stochastic robot
-        # (epsilon-greedy, random action_fn) the record would then describe the last repeat instead of the first run
-        # the "too close" counters cover exactly the k episodes: env g (global) plays `rounds` of them if
-        # (rounds - 1) * E_total + g < k, else one fewer
-        n_full = min(max(k - (rounds - 1) * E_total - lo, 0), E_local)
-        bufs = env.attach_rollout(self.gamma, pool=pool, case_stride=stride,
-                                  first_cases=(mine[:, 1] if rounds > 1 else mine[:, 0]), fin_slots=max(rounds, 2),
-                                  danger_episodes=rounds, danger_short_from=(0 if n_full == E_local else n_full + 1))
+        first, size = env.case_counter[phase], env.case_size[phase]
+        if test_case is not None and device_scenarios is not None:
+            raise NotImplementedError("test_case with device scenarios")
+        plan = episode_plan(first, size, k, E_total, lo, E_local, test_case, contiguous_pool=device_scenarios is not None)
+        rounds = plan.rounds
+        pool = self._load_cases(plan, phase, n, rule, device_scenarios)
+        bufs = env.attach_rollout(self.gamma, pool=pool, case_stride=plan.stride, first_cases=plan.next_case,
+                                  fin_slots=plan.fin_slots, danger_episodes=rounds,
+                                  danger_short_from=plan.danger_short_from)
         horizon = int(round(env.time_limit / env.time_step)) + 2
         limit = max_steps if max_steps is not None else rounds * horizon
         if update_memory and (self.memory is None or self.gamma is None):
             raise ValueError("Memory or gamma value is not set!")
         transformer = (self.target_policy if imitation_learning else self.policy) if update_memory else None
-        rec_s, rec_r, rec_d, rec_i = [], [], [], []
         collect = self.raw_memory is not None or update_raw_ob or cacheFile is not None
         if collect:
             if ws > 1 or action_seq is not None:
                 raise NotImplementedError("data collection runs in one process, one launch per step")
             keep_export, env.export_human_actions = env.export_human_actions, True
-            col_cur, col_ob, col_r, col_d, col_i, col_m = [], [], [], [], [], []
-        t = 0
-        use_loop = self._closed_loop_ok(transformer, action_fn, action_seq, stay) if closed_loop is None else bool(closed_loop)
-        if use_loop and not self._closed_loop_ok(transformer, action_fn, action_seq, stay):
+        auto = self._closed_loop_ok(transformer, action_fn, action_seq, stay)
+        if closed_loop and not auto:
             raise ValueError("closed_loop=True needs an ORCA robot policy choosing every action, ORCA humans, a holonomic "
                              "robot and memory rows that can be made from the trace")
-        self.last_run_closed_loop = use_loop
-        traces = []
-        if use_loop:
-            want_trace = update_memory or collect
-            while t < limit:
-                n = min(128, limit - t)                      # the chunk rule of the action_seq path below
-                tr = env.rollout_orca(self.policy, n, trace=want_trace)
-                if collect:
-                    tr["hrad_after"] = torch.cat([tr["hrad"][1:], env.hrad.unsqueeze(0)])      # radii after each step
-                if want_trace:
-                    traces.append(tr)
-                t += n
-                if int(bufs["fin_count"].min().item()) >= rounds:
-                    break
-            limit = t                                            # skip the per-step loop below
-            if traces:
-                tr = {k: torch.cat([c[k] for c in traces]) for k in traces[0]}
-                if update_memory:
-                    rec_s = trace_state_rows(transformer, tr, env.rrad, env.rgoal, env.rvpref)
-                    rec_r, rec_d, rec_i = tr["reward"], tr["done"].bool(), tr["info"]
-                if collect:
-                    # the arithmetic of the per-step loop below, over the whole trace at once
-                    col_cur = tr["humans"]
-                    col_ob = torch.cat([tr["humans"][..., 0:2] + tr["human_act"] * env.time_step, tr["human_act"],
-                                        tr["hrad_after"].unsqueeze(3)], 3)
-                    col_r, col_d, col_i, col_m = tr["reward"], tr["done"].bool(), tr["info"], tr["dmin"]
-        if action_seq is not None:
+        self.last_run_closed_loop = auto if closed_loop is None else bool(closed_loop)
+        if self.last_run_closed_loop:
+            steps, trace = self._drive_closed_loop(limit, rounds, transformer, collect)
+        elif action_seq is not None:
             if update_memory:
                 raise ValueError("action_seq rollouts record no per-step states; use action_fn with update_memory")
-            limit = min(limit, int(action_seq.shape[0]))
-            while t < limit:
-                n = min(128, limit - t)                      # a launch's time is set by its slowest env group
-                env.rollout(action_seq[t:t + n])
-                t += n
-                if int(bufs["fin_count"].min().item()) >= rounds:
-                    break
-            limit = t                                            # skip the per-step loop below
-        while t < limit:
-            if update_memory:
-                rec_s.append(transformer.transform_batch(env))           # the state the action is chosen in
-            if stay:
-                a = torch.zeros(E_local, 2, dtype=torch.float64, device=env.device)
-            else:
-                a = action_fn(env, t) if action_fn is not None else self._actions(None)
-            if collect:
-                prev_pos = env.hpos.clone()
-                col_cur.append(torch.cat([prev_pos, env.hvel], 2))
-            env.step(a)
-            if collect:
-                # the observation the reference's step() returns, also for envs that finished and were restarted
-                # in-kernel: humans moved by the velocity they chose (same two roundings as the kernel's integrate)
-                pos = prev_pos + env.human_act * env.time_step
-                col_ob.append(torch.cat([pos, env.human_act, env.hrad.unsqueeze(2)], 2))
-                col_r.append(env.reward.clone()); col_d.append(env.done.bool()); col_i.append(env.info.clone())
-                col_m.append(env.dmin.clone())
-            if update_memory:
-                rec_r.append(env.reward.clone()); rec_d.append(env.done.bool()); rec_i.append(env.info.clone())
-            t += 1
-            if t % 32 == 0 and int(bufs["fin_count"].min().item()) >= rounds:
-                break
-        if int(bufs["fin_count"].min().item()) < rounds:
-            raise RuntimeError("rollout did not finish %d episodes per env within %d steps" % (rounds, limit))
+            steps, trace = self._drive_action_seq(action_seq, limit, rounds)
+        else:
+            steps, trace = self._drive_per_step(limit, rounds, transformer, collect, action_fn, stay)
+        if not self._all_finished(rounds):
+            raise RuntimeError("rollout did not finish %d episodes per env within %d steps" % (rounds, steps))
         if update_memory:
-            # only the first `rounds` episodes of each env are the k requested ones: cut each env's trace there
-            stacked = lambda x: x if torch.is_tensor(x) else torch.stack(x)      # (the closed loop hands whole traces)
-            dones = stacked(rec_d)
-            order = torch.cumsum(dones.long(), 0) - dones.long()          # episode number each step belongs to
-            valid = order < rounds
-            gidx = (order * E_total + lo + torch.arange(E_local, device=dones.device).unsqueeze(0))
-            valid &= gidx < k
-            s, v, idx = self._value_targets(stacked(rec_s), stacked(rec_r), dones & valid, stacked(rec_i),
-                                            imitation_learning)
-            # the reference pushes episode by episode (explorer.py:107-110): rows go to the memory in global episode
-            # order (episode g = round * E_total + env), time order inside an episode -- a stable sort of the
-            # (env, time)-ordered rows by their episode number
-            ep_of_row = gidx.t().reshape(-1)[idx]
-            perm = torch.argsort(ep_of_row, stable=True)
-            s, v = s[perm], v[perm]
-            if hasattr(self.memory, "push_batch"):
-                self.memory.push_batch(s, v)
-            else:                                                         # any object with the reference's push()
-                for row_s, row_v in zip(s, v):
-                    self.memory.push((row_s, row_v.reshape(1).to(self.device)))
+            self._push_memory(trace, k, rounds, E_total, lo, imitation_learning)
         if collect:
             env.export_human_actions = keep_export
-            host = lambda x: (x if torch.is_tensor(x) else torch.stack(x)).cpu().numpy()
-            self._emit_collected(host(col_cur), host(col_ob), host(col_r), host(col_d), host(col_i), host(col_m), k,
-                                 rounds, E_total, update_raw_ob, cacheFile)
+            self._emit_collected(trace, k, rounds, E_total, update_raw_ob, cacheFile)
         env.case_counter[phase] = (first + k) % size if test_case is None else (test_case + 1) % size
         # records in global episode order: episode g = r * E_total + global_env
         # (the envs' "too close" counters ride in the same collective, in the rows of their first episode)
@@ -374,30 +448,11 @@ class VecExplorer(object):
         returns = [float(ret[e, r]) for e, r in order]
         infos = [int(inf[e, r]) for e, r in order]
         times = [float(tim[e, r]) for e, r in order]
-        success = sum(1 for c in infos if c == _hip.INFO_REACHGOAL)
-        collision = sum(1 for c in infos if c == _hip.INFO_COLLISION)
-        timeout = sum(1 for c in infos if c == _hip.INFO_TIMEOUT)
-        assert success + collision + timeout == k
-        success_times = [tm for tm, c in zip(times, infos) if c == _hip.INFO_REACHGOAL]
-        avg_nav_time = sum(success_times) / len(success_times) if success_times else env.time_limit
-        extra = "" if episode is None else "in episode {} ".format(episode)
-        if not stay:                                                       # explorer.py:132
-            logging.info("%-5s %shas success rate: %.2f, collision rate: %.2f, nav time: %.2f, total reward: %.4f",
-                         phase.upper(), extra, success / k, collision / k, avg_nav_time, average(returns))
-        if print_failure:
-            logging.info("Collision cases: %s", " ".join(str(i) for i, c in enumerate(infos) if c == _hip.INFO_COLLISION))
-            logging.info("Timeout cases: %s", " ".join(str(i) for i, c in enumerate(infos) if c == _hip.INFO_TIMEOUT))
-        # "too close" statistics of the k episodes (explorer.py:88-90,138-141)
         too_close, dist_sum = int(round(rec["extras"][0].sum().item())), float(rec["extras"][1].sum().item())
-        if phase in ("val", "test"):
-            num_step = sum(times) / env.time_step
-            logging.info("Frequency of being in danger: %.2f and average min separate distance in danger: %.2f",
-                         too_close / num_step, dist_sum / too_close if too_close else 0.0)
+        result, _ = summarize_episodes(returns, infos, times, k, env.time_limit, returnRate, returnNav,
+                                       phase=phase, stay=stay, episode=episode, print_failure=print_failure,
+                                       danger=(too_close, dist_sum), time_step=env.time_step)
         self.last_records = dict(returns=returns, infos=infos, times=times, danger_steps=too_close,
                                  danger_dist_sum=dist_sum)
         env.detach_rollout()
-        if returnRate and returnNav:
-            return average(returns), success / k, collision / k, (k - success - collision) / k, avg_nav_time
-        if returnRate:
-            return average(returns), success / k, collision / k, (k - success - collision) / k
-        return average(returns), success, collision, (k - success - collision)
+        return result

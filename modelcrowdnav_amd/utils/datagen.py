@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from .. import _hip
-from ..rollout import value_targets, average
+from ..rollout import summarize_episodes, value_targets
 
 
 def _ob_rows(ob):
@@ -72,9 +72,7 @@ class _PolicyView(object):
             setattr(self, k, getattr(env, k))
         self.human_times = z(E, W)
         self.hcount = torch.full((E,), W, dtype=torch.int32, device=dev) if masked else None
-        self._st = _hip.EnvState(*[_hip.ptr(t) for t in (self.hpos, self.hvel, self.hgoal, self.hrad, self.hvpref,
-                                                         self.rpos, self.rvel, self.rgoal, self.rrad, self.rvpref,
-                                                         self.rtheta, self.gtime, self.human_times, self.hcount)])
+        self._st = _hip.env_state_of(self)
 
     def refresh(self, count=None):
         env = self.env
@@ -413,22 +411,13 @@ class VecDataGen(object):
                                      self.target_model, dev)
                 self.memory.push_batch(s, v)
             self._last_wave = dict(states=torch.stack(states), rewards=R, dones=D, infos=I, live=n_live)
-        k = num_sample
         infos_l = [int(c) for c in rec["info"]]
-        reach_goal = sum(1 for c in infos_l if c == _hip.INFO_REACHGOAL)
-        collision = sum(1 for c in infos_l if c == _hip.INFO_COLLISION)
         times = [n * dt for n in rec["steps"]]
-        success_times = [t for t, c in zip(times, infos_l) if c == _hip.INFO_REACHGOAL]
-        avg_nav_time = sum(success_times) / len(success_times) if success_times else env.time_limit
-        avg_ret = average(rec["ret"])
+        result, stats = summarize_episodes(rec["ret"], infos_l, times, num_sample, env.time_limit, returnRate, returnNav)
         logging.info("Exp in mix has success rate: %.2f, collision rate: %.2f, nav time: %.2f, total reward: %.4f",
-                     reach_goal / k, collision / k, avg_nav_time, avg_ret)
+                     stats["success"] / num_sample, stats["collision"] / num_sample, stats["avg_nav_time"], result[0])
         self.last_records = dict(returns=rec["ret"], infos=infos_l, times=times, danger_steps=too_close, samples=picks)
-        if returnRate and returnNav:
-            return avg_ret, reach_goal / k, collision / k, (k - reach_goal - collision) / k, avg_nav_time
-        if returnRate:
-            return avg_ret, reach_goal / k, collision / k, (k - reach_goal - collision) / k
-        return avg_ret, reach_goal, collision, (k - reach_goal - collision)
+        return result
 
     @staticmethod
     def _restore_history(sim, hist0, keep):

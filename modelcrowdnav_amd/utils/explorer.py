@@ -16,17 +16,13 @@ for DataGen, `rawob` pairs (humans' [px,py,vx,vy], their next velocities) for th
 SGAN text cache (`cacheFile/<n>.txt`, one `frame<TAB>ped<TAB>x<TAB>y` line per pedestrian and step).
 """
 import copy
-import logging
 import os
 
 import torch
 
 from ..envs.utils.action import ActionRot, ActionXY
 from ..envs.utils import info as I
-
-
-def average(xs):
-    return sum(xs) / len(xs) if xs else 0
+from ..rollout import summarize_episodes
 
 
 def _push(store, item):
@@ -115,8 +111,8 @@ class Explorer(object):
                                       episode=episode, print_failure=print_failure, returnRate=returnRate,
                                       returnNav=returnNav, stay=stay, update_raw_ob=update_raw_ob, cacheFile=cacheFile,
                                       test_case=test_case)
-        outcome = {"success": [], "collision": [], "timeout": []}       # (episode index, time)
-        too_close, min_dist, returns = 0, [], []
+        infos, times, returns = [], [], []                              # per episode: final info code, its time
+        too_close, min_dist = 0, []
         fcount = 0
         for i in range(k):
             ob = self.env.reset(phase, test_case=test_case)
@@ -143,14 +139,10 @@ class Explorer(object):
                 if isinstance(info, I.Danger):
                     too_close += 1
                     min_dist.append(info.min_dist)
-            if isinstance(info, I.ReachGoal):
-                outcome["success"].append((i, self.env.global_time))
-            elif isinstance(info, I.Collision):
-                outcome["collision"].append((i, self.env.global_time))
-            elif isinstance(info, I.Timeout):
-                outcome["timeout"].append((i, self.env.time_limit))
-            else:
+            if not isinstance(info, (I.ReachGoal, I.Collision, I.Timeout)):
                 raise ValueError("Invalid end signal from environment")
+            infos.append(info.code)
+            times.append(self.env.time_limit if isinstance(info, I.Timeout) else self.env.global_time)
             if update_memory and isinstance(info, (I.ReachGoal, I.Collision)):
                 self.update_memory(states, actions, rewards, imitation_learning)
             if cacheFile is not None:                                   # :116-121
@@ -160,27 +152,9 @@ class Explorer(object):
                         fh.write("%s\t%s\t%s\t%s\n" % (fr[0], fr[1], fr[2], fr[3]))
             returns.append(sum([self._discount(t) * r for t, r in enumerate(rewards)]))
 
-        success, collision = len(outcome["success"]), len(outcome["collision"])
-        assert success + collision + len(outcome["timeout"]) == k
-        times = [t for _, t in outcome["success"]]
-        avg_nav_time = sum(times) / len(times) if times else self.env.time_limit
-        extra = "" if episode is None else "in episode {} ".format(episode)
-        if not stay:
-            logging.info("%-5s %shas success rate: %.2f, collision rate: %.2f, nav time: %.2f, total reward: %.4f",
-                         phase.upper(), extra, success / k, collision / k, avg_nav_time, average(returns))
-        if phase in ("val", "test"):
-            total_steps = sum(t for v in outcome.values() for _, t in v) / self.robot.time_step
-            logging.info("Frequency of being in danger: %.2f and average min separate distance in danger: %.2f",
-                         too_close / total_steps, average(min_dist))
-        if print_failure:
-            logging.info("Collision cases: " + " ".join(str(i) for i, _ in outcome["collision"]))
-            logging.info("Timeout cases: " + " ".join(str(i) for i, _ in outcome["timeout"]))
-        timeout_n = k - success - collision
-        if returnRate and returnNav:
-            return average(returns), success / k, collision / k, timeout_n / k, avg_nav_time
-        if returnRate:
-            return average(returns), success / k, collision / k, timeout_n / k
-        return average(returns), success, collision, timeout_n
+        return summarize_episodes(returns, infos, times, k, self.env.time_limit, returnRate, returnNav, phase=phase,
+                                  stay=stay, episode=episode, print_failure=print_failure,
+                                  danger=(too_close, sum(min_dist)), time_step=self.robot.time_step)[0]
 
     @staticmethod
     def someone_is_moving(ob, min_speed=1e-3):

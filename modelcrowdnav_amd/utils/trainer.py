@@ -128,7 +128,7 @@ class Trainer(object):
         """ValueError for what the fused step is not built for.  The memory is looked at again at every call: rows
         arrive after the trainer is made."""
         from .. import _hip
-        from ..policy.sarl import ValueNetwork
+        from ..policy.sarl import ValueNetwork, shipped_shapes
         m = self.model
         why = None
         if not isinstance(m, ValueNetwork) or not m.with_global_state or m.self_state_dim != 6:
@@ -136,9 +136,7 @@ class Trainer(object):
         else:
             sd = m.state_dict()
             D = sd["mlp1.0.weight"].shape[1] if "mlp1.0.weight" in sd else -1
-            expect = {"mlp1.0": (150, D), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
-                      "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
-                      "mlp3.0": (150, 56), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (1, 100)}
+            expect = shipped_shapes(D)
             keys = [k + s for k in expect for s in (".weight", ".bias")]
             if list(sd.keys()) != keys or D not in (13, 61):
                 why = "its layers are not the shipped ones (policy.config:44-50, input_dim 13 or 61)"
