@@ -682,6 +682,57 @@ int64_t mcn_attn_world_workspace_bytes(int32_t E, int32_t N);
 int mcn_attn_world_step(const mcn_attn_world_net *net, const double *hpos, const double *hvel, const int32_t *hcount,
                         void *workspace, double *out_vel, int32_t E, int32_t N, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * AttentionWorld training step (crowd_nav/utils/trainer_sim.py:48-110 on crowd_nav/policy/world_model.py:54-106).
+ * ---------------------------------------------------------------------------------------------- */
+
+/*
+ * The network is the default AttentionWorld: input_dim 4, global state on, mlp1 150-100, mlp2 100-50, attention
+ * 100-100-1, mlp3 (54 inputs: a pedestrian's own state and the scene's pooled feature) 150-100-100-2.  Parameters,
+ * gradient and the two Adam moments are each ONE flat float32 device buffer in state_dict order -- mlp1.0.weight,
+ * mlp1.0.bias, mlp1.2.*, mlp2.0.*, mlp2.2.*, attention.0.*, attention.2.*, attention.4.*, mlp3.0.*, mlp3.2.*, mlp3.4.*,
+ * mlp3.6.* -- every weight row-major [out][in] as torch stores it: mcn_attn_world_train_param_count() = 94953 floats.
+ */
+int64_t mcn_attn_world_train_param_count(void);
+int64_t mcn_attn_world_train_workspace_bytes(int32_t B, int32_t N);                 /* 0 for arguments the step refuses */
+
+/*
+ * mcn_attn_world_loss_grad -- loss = mean((model(cur[rows]) - nxt[rows])^2) over the B 2N outputs of a mini-batch of B
+ * scenes of N pedestrians, and its gradient by every parameter, with the semantics of torch autograd on
+ * AttentionWorld.forward: the softmax is the un-stabilised exp(s) (s != 0) / sum with the mask a constant, the global
+ * state is the mean of mlp1's output over the scene, ReLU passes gradient where its output is > 0, and where torch gives
+ * NaN (a scene whose scores are all exactly 0 is 0 / 0) so does this.
+ * cur: [rows of the memory][4N] float, nxt: [rows of the memory][2N] float, both device.  rows: [B] int64 device, the
+ * memory row of each scene of the batch, or NULL for rows 0 .. B-1.  The kernel TRUSTS the row indices: the caller checks
+ * them against the number of rows the memory holds before it uploads them.
+ * workspace: mcn_attn_world_train_workspace_bytes(B, N) device bytes, 8-byte aligned; grad: [param_count] float device
+ * out, or NULL for the loss alone (the forward pass only; nothing but `loss` is written for the caller); loss: [1] float
+ * device out, written by the second launch only.  Two launches on `stream` (per-workgroup loss and partial gradients,
+ * then their sum in workgroup order): no atomics, so the same inputs give the same bits, and the loss has the same bits
+ * with and without a gradient.  The forward pass and the sums over the batch run in float64, the backward pass in
+ * float32: loss and grad are within float32 rounding of float64 autograd's, mlp3.6.bias comes from float64 sums, and the
+ * gradient of attention.4.bias, which the softmax makes 0, is returned as exactly 0 (or NaN).  Up to 16 rows (scenes x
+ * pedestrians) per workgroup every activation is in LDS; from N = 17 on the float64 buffers and mlp3's activations of a
+ * scene are in the workspace.
+ * MCN_EINVAL before any launch: a NULL params / cur / nxt / workspace / loss, B < 1, N outside 1 .. MCN_MAX_HUMANS.
+ */
+int mcn_attn_world_loss_grad(const float *params, const float *cur, const float *nxt, const int64_t *rows, int32_t B,
+                             int32_t N, void *workspace, float *grad /* or NULL */, float *loss, void *stream);
+
+/*
+ * mcn_adam_step -- torch.optim.Adam without weight decay or amsgrad over flat float32 device buffers of `count`
+ * elements, step number `step` >= 1: m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2,
+ * p -= (lr / (1 - beta1^step)) m / (sqrt(v) / sqrt(1 - beta2^step) + eps), each element in float64 and rounded once per
+ * stored value.  Zero moments with step = 1 make it torch's first step; a gradient of exactly 0 with zero moments leaves
+ * the parameter's bits.  One launch on `stream`.  torch applies lr, the betas and eps as the float64 values the user
+ * wrote; each arrives here as float32 and is taken as the shortest decimal that rounds to it (0.001f means 0.001), so a
+ * value of up to 7 significant digits is applied exactly as torch applies it.
+ * MCN_EINVAL before any launch: a NULL pointer, count < 1, step < 1, an lr, eps or beta that is not finite, a beta
+ * outside [0, 1).
+ */
+int mcn_adam_step(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr, float beta1,
+                  float beta2, float eps, int32_t step, void *stream);
+
 /*
  * Dispatch overrides (host, process-wide, not stream-ordered; for tests and tuning).  Every env-step arithmetic
  * exists in several kernel decompositions with bit-identical results; by default the entry points pick one from

@@ -189,6 +189,15 @@ def _load():
     lib.mcn_attn_world_workspace_bytes.restype = C.c_int64
     lib.mcn_attn_world_step.argtypes = [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]
     lib.mcn_attn_world_step.restype = C.c_int
+    lib.mcn_attn_world_train_param_count.argtypes, lib.mcn_attn_world_train_param_count.restype = [], C.c_int64
+    lib.mcn_attn_world_train_workspace_bytes.argtypes = [_i, _i]
+    lib.mcn_attn_world_train_workspace_bytes.restype = C.c_int64
+    # params, cur, nxt, rows, B, N, workspace, grad (or NULL), loss, stream
+    lib.mcn_attn_world_loss_grad.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]
+    lib.mcn_attn_world_loss_grad.restype = C.c_int
+    # params, exp_avg, exp_avg_sq, grad, count, lr, beta1, beta2, eps, step, stream
+    lib.mcn_adam_step.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _i, _vp]
+    lib.mcn_adam_step.restype = C.c_int
     lib.mcn_sgan_workspace_bytes.argtypes = [_i, _i]
     lib.mcn_sgan_workspace_bytes.restype = C.c_int64
     lib.mcn_sgan_step.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _i, _i, _vp]
@@ -254,7 +263,8 @@ lib = _load()
 EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_last_rollout_form", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_rollout_orca", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_orca_finish", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict",
-            "mcn_sarl_train_param_count", "mcn_sarl_train_workspace_bytes", "mcn_sarl_loss_grad", "mcn_sgd_momentum_step"]
+            "mcn_sarl_train_param_count", "mcn_sarl_train_workspace_bytes", "mcn_sarl_loss_grad", "mcn_sgd_momentum_step",
+            "mcn_attn_world_train_param_count", "mcn_attn_world_train_workspace_bytes", "mcn_attn_world_loss_grad", "mcn_adam_step"]
 
 
 def check(rc, what):

@@ -69,6 +69,15 @@ int launch_sarl_loss_grad(const float *params, int input_dim, const float *state
 int launch_sgd_momentum(float *params, float *momentum_buf, const float *grad, int64_t count, float lr, float momentum,
                         hipStream_t stream);
 
+// world_train.hip
+long attn_world_train_param_count();
+long attn_world_train_workspace_floats(int B, int N);
+int launch_attn_world_loss_grad(const float *params, const float *cur, const float *nxt, const int64_t *rows, int B,
+                                int N, void *workspace, float *grad /* or NULL: the loss only */, float *loss,
+                                hipStream_t stream);
+int launch_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr, float beta1,
+                float beta2, float eps, int step, hipStream_t stream);
+
 // lstm_rl_value.hip
 int launch_lstm_rl(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                    double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val, int32_t *order,

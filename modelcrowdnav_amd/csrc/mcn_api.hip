@@ -550,6 +550,31 @@ int mcn_sgd_momentum_step(float *params, float *momentum_buf, const float *grad,
     return mcn::launch_sgd_momentum(params, momentum_buf, grad, count, lr, momentum, (hipStream_t)stream);
 }
 
+int64_t mcn_attn_world_train_param_count(void) { return (int64_t)mcn::attn_world_train_param_count(); }
+
+int64_t mcn_attn_world_train_workspace_bytes(int32_t B, int32_t N)
+{
+    if (B <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return 0;
+    return (int64_t)mcn::attn_world_train_workspace_floats(B, N) * 4;
+}
+
+int mcn_attn_world_loss_grad(const float *params, const float *cur, const float *nxt, const int64_t *rows, int32_t B,
+                             int32_t N, void *workspace, float *grad, float *loss, void *stream)
+{
+    if (!params || !cur || !nxt || !workspace || !loss) return MCN_EINVAL;
+    if (B < 1 || N < 1 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
+    return mcn::launch_attn_world_loss_grad(params, cur, nxt, rows, B, N, workspace, grad, loss, (hipStream_t)stream);
+}
+
+int mcn_adam_step(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr,
+                  float beta1, float beta2, float eps, int32_t step, void *stream)
+{
+    if (!params || !exp_avg || !exp_avg_sq || !grad || count < 1 || step < 1) return MCN_EINVAL;
+    if (!isfinite(lr) || !isfinite(eps) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
+        return MCN_EINVAL;                              // (a NaN or infinite beta fails the range test)
+    return mcn::launch_adam(params, exp_avg, exp_avg_sq, grad, count, lr, beta1, beta2, eps, step, (hipStream_t)stream);
+}
+
 int mcn_mlp_world_step(const mcn_mlp_world_net *net, const double *hpos, const double *hvel, double *out_vel,
                        int32_t E, int32_t N, void *stream)
 {

@@ -7,8 +7,16 @@ loss (MlpWorld.noise_pre uses it).
 The pairs are stacked into two device tensors once and mini-batches are index slices of them (the reference builds
 two torch DataLoaders over Python lists per call); pairs whose pedestrian count differs from the first pair's are
 dropped, as its collate_fn does (trainer_sim.py:15-23).
+
+`Trainer_Sim(..., fused=True)` (opt-in; `Trainer_Sim.fused_default` for drop-in users) replaces autograd and torch's Adam
+by the HIP training step of csrc/world_train.hip for the default-shaped AttentionWorld: per mini-batch one
+mcn_attn_world_loss_grad and one mcn_adam_step on flat parameter / gradient / moment buffers, the validation pass as
+forward-only launches, the row indices of an epoch uploaded once and its validation losses read back once.  The split,
+the batches, early stopping and the best weights are those of the torch path.  Known difference:
+`model.attention_weights` is not updated, because no torch forward runs.
 """
 import copy
+import ctypes as C
 import logging
 import random
 
@@ -41,7 +49,9 @@ class EarlyStopping(object):
 
 
 class Trainer_Sim(object):
-    def __init__(self, model, memory, device, batch_size, path=None):
+    fused_default = False        # what `fused=None` means; a drop-in user may flip it
+
+    def __init__(self, model, memory, device, batch_size, path=None, fused=None):
         self.model, self.memory, self.device, self.batch_size = model, memory, device, batch_size
         self.criterion = nn.MSELoss().to(device)
         self.optimizer = None
@@ -49,10 +59,20 @@ class Trainer_Sim(object):
         self.patience = 7
         self.path = path
         self.early_stopping = EarlyStopping(patience=self.patience, path=path)
+        self.fused = bool(Trainer_Sim.fused_default if fused is None else fused)
+        self._fz = None                  # fused path: flat params / grad / Adam moments, workspace, step count
+        self.last_rows = None            # fused path: per epoch of the latest call (train row order, validation row order
+        #                                  or None for rows 0 .. n_val-1), device tensors; rows index what _pairs() stacked
+        if self.fused:
+            self._fused_check()
 
     def set_learning_rate(self, learning_rate):
         logging.info("Current learning rate: %f", learning_rate)
         self.optimizer = optim.Adam(self.model.parameters(), lr=learning_rate)
+        if self._fz is not None:         # the reference makes a new optimizer here: moments and step count start over
+            self._fz["m"].zero_()
+            self._fz["v"].zero_()
+            self._fz["step"] = 0
 
     def _pairs(self):
         rows = self.memory.memory if hasattr(self.memory, "memory") else self.memory
@@ -78,6 +98,8 @@ class Trainer_Sim(object):
         shuffles drawn here -- the reference's two DataLoaders draw theirs from torch's global generator."""
         if self.optimizer is None:
             raise ValueError("Learning rate is not set!")
+        if self.fused:
+            return self._fused_optimize(num_epochs, reset, perms)
         (tx, ty), (vx, vy) = self._pairs()
         if tx is None or vx is None:
             raise ValueError("not enough pairs to split into training and validation sets")
@@ -106,6 +128,139 @@ class Trainer_Sim(object):
             es(sum(losses) / len(losses), self.model)
             if es.early_stop:
                 break
+        self.model.load_state_dict(es.best_state)               # load best model
+        self.model.mse = 0 - es.best_score                      # used to add noise to the MLP world
+        return -es.best_score
+
+    # ------------------------------------------------------------------ fused HIP step (csrc/world_train.hip)
+    def _fused_layout(self):
+        """[(state_dict key, offset, shape)] of the flat buffers, and their length: state_dict order, each tensor in
+        torch's own row-major layout (include/mcn.h: mcn_attn_world_train_param_count)."""
+        table, off = [], 0
+        for k, v in self.model.state_dict().items():
+            table.append((k, off, tuple(v.shape)))
+            off += v.numel()
+        return table, off
+
+    def _fused_check(self):
+        """ValueError for what the fused step is not built for."""
+        from .. import _hip
+        from ..policy.world_model import AttentionWorld, MlpWorld
+        m = self.model
+        expect = {"mlp1.0": (150, 4), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
+                  "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
+                  "mlp3.0": (150, 54), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (2, 100)}
+        why = None
+        if isinstance(m, MlpWorld):
+            why = "it is an MlpWorld, which draws dropout masks in training"
+        elif not isinstance(m, AttentionWorld) or m.input_dim != 4 or not m.with_global_state:
+            why = "it is not an AttentionWorld with input_dim 4 and the global state"
+        else:
+            sd = m.state_dict()
+            if list(sd.keys()) != [k + s for k in expect for s in (".weight", ".bias")]:
+                why = "its layers are not the default ones (mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-2)"
+            else:
+                for k, shp in expect.items():
+                    if tuple(sd[k + ".weight"].shape) != shp or tuple(sd[k + ".bias"].shape) != shp[:1]:
+                        why = "%s.weight is %s, expected %s" % (k, tuple(sd[k + ".weight"].shape), shp)
+                        break
+                if why is None and any(v.dtype != torch.float32 for v in sd.values()):
+                    why = "its parameters are not float32"
+                if why is None and self._fused_layout()[1] != int(_hip.lib.mcn_attn_world_train_param_count()):
+                    why = "its parameter count is not mcn_attn_world_train_param_count()"
+        if why is not None:
+            raise ValueError("Trainer_Sim(fused=True): world_train.hip is built for the default AttentionWorld; this model "
+                             "cannot be trained by it: " + why)
+        dev = torch.device(self.device)
+        if dev.type != "cuda":
+            raise ValueError("Trainer_Sim(fused=True) runs HIP kernels: the trainer's device is %s, not a GPU" % (dev,))
+        want = torch.cuda.current_device() if dev.index is None else dev.index
+        for k, p in m.named_parameters():
+            if p.device.type != "cuda" or p.device.index != want:
+                raise ValueError("Trainer_Sim(fused=True): the model lives on %s (%s), the trainer on %s" % (p.device, k, dev))
+
+    def _fused_optimize(self, num_epochs, reset, perms):
+        from .. import _hip
+        self._fused_check()              # the module may have been changed or moved since the trainer was made
+        (tx, ty), (vx, vy) = self._pairs()
+        if tx is None or vx is None:
+            raise ValueError("not enough pairs to split into training and validation sets")
+        dev = tx.device
+        N = int(tx.shape[1]) // 4
+        if tx.shape[1] != 4 * N or ty.shape[1] != 2 * N or vx.shape[1] != 4 * N or vy.shape[1] != 2 * N or \
+                not 1 <= N <= _hip.MAX_HUMANS:
+            raise ValueError("Trainer_Sim(fused=True): pairs are %s -> %s, the model takes [N <= %d][4] -> [N][2]" %
+                             (tuple(tx.shape[1:]), tuple(ty.shape[1:]), _hip.MAX_HUMANS))
+        tx, ty, vx, vy = tx.contiguous(), ty.contiguous(), vx.contiguous(), vy.contiguous()
+        nt, nv, B = int(tx.shape[0]), int(vx.shape[0]), int(self.batch_size)
+        if B < 1:
+            raise ValueError("Trainer_Sim(fused=True): batch size %d" % B)
+        params = [p for _, p in self.model.named_parameters()]
+        table, count = self._fused_layout()
+        z = self._fz
+        if z is None or z["params"].device != dev:
+            z = self._fz = {k: torch.zeros(count, dtype=torch.float32, device=dev) for k in ("params", "grad", "m", "v")}
+            z["ws"], z["step"] = None, 0
+            z["loss"] = torch.zeros(1, dtype=torch.float32, device=dev)      # a training batch's loss (never read back)
+        group = self.optimizer.param_groups[0]
+        lr, (beta1, beta2), eps = float(group["lr"]), group["betas"], float(group["eps"])
+        es = self.early_stopping
+        es.counter, es.early_stop = 0, False
+        if reset:
+            es.best_score = None
+        stream = _hip.stream_ptr(dev)
+        lib, ptr = _hip.lib, _hip.ptr
+        at = lambda t, first, width: C.c_void_p(t.data_ptr() + first * width * t.element_size())
+        self.last_rows = []
+        self.model.eval()                # the mode the torch path leaves the module in
+        with torch.no_grad():
+            # load_state_dict / apply(init_weight) since the last call are honoured: the module is the master copy
+            torch.cat([p.detach().reshape(-1) for p in params], out=z["params"])
+            vloss = None
+            for ep in range(num_epochs):
+                if perms is None:
+                    perm, vperm = torch.randperm(nt, device=dev), None
+                else:
+                    # the kernel trusts the rows: checked here, on the host, before they are uploaded
+                    hp, hv = (torch.as_tensor(q[ep], dtype=torch.long).reshape(-1).cpu() for q in perms)
+                    for h, n, what in ((hp, nt, "training"), (hv, nv, "validation")):
+                        if h.numel() and (int(h.min()) < 0 or int(h.max()) >= n):
+                            raise IndexError("Trainer_Sim(fused=True): a %s permutation names row %d of %d" %
+                                             (what, int(h.max()) if int(h.max()) >= n else int(h.min()), n))
+                    perm, vperm = hp.to(dev), hv.to(dev)
+                self.last_rows.append((perm, vperm))
+                n_rows = nv if vperm is None else int(vperm.numel())
+                n_batches = -(-n_rows // B)
+                # room for the largest batch of this epoch and for one loss per validation batch
+                need = int(lib.mcn_attn_world_train_workspace_bytes(min(B, max(int(perm.numel()), n_rows, 1)), N))
+                if z["ws"] is None or z["ws"].numel() < need:
+                    z["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+                if vloss is None or vloss.numel() < n_batches:
+                    vloss = torch.empty(n_batches, dtype=torch.float32, device=dev)
+                for i in range(0, int(perm.numel()), B):
+                    b = min(B, int(perm.numel()) - i)
+                    _hip.check(lib.mcn_attn_world_loss_grad(ptr(z["params"]), ptr(tx), ptr(ty), at(perm, i, 1), b, N,
+                                                            ptr(z["ws"]), ptr(z["grad"]), ptr(z["loss"]), stream),
+                               "mcn_attn_world_loss_grad")
+                    z["step"] += 1
+                    _hip.check(lib.mcn_adam_step(ptr(z["params"]), ptr(z["m"]), ptr(z["v"]), ptr(z["grad"]), count, lr,
+                                                 beta1, beta2, eps, z["step"], stream), "mcn_adam_step")
+                for k in range(n_batches):
+                    b = min(B, n_rows - k * B)
+                    if vperm is None:        # rows k B .. of the validation tensors, in their own order
+                        rc = lib.mcn_attn_world_loss_grad(ptr(z["params"]), at(vx, k * B, 4 * N), at(vy, k * B, 2 * N), None, b,
+                                                          N, ptr(z["ws"]), None, at(vloss, k, 1), stream)
+                    else:
+                        rc = lib.mcn_attn_world_loss_grad(ptr(z["params"]), ptr(vx), ptr(vy), at(vperm, k * B, 1), b, N,
+                                                          ptr(z["ws"]), None, at(vloss, k, 1), stream)
+                    _hip.check(rc, "mcn_attn_world_loss_grad")
+                losses = vloss[:n_batches].cpu().tolist()      # the epoch's one read-back
+                # p.copy_ (not p.data): the version counters move, so packed HIP weights of the model are re-made
+                for p, (_, off, _shape) in zip(params, table):
+                    p.copy_(z["params"][off:off + p.numel()].view_as(p))
+                es(sum(losses) / len(losses), self.model)
+                if es.early_stop:
+                    break
         self.model.load_state_dict(es.best_state)               # load best model
         self.model.mse = 0 - es.best_score                      # used to add noise to the MLP world
         return -es.best_score

@@ -1,0 +1,157 @@
+"""Float64 yardstick of the world-model training step: the SAME AttentionWorld module (policy/world_model.py) in
+torch.float64 with torch autograd on the CPU -- MSE loss over the B 2N outputs, the gradient as one flat vector in
+state_dict order, Adam written out in float64 tensor operations, and a float64 replay of a whole Trainer_Sim run
+(utils/trainer_sim.py) with given permutations.  Every tolerance of tests/test_fused_world_trainer_gpu.py is measured
+against this; nothing here touches a GPU or the HIP library."""
+import copy
+import random
+
+import numpy as np
+import torch
+
+PARAM_COUNT = 94953
+
+
+def attention_world(seed):
+    """A default AttentionWorld with torch's default initialisation under `seed`, float32 on the CPU."""
+    from modelcrowdnav_amd.policy.world_model import AttentionWorld
+    torch.manual_seed(seed)
+    return AttentionWorld()
+
+
+def layout():
+    """[(state_dict key, offset, shape)] of the flat parameter / gradient / moment buffers, written out by hand:
+    state_dict order, each tensor row-major as torch stores it."""
+    dims = [("mlp1.0", 4, 150), ("mlp1.2", 150, 100), ("mlp2.0", 100, 100), ("mlp2.2", 100, 50),
+            ("attention.0", 200, 100), ("attention.2", 100, 100), ("attention.4", 100, 1),
+            ("mlp3.0", 54, 150), ("mlp3.2", 150, 100), ("mlp3.4", 100, 100), ("mlp3.6", 100, 2)]
+    table, off = [], 0
+    for name, fan_in, fan_out in dims:
+        table.append((name + ".weight", off, (fan_out, fan_in)))
+        off += fan_in * fan_out
+        table.append((name + ".bias", off, (fan_out,)))
+        off += fan_out
+    assert off == PARAM_COUNT
+    return table, off
+
+
+def pairs(rows, N, seed):
+    """`rows` memory rows: current states [rows, 4N] (positions within a few metres, velocities within 1 m/s) and
+    next velocities [rows, 2N], float32."""
+    g = torch.Generator().manual_seed(seed)
+    cur = torch.randn(rows, N, 4, generator=g) * torch.tensor([3.0, 3.0, 0.7, 0.7])
+    nxt = 0.8 * cur[:, :, 2:4] + 0.1 * torch.randn(rows, N, 2, generator=g)
+    return cur.reshape(rows, 4 * N).contiguous(), nxt.reshape(rows, 2 * N).contiguous()
+
+
+def as64(model):
+    m = copy.deepcopy(model).cpu().double()
+    for p in m.parameters():
+        p.grad = None
+    return m
+
+
+def flat(tensors):
+    return np.concatenate([t.detach().cpu().numpy().reshape(-1) for t in tensors])
+
+
+def loss_and_grad(model, cur, nxt):
+    """torch autograd on `model` as it is (its dtype and device): (loss as a Python float of the model's precision,
+    flat gradient as a numpy array in state_dict order)."""
+    for p in model.parameters():
+        p.grad = None
+    loss = torch.nn.functional.mse_loss(model(cur), nxt)
+    loss.backward()
+    return loss.detach().cpu().item(), flat([p.grad for p in model.parameters()])
+
+
+def loss_and_grad64(model, cur, nxt):
+    """The yardstick: loss and flat gradient of the float32 `model` on float32 (cur [B,4N], nxt [B,2N]), every
+    operation in float64."""
+    return loss_and_grad(as64(model), cur.detach().cpu().double(), nxt.detach().cpu().double())
+
+
+def tensor_errors(got_flat, want_flat):
+    """{state_dict key: (max |got - want|, max |want|)} over the tensors of the flat layout: numerator and denominator
+    of the relative error, kept apart because a tensor's float64 gradient can be exactly 0 (one pedestrian: the softmax
+    weight is 1 whatever the score).  Two errors against the same `want` compare by their numerators."""
+    table, total = layout()
+    assert got_flat.shape == want_flat.shape == (total,)
+    out = {}
+    for name, off, shape in table:
+        n = int(np.prod(shape))
+        g, w = got_flat[off:off + n].astype(np.float64), want_flat[off:off + n].astype(np.float64)
+        out[name] = (float(np.abs(g - w).max()), float(np.abs(w).max()))
+    return out
+
+
+def adam64(p, m, v, g, step, lr, beta1, beta2, eps):
+    """One step of torch.optim.Adam's rule (no weight decay, no amsgrad) on float64 tensors, step number `step` >= 1;
+    returns the new (p, m, v)."""
+    m = beta1 * m + (1 - beta1) * g
+    v = beta2 * v + (1 - beta2) * g * g
+    p = p - (lr / (1 - beta1 ** step)) * m / (v.sqrt() / (1 - beta2 ** step) ** 0.5 + eps)
+    return p, m, v
+
+
+class Adam64(object):
+    """adam64 over the parameters of a float64 module, with the moments and the step count kept between calls."""
+
+    def __init__(self, module, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+        self.params = list(module.parameters())
+        self.lr, self.beta1, self.beta2, self.eps = lr, beta1, beta2, eps
+        self.m = [torch.zeros_like(p) for p in self.params]
+        self.v = [torch.zeros_like(p) for p in self.params]
+        self.step_count = 0
+
+    def step(self):
+        self.step_count += 1
+        with torch.no_grad():
+            for k, p in enumerate(self.params):
+                q, self.m[k], self.v[k] = adam64(p, self.m[k], self.v[k], p.grad, self.step_count, self.lr, self.beta1,
+                                                 self.beta2, self.eps)
+                p.copy_(q)
+
+
+def replay64(model, rows, calls, perms, batch_size, lr, patience=7, seed=None):
+    """A whole Trainer_Sim run in float64, from the float32 `model`'s weights: `rows` is the memory (a list of
+    (cur [N,4], nxt [N,2]) pairs, shuffled IN PLACE by each call as the trainer does -- pass a copy of the list the
+    trainer gets, and seed Python's generator alike with `seed`), `calls` the num_epochs of each optimize_epoch call,
+    perms[c] = (train [epochs][n_train], validation [epochs][n_val]) its row orders.  One Adam state over all calls, the
+    best score kept from call to call (reset=False), the best weights loaded at the end of each call.
+    Returns (best validation loss of each call, every validation loss in order, the trained float64 module)."""
+    m = as64(model)
+    opt = Adam64(m, lr)
+    if seed is not None:
+        random.seed(seed)
+    best_score, best_state, bests, every = None, None, [], []
+    for c, epochs in enumerate(calls):
+        random.shuffle(rows)
+        n_train = int(len(rows) * 0.8)
+        stack = lambda part, k: torch.stack([torch.as_tensor(p[k]).double() for p in part]).reshape(len(part), -1)
+        tx, ty, vx, vy = stack(rows[:n_train], 0), stack(rows[:n_train], 1), stack(rows[n_train:], 0), stack(rows[n_train:], 1)
+        counter = 0
+        for ep in range(epochs):
+            perm = torch.as_tensor(np.asarray(perms[c][0][ep]), dtype=torch.long)
+            vperm = torch.as_tensor(np.asarray(perms[c][1][ep]), dtype=torch.long)
+            for i in range(0, tx.shape[0], batch_size):
+                idx = perm[i:i + batch_size]
+                for p in m.parameters():
+                    p.grad = None
+                torch.nn.functional.mse_loss(m(tx[idx]), ty[idx]).backward()
+                opt.step()
+            with torch.no_grad():
+                ex, ey = vx[vperm], vy[vperm]
+                losses = [torch.nn.functional.mse_loss(m(ex[i:i + batch_size]), ey[i:i + batch_size]).item()
+                          for i in range(0, ex.shape[0], batch_size)]
+            val = sum(losses) / len(losses)
+            every.append(val)
+            if best_score is None or not (-val < best_score):
+                best_score, best_state, counter = -val, copy.deepcopy(m.state_dict()), 0
+            else:
+                counter += 1
+                if counter >= patience:
+                    break
+        m.load_state_dict(best_state)
+        bests.append(-best_score)
+    return bests, every, m

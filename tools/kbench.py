@@ -7,6 +7,7 @@ human-policy modes, measured with HIP events around a hipGraph of back-to-back l
     python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
     python tools/kbench.py --finish [--humans 5,10] [--sizes 4096]   (mcn_orca_finish vs one mcn_orca_batch launch per step)
     python tools/kbench.py --trainer [--humans 5,10]   (Trainer.optimize_batch(100): fused HIP step vs torch autograd)
+    python tools/kbench.py --world-trainer [--humans 5,10]   (Trainer_Sim.optimize_epoch(3): fused HIP step vs torch autograd)
 """
 import argparse
 import os
@@ -112,7 +113,14 @@ def main():
     ap.add_argument("--trainer", action="store_true",
                     help="time Trainer.optimize_batch(100) at batch 100 x --humans: fused HIP step (fused=True) against "
                          "the torch path, five alternating repeats")
+    ap.add_argument("--world-trainer", action="store_true",
+                    help="time Trainer_Sim.optimize_epoch(3) on 25 000 synthetic pairs at batch 100 x --humans: fused HIP "
+                         "step (fused=True) against the torch path, five alternating repeats")
     a = ap.parse_args()
+    if a.world_trainer:
+        for N in [int(x) for x in str(a.humans).split(",")]:
+            world_trainer_bench(N)
+        return
     if a.trainer:
         for N in [int(x) for x in str(a.humans).split(",")]:
             trainer_bench(N)
@@ -246,6 +254,55 @@ def trainer_bench(N, batch=100, num_batches=100, rows=20000, reps=5):
         print("trainer N=%d batch=%d optimize_batch(%d) %-5s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats; %.1f us / step)"
               % (N, batch, num_batches, name, np.median(t), t.min(), t.max(), reps, np.median(t) * 1e3 / num_batches))
     print("trainer N=%d: torch / fused = %.2f (medians)" % (N, np.median(times["torch"]) / np.median(times["fused"])))
+
+
+def world_trainer_bench(N, batch=100, epochs=3, rows=25000, reps=5):
+    """Wall time of one Trainer_Sim.optimize_epoch(epochs) call -- what the model-based training loop makes once per
+    training episode -- with the fused HIP step and with torch autograd + optim.Adam, on the same seeded AttentionWorld and
+    a synthetic pair memory sized like the reference's `rawob` after its initial episodes (500 episodes of about 50
+    steps).  A call is: shuffle and stack the memory (the same host work on both paths), then per epoch 200 training
+    steps and 50 validation batches; 3 epochs cannot stop early (patience 7).  The two paths alternate within one
+    process (fused, torch, fused, ...) so that clock and cache state drift hits both; one untimed call of each first.
+    Also printed: the stacking alone, which both paths pay."""
+    import copy
+    import time
+    from modelcrowdnav_amd.policy.world_model import AttentionWorld
+    from modelcrowdnav_amd.utils.trainer_sim import Trainer_Sim
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = AttentionWorld()
+    g = torch.Generator().manual_seed(1)
+    cur = torch.randn(rows, N, 4, generator=g) * torch.tensor([3.0, 3.0, 0.7, 0.7])
+    nxt = 0.8 * cur[:, :, 2:4] + 0.1 * torch.randn(rows, N, 2, generator=g)
+    memory = [(cur[i], nxt[i]) for i in range(rows)]
+    trainers = {}
+    for name, fused in (("fused", True), ("torch", False)):
+        tr = Trainer_Sim(copy.deepcopy(model).to(dev), list(memory), dev, batch, fused=fused)
+        tr.set_learning_rate(0.001)
+        tr.optimize_epoch(1, reset=True)                     # untimed: allocations, module load, first-launch costs
+        trainers[name] = tr
+    times = {"fused": [], "torch": [], "stack": []}
+    steps = epochs * -(-int(rows * 0.8) // batch)
+    for _ in range(reps):
+        for name in ("fused", "torch"):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            trainers[name].optimize_epoch(epochs, reset=True)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3)
+        t0 = time.perf_counter()
+        trainers["torch"]._pairs()
+        torch.cuda.synchronize()
+        times["stack"].append((time.perf_counter() - t0) * 1e3)
+    for name in ("fused", "torch", "stack"):
+        t = np.asarray(times[name])
+        what = "optimize_epoch(%d) %-5s" % (epochs, name) if name != "stack" else "of which _pairs()      "
+        print("world trainer N=%d batch=%d rows=%d %s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats)"
+              % (N, batch, rows, what, np.median(t), t.min(), t.max(), reps))
+    f, t, k = (float(np.median(times[n])) for n in ("fused", "torch", "stack"))
+    print("world trainer N=%d: torch / fused = %.2f (medians); without the stacking %.2f; per training step incl. its share "
+          "of validation: fused %.1f us, torch %.1f us (%d steps)" % (N, t / f, (t - k) / (f - k), (f - k) * 1e3 / steps,
+                                                                   (t - k) * 1e3 / steps, steps))
 
 
 def closed_loop_bench(E, N, T=128, reps=5):
