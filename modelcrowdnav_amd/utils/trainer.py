@@ -17,13 +17,14 @@ by the HIP training step of csrc/sarl_train.hip: per mini-batch three launches (
 sum, SGD-momentum) on flat parameter / gradient / momentum buffers, the row indices of all batches of a call uploaded
 once and the losses read back once.  It draws the same batches from the same generator as the torch path.
 """
-import ctypes as C
 import logging
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 import torch.optim as optim
+
+from . import _fused
 
 
 class Trainer(object):
@@ -116,13 +117,7 @@ class Trainer(object):
 
     # ------------------------------------------------------------------ fused HIP step (csrc/sarl_train.hip)
     def _fused_layout(self):
-        """[(state_dict key, offset, shape)] of the flat buffers, and their length: state_dict order, each tensor in
-        torch's own row-major layout (include/mcn.h: mcn_sarl_train_param_count)."""
-        table, off = [], 0
-        for k, v in self.model.state_dict().items():
-            table.append((k, off, tuple(v.shape)))
-            off += v.numel()
-        return table, off
+        return _fused.layout(self.model)
 
     def _fused_check(self):
         """ValueError for what the fused step is not built for.  The memory is looked at again at every call: rows
@@ -130,25 +125,15 @@ class Trainer(object):
         from .. import _hip
         from ..policy.sarl import ValueNetwork, shipped_shapes
         m = self.model
-        why = None
         if not isinstance(m, ValueNetwork) or not m.with_global_state or m.self_state_dim != 6:
             why = "it is not a SARL ValueNetwork with the global state and a 6-wide self state"
         else:
             sd = m.state_dict()
             D = sd["mlp1.0.weight"].shape[1] if "mlp1.0.weight" in sd else -1
-            expect = shipped_shapes(D)
-            keys = [k + s for k in expect for s in (".weight", ".bias")]
-            if list(sd.keys()) != keys or D not in (13, 61):
-                why = "its layers are not the shipped ones (policy.config:44-50, input_dim 13 or 61)"
-            else:
-                for k, shp in expect.items():
-                    if tuple(sd[k + ".weight"].shape) != shp or tuple(sd[k + ".bias"].shape) != shp[:1]:
-                        why = "%s.weight is %s, expected %s" % (k, tuple(sd[k + ".weight"].shape), shp)
-                        break
-                if why is None and any(v.dtype != torch.float32 for v in sd.values()):
-                    why = "its parameters are not float32"
-                if why is None and self._fused_layout()[1] != int(_hip.lib.mcn_sarl_train_param_count(D)):
-                    why = "its parameter count is not mcn_sarl_train_param_count(%d)" % D
+            why = _fused.mismatch(sd, shipped_shapes(D) if D in (13, 61) else {},      # (no layers: any state_dict differs)
+                                  lambda: int(_hip.lib.mcn_sarl_train_param_count(D)),
+                                  "its layers are not the shipped ones (policy.config:44-50, input_dim 13 or 61)",
+                                  "its parameter count is not mcn_sarl_train_param_count(%d)" % D)
         if why is not None:
             raise ValueError("Trainer(fused=True): sarl_train.hip is built for the shipped SARL value network; this model "
                              "cannot be trained by it: " + why)
@@ -181,9 +166,9 @@ class Trainer(object):
             raise ValueError("Trainer(fused=True): the memory holds no rows to train on")
         self.last_rows = batches
         rows = torch.cat(batches)
-        if int(rows.min()) < 0 or int(rows.max()) >= n:          # the kernel trusts the rows: checked here, on the host
-            raise IndexError("Trainer(fused=True): a batch names memory row %d; the memory holds %d rows" %
-                             (int(rows.max()) if int(rows.max()) >= n else int(rows.min()), n))
+        bad = _fused.bad_row(rows, n)                            # the kernel trusts the rows: checked here, on the host
+        if bad is not None:
+            raise IndexError("Trainer(fused=True): a batch names memory row %d; the memory holds %d rows" % (bad, n))
         dev = self.memory._states.device
         params = [p for _, p in self.model.named_parameters()]
         if any(p.device != dev for p in params):
@@ -194,40 +179,29 @@ class Trainer(object):
         if states.dim() != 3 or D != table[0][2][1] or not 1 <= N <= _hip.MAX_HUMANS:
             raise ValueError("Trainer(fused=True): memory states are %s, the model takes [N <= %d][%d]" %
                              (tuple(states.shape[1:]), _hip.MAX_HUMANS, table[0][2][1]))
-        z = self._fz
-        if z is None or z["params"].numel() != count or z["params"].device != dev:
-            z = self._fz = {k: torch.zeros(count, dtype=torch.float32, device=dev) for k in ("params", "grad", "mom")}
-            z["ws"] = None
+        z = self._fz = _fused.buffers(self._fz, ("params", "grad", "mom"), params, dev)
         self._flat = z["grad"]                                   # data parallel: the flat gradient is the bucket
-        need = max(int(_hip.lib.mcn_sarl_train_workspace_bytes(int(b.numel()), N, D)) for b in batches)
-        if z["ws"] is None or z["ws"].numel() < need:
-            z["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _fused.workspace(z, max(int(_hip.lib.mcn_sarl_train_workspace_bytes(int(b.numel()), N, D)) for b in batches))
         group = self.optimizer.param_groups[0]
         lr, momentum = float(group["lr"]), float(group["momentum"])
         grouped, world = self._grouped(), self._world()
         with torch.no_grad():
-            # load_state_dict / sync_weights since the last call are honoured: the module is the master copy
-            torch.cat([p.detach().reshape(-1) for p in params], out=z["params"])
             rows_dev = rows.to(dev)
             losses = torch.empty(len(batches), dtype=torch.float32, device=dev)
-            stream = _hip.stream_ptr(dev)
+            stream, lib, ptr = _hip.stream_ptr(dev), _hip.lib, _hip.ptr
             at = 0
             for s, b in enumerate(batches):
                 B = int(b.numel())
-                _hip.check(_hip.lib.mcn_sarl_loss_grad(
-                    _hip.ptr(z["params"]), D, _hip.ptr(states), _hip.ptr(values), C.c_void_p(rows_dev.data_ptr() + 8 * at),
-                    B, N, _hip.ptr(z["ws"]), _hip.ptr(z["grad"]), C.c_void_p(losses.data_ptr() + 4 * s), stream),
-                    "mcn_sarl_loss_grad")
+                _hip.check(lib.mcn_sarl_loss_grad(ptr(z["params"]), D, ptr(states), ptr(values), _fused.at(rows_dev, at), B, N,
+                                                  ptr(ws), ptr(z["grad"]), _fused.at(losses, s), stream), "mcn_sarl_loss_grad")
                 at += B
                 if grouped:
                     self._collective(dist.all_reduce, z["grad"])          # one bucket, one collective
                     if world > 1:
                         z["grad"].div_(world)
-                _hip.check(_hip.lib.mcn_sgd_momentum_step(_hip.ptr(z["params"]), _hip.ptr(z["mom"]), _hip.ptr(z["grad"]),
-                                                          count, lr, momentum, stream), "mcn_sgd_momentum_step")
-            # p.copy_ (not p.data): the version counters move, so packed HIP weights of the model are re-made
-            for p, (_, off, _shape) in zip(params, table):
-                p.copy_(z["params"][off:off + p.numel()].view_as(p))
+                _hip.check(lib.mcn_sgd_momentum_step(ptr(z["params"]), ptr(z["mom"]), ptr(z["grad"]), count, lr, momentum,
+                                                     stream), "mcn_sgd_momentum_step")
+            _fused.store(z, params, table)
             return losses.cpu().tolist()
 
     def _fused_epoch(self, num_epochs, perms):

@@ -16,13 +16,14 @@ the batches, early stopping and the best weights are those of the torch path.  K
 `model.attention_weights` is not updated, because no torch forward runs.
 """
 import copy
-import ctypes as C
 import logging
 import random
 
 import torch
 import torch.nn as nn
 import torch.optim as optim
+
+from . import _fused
 
 
 class EarlyStopping(object):
@@ -134,13 +135,7 @@ class Trainer_Sim(object):
 
     # ------------------------------------------------------------------ fused HIP step (csrc/world_train.hip)
     def _fused_layout(self):
-        """[(state_dict key, offset, shape)] of the flat buffers, and their length: state_dict order, each tensor in
-        torch's own row-major layout (include/mcn.h: mcn_attn_world_train_param_count)."""
-        table, off = [], 0
-        for k, v in self.model.state_dict().items():
-            table.append((k, off, tuple(v.shape)))
-            off += v.numel()
-        return table, off
+        return _fused.layout(self.model)
 
     def _fused_check(self):
         """ValueError for what the fused step is not built for."""
@@ -150,24 +145,15 @@ class Trainer_Sim(object):
         expect = {"mlp1.0": (150, 4), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
                   "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
                   "mlp3.0": (150, 54), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (2, 100)}
-        why = None
         if isinstance(m, MlpWorld):
             why = "it is an MlpWorld, which draws dropout masks in training"
         elif not isinstance(m, AttentionWorld) or m.input_dim != 4 or not m.with_global_state:
             why = "it is not an AttentionWorld with input_dim 4 and the global state"
         else:
-            sd = m.state_dict()
-            if list(sd.keys()) != [k + s for k in expect for s in (".weight", ".bias")]:
-                why = "its layers are not the default ones (mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-2)"
-            else:
-                for k, shp in expect.items():
-                    if tuple(sd[k + ".weight"].shape) != shp or tuple(sd[k + ".bias"].shape) != shp[:1]:
-                        why = "%s.weight is %s, expected %s" % (k, tuple(sd[k + ".weight"].shape), shp)
-                        break
-                if why is None and any(v.dtype != torch.float32 for v in sd.values()):
-                    why = "its parameters are not float32"
-                if why is None and self._fused_layout()[1] != int(_hip.lib.mcn_attn_world_train_param_count()):
-                    why = "its parameter count is not mcn_attn_world_train_param_count()"
+            why = _fused.mismatch(
+                m.state_dict(), expect, lambda: int(_hip.lib.mcn_attn_world_train_param_count()),
+                "its layers are not the default ones (mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-2)",
+                "its parameter count is not mcn_attn_world_train_param_count()")
         if why is not None:
             raise ValueError("Trainer_Sim(fused=True): world_train.hip is built for the default AttentionWorld; this model "
                              "cannot be trained by it: " + why)
@@ -197,10 +183,9 @@ class Trainer_Sim(object):
             raise ValueError("Trainer_Sim(fused=True): batch size %d" % B)
         params = [p for _, p in self.model.named_parameters()]
         table, count = self._fused_layout()
-        z = self._fz
-        if z is None or z["params"].device != dev:
-            z = self._fz = {k: torch.zeros(count, dtype=torch.float32, device=dev) for k in ("params", "grad", "m", "v")}
-            z["ws"], z["step"] = None, 0
+        z = self._fz = _fused.buffers(self._fz, ("params", "grad", "m", "v"), params, dev)
+        if "step" not in z:
+            z["step"] = 0
             z["loss"] = torch.zeros(1, dtype=torch.float32, device=dev)      # a training batch's loss (never read back)
         group = self.optimizer.param_groups[0]
         lr, (beta1, beta2), eps = float(group["lr"]), group["betas"], float(group["eps"])
@@ -209,13 +194,10 @@ class Trainer_Sim(object):
         if reset:
             es.best_score = None
         stream = _hip.stream_ptr(dev)
-        lib, ptr = _hip.lib, _hip.ptr
-        at = lambda t, first, width: C.c_void_p(t.data_ptr() + first * width * t.element_size())
+        lib, ptr, at = _hip.lib, _hip.ptr, _fused.at
         self.last_rows = []
         self.model.eval()                # the mode the torch path leaves the module in
         with torch.no_grad():
-            # load_state_dict / apply(init_weight) since the last call are honoured: the module is the master copy
-            torch.cat([p.detach().reshape(-1) for p in params], out=z["params"])
             vloss = None
             for ep in range(num_epochs):
                 if perms is None:
@@ -224,23 +206,21 @@ class Trainer_Sim(object):
                     # the kernel trusts the rows: checked here, on the host, before they are uploaded
                     hp, hv = (torch.as_tensor(q[ep], dtype=torch.long).reshape(-1).cpu() for q in perms)
                     for h, n, what in ((hp, nt, "training"), (hv, nv, "validation")):
-                        if h.numel() and (int(h.min()) < 0 or int(h.max()) >= n):
-                            raise IndexError("Trainer_Sim(fused=True): a %s permutation names row %d of %d" %
-                                             (what, int(h.max()) if int(h.max()) >= n else int(h.min()), n))
+                        bad = _fused.bad_row(h, n)
+                        if bad is not None:
+                            raise IndexError("Trainer_Sim(fused=True): a %s permutation names row %d of %d" % (what, bad, n))
                     perm, vperm = hp.to(dev), hv.to(dev)
                 self.last_rows.append((perm, vperm))
                 n_rows = nv if vperm is None else int(vperm.numel())
                 n_batches = -(-n_rows // B)
                 # room for the largest batch of this epoch and for one loss per validation batch
-                need = int(lib.mcn_attn_world_train_workspace_bytes(min(B, max(int(perm.numel()), n_rows, 1)), N))
-                if z["ws"] is None or z["ws"].numel() < need:
-                    z["ws"] = torch.empty(need, dtype=torch.uint8, device=dev)
+                ws = _fused.workspace(z, int(lib.mcn_attn_world_train_workspace_bytes(min(B, max(int(perm.numel()), n_rows, 1)), N)))
                 if vloss is None or vloss.numel() < n_batches:
                     vloss = torch.empty(n_batches, dtype=torch.float32, device=dev)
                 for i in range(0, int(perm.numel()), B):
                     b = min(B, int(perm.numel()) - i)
                     _hip.check(lib.mcn_attn_world_loss_grad(ptr(z["params"]), ptr(tx), ptr(ty), at(perm, i, 1), b, N,
-                                                            ptr(z["ws"]), ptr(z["grad"]), ptr(z["loss"]), stream),
+                                                            ptr(ws), ptr(z["grad"]), ptr(z["loss"]), stream),
                                "mcn_attn_world_loss_grad")
                     z["step"] += 1
                     _hip.check(lib.mcn_adam_step(ptr(z["params"]), ptr(z["m"]), ptr(z["v"]), ptr(z["grad"]), count, lr,
@@ -249,15 +229,13 @@ class Trainer_Sim(object):
                     b = min(B, n_rows - k * B)
                     if vperm is None:        # rows k B .. of the validation tensors, in their own order
                         rc = lib.mcn_attn_world_loss_grad(ptr(z["params"]), at(vx, k * B, 4 * N), at(vy, k * B, 2 * N), None, b,
-                                                          N, ptr(z["ws"]), None, at(vloss, k, 1), stream)
+                                                          N, ptr(ws), None, at(vloss, k, 1), stream)
                     else:
                         rc = lib.mcn_attn_world_loss_grad(ptr(z["params"]), ptr(vx), ptr(vy), at(vperm, k * B, 1), b, N,
-                                                          ptr(z["ws"]), None, at(vloss, k, 1), stream)
+                                                          ptr(ws), None, at(vloss, k, 1), stream)
                     _hip.check(rc, "mcn_attn_world_loss_grad")
                 losses = vloss[:n_batches].cpu().tolist()      # the epoch's one read-back
-                # p.copy_ (not p.data): the version counters move, so packed HIP weights of the model are re-made
-                for p, (_, off, _shape) in zip(params, table):
-                    p.copy_(z["params"][off:off + p.numel()].view_as(p))
+                _fused.store(z, params, table)
                 es(sum(losses) / len(losses), self.model)
                 if es.early_stop:
                     break

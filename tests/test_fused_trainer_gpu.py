@@ -11,10 +11,11 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from tests import fused_train_harness as F  # noqa: E402
 from tests import trainer_ref as R  # noqa: E402
+from tests.fused_train_harness import MARGIN, SENTINEL  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MARGIN = 4.0        # both float32 accumulations, differing in summation order only: workgroup partials against a GEMM
 
 
 def _dev():
@@ -33,8 +34,8 @@ def kernel_loss_grad(model, states, values, rows, B):
     params = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).to(dev, torch.float32).contiguous()
     assert params.numel() == count
     ws = torch.empty(int(_hip.lib.mcn_sarl_train_workspace_bytes(B, N, D)), dtype=torch.uint8, device=dev)
-    grad = torch.full((count,), 12345.0, dtype=torch.float32, device=dev)
-    loss = torch.full((1,), 12345.0, dtype=torch.float32, device=dev)
+    grad = torch.full((count,), SENTINEL, dtype=torch.float32, device=dev)
+    loss = torch.full((1,), SENTINEL, dtype=torch.float32, device=dev)
     rows_dev = None if rows is None else rows.to(dev, torch.long).contiguous()
     assert rows is None or (rows_dev.numel() == B and int(rows_dev.min()) >= 0 and int(rows_dev.max()) < states.shape[0])
     assert rows is not None or B <= states.shape[0]
@@ -57,31 +58,12 @@ def _three_ways(model, states, values, rows, B):
     return (k_loss, k_grad), (t_loss, t_grad), (d_loss, d_grad)
 
 
-def _parity(what, kernel, torch32, ref64, D):
-    """The metric: per parameter tensor max |g - g64| / max |g64| and |loss - loss64| / |loss64|; the kernel's
-    may be MARGIN times torch's float32 figure for the same inputs.  Both figures of a tensor share the denominator
-    max |g64|, so the numerators are compared: the same inequality, and it still says something where the float64
-    gradient of a tensor is exactly 0 (attention with one human).  Returns what misses the bound, as text."""
-    ek, et = R.tensor_errors(kernel[1], ref64[1], D), R.tensor_errors(torch32[1], ref64[1], D)
-    lk, lt = abs(kernel[0] - ref64[0]) / abs(ref64[0]), abs(torch32[0] - ref64[0]) / abs(ref64[0])
-    # printed: the worst tensor among those that HAVE a gradient (attention.4.bias has none: a common shift of the
-    # scores does not move the softmax, its float64 "gradient" is 1e-19 of rounding noise; its absolute figure follows)
-    rel = lambda e: max([num / den for num, den in e.values() if den > 1e-12])
-    print("%s: loss err kernel %.3g torch %.3g | worst grad err kernel %.3g torch %.3g | attention.4.bias abs kernel %.3g "
-          "torch %.3g" % (what, lk, lt, rel(ek), rel(et), ek["attention.4.bias"][0], et["attention.4.bias"][0]))
-    bad = ["%s kernel %.3g > %g x torch %.3g (max |g64| %.3g)" % (k, ek[k][0], MARGIN, et[k][0], ek[k][1])
-           for k in ek if not ek[k][0] <= MARGIN * et[k][0]]
-    if not lk <= MARGIN * lt:
-        bad.append("loss kernel %.3g > %g x torch %.3g" % (lk, MARGIN, lt))
-    return ["%s: %s" % (what, b) for b in bad]
-
-
 def _assert_parity(what, kernel, torch32, ref64, D):
-    bad = _parity(what, kernel, torch32, ref64, D)
+    bad = F.parity(what, kernel, torch32, ref64, R.layout(D))
     assert not bad, "\n".join(bad)
 
 
-SHAPES = [(1, 1), (1, 5), (3, 2), (7, 5), (100, 5), (33, 10), (2, 32)]
+SHAPES = [(1, 1), (1, 2), (1, 5), (3, 2), (5, 3), (3, 4), (7, 5), (100, 5), (33, 10), (2, 20), (2, 21), (2, 32)]
 
 
 @pytest.mark.parametrize("input_dim", [13, 61])
@@ -89,8 +71,10 @@ SHAPES = [(1, 1), (1, 5), (3, 2), (7, 5), (100, 5), (33, 10), (2, 32)]
 def test_gradient_parity_with_float64(B, N, input_dim):
     """Loss and gradient of one mini-batch against float64 autograd, for two weight seeds, with the batch as rows
     0 .. B-1 (rows = NULL) and as a shuffled, non-contiguous index list into a memory of B + 9 rows.  Shapes: one state
-    of one human, a group that is not full, several workgroups with a short last one (7 x 5, 100 x 5), one state per
-    workgroup (33 x 10) and the largest crowd (2 x 32).
+    of one human, a group that is not full, several states per workgroup with a short last group (1 x 2, 3 x 2, 5 x 3,
+    3 x 4: the grouping this kernel shares with the world model's), several workgroups with a short last one (7 x 5,
+    100 x 5), one state per workgroup (33 x 10), both sides of the LDS / workspace threshold of the float64 row buffers
+    (20 | 21) and the largest crowd (2 x 32).
 
     Bound: MARGIN = 4 times the error of torch's float32 autograd on the GPU on the same inputs, per parameter tensor
     and for the loss.
@@ -109,7 +93,7 @@ def test_gradient_parity_with_float64(B, N, input_dim):
         shuffled = torch.randperm(B + 9, generator=torch.Generator().manual_seed(seed))[:B]
         for rows in (None, shuffled):
             what = "B %d N %d D %d seed %d rows %s" % (B, N, input_dim, seed, "NULL" if rows is None else "shuffled")
-            bad += _parity(what, *_three_ways(model, states, values, rows, B), D=input_dim)
+            bad += F.parity(what, *_three_ways(model, states, values, rows, B), R.layout(input_dim))
     assert not bad, "\n".join(bad)
 
 
@@ -123,7 +107,7 @@ def test_two_calls_give_the_same_bits(B, N, input_dim):
     a = kernel_loss_grad(model, states.to(_dev()), values.to(_dev()), rows, B)
     b = kernel_loss_grad(model, states.to(_dev()), values.to(_dev()), rows, B)
     assert a[2] == b[2] and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
-    assert np.isfinite(a[1]).all() and not (a[1] == 12345.0).any()
+    assert np.isfinite(a[1]).all() and not (a[1] == SENTINEL).any()
 
 
 @pytest.mark.parametrize("B,N", [(7, 5), (3, 2)])
@@ -165,11 +149,6 @@ def test_dead_relu_layer_stops_the_gradient_exactly():
     _assert_parity("dead mlp1.2", kernel, torch32, ref64, D)
 
 
-def _ulps(a, b):
-    """|a - b| in units of b's spacing, elementwise (float32)."""
-    return np.abs(a.astype(np.float64) - b.astype(np.float64)) / np.spacing(np.abs(b)).astype(np.float64)
-
-
 def test_sgd_momentum_kernel_is_torchs_rule():
     """Five steps from a zero buffer against torch.optim.SGD(momentum=0.9) on a flat device tensor (a count that is no
     multiple of the workgroup, several workgroups).  The kernel forms buf = momentum buf + grad in two roundings, as
@@ -194,7 +173,7 @@ def test_sgd_momentum_kernel_is_torchs_rule():
                                                   _hip.stream_ptr(dev)), "mcn_sgd_momentum_step")
         torch.cuda.synchronize()
         wp, wb = want.detach().cpu().numpy(), opt.state[want]["momentum_buffer"].cpu().numpy()
-        up, ub = _ulps(p.cpu().numpy(), wp), _ulps(buf.cpu().numpy(), wb)
+        up, ub = F.ulps(p.cpu().numpy(), wp), F.ulps(buf.cpu().numpy(), wb)
         print("step %d: params differ in %d of %d elements (max %.2f ulp), momentum in %d (max %.2f ulp)" %
               (s, int((up > 0).sum()), count, up.max(), int((ub > 0).sum()), ub.max()))
         assert up.max() <= 1.0 and ub.max() <= 1.0
@@ -365,7 +344,7 @@ def test_fused_step_writes_back_and_reads_the_module():
     assert np.array_equal(tr._fz["mom"].cpu().numpy().view(np.uint32), grad.view(np.uint32))
     after = torch.cat([p.detach().reshape(-1) for p in pol.model.parameters()]).cpu().numpy()
     want = (before.astype(np.float64) - np.float64(np.float32(0.02)) * grad.astype(np.float64)).astype(np.float32)
-    assert _ulps(after, want).max() <= 1.0 and not np.array_equal(after, before)
+    assert F.ulps(after, want).max() <= 1.0 and not np.array_equal(after, before)
 
 
 def test_fused_trainer_in_a_process_group_of_one(tmp_path):

@@ -11,10 +11,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+from tests import fused_train_harness as F  # noqa: E402
 from tests import world_trainer_ref as R  # noqa: E402
-
-MARGIN = 4.0        # both float32 accumulations, differing in summation order only
-SENTINEL = 12345.0
+from tests.fused_train_harness import MARGIN, SENTINEL  # noqa: E402
 
 
 def _dev():
@@ -59,28 +58,11 @@ def _three_ways(model, cur, nxt, rows, B):
 
 
 def _parity(what, kernel, torch32, ref64):
-    """The metric of tests/test_fused_trainer_gpu.py::_parity: per parameter tensor max |g - g64| (the numerators of the
-    relative errors, which share the denominator max |g64|) and |loss - loss64| / |loss64|; the kernel's may be MARGIN
-    times torch's float32 figure for the same inputs.  Returns what misses the bound, as text."""
-    ek, et = R.tensor_errors(kernel[1], ref64[1]), R.tensor_errors(torch32[1], ref64[1])
-    lk, lt = abs(kernel[0] - ref64[0]) / abs(ref64[0]), abs(torch32[0] - ref64[0]) / abs(ref64[0])
-    rel = lambda e: max([num / den for num, den in e.values() if den > 1e-12])
-    print("%s: loss err kernel %.3g torch %.3g | worst grad err kernel %.3g torch %.3g | attention.4.bias abs kernel %.3g "
-          "torch %.3g float64 %.3g" % (what, lk, lt, rel(ek), rel(et), ek["attention.4.bias"][0], et["attention.4.bias"][0],
-                                       ek["attention.4.bias"][1]))
-    bad = ["%s kernel %.3g > %g x torch %.3g (max |g64| %.3g)" % (k, ek[k][0], MARGIN, et[k][0], ek[k][1])
-           for k in ek if not ek[k][0] <= MARGIN * et[k][0]]
-    if not lk <= MARGIN * lt:
-        bad.append("loss kernel %.3g > %g x torch %.3g" % (lk, MARGIN, lt))
-    return ["%s: %s" % (what, b) for b in bad]
+    return F.parity(what, kernel, torch32, ref64, R.layout())
 
 
 def _slot(name):
-    table, _ = R.layout()
-    for k, off, shp in table:
-        if k == name:
-            return off, int(np.prod(shp))
-    raise KeyError(name)
+    return F.slot(R.layout(), name)
 
 
 # one scene of one pedestrian (weight 1: attention has no gradient); workgroups that are not full and a short last one
@@ -184,11 +166,6 @@ def test_dead_relu_layer_stops_the_gradient_exactly():
     assert not bad, "\n".join(bad)
 
 
-def _ulps(a, ref):
-    """|a - ref| in units of the float32 spacing at ref, elementwise."""
-    return np.abs(a.astype(np.float64) - ref) / np.spacing(np.abs(ref).astype(np.float32)).astype(np.float64)
-
-
 def test_adam_kernel_is_torchs_rule():
     """1, 2 and 10 steps of mcn_adam_step from zero moments on random parameters and gradients (a count that is no
     multiple of the workgroup, several workgroups, a block of exactly-zero gradients) against the float64 rule
@@ -221,7 +198,7 @@ def test_adam_kernel_is_torchs_rule():
         torch.cuda.synchronize()
         p64, m64, v64 = R.adam64(p64, m64, v64, gr.double(), s, lr, beta1, beta2, eps)
         if s in (1, 2, 10):
-            uk, ut = _ulps(p.cpu().numpy(), p64.numpy()), _ulps(want.detach().cpu().numpy(), p64.numpy())
+            uk, ut = F.ulps(p.cpu().numpy(), p64.numpy()), F.ulps(want.detach().cpu().numpy(), p64.numpy())
             print("step %d: max error in float32 spacings of the parameter: kernel %.3g, torch %.3g" % (s, uk.max(), ut.max()))
             assert uk.max() <= MARGIN * max(ut.max(), 1.0)
             assert torch.equal(p.cpu()[zero], p0[zero]) and not m.cpu()[zero].any() and not v.cpu()[zero].any()
@@ -229,8 +206,8 @@ def test_adam_kernel_is_torchs_rule():
             for name, mine, ref, theirs in (("exp_avg", m, m64, st["exp_avg"]), ("exp_avg_sq", v, v64, st["exp_avg_sq"])):
                 live = np.ones(count, bool)
                 live[zero] = False
-                uk = _ulps(mine.cpu().numpy()[live], ref.numpy()[live])
-                ut = _ulps(theirs.cpu().numpy()[live], ref.numpy()[live])
+                uk = F.ulps(mine.cpu().numpy()[live], ref.numpy()[live])
+                ut = F.ulps(theirs.cpu().numpy()[live], ref.numpy()[live])
                 print("step %d: %s kernel %.3g, torch %.3g spacings" % (s, name, uk.max(), ut.max()))
                 assert uk.max() <= MARGIN * max(ut.max(), 1.0), name
     assert not torch.equal(p.cpu(), p0)
@@ -419,7 +396,7 @@ def test_fused_world_trainer_writes_back_and_reads_the_module():
     want, m64, v64 = R.adam64(before, torch.zeros_like(before), torch.zeros_like(before), g64, 1, lr, b1, b2, eps)
     assert np.array_equal(tr._fz["m"].cpu().numpy(), m64.float().numpy())
     after = torch.cat([p.detach().reshape(-1) for p in model.parameters()]).cpu().numpy()
-    assert _ulps(after, want.numpy()).max() <= 1.0 and not np.array_equal(after, before.float().numpy())
+    assert F.ulps(after, want.numpy()).max() <= 1.0 and not np.array_equal(after, before.float().numpy())
 
 
 def _reseeded(memory, seed):

@@ -3,10 +3,10 @@ torch.float64 with torch autograd on the CPU -- MSE loss, the gradient as one fl
 SGD-momentum steps on given batches by torch's own rule (buf = momentum buf + grad with the first buf = grad,
 p = p - lr buf), written out in float64 tensor ops.  Every tolerance of tests/test_fused_trainer_gpu.py is measured
 against this; nothing here touches a GPU or the HIP library's kernels."""
-import copy
-
 import numpy as np
 import torch
+
+from tests.fused_train_harness import as64, loss_and_grad, loss_and_grad64  # noqa: F401  (the yardstick, as R.*)
 
 SHIPPED = dict(mlp1=[150, 100], mlp2=[100, 50], mlp3=[150, 100, 100, 1], attention=[100, 100, 1])
 
@@ -43,33 +43,6 @@ def states_and_values(rows, N, input_dim, seed):
     return s, torch.randn(rows, 1, generator=g)
 
 
-def as64(model):
-    m = copy.deepcopy(model).cpu().double()
-    for p in m.parameters():
-        p.grad = None
-    return m
-
-
-def flat(tensors):
-    return np.concatenate([t.detach().cpu().numpy().reshape(-1) for t in tensors])
-
-
-def loss_and_grad(model, states, values):
-    """torch autograd on `model` as it is (its dtype and device): (loss as a Python float of the model's precision,
-    flat gradient as a numpy array in state_dict order)."""
-    for p in model.parameters():
-        p.grad = None
-    loss = torch.nn.functional.mse_loss(model(states), values)
-    loss.backward()
-    return loss.detach().cpu().item(), flat([p.grad for p in model.parameters()])
-
-
-def loss_and_grad64(model, states, values):
-    """The yardstick: loss and flat gradient of the float32 `model` on float32 (states [B,N,D], values [B,1]), every
-    operation in float64."""
-    return loss_and_grad(as64(model), states.detach().cpu().double(), values.detach().cpu().double())
-
-
 def sgd64(model, states, values, batches, lr, momentum=0.9, buf=None):
     """k = len(batches) SGD-momentum steps in float64 from the float32 `model`'s weights: step s trains on the memory
     rows batches[s].  Returns (losses [k], trained float64 module, momentum buffers)."""
@@ -89,18 +62,3 @@ def sgd64(model, states, values, batches, lr, momentum=0.9, buf=None):
             for p, b in zip(m.parameters(), buf):
                 p.sub_(lr * b)
     return losses, m, buf
-
-
-def tensor_errors(got_flat, want_flat, input_dim):
-    """{state_dict key: (max |got - want|, max |want|)} over the tensors of the flat layout: numerator and denominator
-    of the relative error max |got - want| / max |want|, kept apart because a tensor's float64 gradient can be exactly
-    0 (one human: the softmax weight is 1 whatever the score, so attention gets no gradient), where the quotient is
-    0 / 0 or x / 0.  Two errors against the same `want` compare by their numerators."""
-    table, total = layout(input_dim)
-    assert got_flat.shape == want_flat.shape == (total,)
-    out = {}
-    for name, off, shape in table:
-        n = int(np.prod(shape))
-        g, w = got_flat[off:off + n].astype(np.float64), want_flat[off:off + n].astype(np.float64)
-        out[name] = (float(np.abs(g - w).max()), float(np.abs(w).max()))
-    return out

@@ -9,6 +9,8 @@ import random
 import numpy as np
 import torch
 
+from tests.fused_train_harness import as64, loss_and_grad, loss_and_grad64  # noqa: F401  (the yardstick, as R.*)
+
 PARAM_COUNT = 94953
 
 
@@ -42,47 +44,6 @@ def pairs(rows, N, seed):
     cur = torch.randn(rows, N, 4, generator=g) * torch.tensor([3.0, 3.0, 0.7, 0.7])
     nxt = 0.8 * cur[:, :, 2:4] + 0.1 * torch.randn(rows, N, 2, generator=g)
     return cur.reshape(rows, 4 * N).contiguous(), nxt.reshape(rows, 2 * N).contiguous()
-
-
-def as64(model):
-    m = copy.deepcopy(model).cpu().double()
-    for p in m.parameters():
-        p.grad = None
-    return m
-
-
-def flat(tensors):
-    return np.concatenate([t.detach().cpu().numpy().reshape(-1) for t in tensors])
-
-
-def loss_and_grad(model, cur, nxt):
-    """torch autograd on `model` as it is (its dtype and device): (loss as a Python float of the model's precision,
-    flat gradient as a numpy array in state_dict order)."""
-    for p in model.parameters():
-        p.grad = None
-    loss = torch.nn.functional.mse_loss(model(cur), nxt)
-    loss.backward()
-    return loss.detach().cpu().item(), flat([p.grad for p in model.parameters()])
-
-
-def loss_and_grad64(model, cur, nxt):
-    """The yardstick: loss and flat gradient of the float32 `model` on float32 (cur [B,4N], nxt [B,2N]), every
-    operation in float64."""
-    return loss_and_grad(as64(model), cur.detach().cpu().double(), nxt.detach().cpu().double())
-
-
-def tensor_errors(got_flat, want_flat):
-    """{state_dict key: (max |got - want|, max |want|)} over the tensors of the flat layout: numerator and denominator
-    of the relative error, kept apart because a tensor's float64 gradient can be exactly 0 (one pedestrian: the softmax
-    weight is 1 whatever the score).  Two errors against the same `want` compare by their numerators."""
-    table, total = layout()
-    assert got_flat.shape == want_flat.shape == (total,)
-    out = {}
-    for name, off, shape in table:
-        n = int(np.prod(shape))
-        g, w = got_flat[off:off + n].astype(np.float64), want_flat[off:off + n].astype(np.float64)
-        out[name] = (float(np.abs(g - w).max()), float(np.abs(w).max()))
-    return out
 
 
 def adam64(p, m, v, g, step, lr, beta1, beta2, eps):
