@@ -572,6 +572,64 @@ int mcn_sgd_momentum_step(float *params, float *momentum_buf, const float *grad,
                           void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CADRL and LSTM-RL value-network training steps (crowd_nav/utils/trainer.py:64-82 on crowd_nav/policy/cadrl.py:21-29 and
+ * crowd_nav/policy/lstm_rl.py:9-33).  The update of both is mcn_sgd_momentum_step.
+ * ---------------------------------------------------------------------------------------------- */
+
+/*
+ * The network is the shipped CADRL ValueNetwork: value_network 13-150-100-100-1 with ReLU between the layers.
+ * Parameters, gradient and momentum are each ONE flat float32 device buffer in state_dict order -- value_network.0.weight,
+ * value_network.0.bias, value_network.2.*, value_network.4.*, value_network.6.* -- every weight row-major [out][in] as
+ * torch stores it: mcn_cadrl_train_param_count() = 27401 floats.
+ */
+int64_t mcn_cadrl_train_param_count(void);
+int64_t mcn_cadrl_train_workspace_bytes(int32_t B);                                 /* 0 for arguments the step refuses */
+
+/*
+ * mcn_cadrl_loss_grad -- loss = mean_b (V(states[rows[b]]) - values[rows[b]])^2 over a mini-batch of B states and its
+ * gradient by every parameter, with the semantics of torch autograd on ValueNetwork.forward in float32: ReLU passes
+ * gradient where its output is > 0, and NaN goes where torch's goes.
+ * states: [rows of the memory][13] float (one rotated joint row per state), values: [rows of the memory] float, both
+ * device.  rows: [B] int64 device, the memory row of each state of the batch, or NULL for rows 0 .. B-1.  The kernel
+ * TRUSTS the row indices: the caller checks them against the number of rows the memory holds before it uploads them.
+ * workspace: mcn_cadrl_train_workspace_bytes(B) device bytes, 8-byte aligned; grad: [param_count] float device out;
+ * loss: [1] float device out.  Two launches on `stream` (per-workgroup partial gradients of 8 states each, then their sum
+ * in workgroup order): no atomics, so the same inputs give the same bits.  The forward pass and the sums over the batch
+ * run in float64, the backward pass in float32: loss and grad are within float32 rounding of float64 autograd's; the loss
+ * and the gradient of value_network.6.bias are float64 sums rounded once.
+ * MCN_EINVAL before any launch: a NULL params / states / values / workspace / grad / loss, B < 1.
+ */
+int mcn_cadrl_loss_grad(const float *params, const float *states, const float *values, const int64_t *rows, int32_t B,
+                        void *workspace, float *grad, float *loss, void *stream);
+
+/*
+ * The network is the shipped LSTM-RL ValueNetwork1: nn.LSTM(13, 50, batch_first) over the N rows of a state from zero
+ * h0 / c0, then mlp 56-150-100-100-1 on [columns 0 .. 5 of the state's row 0 | h_N].  The flat float32 buffers are in
+ * state_dict order, which puts the MLP FIRST: mlp.0.weight, mlp.0.bias, mlp.2.*, mlp.4.*, mlp.6.*, lstm.weight_ih_l0
+ * [200][13], lstm.weight_hh_l0 [200][50], lstm.bias_ih_l0 [200], lstm.bias_hh_l0 [200]; the gate rows are torch's (i, f, g,
+ * o: rows 0-49, 50-99, 100-149, 150-199).  mcn_lstm_rl_train_param_count() = 46851 floats.
+ */
+int64_t mcn_lstm_rl_train_param_count(void);
+int64_t mcn_lstm_rl_train_workspace_bytes(int32_t B, int32_t N);                    /* 0 for arguments the step refuses */
+
+/*
+ * mcn_lstm_rl_loss_grad -- the same loss and its gradient for ValueNetwork1, with the semantics of torch autograd on its
+ * forward in float32: gates_t = W_ih x_t + b_ih + W_hh h_{t-1} + b_hh, c_t = f c_{t-1} + i g, h_t = o tanh(c_t);
+ * sigmoid' = y (1 - y), tanh' = 1 - y^2, ReLU passes gradient where its output is > 0, NaN goes where torch's goes.
+ * states: [rows of the memory][N][13] float, the rows of a state in the order the LSTM takes them (the memory holds them
+ * sorted by LstmRL.transform_batch: nothing is sorted here); values, rows, workspace (mcn_lstm_rl_train_workspace_bytes(B,
+ * N) bytes), grad, loss and the two launches as for mcn_cadrl_loss_grad, a workgroup taking 8 / N states for N <= 4 and one
+ * state above; every activation of every step stays in LDS for all N <= MCN_MAX_HUMANS.  h and c are carried in float64
+ * and the gates' sigmoid and tanh are evaluated in float64 (finite for any finite pre-activation); back through time runs
+ * in float32.  lstm.bias_ih_l0 and lstm.bias_hh_l0 get the same bits; with N = 1 (h_0 = 0) lstm.weight_hh_l0 gets exactly
+ * 0.
+ * MCN_EINVAL before any launch: a NULL params / states / values / workspace / grad / loss, B < 1, N outside
+ * 1 .. MCN_MAX_HUMANS.
+ */
+int mcn_lstm_rl_loss_grad(const float *params, const float *states, const float *values, const int64_t *rows, int32_t B,
+                          int32_t N, void *workspace, float *grad, float *loss, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Social-GAN one-step world model (crowd_nav/policy/world_model.py:134-268, sgan/models.py:501-553).
  * ---------------------------------------------------------------------------------------------- */
 

@@ -176,6 +176,15 @@ def _load():
     # params, momentum_buf, grad, count, lr, momentum, stream
     lib.mcn_sgd_momentum_step.argtypes = [_vp, _vp, _vp, C.c_int64, _f, _f, _vp]
     lib.mcn_sgd_momentum_step.restype = C.c_int
+    lib.mcn_cadrl_train_param_count.argtypes, lib.mcn_cadrl_train_param_count.restype = [], C.c_int64
+    lib.mcn_cadrl_train_workspace_bytes.argtypes, lib.mcn_cadrl_train_workspace_bytes.restype = [_i], C.c_int64
+    # params, states, values, rows, B, workspace, grad, loss, stream
+    lib.mcn_cadrl_loss_grad.argtypes, lib.mcn_cadrl_loss_grad.restype = [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp], C.c_int
+    lib.mcn_lstm_rl_train_param_count.argtypes, lib.mcn_lstm_rl_train_param_count.restype = [], C.c_int64
+    lib.mcn_lstm_rl_train_workspace_bytes.argtypes, lib.mcn_lstm_rl_train_workspace_bytes.restype = [_i, _i], C.c_int64
+    # params, states, values, rows, B, N, workspace, grad, loss, stream
+    lib.mcn_lstm_rl_loss_grad.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]
+    lib.mcn_lstm_rl_loss_grad.restype = C.c_int
     lib.mcn_lstm_rl_predict.argtypes = [C.POINTER(LstmRLNet), C.POINTER(EnvState), _vp, _i, _d, _d, _i, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _d, C.c_uint64, _i, _i, _vp]
     lib.mcn_lstm_rl_predict.restype = C.c_int
@@ -264,7 +273,9 @@ EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict",
             "mcn_sarl_train_param_count", "mcn_sarl_train_workspace_bytes", "mcn_sarl_loss_grad", "mcn_sgd_momentum_step",
-            "mcn_attn_world_train_param_count", "mcn_attn_world_train_workspace_bytes", "mcn_attn_world_loss_grad", "mcn_adam_step"]
+            "mcn_attn_world_train_param_count", "mcn_attn_world_train_workspace_bytes", "mcn_attn_world_loss_grad", "mcn_adam_step",
+            "mcn_cadrl_train_param_count", "mcn_cadrl_train_workspace_bytes", "mcn_cadrl_loss_grad",
+            "mcn_lstm_rl_train_param_count", "mcn_lstm_rl_train_workspace_bytes", "mcn_lstm_rl_loss_grad"]
 
 
 def check(rc, what):

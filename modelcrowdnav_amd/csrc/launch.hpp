@@ -78,6 +78,16 @@ int launch_attn_world_loss_grad(const float *params, const float *cur, const flo
 int launch_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr, float beta1,
                 float beta2, float eps, int step, hipStream_t stream);
 
+// value_train.hip
+long cadrl_train_param_count();
+long cadrl_train_workspace_floats(int B);
+int launch_cadrl_loss_grad(const float *params, const float *states, const float *values, const int64_t *rows, int B,
+                           void *workspace, float *grad, float *loss, hipStream_t stream);
+long lstm_rl_train_param_count();
+long lstm_rl_train_workspace_floats(int B, int N);
+int launch_lstm_rl_loss_grad(const float *params, const float *states, const float *values, const int64_t *rows, int B,
+                             int N, void *workspace, float *grad, float *loss, hipStream_t stream);
+
 // lstm_rl_value.hip
 int launch_lstm_rl(const mcn_lstm_rl_net *net, const mcn_env_state *st, const double *actions, int A, double dt,
                    double gamma_pow, int kinematics, double *values, int32_t *best, double *best_val, int32_t *order,

@@ -550,6 +550,37 @@ int mcn_sgd_momentum_step(float *params, float *momentum_buf, const float *grad,
     return mcn::launch_sgd_momentum(params, momentum_buf, grad, count, lr, momentum, (hipStream_t)stream);
 }
 
+int64_t mcn_cadrl_train_param_count(void) { return (int64_t)mcn::cadrl_train_param_count(); }
+
+int64_t mcn_cadrl_train_workspace_bytes(int32_t B)
+{
+    if (B <= 0) return 0;
+    return (int64_t)mcn::cadrl_train_workspace_floats(B) * 4;
+}
+
+int mcn_cadrl_loss_grad(const float *params, const float *states, const float *values, const int64_t *rows, int32_t B,
+                        void *workspace, float *grad, float *loss, void *stream)
+{
+    if (!params || !states || !values || !workspace || !grad || !loss || B < 1) return MCN_EINVAL;
+    return mcn::launch_cadrl_loss_grad(params, states, values, rows, B, workspace, grad, loss, (hipStream_t)stream);
+}
+
+int64_t mcn_lstm_rl_train_param_count(void) { return (int64_t)mcn::lstm_rl_train_param_count(); }
+
+int64_t mcn_lstm_rl_train_workspace_bytes(int32_t B, int32_t N)
+{
+    if (B <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return 0;
+    return (int64_t)mcn::lstm_rl_train_workspace_floats(B, N) * 4;
+}
+
+int mcn_lstm_rl_loss_grad(const float *params, const float *states, const float *values, const int64_t *rows, int32_t B,
+                          int32_t N, void *workspace, float *grad, float *loss, void *stream)
+{
+    if (!params || !states || !values || !workspace || !grad || !loss) return MCN_EINVAL;
+    if (B < 1 || N < 1 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
+    return mcn::launch_lstm_rl_loss_grad(params, states, values, rows, B, N, workspace, grad, loss, (hipStream_t)stream);
+}
+
 int64_t mcn_attn_world_train_param_count(void) { return (int64_t)mcn::attn_world_train_param_count(); }
 
 int64_t mcn_attn_world_train_workspace_bytes(int32_t B, int32_t N)

@@ -6,7 +6,7 @@
 //                           loss and back-propagates through mlp3, the pooling, the masked softmax, attention, the
 //                           mean (global state), mlp2 and mlp1.  Its gradient of EVERY parameter goes into its own
 //                           slice of the workspace: no atomics, no workgroup looks at another one's data.
-//   train_grad_reduce_kernel (train_attention.hpp) sums the slices in workgroup order into the flat gradient and
+//   train_grad_reduce_kernel (train_reduce.hpp) sums the slices in workgroup order into the flat gradient and
 //                           writes the loss.
 //   sgd_momentum_kernel     buf = momentum buf + grad, p = p - lr buf over the flat buffers.
 //
@@ -18,7 +18,8 @@
 // what float64 arithmetic gives, which single numbers need to stand a comparison with float64.  The semantics are those of torch autograd on ValueNetwork.forward: the softmax is the
 // un-stabilised exp(s) (s != 0) / sum with the mask a constant, ReLU passes gradient where its output is > 0, and NaN
 // goes where torch's goes (a state whose scores are all exactly 0 is 0 / 0).
-#include "train_attention.hpp"  // the layer table, the grouping, the trunk and the reduce kernel; NT, lin_fwd, lin_bwd_*
+#include "train_attention.hpp"  // the layer table and the trunk; NT, lin_fwd, lin_bwd_*
+#include "train_reduce.hpp"     // the grouping and the reduce kernel
 
 namespace {
 

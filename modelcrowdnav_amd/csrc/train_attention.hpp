@@ -2,9 +2,9 @@
 // world_train.hip: the AttentionWorld world model) have in common.  Both networks are the same trunk -- mlp1, the mean
 // over the crowd (global state), mlp2, attention, the un-stabilised masked softmax -- under a different head: mlp3 once per
 // state on [self state | pooled feature] with one output, or once per pedestrian on [own state | pooled feature] with two.
-// Here are the layer table of the flat buffers, the grouping of a batch into workgroups, the trunk's buffers with its
-// forward and backward pass, and the kernel that sums the workgroups' slices.  Each .hip keeps its gather, its head, its
-// loss, its LDS budget and its optimizer.
+// Here are the layer table of the flat buffers and the trunk's buffers with its forward and backward pass; the grouping of
+// a batch into workgroups and the kernel that sums their slices are in train_reduce.hpp.  Each .hip keeps its gather, its
+// head, its loss, its LDS budget and its optimizer.
 #pragma once
 #include "launch.hpp"
 #include "train_linear.hpp"    // NT, CH, lin_fwd, lin_bwd_x, lin_bwd_w
@@ -34,17 +34,6 @@ TrainOffsets train_offsets(int D, int J, int OUT)
     t.total = at;
     return t;
 }
-
-// ---- grouping: a workgroup takes G states (scenes) of N rows each -- up to 8 rows for small crowds, one state from 5
-// humans on (N <= 32 rows) -- and leaves its partial gradient of every parameter in its own slice of the workspace
-int group_states(int N) { return N > 4 ? 1 : 8 / N; }
-long train_groups(int B, int N)
-{
-    const int G = group_states(N);
-    return ((long)B + G - 1) / G;
-}
-// floats of all slices, padded to whole float64s: the workgroups' float64 sums follow them
-long slice_floats(long groups, int total) { return (groups * total + 1) / 2 * 2; }
 
 // ---- the trunk's buffers.  Float64: what the forward pass hands from layer to layer; float32: the copies the backward
 // pass reads, and its temporaries.  Elements per row (one human of one state) and per state, as carve_trunk takes them;
@@ -220,42 +209,6 @@ __device__ __forceinline__ void trunk_backward(const float *__restrict__ P, floa
     lin_bwd_x<false>(P + of.w[L1B], 150, t.DH, 100, t.T1, 152, t.H1, 152, R, 150, 100);
     __syncthreads();
     lin_bwd_w(t.T1, 152, X, ldx, 1, gP + of.w[L1A], D, gP + of.b[L1A], R, D, 150);
-}
-
-// ---- the sum over the workgroups.  A workgroup leaves `nsums` float64 sums at ws_sums[nsums g ..]: first its squared
-// errors, then its d loss / d output, one per output.  loss = (sum of the squared errors) / divisor, and with a gradient
-// asked for grad[p] = sum over the workgroups' slices in index order -- except the output layer's bias (the nbias indices
-// from bias_at), which is summed from those float64 sums, before any float32 rounding.  All sums over the workgroups run in
-// float64 in a fixed order and are rounded once.  Thread `total` has the loss; without a gradient thread 0 has it and
-// nothing else is written.
-__global__ __launch_bounds__(256) void train_grad_reduce_kernel(const float *__restrict__ ws,
-                                                                const double *__restrict__ ws_sums, int groups, int total,
-                                                                int nsums, int bias_at, int nbias, double divisor,
-                                                                float *__restrict__ grad, float *__restrict__ loss)
-{
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const int last = grad ? total : 0;
-    if (p > last) return;
-    double acc;
-    if (p == last || (p >= bias_at && p < bias_at + nbias)) {
-        const int k = p == last ? 0 : 1 + p - bias_at;
-        acc = ws_sums[k];
-        for (int g = 1; g < groups; ++g) acc += ws_sums[nsums * g + k];
-    } else {
-        acc = ws[p];
-        for (int g = 1; g < groups; ++g) acc += (double)ws[(size_t)g * total + p];
-    }
-    if (p == last) *loss = (float)(acc / divisor);
-    else grad[p] = (float)acc;
-}
-
-int launch_train_grad_reduce(const float *ws, const double *ws_sums, long groups, int total, int nsums, int bias_at,
-                             int nbias, double divisor, float *grad, float *loss, hipStream_t stream)
-{
-    const unsigned blocks = grad ? (unsigned)((total + 1 + 255) / 256) : 1u;
-    hipLaunchKernelGGL(train_grad_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, ws_sums, (int)groups, total, nsums,
-                       bias_at, nbias, divisor, grad, loss);
-    return hipGetLastError() == hipSuccess ? MCN_OK : MCN_ELAUNCH;
 }
 
 }  // namespace

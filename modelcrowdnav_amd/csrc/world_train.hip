@@ -8,7 +8,7 @@
 //                                 masked softmax, attention, the mean (global state), mlp2 and mlp1.  Its gradient of
 //                                 EVERY parameter goes into its own slice of the workspace: no atomics, no workgroup
 //                                 looks at another one's data.
-//   train_grad_reduce_kernel      (train_attention.hpp) sums the slices in workgroup order into the flat gradient and
+//   train_grad_reduce_kernel      (train_reduce.hpp) sums the slices in workgroup order into the flat gradient and
 //                                 writes the loss (the only writer of `loss`; without a gradient it writes nothing else).
 //   adam_kernel                   torch.optim.Adam (no weight decay, no amsgrad) over the flat buffers.
 //
@@ -23,7 +23,8 @@
 // workspace instead, and LDS holds the rest (139 652 B at 32 rows).
 #include <cstdio>
 #include <cstdlib>
-#include "train_attention.hpp"  // the layer table, the grouping, the trunk and the reduce kernel; NT, lin_fwd, lin_bwd_*
+#include "train_attention.hpp"  // the layer table and the trunk; NT, lin_fwd, lin_bwd_*
+#include "train_reduce.hpp"     // the grouping and the reduce kernel
 
 namespace {
 

@@ -8,7 +8,8 @@ actions (propagate :104-129, rotate :217-252, compute_reward multi_human_rl.py:6
 the GPU in one look-ahead launch per step: sarl_value.hip (policy/sarl.py), lstm_rl_value.hip
 (policy/lstm_rl.py and CADRL's own single-human network below).  The launch plumbing shared by
 all of them (`_lookahead`, `_query_env`, `predict_batch`) lives in CADRL; each policy supplies
-`_pack` (weights -> MFMA fragments) and the `_launch` hook.
+`_pack` (weights -> MFMA fragments) and the `_launch` hook.  Training: the default `Trainer` runs CADRL's own
+ValueNetwork through torch autograd, `Trainer(fused=True)` through csrc/value_train.hip (`mcn_cadrl_loss_grad`).
 """
 import ctypes as C
 import itertools

@@ -1,8 +1,9 @@
 """LSTM-RL (reference: crowd_nav/policy/lstm_rl.py:9-103).
 
 ValueNetwork1 keeps the reference's module tree, so `state_dict()` keys are mlp.{0,2,4,6} and
-lstm.{weight,bias}_{ih,hh}_l0 and `rl_model.pth` files load unchanged.  Its torch forward exists for training; every
-inference on the rollout path (`LstmRL.predict`, `LstmRL.predict_batch`) is one lstm_rl_value.hip launch on weights
+lstm.{weight,bias}_{ih,hh}_l0 and `rl_model.pth` files load unchanged.  Its torch forward exists for training with the
+default `Trainer`; `Trainer(fused=True)` trains it without autograd through csrc/value_train.hip
+(`mcn_lstm_rl_loss_grad`: the LSTM forward and back through time, then the MLP).  Every inference on the rollout path (`LstmRL.predict`, `LstmRL.predict_batch`) is one lstm_rl_value.hip launch on weights
 re-packed into MFMA operand order.  The humans are taken in the order LstmRL.predict sorts them in (decreasing distance
 to the robot, stable); the batched path sorts on the device (mcn_lstm_rl_order / the look-ahead kernel: one
 definition), the E = 1 path on the host exactly as the reference does.

@@ -1,5 +1,5 @@
 """What Trainer(fused=True) and Trainer_Sim(fused=True) both do to a module's parameters on the way to the HIP training
-steps (csrc/sarl_train.hip, csrc/world_train.hip): the flat float32 buffers and their layout, the check of a state_dict
+steps (csrc/sarl_train.hip, csrc/value_train.hip, csrc/world_train.hip): the flat float32 buffers and their layout, the check of a state_dict
 against a shape table, the workspace, and the pointer and row arithmetic of a launch."""
 import ctypes as C
 
@@ -8,7 +8,7 @@ import torch
 
 def layout(model):
     """[(state_dict key, offset, shape)] of the flat buffers, and their length: state_dict order, each tensor in
-    torch's own row-major layout (include/mcn.h: mcn_sarl_train_param_count, mcn_attn_world_train_param_count)."""
+    torch's own row-major layout (include/mcn.h: mcn_sarl_train_param_count and its like)."""
     table, off = [], 0
     for k, v in model.state_dict().items():
         table.append((k, off, tuple(v.shape)))
@@ -16,14 +16,23 @@ def layout(model):
     return table, off
 
 
+def linear_shapes(layers):
+    """{state_dict key: shape} of the Linear layers `layers` ({layer: weight shape}): each one's .weight, then its .bias."""
+    out = {}
+    for k, shp in layers.items():
+        out[k + ".weight"], out[k + ".bias"] = tuple(shp), tuple(shp[:1])
+    return out
+
+
 def mismatch(sd, expect, count, layers_why, count_why):
-    """Why the state_dict `sd` is not the network of `expect` ({layer: weight shape}) in float32 with count() parameters
-    (the library's own figure, asked for last), or None: the caller's two texts, or the first layer of another shape."""
-    if list(sd.keys()) != [k + s for k in expect for s in (".weight", ".bias")]:
+    """Why the state_dict `sd` is not the network of `expect` ({state_dict key: shape}, in state_dict order) in float32
+    with count() parameters (the library's own figure, asked for last), or None: the caller's two texts, or the first
+    tensor of another shape."""
+    if list(sd.keys()) != list(expect):
         return layers_why
     for k, shp in expect.items():
-        if tuple(sd[k + ".weight"].shape) != shp or tuple(sd[k + ".bias"].shape) != shp[:1]:
-            return "%s.weight is %s, expected %s" % (k, tuple(sd[k + ".weight"].shape), shp)
+        if tuple(sd[k].shape) != shp:
+            return "%s is %s, expected %s" % (k, tuple(sd[k].shape), shp)
     if any(v.dtype != torch.float32 for v in sd.values()):
         return "its parameters are not float32"
     return count_why if sum(v.numel() for v in sd.values()) != count() else None

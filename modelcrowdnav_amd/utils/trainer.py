@@ -13,10 +13,13 @@ The arithmetic (one SGD-momentum step of the MSE loss) is pinned against the ref
 tests/golden/g10_trainer.npz (tests/test_training_cpu.py).
 
 `Trainer(..., fused=True)` (opt-in; `Trainer.fused_default` for drop-in users) replaces autograd and the torch optimizer
-by the HIP training step of csrc/sarl_train.hip: per mini-batch three launches (loss and per-workgroup gradients, their
-sum, SGD-momentum) on flat parameter / gradient / momentum buffers, the row indices of all batches of a call uploaded
-once and the losses read back once.  It draws the same batches from the same generator as the torch path.
+by a HIP training step: per mini-batch three launches (loss and per-workgroup gradients, their sum, SGD-momentum) on flat
+parameter / gradient / momentum buffers, the row indices of all batches of a call uploaded once and the losses read back
+once.  It draws the same batches from the same generator as the torch path.  Which file trains what (`_fused_step`):
+csrc/sarl_train.hip the shipped SARL / OM-SARL ValueNetwork, csrc/value_train.hip the shipped LSTM-RL ValueNetwork1 and
+the shipped CADRL ValueNetwork; the SGD-momentum kernel (sarl_train.hip) is the same for all three.
 """
+import collections
 import logging
 
 import torch
@@ -25,6 +28,62 @@ import torch.nn as nn
 import torch.optim as optim
 
 from . import _fused
+
+
+# What differs between the fused steps: the launch's name, the shape of one state in the memory (None: the human count N,
+# 1 .. MCN_MAX_HUMANS), and the library's workspace(B, N) and launch(params, states, values, rows, B, N, ws, grad, loss,
+# stream) with the network's own extra arguments bound.
+_Step = collections.namedtuple("_Step", "name state_shape workspace launch")
+
+
+def _fused_step(m):
+    """(the _Step that trains the module `m`, None), or (None, why there is none)."""
+    from .. import _hip
+    from ..policy import cadrl, lstm_rl, sarl
+    lib = _hip.lib
+    if isinstance(m, lstm_rl.ValueNetwork1):
+        expect = dict(_fused.linear_shapes({"mlp.0": (150, 56), "mlp.2": (100, 150), "mlp.4": (100, 100), "mlp.6": (1, 100)}),
+                      **{"lstm.weight_ih_l0": (200, 13), "lstm.weight_hh_l0": (200, 50), "lstm.bias_ih_l0": (200,),
+                         "lstm.bias_hh_l0": (200,)})
+        why = "its self state is not 6 wide" if m.self_state_dim != 6 else _fused.mismatch(
+            m.state_dict(), expect, lambda: int(lib.mcn_lstm_rl_train_param_count()),
+            "its tensors are not the shipped ones (policy.config [lstm_rl]: global_state_dim = 50, mlp2_dims = 150, 100, 100, 1)",
+            "its parameter count is not mcn_lstm_rl_train_param_count()")
+        if why is not None:
+            return None, ("value_train.hip is built for the shipped LSTM-RL ValueNetwork1; this model cannot be trained by "
+                          "it: " + why)
+        return _Step("mcn_lstm_rl_loss_grad", (None, 13), lib.mcn_lstm_rl_train_workspace_bytes, lib.mcn_lstm_rl_loss_grad), None
+    if isinstance(m, cadrl.ValueNetwork):
+        why = _fused.mismatch(
+            m.state_dict(), _fused.linear_shapes({"value_network.0": (150, 13), "value_network.2": (100, 150),
+                                                  "value_network.4": (100, 100), "value_network.6": (1, 100)}),
+            lambda: int(lib.mcn_cadrl_train_param_count()),
+            "its layers are not the shipped ones (policy.config [cadrl]: mlp_dims = 150, 100, 100, 1)",
+            "its parameter count is not mcn_cadrl_train_param_count()")
+        if why is not None:
+            return None, ("value_train.hip is built for the shipped CADRL ValueNetwork; this model cannot be trained by it: "
+                          + why)
+        return _Step("mcn_cadrl_loss_grad", (13,), lambda B, N: lib.mcn_cadrl_train_workspace_bytes(B),
+                     lambda params, states, values, rows, B, N, *out: lib.mcn_cadrl_loss_grad(params, states, values, rows, B,
+                                                                                                *out)), None
+    if isinstance(m, sarl.ValueNetwork):
+        if not m.with_global_state or m.self_state_dim != 6:
+            why = "it is not a SARL ValueNetwork with the global state and a 6-wide self state"
+        else:
+            sd = m.state_dict()
+            D = sd["mlp1.0.weight"].shape[1] if "mlp1.0.weight" in sd else -1
+            why = _fused.mismatch(sd, _fused.linear_shapes(sarl.shipped_shapes(D)) if D in (13, 61) else {},   # (no layers:
+                                  lambda: int(lib.mcn_sarl_train_param_count(D)),                  # any state_dict differs)
+                                  "its layers are not the shipped ones (policy.config:44-50, input_dim 13 or 61)",
+                                  "its parameter count is not mcn_sarl_train_param_count(%d)" % D)
+        if why is not None:
+            return None, ("sarl_train.hip is built for the shipped SARL value network; this model cannot be trained by it: "
+                          + why)
+        return _Step("mcn_sarl_loss_grad", (None, D), lambda B, N: lib.mcn_sarl_train_workspace_bytes(B, N, D),
+                     lambda params, *rest: lib.mcn_sarl_loss_grad(params, D, *rest)), None
+    return None, ("the HIP training steps are built for the shipped SARL value network (sarl_train.hip), the shipped LSTM-RL "
+                  "ValueNetwork1 and the shipped CADRL ValueNetwork (value_train.hip); this model is a %s, which none of "
+                  "them can train" % type(m).__name__)
 
 
 class Trainer(object):
@@ -42,6 +101,7 @@ class Trainer(object):
         self._gen = torch.Generator()
         self.fused = bool(Trainer.fused_default if fused is None else fused)
         self._fz = None                  # fused path: flat params / grad / momentum, workspace
+        self._step_hip = None            # fused path: the _Step that trains this model
         self.last_rows = None            # fused path: the memory rows of each mini-batch of the latest call (host)
         if self.fused:
             self._fused_check()
@@ -115,28 +175,16 @@ class Trainer(object):
         self.optimizer.step()
         return loss.data.item()
 
-    # ------------------------------------------------------------------ fused HIP step (csrc/sarl_train.hip)
+    # ------------------------------------------------------------------ fused HIP step (csrc/sarl_train.hip, value_train.hip)
     def _fused_layout(self):
         return _fused.layout(self.model)
 
     def _fused_check(self):
         """ValueError for what the fused step is not built for.  The memory is looked at again at every call: rows
         arrive after the trainer is made."""
-        from .. import _hip
-        from ..policy.sarl import ValueNetwork, shipped_shapes
-        m = self.model
-        if not isinstance(m, ValueNetwork) or not m.with_global_state or m.self_state_dim != 6:
-            why = "it is not a SARL ValueNetwork with the global state and a 6-wide self state"
-        else:
-            sd = m.state_dict()
-            D = sd["mlp1.0.weight"].shape[1] if "mlp1.0.weight" in sd else -1
-            why = _fused.mismatch(sd, shipped_shapes(D) if D in (13, 61) else {},      # (no layers: any state_dict differs)
-                                  lambda: int(_hip.lib.mcn_sarl_train_param_count(D)),
-                                  "its layers are not the shipped ones (policy.config:44-50, input_dim 13 or 61)",
-                                  "its parameter count is not mcn_sarl_train_param_count(%d)" % D)
+        self._step_hip, why = _fused_step(self.model)
         if why is not None:
-            raise ValueError("Trainer(fused=True): sarl_train.hip is built for the shipped SARL value network; this model "
-                             "cannot be trained by it: " + why)
+            raise ValueError("Trainer(fused=True): " + why)
         self._fused_check_memory()
         dev = torch.device(self.device)
         if dev.type != "cuda":
@@ -149,6 +197,13 @@ class Trainer(object):
                              "tensor store), which the fused step cannot gather" % len(mem._odd))
         st = getattr(mem, "_states", None)
         if st is not None:
+            from .. import _hip
+            want = self._step_hip.state_shape
+            got = tuple(st.shape[1:])
+            if len(got) != len(want) or any(g != w if w is not None else not 1 <= g <= _hip.MAX_HUMANS
+                                            for g, w in zip(got, want)):
+                raise ValueError("Trainer(fused=True): memory states are %s, the model takes %s" %
+                                 (got, "".join("[N <= %d]" % _hip.MAX_HUMANS if w is None else "[%d]" % w for w in want)))
             dev = torch.device(self.device)
             same = st.device.type == dev.type and (dev.type != "cuda" or st.device.index ==
                                                    (torch.cuda.current_device() if dev.index is None else dev.index))
@@ -174,14 +229,12 @@ class Trainer(object):
         if any(p.device != dev for p in params):
             raise ValueError("Trainer(fused=True): the model lives on %s, the memory on %s" % (params[0].device, dev))
         states, values = self.memory._states, self.memory._values
-        N, D = int(states.shape[1]), int(states.shape[2])
+        step = self._step_hip
+        N = int(states.shape[1]) if step.state_shape[0] is None else 1
         table, count = self._fused_layout()
-        if states.dim() != 3 or D != table[0][2][1] or not 1 <= N <= _hip.MAX_HUMANS:
-            raise ValueError("Trainer(fused=True): memory states are %s, the model takes [N <= %d][%d]" %
-                             (tuple(states.shape[1:]), _hip.MAX_HUMANS, table[0][2][1]))
         z = self._fz = _fused.buffers(self._fz, ("params", "grad", "mom"), params, dev)
         self._flat = z["grad"]                                   # data parallel: the flat gradient is the bucket
-        ws = _fused.workspace(z, max(int(_hip.lib.mcn_sarl_train_workspace_bytes(int(b.numel()), N, D)) for b in batches))
+        ws = _fused.workspace(z, max(int(step.workspace(int(b.numel()), N)) for b in batches))
         group = self.optimizer.param_groups[0]
         lr, momentum = float(group["lr"]), float(group["momentum"])
         grouped, world = self._grouped(), self._world()
@@ -192,8 +245,8 @@ class Trainer(object):
             at = 0
             for s, b in enumerate(batches):
                 B = int(b.numel())
-                _hip.check(lib.mcn_sarl_loss_grad(ptr(z["params"]), D, ptr(states), ptr(values), _fused.at(rows_dev, at), B, N,
-                                                  ptr(ws), ptr(z["grad"]), _fused.at(losses, s), stream), "mcn_sarl_loss_grad")
+                _hip.check(step.launch(ptr(z["params"]), ptr(states), ptr(values), _fused.at(rows_dev, at), B, N, ptr(ws),
+                                       ptr(z["grad"]), _fused.at(losses, s), stream), step.name)
                 at += B
                 if grouped:
                     self._collective(dist.all_reduce, z["grad"])          # one bucket, one collective

@@ -151,7 +151,7 @@ class Trainer_Sim(object):
             why = "it is not an AttentionWorld with input_dim 4 and the global state"
         else:
             why = _fused.mismatch(
-                m.state_dict(), expect, lambda: int(_hip.lib.mcn_attn_world_train_param_count()),
+                m.state_dict(), _fused.linear_shapes(expect), lambda: int(_hip.lib.mcn_attn_world_train_param_count()),
                 "its layers are not the default ones (mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-2)",
                 "its parameter count is not mcn_attn_world_train_param_count()")
         if why is not None:

@@ -6,7 +6,9 @@ human-policy modes, measured with HIP events around a hipGraph of back-to-back l
     python tools/kbench.py --sgan-predict --sizes 4096 --humans 10,5 --samples 1,20 --steps 8,12
     python tools/kbench.py --lstm-rl|--cadrl [--humans 5,10]   (look-ahead launch vs the torch forward it replaces)
     python tools/kbench.py --finish [--humans 5,10] [--sizes 4096]   (mcn_orca_finish vs one mcn_orca_batch launch per step)
-    python tools/kbench.py --trainer [--humans 5,10]   (Trainer.optimize_batch(100): fused HIP step vs torch autograd)
+    python tools/kbench.py --trainer [--policy sarl|lstm_rl|cadrl] [--humans 5,10]
+                                        (Trainer.optimize_batch(100): fused HIP step vs torch autograd; CADRL has one
+                                        row per state whatever --humans says)
     python tools/kbench.py --world-trainer [--humans 5,10]   (Trainer_Sim.optimize_epoch(3): fused HIP step vs torch autograd)
 """
 import argparse
@@ -113,6 +115,8 @@ def main():
     ap.add_argument("--trainer", action="store_true",
                     help="time Trainer.optimize_batch(100) at batch 100 x --humans: fused HIP step (fused=True) against "
                          "the torch path, five alternating repeats")
+    ap.add_argument("--policy", default="sarl", choices=("sarl", "lstm_rl", "cadrl"),
+                    help="with --trainer: the value network that is trained")
     ap.add_argument("--world-trainer", action="store_true",
                     help="time Trainer_Sim.optimize_epoch(3) on 25 000 synthetic pairs at batch 100 x --humans: fused HIP "
                          "step (fused=True) against the torch path, five alternating repeats")
@@ -122,8 +126,8 @@ def main():
             world_trainer_bench(N)
         return
     if a.trainer:
-        for N in [int(x) for x in str(a.humans).split(",")]:
-            trainer_bench(N)
+        for N in [1] if a.policy == "cadrl" else [int(x) for x in str(a.humans).split(",")]:
+            trainer_bench(N, policy=a.policy)
         return
     if a.closed_loop:
         for N in [int(x) for x in str(a.humans).split(",")]:
@@ -212,26 +216,30 @@ def main():
 
 
 
-def trainer_bench(N, batch=100, num_batches=100, rows=20000, reps=5):
+def trainer_bench(N, batch=100, num_batches=100, rows=20000, reps=5, policy="sarl"):
     """Wall time of one Trainer.optimize_batch(num_batches) call -- what train.py makes after every episode -- with the
-    fused HIP step and with torch autograd + optim.SGD, on the same seeded SARL network and device memory.  The two
+    fused HIP step and with torch autograd + optim.SGD, on the same seeded value network of `policy` (sarl, lstm_rl, or
+    cadrl with its one 13-wide row per state) and device memory.  The two
     paths alternate within one process (fused, torch, fused, ...) so that clock and cache state drift hits both; one
     untimed call of each first.  The call ends with its own device-to-host copy of the losses, so host time is device
     time plus launch overhead: that overhead is what the fused step is about."""
     import copy
     import time
     from modelcrowdnav_amd import configs
-    from modelcrowdnav_amd.policy.sarl import SARL
+    from modelcrowdnav_amd.policy.policy_factory import policy_factory
     from modelcrowdnav_amd.utils.memory import ReplayMemory
     from modelcrowdnav_amd.utils.trainer import Trainer
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    pol = SARL()
+    pol = policy_factory[policy]()
     pol.configure(configs.policy_config())
     g = torch.Generator().manual_seed(1)
     states = torch.randn(rows, N, 13, generator=g)
     states[:, :, :6] = states[:, :1, :6]
     values = torch.tanh(states[:, :, 6].mean(1))
+    tag = "trainer" if policy == "sarl" else "trainer %s" % policy
+    if policy == "cadrl":
+        states = states[:, 0]
     mem = ReplayMemory(rows, device=dev)
     mem.push_batch(states.to(dev), values.to(dev))
     trainers = {}
@@ -251,9 +259,9 @@ def trainer_bench(N, batch=100, num_batches=100, rows=20000, reps=5):
             times[name].append((time.perf_counter() - t0) * 1e3)
     for name in ("fused", "torch"):
         t = np.asarray(times[name])
-        print("trainer N=%d batch=%d optimize_batch(%d) %-5s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats; %.1f us / step)"
-              % (N, batch, num_batches, name, np.median(t), t.min(), t.max(), reps, np.median(t) * 1e3 / num_batches))
-    print("trainer N=%d: torch / fused = %.2f (medians)" % (N, np.median(times["torch"]) / np.median(times["fused"])))
+        print("%s N=%d batch=%d optimize_batch(%d) %-5s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats; %.1f us / step)"
+              % (tag, N, batch, num_batches, name, np.median(t), t.min(), t.max(), reps, np.median(t) * 1e3 / num_batches))
+    print("%s N=%d: torch / fused = %.2f (medians)" % (tag, N, np.median(times["torch"]) / np.median(times["fused"])))
 
 
 def world_trainer_bench(N, batch=100, epochs=3, rows=25000, reps=5):
