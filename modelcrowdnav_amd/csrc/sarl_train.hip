@@ -3,9 +3,10 @@
 //
 //   sarl_loss_grad_kernel   one workgroup per G states (at most 8 rows, or one state).  It gathers its rows of the replay
 //                           memory, runs the forward pass with every activation kept in LDS, forms its share of the
-//                           loss and back-propagates through mlp3, the pooling, the masked softmax, attention, the
-//                           mean (global state), mlp2 and mlp1.  Its gradient of EVERY parameter goes into its own
-//                           slice of the workspace: no atomics, no workgroup looks at another one's data.
+//                           loss and back-propagates through mlp3 (train_head.hpp: head_step), the pooling, the masked
+//                           softmax, attention, the mean (global state), mlp2 and mlp1 (train_attention.hpp: the trunk).
+//                           Its gradient of EVERY parameter goes into its own slice of the workspace: no atomics, no
+//                           workgroup looks at another one's data.
 //   train_grad_reduce_kernel (train_reduce.hpp) sums the slices in workgroup order into the flat gradient and
 //                           writes the loss.
 //   sgd_momentum_kernel     buf = momentum buf + grad, p = p - lr buf over the flat buffers.
@@ -15,25 +16,34 @@
 // The backward pass is plain float32.  The forward pass accumulates and hands its activations from layer to layer in
 // float64 (float32 copies of them stay in LDS for the backward pass), and the loss, d loss / d v and the sums over the
 // workgroups are float64 rounded once: a value v, the loss and the gradient of mlp3.6.bias are then the float32 nearest to
-// what float64 arithmetic gives, which single numbers need to stand a comparison with float64.  The semantics are those of torch autograd on ValueNetwork.forward: the softmax is the
-// un-stabilised exp(s) (s != 0) / sum with the mask a constant, ReLU passes gradient where its output is > 0, and NaN
-// goes where torch's goes (a state whose scores are all exactly 0 is 0 / 0).
+// what float64 arithmetic gives, which single numbers need to stand a comparison with float64.  The semantics are those
+// of torch autograd on ValueNetwork.forward: the softmax is the un-stabilised exp(s) (s != 0) / sum with the mask a
+// constant, ReLU passes gradient where its output is > 0, and NaN goes where torch's goes (a state whose scores are all
+// exactly 0 is 0 / 0).
 #include "train_attention.hpp"  // the layer table and the trunk; NT, lin_fwd, lin_bwd_*
+#include "train_head.hpp"       // mlp3 with the loss
 #include "train_reduce.hpp"     // the grouping and the reduce kernel
 
 namespace {
 
-// LDS elements per row (one human of one state) and per state: the trunk's and, carved by the kernel after them, this
-// head's (the gathered input; joint state, mlp3's activations and two backward buffers, the value's target and gradient)
+// LDS elements per row (one human of one state) and per state: the trunk's and, carved by the kernel after them, the
+// gathered input, the joint state and the head's
 constexpr int XS = 64;                   // row stride of the gathered input (input_dim <= 61)
+constexpr int JOINT = 6 + 50;            // mlp3's input: [self state | pooled feature]
 constexpr int ROW_FLOATS = XS + TRUNK_ROW_FLOATS;
-constexpr int STATE_FLOATS = TRUNK_STATE_FLOATS + 56 + 152 + 100 + 100 + 152 + 152 + 2;
+constexpr int STATE_FLOATS = TRUNK_STATE_FLOATS + JOINT + HEAD_STATE_FLOATS;
 constexpr int ROW_DOUBLES = TRUNK_ROW_DOUBLES;
-constexpr int STATE_DOUBLES = TRUNK_STATE_DOUBLES + 56 + 152 + 100 + 100 + 1;
+constexpr int STATE_DOUBLES = TRUNK_STATE_DOUBLES + JOINT + HEAD_STATE_DOUBLES;
 constexpr int LDS_DOUBLES = 20450;                                    // 163 600 B of the CU's 163 840
 constexpr int ROWS64_IN_LDS = 20;        // up to here the rows' float64 buffers fit LDS too; above, they live in the workspace
 
-TrainOffsets sarl_offsets(int D) { return train_offsets(D, 6 + 50, 1); }   // mlp3 on [self state | pooled feature] -> v
+TrainOffsets sarl_offsets(int D) { return train_offsets(D, JOINT, 1); }     // mlp3 on [self state | pooled feature] -> v
+__device__ __forceinline__ HeadOffsets head_of(const TrainOffsets &of)      // mlp3's four layers, as head_step takes them
+{
+    HeadOffsets h;
+    for (int l = 0; l < 4; ++l) h.w[l] = of.w[L3A + l], h.b[l] = of.b[L3A + l];
+    return h;
+}
 bool rows64_in_lds(int N) { return N <= ROWS64_IN_LDS; }
 bool group_fits(int G, int N)
 {
@@ -66,9 +76,9 @@ __global__ __launch_bounds__(NT) void sarl_loss_grad_kernel(const float *__restr
     auto take = [&at](int n) { float *q = at; at += n; return q; };
     float *X = take(Rcap * XS);
     const Trunk t = carve_trunk(st64, row64, at, G, Rcap);
-    double *Jd = taked(G * 56), *M1d = taked(G * 152), *M2d = taked(G * 100), *M3d = taked(G * 100), *Vd = taked(G);
-    float *J = take(G * 56), *M1 = take(G * 152), *M2 = take(G * 100), *M3 = take(G * 100);
-    float *U0 = take(G * 152), *U1 = take(G * 152), *Yt = take(G), *DV = take(G);
+    double *Jd = taked(G * JOINT);
+    float *J = take(G * JOINT);
+    const Head h = carve_head(st64, at, G);
 
     // ---- gather: rows[b] (or b) picks the state and its value out of the replay memory
     for (int it = tid; it < R * D; it += NT) {
@@ -76,13 +86,13 @@ __global__ __launch_bounds__(NT) void sarl_loss_grad_kernel(const float *__restr
         const int64_t row = rows ? rows[b0 + g] : (int64_t)(b0 + g);
         X[r * XS + d] = states[(row * N + n) * D + d];
     }
-    if (tid < Gc) Yt[tid] = values[rows ? rows[b0 + tid] : (int64_t)(b0 + tid)];
+    if (tid < Gc) h.Yt[tid] = values[rows ? rows[b0 + tid] : (int64_t)(b0 + tid)];
     __syncthreads();
 
     // ---- forward (float64 from layer to layer; the float32 copies are what the backward pass reads)
     trunk_forward(P, of, X, XS, D, t, Gc, N, R);
-    for (int it = tid; it < Gc * 56; it += NT) {                        // joint state: [self state | pooled feature]
-        const int g = it / 56, j = it - g * 56;
+    for (int it = tid; it < Gc * JOINT; it += NT) {                     // joint state: [self state | pooled feature]
+        const int g = it / JOINT, j = it - g * JOINT;
         double acc;
         if (j < 6) acc = X[(g * N) * XS + j];
         else {
@@ -93,46 +103,12 @@ __global__ __launch_bounds__(NT) void sarl_loss_grad_kernel(const float *__restr
         J[it] = (float)acc;
     }
     __syncthreads();
-    lin_fwd<double, false, true>(P + of.w[L3A], 56, P + of.b[L3A], Jd, 56, 1, M1d, 152, M1, 152, Gc, 56, 150);
-    __syncthreads();
-    lin_fwd<double, false, true>(P + of.w[L3B], 150, P + of.b[L3B], M1d, 152, 1, M2d, 100, M2, 100, Gc, 150, 100);
-    __syncthreads();
-    lin_fwd<double, false, true>(P + of.w[L3C], 100, P + of.b[L3C], M2d, 100, 1, M3d, 100, M3, 100, Gc, 100, 100);
-    __syncthreads();
-    lin_fwd<double, false, false>(P + of.w[L3D], 100, P + of.b[L3D], M3d, 100, 1, Vd, 1, nullptr, 0, Gc, 100, 1);
-    __syncthreads();
 
-    // ---- loss: this group's sum of squared errors and of d loss / d v = 2 (v - y) / B, both float64
-    if (tid == 0) {
-        double acc = 0.0, dsum = 0.0;
-        for (int g = 0; g < Gc; ++g) {
-            const double d = Vd[g] - (double)Yt[g];
-            const double dv = 2.0 * d / (double)B;
-            acc += d * d;
-            dsum += dv;
-            DV[g] = (float)dv;
-        }
-        ws_sums[2 * blockIdx.x] = acc;
-        ws_sums[2 * blockIdx.x + 1] = dsum;             // the gradient of mlp3.6.bias, before any float32 rounding
-    }
-    __syncthreads();
+    // ---- mlp3, forward and backward, with the loss: h.U1[g][6 + j] = d loss / d pooled
+    head_step<double, true>(P, gP, head_of(of), Jd, JOINT, J, JOINT, JOINT, h, Gc, B, ws_sums);
 
-    // ---- backward: mlp3
-    lin_bwd_w(DV, 1, M3, 100, 1, gP + of.w[L3D], 100, gP + of.b[L3D], Gc, 100, 1);
-    lin_bwd_x<false>(P + of.w[L3D], 100, DV, 1, U0, 152, M3, 100, Gc, 100, 1);
-    __syncthreads();
-    lin_bwd_w(U0, 152, M2, 100, 1, gP + of.w[L3C], 100, gP + of.b[L3C], Gc, 100, 100);
-    lin_bwd_x<false>(P + of.w[L3C], 100, U0, 152, U1, 152, M2, 100, Gc, 100, 100);
-    __syncthreads();
-    lin_bwd_w(U1, 152, M1, 152, 1, gP + of.w[L3B], 150, gP + of.b[L3B], Gc, 150, 100);
-    lin_bwd_x<false>(P + of.w[L3B], 150, U1, 152, U0, 152, M1, 152, Gc, 150, 100);
-    __syncthreads();
-    lin_bwd_w(U0, 152, J, 56, 1, gP + of.w[L3A], 56, gP + of.b[L3A], Gc, 56, 150);
-    lin_bwd_x<false>(P + of.w[L3A], 56, U0, 152, U1, 152, nullptr, 0, Gc, 56, 150);      // U1[g][6 + j] = d pooled
-    __syncthreads();
-
-    // ---- the trunk: pooling, softmax, attention, the mean, mlp2, mlp1
-    trunk_backward(P, gP, of, X, XS, D, U1 + 6, 152, t, Gc, N, R);
+    // ---- backward, the trunk: pooling, softmax, attention, the mean, mlp2, mlp1
+    trunk_backward(P, gP, of, X, XS, D, h.U1 + 6, 152, t, Gc, N, R);
 }
 
 // torch.optim.SGD(momentum, dampening 0, no weight decay, not nesterov): buf.mul_(momentum).add_(grad), then

@@ -4,7 +4,8 @@
 // state on [self state | pooled feature] with one output, or once per pedestrian on [own state | pooled feature] with two.
 // Here are the layer table of the flat buffers and the trunk's buffers with its forward and backward pass; the grouping of
 // a batch into workgroups and the kernel that sums their slices are in train_reduce.hpp.  Each .hip keeps its gather, its
-// head, its loss, its LDS budget and its optimizer.
+// LDS budget and its optimizer; SARL's head and loss are train_head.hpp's (shared with value_train.hip), the world model's
+// per-pedestrian head and loss are its own.
 #pragma once
 #include "launch.hpp"
 #include "train_linear.hpp"    // NT, CH, lin_fwd, lin_bwd_x, lin_bwd_w

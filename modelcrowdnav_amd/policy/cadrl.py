@@ -13,9 +13,18 @@ ValueNetwork through torch autograd, `Trainer(fused=True)` through csrc/value_tr
 """
 import ctypes as C
 import itertools
+import logging
+from types import SimpleNamespace
 
 import numpy as np
+import torch
 import torch.nn as nn
+
+from .. import _hip
+from .._pack import ident as _ident, natural as _natural, pack_layers
+from ..envs.policy.policy import Policy
+from ..envs.utils.action import ActionRot, ActionXY
+from ..envs.utils.state import FullState, ObservableState
 
 
 def mlp(input_dim, mlp_dims, last_relu=False):
@@ -45,20 +54,6 @@ def build_action_space(v_pref, kinematics="holonomic", speed_samples=5, rotation
     for rot, spd in itertools.product(rotations, speeds):
         rows.append((spd * np.cos(rot), spd * np.sin(rot)) if holonomic else (spd, rot))
     return np.array(rows, dtype=np.float64), speeds, rotations
-
-
-# ---------------------------------------------------------------------------------------------
-import logging
-
-import torch
-
-from .. import _hip
-from types import SimpleNamespace
-
-from .._pack import ident as _ident, natural as _natural, pack_layers
-from ..envs.policy.policy import Policy
-from ..envs.utils.action import ActionRot, ActionXY
-from ..envs.utils.state import FullState, ObservableState
 
 
 def rotate(state, kinematics):
@@ -95,12 +90,17 @@ def _state_arrays(model):
     return {k: v.detach().to("cpu", torch.float32).contiguous().numpy() for k, v in model.state_dict().items()}
 
 
+def shipped_shapes():
+    """Weight shapes of the shipped CADRL ValueNetwork (policy.config [cadrl]) by state_dict key prefix, in state_dict
+    order: what lstm_rl_value.hip and value_train.hip are built for."""
+    return {"value_network.0": (150, 13), "value_network.2": (100, 150), "value_network.4": (100, 100),
+            "value_network.6": (1, 100)}
+
+
 def pack_cadrl_network(model, dev):
     """CADRL ValueNetwork -> (ctypes mcn_cadrl_net, [device tensors kept alive])."""
     sd = _state_arrays(model)
-    expect = {"value_network.0": (150, 13), "value_network.2": (100, 150), "value_network.4": (100, 100),
-              "value_network.6": (1, 100)}
-    for k, shp in expect.items():
+    for k, shp in shipped_shapes().items():
         if k + ".weight" not in sd or tuple(sd[k + ".weight"].shape) != shp:
             raise ValueError("lstm_rl_value.hip is built for the shipped CADRL dimensions (policy.config [cadrl] "
                              "mlp_dims = 150, 100, 100, 1); %s.weight is %s" % (k, sd.get(k + ".weight", np.zeros(0)).shape))

@@ -52,11 +52,20 @@ def _gate_omap(hidden=50, tiles=4):
     return om
 
 
+def shipped_shapes():
+    """Shapes of the shipped LSTM-RL ValueNetwork1 (policy.config [lstm_rl]), in state_dict order: the weight shapes of
+    the MLP's layers by state_dict key prefix, then the LSTM's tensors by state_dict key.  What lstm_rl_value.hip and
+    value_train.hip are built for."""
+    return ({"mlp.0": (150, 56), "mlp.2": (100, 150), "mlp.4": (100, 100), "mlp.6": (1, 100)},
+            {"lstm.weight_ih_l0": (200, 13), "lstm.weight_hh_l0": (200, 50), "lstm.bias_ih_l0": (200,),
+             "lstm.bias_hh_l0": (200,)})
+
+
 def pack_lstm_rl_network(model, dev):
     """ValueNetwork1 -> (ctypes mcn_lstm_rl_net, [device tensors kept alive])."""
     sd = _state_arrays(model)
-    expect = {"lstm.weight_ih_l0": (200, 13), "lstm.weight_hh_l0": (200, 50), "mlp.0.weight": (150, 56),
-              "mlp.2.weight": (100, 150), "mlp.4.weight": (100, 100), "mlp.6.weight": (1, 100)}
+    layers, lstm = shipped_shapes()
+    expect = dict({k: shp for k, shp in lstm.items() if len(shp) == 2}, **{k + ".weight": shp for k, shp in layers.items()})
     for k, shp in expect.items():
         if k not in sd or tuple(sd[k].shape) != shp:
             raise ValueError("lstm_rl_value.hip is built for the shipped LSTM-RL dimensions (policy.config [lstm_rl]: "

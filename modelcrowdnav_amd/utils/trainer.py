@@ -17,7 +17,8 @@ by a HIP training step: per mini-batch three launches (loss and per-workgroup gr
 parameter / gradient / momentum buffers, the row indices of all batches of a call uploaded once and the losses read back
 once.  It draws the same batches from the same generator as the torch path.  Which file trains what (`_fused_step`):
 csrc/sarl_train.hip the shipped SARL / OM-SARL ValueNetwork, csrc/value_train.hip the shipped LSTM-RL ValueNetwork1 and
-the shipped CADRL ValueNetwork; the SGD-momentum kernel (sarl_train.hip) is the same for all three.
+the shipped CADRL ValueNetwork; the 150-100-100-1 head with its loss (train_head.hpp) and the SGD-momentum kernel
+(sarl_train.hip) are the same for all three.
 """
 import collections
 import logging
@@ -42,9 +43,8 @@ def _fused_step(m):
     from ..policy import cadrl, lstm_rl, sarl
     lib = _hip.lib
     if isinstance(m, lstm_rl.ValueNetwork1):
-        expect = dict(_fused.linear_shapes({"mlp.0": (150, 56), "mlp.2": (100, 150), "mlp.4": (100, 100), "mlp.6": (1, 100)}),
-                      **{"lstm.weight_ih_l0": (200, 13), "lstm.weight_hh_l0": (200, 50), "lstm.bias_ih_l0": (200,),
-                         "lstm.bias_hh_l0": (200,)})
+        layers, lstm = lstm_rl.shipped_shapes()
+        expect = dict(_fused.linear_shapes(layers), **lstm)
         why = "its self state is not 6 wide" if m.self_state_dim != 6 else _fused.mismatch(
             m.state_dict(), expect, lambda: int(lib.mcn_lstm_rl_train_param_count()),
             "its tensors are not the shipped ones (policy.config [lstm_rl]: global_state_dim = 50, mlp2_dims = 150, 100, 100, 1)",
@@ -55,8 +55,7 @@ def _fused_step(m):
         return _Step("mcn_lstm_rl_loss_grad", (None, 13), lib.mcn_lstm_rl_train_workspace_bytes, lib.mcn_lstm_rl_loss_grad), None
     if isinstance(m, cadrl.ValueNetwork):
         why = _fused.mismatch(
-            m.state_dict(), _fused.linear_shapes({"value_network.0": (150, 13), "value_network.2": (100, 150),
-                                                  "value_network.4": (100, 100), "value_network.6": (1, 100)}),
+            m.state_dict(), _fused.linear_shapes(cadrl.shipped_shapes()),
             lambda: int(lib.mcn_cadrl_train_param_count()),
             "its layers are not the shipped ones (policy.config [cadrl]: mlp_dims = 150, 100, 100, 1)",
             "its parameter count is not mcn_cadrl_train_param_count()")

@@ -1,4 +1,4 @@
-"""Child process of tests/test_fused_trainer_gpu.py: Trainer(fused=True) on cuda:0 without a process group, then -- from
+"""Child process of tests/test_fused_value_trainers_gpu.py: Trainer(fused=True) on cuda:0 without a process group, then -- from
 the same weights and the same draws -- inside a process group of ONE rank, where every step runs the all-reduce of the
 flat gradient between mcn_sarl_loss_grad and mcn_sgd_momentum_step.  Started as a fresh
 `python -m tests.fused_dp_worker <port> <backend> <out.pt>` process; both results go into <out.pt>."""
@@ -16,10 +16,10 @@ def main():
     from modelcrowdnav_amd import dist as mdist
     from modelcrowdnav_amd.utils.memory import ReplayMemory
     from modelcrowdnav_amd.utils.trainer import Trainer
-    from tests import trainer_ref as R
+    from tests import value_trainer_ref as R
     dev = torch.device("cuda", 0)
-    model0 = R.value_network(13, 4)
-    states, values = R.states_and_values(77, 5, 13, seed=31)
+    model0 = R.value_network("sarl", 4)
+    states, values = R.states_and_values("sarl", 77, 5, seed=31)
 
     def run():
         model = copy.deepcopy(model0).to(dev)

@@ -1,4 +1,4 @@
-"""What the tests of the two fused training steps share (tests/test_fused_trainer_gpu.py with tests/trainer_ref.py,
+"""What the tests of the fused training steps share (tests/test_fused_value_trainers_gpu.py with tests/value_trainer_ref.py,
 tests/test_fused_world_trainer_gpu.py with tests/world_trainer_ref.py): the float64 yardstick of a loss and its gradient
 -- the module itself in torch.float64 under torch autograd on the CPU -- and the comparing code, whose bound is a multiple
 of what torch's own float32 path is away from that yardstick on the same inputs.  Nothing here touches a GPU or the HIP

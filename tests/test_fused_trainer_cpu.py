@@ -1,7 +1,7 @@
 """CPU: the host side of the fused SARL training step (csrc/sarl_train.hip; include/mcn.h: mcn_sarl_train_param_count,
 mcn_sarl_train_workspace_bytes, mcn_sarl_loss_grad, mcn_sgd_momentum_step; utils/trainer.py: Trainer(fused=True)) -- the
 flat layout, the sizes, the argument validation (before any launch) and the refusals of the Python path.  The kernels
-themselves are tested on the device by tests/test_fused_trainer_gpu.py."""
+themselves are tested on the device by tests/test_fused_value_trainers_gpu.py."""
 import os
 import subprocess
 import sys
@@ -9,9 +9,10 @@ import sys
 import pytest
 import torch
 
-from tests import trainer_ref as R
+from tests import value_trainer_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+POLICY = {13: "sarl", 61: "sarl_om"}    # value_trainer_ref's name of the network with that input_dim
 
 
 def _sarl_model(with_om=False):
@@ -34,13 +35,13 @@ def test_param_count_is_the_configured_models():
 
 @pytest.mark.parametrize("input_dim", [13, 61])
 def test_flat_layout_is_state_dict_order(input_dim):
-    """The hand-written (name, offset, shape) table of tests/trainer_ref.py against the layout the Trainer uses and
+    """The hand-written (name, offset, shape) table of tests/value_trainer_ref.py against the layout the Trainer uses and
     against the module's own state_dict."""
     from modelcrowdnav_amd import _hip
     from modelcrowdnav_amd.utils.memory import ReplayMemory
     from modelcrowdnav_amd.utils.trainer import Trainer
-    model = R.value_network(input_dim, seed=0)
-    table, total = R.layout(input_dim)
+    model = R.value_network(POLICY[input_dim], seed=0)
+    table, total = R.layout(POLICY[input_dim])
     assert total == _hip.lib.mcn_sarl_train_param_count(input_dim)
     assert [(k, tuple(v.shape)) for k, v in model.state_dict().items()] == [(k, shp) for k, _, shp in table]
     assert [k for k, _ in model.named_parameters()] == [k for k, _, _ in table]
@@ -123,7 +124,9 @@ def test_training_entry_points_validate_on_host():
 
 def _memory(N=5, D=13, rows=8):
     from modelcrowdnav_amd.utils.memory import ReplayMemory
-    s, v = R.states_and_values(rows, N, D, seed=3)
+    s, v = R.states_and_values("sarl", rows, N, seed=3)
+    if D != 13:
+        s = torch.randn(rows, N, D, generator=torch.Generator().manual_seed(3))
     mem = ReplayMemory(32)
     mem.push_batch(s, v)
     return mem
@@ -144,7 +147,7 @@ def test_fused_trainer_refuses_what_it_is_not_built_for():
         Trainer(ValueNetwork(14, 6, [150, 100], [100, 50], [150, 100, 100, 1], [100, 100, 1], True, 1.0, 4), _memory(D=14),
                 cpu, 4, fused=True)
     # a memory with a row of another human count
-    model = R.value_network(13, seed=0)
+    model = R.value_network("sarl", seed=0)
     odd = _memory()
     odd.push((torch.zeros(3, 13), torch.zeros(1)))
     assert odd._odd

@@ -13,6 +13,7 @@ import torch
 from tests import value_trainer_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+POLICIES = ("lstm_rl", "cadrl")     # the networks of value_train.hip (SARL's host side: tests/test_fused_trainer_cpu.py)
 NEW_SYMBOLS = ["mcn_cadrl_train_param_count", "mcn_cadrl_train_workspace_bytes", "mcn_cadrl_loss_grad",
                "mcn_lstm_rl_train_param_count", "mcn_lstm_rl_train_workspace_bytes", "mcn_lstm_rl_loss_grad"]
 
@@ -39,7 +40,7 @@ def _configured(policy):
     return p.model
 
 
-@pytest.mark.parametrize("policy", R.POLICIES)
+@pytest.mark.parametrize("policy", POLICIES)
 def test_param_count_and_flat_layout_are_state_dict_order(policy):
     """The library's count, the hand-written table, the layout the Trainer uses, the seeded module's and the configured
     policy's own state_dict all agree: for LSTM-RL that pins the MLP before the four LSTM tensors."""
@@ -132,7 +133,7 @@ def _memory(policy, N=5, rows=8):
     return mem
 
 
-@pytest.mark.parametrize("policy", R.POLICIES)
+@pytest.mark.parametrize("policy", POLICIES)
 def test_fused_trainer_takes_the_shipped_model_and_only_that(policy):
     from modelcrowdnav_amd.policy.cadrl import ValueNetwork
     from modelcrowdnav_amd.policy.lstm_rl import ValueNetwork1
@@ -187,7 +188,7 @@ def test_unknown_class_names_all_three_networks():
         assert text in str(e.value), text
 
 
-@pytest.mark.parametrize("policy", R.POLICIES)
+@pytest.mark.parametrize("policy", POLICIES)
 def test_unfused_trainer_is_unaffected(policy):
     """fused=False (and the default) takes the torch path whatever the memory holds, and leaves no fused state."""
     from modelcrowdnav_amd.utils.trainer import Trainer
@@ -220,7 +221,7 @@ def load_g26(policy, golden_dir, device, fused):
     return g, model, states, values.reshape(-1, 1), Trainer(model.to(device), mem, device, 100, fused=fused)
 
 
-@pytest.mark.parametrize("policy", R.POLICIES)
+@pytest.mark.parametrize("policy", POLICIES)
 def test_default_trainer_matches_reference_trainer(policy, golden_dir):
     """The default torch path against the REAL reference Trainer on the reference's own ValueNetwork1 / ValueNetwork
     (tests/golden_tools/gen_golden_value_trainers.py): same weights, same one-batch memory, lr 0.01, three
