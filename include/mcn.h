@@ -791,6 +791,64 @@ int mcn_attn_world_loss_grad(const float *params, const float *cur, const float 
 int mcn_adam_step(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr, float beta1,
                   float beta2, float eps, int32_t step, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * MlpWorld training step (crowd_nav/utils/trainer_sim.py:48-110 on crowd_nav/policy/world_model.py:22-51).
+ * ---------------------------------------------------------------------------------------------- */
+
+/*
+ * The dropout mask of the MlpWorld training step.  torch's Philox stream cannot be reproduced from outside torch, so the
+ * step draws its masks from a stateless counter hash, the same code on the host and on the device
+ * (csrc/dropout_hash.hpp).  All arithmetic is on uint64 and wraps:
+ *
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   key  = mix(seed + 0x9E3779B97F4A7C15 * (2 * step + layer + 1))
+ *   r    = mix(key  + 0x9E3779B97F4A7C15 * (256 * slot + unit + 1))
+ *   keep = (r >> 40) < T,   T = llrint((1 - p) * 2^24)
+ *
+ * layer: 0 after mlp.1 (128 units), 1 after mlp.4 (64 units); slot: the scene's position in the mini-batch (not its
+ * memory row); unit: the feature; step: the caller's count of training steps.  The mask is a function of these five
+ * numbers and p alone: it does not depend on how scenes are dealt to workgroups.  A kept unit is multiplied by
+ * 1 / (1 - p), a dropped one by 0 -- a multiplication in both passes, after the ReLU's own select, so NaN and Inf travel
+ * as through nn.Dropout.  p arrives as float32 and is applied as the decimal that was written (0.1f means 0.1, as
+ * mcn_adam_step takes its hyper-parameters): T is 8388608 for 0.5, 15099494 for 0.1f, 1677722 for 0.9f, 16777216 for 0
+ * (every unit kept, multiplied by exactly 1).
+ * r >> 40 for (seed, step, layer, slot, unit): (0,0,0,0,0) 10946269; (0,0,1,0,0) 4634430; (0,1,0,0,0) 15607633;
+ * (1,0,0,0,0) 6177195; (12345,7,1,99,127) 13549691; (2^64-1, 2^40, 1, 3, 63) 822369.
+ *
+ * mcn_dropout_mask -- the mask of one layer of one step on the HOST (no GPU involved): keep[b * width + u] = 1 where unit
+ * u of slot b is kept, else 0.  MCN_EINVAL: keep NULL, B < 1, width outside 1 .. 256, layer outside 0 .. 1, p not in [0, 1).
+ */
+int mcn_dropout_mask(uint64_t seed, uint64_t step, int32_t layer, int32_t B, int32_t width, float p,
+                     uint8_t *keep /* host, [B][width] */);
+
+/*
+ * The network is MlpWorld(N): 4N -> 128 -> 64 -> 12 -> 2N, ReLU after the first three layers, dropout after the first two,
+ * tanh on the output.  Parameters, gradient and the two Adam moments are each ONE flat float32 device buffer in
+ * state_dict order -- mlp.0.weight, mlp.0.bias, mlp.3.*, mlp.6.*, mlp.8.* -- every weight row-major [out][in] as torch
+ * stores it.
+ */
+int64_t mcn_mlp_world_train_param_count(int32_t N);            /* 538 N + 9164 (N = 5: 11854); 0 outside 1 .. MCN_MAX_HUMANS */
+int64_t mcn_mlp_world_train_workspace_bytes(int32_t B, int32_t N);   /* 0 for arguments the step refuses */
+
+/*
+ * mcn_mlp_world_loss_grad -- loss = mean((model(cur[rows]) - nxt[rows])^2) over the B 2N outputs of a mini-batch of B
+ * scenes of N pedestrians.  With grad it is the TRAIN-mode pass -- dropout with probability drop_p and the masks defined
+ * above for (seed, step), slot b being scene b of the batch -- and grad receives the gradient by every parameter, with
+ * the semantics of torch autograd (ReLU passes gradient where its output is > 0).  grad == NULL is the EVAL-mode forward
+ * pass, which is what validation runs: no dropout, drop_p / seed / step are ignored (drop_p is still validated), and
+ * nothing but `loss` is written for the caller.  With drop_p == 0 both modes give the same loss bits.
+ * cur, nxt, rows, workspace (mcn_mlp_world_train_workspace_bytes(B, N) device bytes, 8-byte aligned), loss and the two
+ * launches on `stream` are those of mcn_attn_world_loss_grad: the kernel TRUSTS the row indices, there are no atomics and
+ * the same inputs give the same bits.  The forward pass, tanh, d loss / d z = d loss / d out (1 - out^2) and the sums over
+ * the batch run in float64, the backward pass in float32; mlp.8.bias comes from float64 sums.  One workgroup takes 8
+ * scenes, every activation in LDS.
+ * MCN_EINVAL before any launch: a NULL params / cur / nxt / workspace / loss, B < 1, N outside 1 .. MCN_MAX_HUMANS,
+ * drop_p outside [0, 1) or not finite.
+ */
+int mcn_mlp_world_loss_grad(const float *params, const float *cur, const float *nxt, const int64_t *rows, int32_t B, int32_t N,
+                            float drop_p, uint64_t seed, uint64_t step, void *workspace,
+                            float *grad /* or NULL */, float *loss, void *stream);
+
 /*
  * Dispatch overrides (host, process-wide, not stream-ordered; for tests and tuning).  Every env-step arithmetic
  * exists in several kernel decompositions with bit-identical results; by default the entry points pick one from

@@ -207,6 +207,15 @@ def _load():
     # params, exp_avg, exp_avg_sq, grad, count, lr, beta1, beta2, eps, step, stream
     lib.mcn_adam_step.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, _f, _f, _f, _f, _i, _vp]
     lib.mcn_adam_step.restype = C.c_int
+    lib.mcn_mlp_world_train_param_count.argtypes, lib.mcn_mlp_world_train_param_count.restype = [_i], C.c_int64
+    lib.mcn_mlp_world_train_workspace_bytes.argtypes = [_i, _i]
+    lib.mcn_mlp_world_train_workspace_bytes.restype = C.c_int64
+    # params, cur, nxt, rows, B, N, drop_p, seed, step, workspace, grad (or NULL), loss, stream
+    lib.mcn_mlp_world_loss_grad.argtypes = [_vp, _vp, _vp, _vp, _i, _i, _f, C.c_uint64, C.c_uint64, _vp, _vp, _vp, _vp]
+    lib.mcn_mlp_world_loss_grad.restype = C.c_int
+    # seed, step, layer, B, width, p, keep (host)
+    lib.mcn_dropout_mask.argtypes = [C.c_uint64, C.c_uint64, _i, _i, _i, _f, _vp]
+    lib.mcn_dropout_mask.restype = C.c_int
     lib.mcn_sgan_workspace_bytes.argtypes = [_i, _i]
     lib.mcn_sgan_workspace_bytes.restype = C.c_int64
     lib.mcn_sgan_step.argtypes = [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _d, _i, _i, _vp]
@@ -274,6 +283,7 @@ EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict",
             "mcn_sarl_train_param_count", "mcn_sarl_train_workspace_bytes", "mcn_sarl_loss_grad", "mcn_sgd_momentum_step",
             "mcn_attn_world_train_param_count", "mcn_attn_world_train_workspace_bytes", "mcn_attn_world_loss_grad", "mcn_adam_step",
+            "mcn_dropout_mask", "mcn_mlp_world_train_param_count", "mcn_mlp_world_train_workspace_bytes", "mcn_mlp_world_loss_grad",
             "mcn_cadrl_train_param_count", "mcn_cadrl_train_workspace_bytes", "mcn_cadrl_loss_grad",
             "mcn_lstm_rl_train_param_count", "mcn_lstm_rl_train_workspace_bytes", "mcn_lstm_rl_loss_grad"]
 

@@ -12,6 +12,7 @@ namespace mcn {
 
 // mcn_api.hip
 bool tuning_sarl_x3();              // mcn_tuning.sarl_x3 (-1 / 1: use the x3 fragments when given, 0: never)
+double written_as(float x);         // a float32 hyper-parameter as the decimal that was written: 0.001f -> 0.001
 
 // Env kernels.  mcn_api.hip plans (env_dispatch.hpp); each launcher gets its part of the plan, picks the instantiation,
 // sizes the grid and launches.  None reports errors: the caller reads hipGetLastError() after each launch group.
@@ -77,6 +78,14 @@ int launch_attn_world_loss_grad(const float *params, const float *cur, const flo
                                 hipStream_t stream);
 int launch_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr, float beta1,
                 float beta2, float eps, int step, hipStream_t stream);
+
+// world_mlp_train.hip (the masks: dropout_hash.hpp)
+long mlp_world_train_param_count(int N);
+long mlp_world_train_workspace_floats(int B, int N);
+int launch_mlp_world_loss_grad(const float *params, const float *cur, const float *nxt, const int64_t *rows, int B, int N,
+                               float drop_p, uint64_t seed, uint64_t step, void *workspace,
+                               float *grad /* or NULL: the eval-mode loss only */, float *loss, hipStream_t stream);
+int dropout_mask_host(uint64_t seed, uint64_t step, int layer, int B, int width, float p, uint8_t *keep);
 
 // value_train.hip
 long cadrl_train_param_count();

@@ -3,6 +3,7 @@
 // is never started on shapes its indexing does not assume.
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <math.h>
 #include <mutex>
@@ -46,6 +47,28 @@ static mcn_tuning tuning()
 }
 
 namespace mcn { bool tuning_sarl_x3() { return tuning().sarl_x3 != 0; } }
+
+namespace mcn {
+
+// A hyper-parameter that the C ABI carries as float32 (mcn_adam_step's lr, betas and eps; mcn_mlp_world_loss_grad's and
+// mcn_dropout_mask's drop_p), as the float64 that was written.
+// torch applies the hyper-parameters as the Python floats (float64) the user wrote -- 1e-3, 0.9, 0.999, 1e-8 -- and the C
+// ABI carries them as float32, 5e-8 away.  That is enough to show: lr 0.001f in place of 0.001 moves every step by 5e-8 of
+// itself, and on the recorded reference run (tests/golden/g20_trainer_sim.npz) that flipped one ReLU of one row at the
+// sixth step, after which single weights were 2.6e-5 from the float64 replay instead of 8e-8.  So the float64 is
+// recovered: the shortest decimal that rounds to the given float32, which is what was written for anything of up to 7
+// digits.
+double written_as(float x)
+{
+    char buf[40];
+    for (int digits = 1; digits <= 8; ++digits) {
+        snprintf(buf, sizeof buf, "%.*e", digits - 1, (double)x);
+        if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
+    }
+    return (double)x;
+}
+
+}  // namespace mcn
 
 // bf16 round-to-nearest-even of a float32 (NaN kept quiet), as the device's v_cvt_pk_bf16_f32
 static uint16_t bf16_rne(float x)
@@ -604,6 +627,35 @@ int mcn_adam_step(float *params, float *exp_avg, float *exp_avg_sq, const float 
     if (!isfinite(lr) || !isfinite(eps) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f))
         return MCN_EINVAL;                              // (a NaN or infinite beta fails the range test)
     return mcn::launch_adam(params, exp_avg, exp_avg_sq, grad, count, lr, beta1, beta2, eps, step, (hipStream_t)stream);
+}
+
+int64_t mcn_mlp_world_train_param_count(int32_t N)
+{
+    if (N <= 0 || N > MCN_MAX_HUMANS) return 0;
+    return (int64_t)mcn::mlp_world_train_param_count(N);
+}
+
+int64_t mcn_mlp_world_train_workspace_bytes(int32_t B, int32_t N)
+{
+    if (B <= 0 || N <= 0 || N > MCN_MAX_HUMANS) return 0;
+    return (int64_t)mcn::mlp_world_train_workspace_floats(B, N) * 4;
+}
+
+int mcn_mlp_world_loss_grad(const float *params, const float *cur, const float *nxt, const int64_t *rows, int32_t B,
+                            int32_t N, float drop_p, uint64_t seed, uint64_t step, void *workspace, float *grad,
+                            float *loss, void *stream)
+{
+    if (!params || !cur || !nxt || !workspace || !loss) return MCN_EINVAL;
+    if (B < 1 || N < 1 || N > MCN_MAX_HUMANS) return MCN_EINVAL;
+    if (!(drop_p >= 0.f && drop_p < 1.f)) return MCN_EINVAL;          // (a NaN or infinite drop_p fails the range test)
+    return mcn::launch_mlp_world_loss_grad(params, cur, nxt, rows, B, N, drop_p, seed, step, workspace, grad, loss,
+                                           (hipStream_t)stream);
+}
+
+int mcn_dropout_mask(uint64_t seed, uint64_t step, int32_t layer, int32_t B, int32_t width, float p, uint8_t *keep)
+{
+    if (!keep || B < 1 || width < 1 || width > 256 || layer < 0 || layer > 1 || !(p >= 0.f && p < 1.f)) return MCN_EINVAL;
+    return mcn::dropout_mask_host(seed, step, layer, B, width, p, keep);
 }
 
 int mcn_mlp_world_step(const mcn_mlp_world_net *net, const double *hpos, const double *hvel, double *out_vel,

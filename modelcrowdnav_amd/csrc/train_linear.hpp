@@ -1,4 +1,4 @@
-// train_linear.hpp -- the linear-layer building blocks of the training kernels (sarl_train.hip, world_train.hip, value_train.hip): the
+// train_linear.hpp -- the linear-layer building blocks of the training kernels (sarl_train.hip, world_train.hip, world_mlp_train.hip, value_train.hip): the
 // forward pass of one layer in float64 with float32 copies for the backward pass, and the two halves of its backward pass
 // in float32.  A workgroup of NT threads works on R rows kept in LDS (or in its own piece of the workspace); the weights
 // come from the flat parameter buffer, row-major [out][in] as torch holds them.

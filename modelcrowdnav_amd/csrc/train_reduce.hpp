@@ -1,4 +1,4 @@
-// train_reduce.hpp -- what every training step (sarl_train.hip, world_train.hip, value_train.hip) does after its
+// train_reduce.hpp -- what every training step (sarl_train.hip, world_train.hip, world_mlp_train.hip, value_train.hip) does after its
 // loss/gradient kernel: how a batch is grouped into workgroups, how their slices lie in the workspace, and the kernel that
 // sums the slices in workgroup order into the flat gradient and writes the loss.
 #pragma once

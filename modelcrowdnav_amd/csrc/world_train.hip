@@ -21,8 +21,6 @@
 // From 17 pedestrians on -- one scene per workgroup, up to MCN_MAX_HUMANS = 32 rows -- the float64 row buffers and
 // mlp3's float32 activations (which are per pedestrian here, not per state) are the workgroup's own piece of the
 // workspace instead, and LDS holds the rest (139 652 B at 32 rows).
-#include <cstdio>
-#include <cstdlib>
 #include "train_attention.hpp"  // the layer table and the trunk; NT, lin_fwd, lin_bwd_*
 #include "train_reduce.hpp"     // the grouping and the reduce kernel
 
@@ -215,22 +213,6 @@ int launch_attn_world_loss_grad(const float *params, const float *cur, const flo
     if (hipGetLastError() != hipSuccess) return MCN_ELAUNCH;
     return launch_train_grad_reduce(ws, ws_sums, groups, of.total, 4, of.b[L3D], DOUT, (double)B * (double)(N * DOUT), grad,
                                     loss, stream);
-}
-
-// torch applies the hyper-parameters as the Python floats (float64) the user wrote -- 1e-3, 0.9, 0.999, 1e-8 -- and the C
-// ABI carries them as float32, 5e-8 away.  That is enough to show: lr 0.001f in place of 0.001 moves every step by 5e-8 of
-// itself, and on the recorded reference run (tests/golden/g20_trainer_sim.npz) that flipped one ReLU of one row at the
-// sixth step, after which single weights were 2.6e-5 from the float64 replay instead of 8e-8.  So the float64 is
-// recovered: the shortest decimal that rounds to the given float32, which is what was written for anything of up to 7
-// digits.
-static double written_as(float x)
-{
-    char buf[40];
-    for (int digits = 1; digits <= 8; ++digits) {
-        snprintf(buf, sizeof buf, "%.*e", digits - 1, (double)x);
-        if (strtof(buf, nullptr) == x) return strtod(buf, nullptr);
-    }
-    return (double)x;
 }
 
 int launch_adam(float *params, float *exp_avg, float *exp_avg_sq, const float *grad, int64_t count, float lr, float beta1,

@@ -1,5 +1,5 @@
 """What Trainer(fused=True) and Trainer_Sim(fused=True) both do to a module's parameters on the way to the HIP training
-steps (csrc/sarl_train.hip, csrc/value_train.hip, csrc/world_train.hip): the flat float32 buffers and their layout, the check of a state_dict
+steps (csrc/sarl_train.hip, csrc/value_train.hip, csrc/world_train.hip, csrc/world_mlp_train.hip): the flat float32 buffers and their layout, the check of a state_dict
 against a shape table, the workspace, and the pointer and row arithmetic of a launch."""
 import ctypes as C
 

@@ -14,7 +14,17 @@ mcn_attn_world_loss_grad and one mcn_adam_step on flat parameter / gradient / mo
 forward-only launches, the row indices of an epoch uploaded once and its validation losses read back once.  The split,
 the batches, early stopping and the best weights are those of the torch path.  Known difference:
 `model.attention_weights` is not updated, because no torch forward runs.
+
+An MlpWorld (4N -> 128 -> 64 -> 12 -> 2N, both Dropouts with the same p in [0, 1)) is trained the same way by
+csrc/world_mlp_train.hip: mcn_mlp_world_loss_grad in place of mcn_attn_world_loss_grad, everything else as above
+(`_fused_step` picks the step by the model's class).  Its dropout masks come from the library's own counter hash
+(include/mcn.h: mcn_dropout_mask) under `trainer.dropout_seed` -- settable; by default torch.initial_seed(), read at the
+first fused call -- and a count of the fused training steps since the trainer was made, which nothing resets: a round
+that starts Adam over (set_learning_rate) does not replay the masks of an earlier round.  Two known differences from
+the torch path: the masks are not torch's; and without `perms` the torch path's LATER permutations differ from the
+fused path's, because its dropout draws from the same device generator as `randperm`.
 """
+import collections
 import copy
 import logging
 import random
@@ -24,6 +34,60 @@ import torch.nn as nn
 import torch.optim as optim
 
 from . import _fused
+
+
+# What differs between the fused steps: the launch's name, the library's workspace(B, N) and launch(params, cur, nxt, rows,
+# B, N, ws, grad, loss, stream, mask_step) -- mask_step is the trainer's count of fused training steps, which only a step
+# with dropout looks at --, the model's own pedestrian count (None: any) and what the device refusal says.
+_Step = collections.namedtuple("_Step", "name workspace launch humans no_gpu")
+
+
+def _fused_step(trainer):
+    """(the _Step that trains trainer.model, None), or (None, why there is none)."""
+    from .. import _hip
+    from ..policy.world_model import AttentionWorld, MlpWorld
+    lib, m = _hip.lib, trainer.model
+    if isinstance(m, MlpWorld):
+        lin = [k for k in m.mlp if isinstance(k, nn.Linear)]
+        N = lin[0].in_features // 4 if lin else 0
+        expect = {"mlp.0": (128, 4 * N), "mlp.3": (64, 128), "mlp.6": (12, 64), "mlp.8": (2 * N, 12)}
+        drops = [float(k.p) for k in m.mlp if isinstance(k, nn.Dropout)]
+        if not lin or lin[0].in_features != 4 * N or not 1 <= N <= _hip.MAX_HUMANS:
+            why = "mlp.0 takes %s inputs, not 4 N with N in 1 .. %d" % (lin[0].in_features if lin else "no", _hip.MAX_HUMANS)
+        else:
+            why = _fused.mismatch(
+                m.state_dict(), _fused.linear_shapes(expect), lambda: int(lib.mcn_mlp_world_train_param_count(N)),
+                "its layers are not MlpWorld's (mlp.0, mlp.3, mlp.6, mlp.8: 4N-128-64-12-2N)",
+                "its parameter count is not mcn_mlp_world_train_param_count(N)")
+        if why is None and (len(drops) != 2 or drops[0] != drops[1]):
+            why = "its dropout rates are %s, not one rate for both layers" % (drops,)
+        if why is None and not 0.0 <= drops[0] < 1.0:
+            why = "its dropout rate is %g, outside [0, 1)" % drops[0]
+        if why is not None:
+            return None, "world_mlp_train.hip is built for MlpWorld (4N-128-64-12-2N); this model cannot be trained by it: " + why
+        p = drops[0]
+
+        def launch(params, cur, nxt, rows, B, n, ws, grad, loss, stream, mask_step):
+            return lib.mcn_mlp_world_loss_grad(params, cur, nxt, rows, B, n, p, trainer._mask_seed(), mask_step, ws, grad,
+                                               loss, stream)
+        return _Step("mcn_mlp_world_loss_grad", lib.mcn_mlp_world_train_workspace_bytes, launch, N,
+                     "the MlpWorld step draws its dropout masks on the device; "), None
+    expect = {"mlp1.0": (150, 4), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
+              "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
+              "mlp3.0": (150, 54), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (2, 100)}
+    if not isinstance(m, AttentionWorld) or m.input_dim != 4 or not m.with_global_state:
+        why = "it is not an AttentionWorld with input_dim 4 and the global state"
+    else:
+        why = _fused.mismatch(
+            m.state_dict(), _fused.linear_shapes(expect), lambda: int(lib.mcn_attn_world_train_param_count()),
+            "its layers are not the default ones (mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-2)",
+            "its parameter count is not mcn_attn_world_train_param_count()")
+    if why is not None:
+        return None, "world_train.hip is built for the default AttentionWorld; this model cannot be trained by it: " + why
+
+    def launch(params, cur, nxt, rows, B, n, ws, grad, loss, stream, mask_step):
+        return lib.mcn_attn_world_loss_grad(params, cur, nxt, rows, B, n, ws, grad, loss, stream)
+    return _Step("mcn_attn_world_loss_grad", lib.mcn_attn_world_train_workspace_bytes, launch, None, ""), None
 
 
 class EarlyStopping(object):
@@ -62,6 +126,8 @@ class Trainer_Sim(object):
         self.early_stopping = EarlyStopping(patience=self.patience, path=path)
         self.fused = bool(Trainer_Sim.fused_default if fused is None else fused)
         self._fz = None                  # fused path: flat params / grad / Adam moments, workspace, step count
+        self.dropout_seed = None         # fused MlpWorld: the seed of the masks; None = torch.initial_seed() at the first call
+        self.mask_step = 0               # fused training steps since the trainer was made: the masks' step, never reset
         self.last_rows = None            # fused path: per epoch of the latest call (train row order, validation row order
         #                                  or None for rows 0 .. n_val-1), device tensors; rows index what _pairs() stacked
         if self.fused:
@@ -133,35 +199,26 @@ class Trainer_Sim(object):
         self.model.mse = 0 - es.best_score                      # used to add noise to the MLP world
         return -es.best_score
 
-    # ------------------------------------------------------------------ fused HIP step (csrc/world_train.hip)
+    # ------------------------------------------------------------------ fused HIP step (csrc/world_train.hip, world_mlp_train.hip)
     def _fused_layout(self):
         return _fused.layout(self.model)
 
+    def _mask_seed(self):
+        if self.dropout_seed is None:
+            self.dropout_seed = int(torch.initial_seed())
+        return int(self.dropout_seed) & 0xFFFFFFFFFFFFFFFF
+
     def _fused_check(self):
         """ValueError for what the fused step is not built for."""
-        from .. import _hip
-        from ..policy.world_model import AttentionWorld, MlpWorld
-        m = self.model
-        expect = {"mlp1.0": (150, 4), "mlp1.2": (100, 150), "mlp2.0": (100, 100), "mlp2.2": (50, 100),
-                  "attention.0": (100, 200), "attention.2": (100, 100), "attention.4": (1, 100),
-                  "mlp3.0": (150, 54), "mlp3.2": (100, 150), "mlp3.4": (100, 100), "mlp3.6": (2, 100)}
-        if isinstance(m, MlpWorld):
-            why = "it is an MlpWorld, which draws dropout masks in training"
-        elif not isinstance(m, AttentionWorld) or m.input_dim != 4 or not m.with_global_state:
-            why = "it is not an AttentionWorld with input_dim 4 and the global state"
-        else:
-            why = _fused.mismatch(
-                m.state_dict(), _fused.linear_shapes(expect), lambda: int(_hip.lib.mcn_attn_world_train_param_count()),
-                "its layers are not the default ones (mlp1 150-100, mlp2 100-50, attention 100-100-1, mlp3 150-100-100-2)",
-                "its parameter count is not mcn_attn_world_train_param_count()")
+        self._step_hip, why = _fused_step(self)
         if why is not None:
-            raise ValueError("Trainer_Sim(fused=True): world_train.hip is built for the default AttentionWorld; this model "
-                             "cannot be trained by it: " + why)
+            raise ValueError("Trainer_Sim(fused=True): " + why)
         dev = torch.device(self.device)
         if dev.type != "cuda":
-            raise ValueError("Trainer_Sim(fused=True) runs HIP kernels: the trainer's device is %s, not a GPU" % (dev,))
+            raise ValueError("Trainer_Sim(fused=True) runs HIP kernels: %sthe trainer's device is %s, not a GPU" %
+                             (self._step_hip.no_gpu, dev))
         want = torch.cuda.current_device() if dev.index is None else dev.index
-        for k, p in m.named_parameters():
+        for k, p in self.model.named_parameters():
             if p.device.type != "cuda" or p.device.index != want:
                 raise ValueError("Trainer_Sim(fused=True): the model lives on %s (%s), the trainer on %s" % (p.device, k, dev))
 
@@ -177,6 +234,10 @@ class Trainer_Sim(object):
                 not 1 <= N <= _hip.MAX_HUMANS:
             raise ValueError("Trainer_Sim(fused=True): pairs are %s -> %s, the model takes [N <= %d][4] -> [N][2]" %
                              (tuple(tx.shape[1:]), tuple(ty.shape[1:]), _hip.MAX_HUMANS))
+        step = self._step_hip
+        if step.humans is not None and step.humans != N:
+            raise ValueError("Trainer_Sim(fused=True): the pairs hold %d pedestrians, the model is built for %d" %
+                             (N, step.humans))
         tx, ty, vx, vy = tx.contiguous(), ty.contiguous(), vx.contiguous(), vy.contiguous()
         nt, nv, B = int(tx.shape[0]), int(vx.shape[0]), int(self.batch_size)
         if B < 1:
@@ -214,26 +275,26 @@ class Trainer_Sim(object):
                 n_rows = nv if vperm is None else int(vperm.numel())
                 n_batches = -(-n_rows // B)
                 # room for the largest batch of this epoch and for one loss per validation batch
-                ws = _fused.workspace(z, int(lib.mcn_attn_world_train_workspace_bytes(min(B, max(int(perm.numel()), n_rows, 1)), N)))
+                ws = _fused.workspace(z, int(step.workspace(min(B, max(int(perm.numel()), n_rows, 1)), N)))
                 if vloss is None or vloss.numel() < n_batches:
                     vloss = torch.empty(n_batches, dtype=torch.float32, device=dev)
                 for i in range(0, int(perm.numel()), B):
                     b = min(B, int(perm.numel()) - i)
-                    _hip.check(lib.mcn_attn_world_loss_grad(ptr(z["params"]), ptr(tx), ptr(ty), at(perm, i, 1), b, N,
-                                                            ptr(ws), ptr(z["grad"]), ptr(z["loss"]), stream),
-                               "mcn_attn_world_loss_grad")
+                    _hip.check(step.launch(ptr(z["params"]), ptr(tx), ptr(ty), at(perm, i, 1), b, N, ptr(ws), ptr(z["grad"]),
+                                           ptr(z["loss"]), stream, self.mask_step), step.name)
                     z["step"] += 1
+                    self.mask_step += 1
                     _hip.check(lib.mcn_adam_step(ptr(z["params"]), ptr(z["m"]), ptr(z["v"]), ptr(z["grad"]), count, lr,
                                                  beta1, beta2, eps, z["step"], stream), "mcn_adam_step")
                 for k in range(n_batches):
                     b = min(B, n_rows - k * B)
                     if vperm is None:        # rows k B .. of the validation tensors, in their own order
-                        rc = lib.mcn_attn_world_loss_grad(ptr(z["params"]), at(vx, k * B, 4 * N), at(vy, k * B, 2 * N), None, b,
-                                                          N, ptr(ws), None, at(vloss, k, 1), stream)
+                        rc = step.launch(ptr(z["params"]), at(vx, k * B, 4 * N), at(vy, k * B, 2 * N), None, b, N, ptr(ws), None,
+                                         at(vloss, k, 1), stream, 0)
                     else:
-                        rc = lib.mcn_attn_world_loss_grad(ptr(z["params"]), ptr(vx), ptr(vy), at(vperm, k * B, 1), b, N,
-                                                          ptr(ws), None, at(vloss, k, 1), stream)
-                    _hip.check(rc, "mcn_attn_world_loss_grad")
+                        rc = step.launch(ptr(z["params"]), ptr(vx), ptr(vy), at(vperm, k * B, 1), b, N, ptr(ws), None,
+                                         at(vloss, k, 1), stream, 0)
+                    _hip.check(rc, step.name)
                 losses = vloss[:n_batches].cpu().tolist()      # the epoch's one read-back
                 _fused.store(z, params, table)
                 es(sum(losses) / len(losses), self.model)

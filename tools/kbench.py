@@ -9,7 +9,7 @@ human-policy modes, measured with HIP events around a hipGraph of back-to-back l
     python tools/kbench.py --trainer [--policy sarl|lstm_rl|cadrl] [--humans 5,10]
                                         (Trainer.optimize_batch(100): fused HIP step vs torch autograd; CADRL has one
                                         row per state whatever --humans says)
-    python tools/kbench.py --world-trainer [--humans 5,10]   (Trainer_Sim.optimize_epoch(3): fused HIP step vs torch autograd)
+    python tools/kbench.py --world-trainer [--world mlp|attention] [--humans 5,10]   (Trainer_Sim.optimize_epoch(3): fused HIP step vs torch autograd)
 """
 import argparse
 import os
@@ -120,10 +120,12 @@ def main():
     ap.add_argument("--world-trainer", action="store_true",
                     help="time Trainer_Sim.optimize_epoch(3) on 25 000 synthetic pairs at batch 100 x --humans: fused HIP "
                          "step (fused=True) against the torch path, five alternating repeats")
+    ap.add_argument("--world", default="attention", choices=("attention", "mlp"),
+                    help="with --world-trainer: the world model that is trained (mlp: MlpWorld with its default dropout 0.5)")
     a = ap.parse_args()
     if a.world_trainer:
         for N in [int(x) for x in str(a.humans).split(",")]:
-            world_trainer_bench(N)
+            world_trainer_bench(N, world=a.world)
         return
     if a.trainer:
         for N in [1] if a.policy == "cadrl" else [int(x) for x in str(a.humans).split(",")]:
@@ -264,21 +266,22 @@ def trainer_bench(N, batch=100, num_batches=100, rows=20000, reps=5, policy="sar
     print("%s N=%d: torch / fused = %.2f (medians)" % (tag, N, np.median(times["torch"]) / np.median(times["fused"])))
 
 
-def world_trainer_bench(N, batch=100, epochs=3, rows=25000, reps=5):
+def world_trainer_bench(N, batch=100, epochs=3, rows=25000, reps=5, world="attention"):
     """Wall time of one Trainer_Sim.optimize_epoch(epochs) call -- what the model-based training loop makes once per
-    training episode -- with the fused HIP step and with torch autograd + optim.Adam, on the same seeded AttentionWorld and
-    a synthetic pair memory sized like the reference's `rawob` after its initial episodes (500 episodes of about 50
+    training episode -- with the fused HIP step and with torch autograd + optim.Adam, on the same seeded AttentionWorld (or, with
+    world="mlp", MlpWorld(N) with its default dropout) and a synthetic pair memory sized like the reference's `rawob` after its initial episodes (500 episodes of about 50
     steps).  A call is: shuffle and stack the memory (the same host work on both paths), then per epoch 200 training
     steps and 50 validation batches; 3 epochs cannot stop early (patience 7).  The two paths alternate within one
     process (fused, torch, fused, ...) so that clock and cache state drift hits both; one untimed call of each first.
     Also printed: the stacking alone, which both paths pay."""
     import copy
     import time
-    from modelcrowdnav_amd.policy.world_model import AttentionWorld
+    from modelcrowdnav_amd.policy.world_model import AttentionWorld, MlpWorld
     from modelcrowdnav_amd.utils.trainer_sim import Trainer_Sim
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
-    model = AttentionWorld()
+    model = MlpWorld(N) if world == "mlp" else AttentionWorld()
+    tag = "world trainer" if world == "attention" else "world trainer (mlp)"
     g = torch.Generator().manual_seed(1)
     cur = torch.randn(rows, N, 4, generator=g) * torch.tensor([3.0, 3.0, 0.7, 0.7])
     nxt = 0.8 * cur[:, :, 2:4] + 0.1 * torch.randn(rows, N, 2, generator=g)
@@ -305,11 +308,11 @@ def world_trainer_bench(N, batch=100, epochs=3, rows=25000, reps=5):
     for name in ("fused", "torch", "stack"):
         t = np.asarray(times[name])
         what = "optimize_epoch(%d) %-5s" % (epochs, name) if name != "stack" else "of which _pairs()      "
-        print("world trainer N=%d batch=%d rows=%d %s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats)"
-              % (N, batch, rows, what, np.median(t), t.min(), t.max(), reps))
+        print("%s N=%d batch=%d rows=%d %s: median %8.2f ms  min %8.2f  max %8.2f  (%d repeats)"
+              % (tag, N, batch, rows, what, np.median(t), t.min(), t.max(), reps))
     f, t, k = (float(np.median(times[n])) for n in ("fused", "torch", "stack"))
-    print("world trainer N=%d: torch / fused = %.2f (medians); without the stacking %.2f; per training step incl. its share "
-          "of validation: fused %.1f us, torch %.1f us (%d steps)" % (N, t / f, (t - k) / (f - k), (f - k) * 1e3 / steps,
+    print("%s N=%d: torch / fused = %.2f (medians); without the stacking %.2f; per training step incl. its share "
+          "of validation: fused %.1f us, torch %.1f us (%d steps)" % (tag, N, t / f, (t - k) / (f - k), (f - k) * 1e3 / steps,
                                                                    (t - k) * 1e3 / steps, steps))
 
 
