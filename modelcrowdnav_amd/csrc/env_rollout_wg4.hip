@@ -5,12 +5,14 @@
 // and the scalar instructions they stand for 4.6 - 5.0 (profiles/r04_valu_issue.txt, profiles/r18_orca_issue.txt).  The
 // other forms keep the flags, and so the code, they had.
 #include "env_rollout_common.hpp"
+#include "wg4_barrier_plan.hpp"
 
 namespace mcn {
 
 // Four-wavefront form (env_rollout_wg4_kernel): workgroups of EW envs on FOUR wavefronts -- three ORCA wavefronts
-// for the EW * NT quads, dealt in order
-// (quad q = env q / NT, human q % NT, so an env may straddle two wavefronts), and one float64 wavefront with eight
+// for the EW * NT quads, dealt BY ENV: ORCA wavefront w holds envs 3 w .. 3 w + 2 of the workgroup (wavefront 2 two envs,
+// 10 quads), quad 5 le + h of the wavefront is (env 3 w + le, human h), so no env straddles two wavefronts and a quad's
+// four candidates sit in its own wavefront; and one float64 wavefront with eight
 // lanes per env: lane 8 g + h is (env g, human h) for h < NT, lanes h >= NT are idle (they hold no distance: +inf, and
 // no overlap), so an env's minimum distance and overlap count are three DPP exchanges inside its eight lanes.
 // The float64 wavefront is workgroup wave 3: the hardware deals a workgroup's waves one to each SIMD and starts the
@@ -22,63 +24,78 @@ namespace mcn {
 //
 // The float64 wavefront OWNS every float64 value of the env: the robot, the clock, the records and the humans' position,
 // velocity, goal, radius, v_pref and human_times -- one human per lane, loaded in its prologue, integrated or restarted
-// from the pool by it, stored in its epilogue.  The ORCA wavefronts are float32 only: per step they read their human's
-// operands and their candidate's from LDS (what and when: below), run quad_orca_core (quad_common.hpp) and publish the new velocity as two
-// floats.  The four lanes of a quad would each repeat the float64 -> float32 conversions, the integrate and the restart
-// test; the float64 wavefront does them once per human and has the cycles to spare, and on a SIMD that holds two
-// wavefronts every instruction taken out of the ORCA stream is taken out of its neighbour's way too.
-// The roles meet through LDS at two points of the step: hand-off 1, ORCA -> float64, the new velocities; hand-off 2,
-// float64 -> ORCA, the new positions (the float64 wavefront integrates between the two).  Between the two all four
-// wavefronts wait for one serial chain, so only what depends on the new velocity is on it: read (rx, ry), two
-// conversions, the integrate, goal - pos, four conversions, one 16-byte write.  Everything else stays off it:
+// from the pool by it, stored in its epilogue.  The ORCA wavefronts run quad_orca_core (quad_common.hpp) and publish the
+// new velocity as two floats.  Each quad also carries a float64 COPY of its human's position and goal (8 VGPRs of the
+// ~59 the ORCA role leaves unused in the kernel's allocation, which is the float64 role's): after the solve every lane of
+// the quad executes the owner's statements on it, pos + (double)r * dt and quad_orca_position_pack(pos, goal) -- the
+// same operations on the same operands, so the same bits as the owner's -- and has its next step's position operands
+// without waiting for anybody.  A candidate's position and velocity come from a quad of the same wavefront, through a
+// slot of the wavefront's own line table, which is dead between two solves.  So a normal step has ONE workgroup barrier,
+// the hand-off: before it the ORCA wavefronts publish (rx, ry) to s_res[t & 1] and the float64 wavefront the workgroup's
+// restart flag to s_flag[t & 1]; behind it the ORCA wavefronts read the flag and their candidate's slot (one LDS round trip)
+// and start the next solve, and the float64 wavefront reads s_res[t & 1], integrates its own copy and goes on with its
+// step: s_hpos, velocity register, human_times, then the next step's swept test, pairs, ladder, accounting and restart
+// fetch.  Both arrays are indexed by step parity: what is read behind the hand-off of step t is next written before the
+// hand-off of step t + 2, i.e. behind that of step t + 1, which the reader reaches only with its reads complete.
+//
+// What stays off the ORCA wavefronts' step:
 //   * the velocity never leaves float32: the solve's velocity operands are the floats the ORCA wavefronts produced
 //     (float32 -> float64 -> float32 gives the same bits back): the owner's are the (rx, ry) its quad still holds, the
-//     candidate's are read from s_res;
+//     candidate's come with its position;
 //   * frad and the maximum speed change only on a restart and live in s_inv, written in the prologue and by restart lanes;
 //     the ORCA wavefronts keep them, and the candidate's frad, in registers from one restart step to the next;
-//   * what a restarted human publishes (position pack, start velocity, s_inv) is converted BEFORE hand-off 1, where the
-//     float64 wavefront would idle anyway, and stored between the hand-offs behind one wave-uniform branch;
-//   * the float64 wavefront's private arrays, its register update and the human_times test come after hand-off 2.
+//   * what a restarted human publishes (start velocity, s_inv) is converted BEFORE the hand-off, where the
+//     float64 wavefront would idle anyway.
 // Each value is produced by the operation, on the operands, that the other forms use, so the same bits.
 //
-// The top of an ORCA wavefront's step reads only what hand-off 2 published, the two position packs.  Everything else the
-// solve needs is final at hand-off 1 and is fetched or kept: the candidate's velocity is read
-// BETWEEN the hand-offs, where the ORCA wavefronts wait for the float64 chain anyway -- except on a restart step, when a
-// restart lane overwrites its human's velocity and s_inv inside that very interval.  The float64 wavefront knows
-// any_restart when its ladder ends and stores it to s_flag[0] there; the ORCA wavefronts read it between the hand-offs,
-// make it a scalar, and on a restart step (and on step 0 of every launch, whose operands the prologue seeded) take the
-// SLOW PATH behind hand-off 2: own and candidate's velocity, (frad, ms) and the candidate's frad from LDS.  s_res is one
-// buffer, so those reads are fenced from the next solves' writes by a THIRD BARRIER, which all four wavefronts execute
-// on such steps and no other: the float64 wavefront branches on its own any_restart (and the prologue's second barrier
-// stands for step 0), the ORCA wavefronts on the flag it stored, so every wavefront counts the same barriers (after the
-// launch's last step the ORCA wavefronts execute it behind their loop, with nothing to read).
-// The three intervals of a step and who touches what in them (W = writes, R = reads; f64 = the float64 wavefront):
-//   A  hand-off 2 of the step before (or the prologue's barriers) -> hand-off 1: the solve
-//   B  hand-off 1 -> hand-off 2: the float64 chain
-//   C  restart steps only: hand-off 2 -> the third barrier (the head of the next step's interval A)
-//              A                                   B                                        C
-//   s_pack     R ORCA (top of step)                W f64 (every lane; restart lanes theirs)  R ORCA (it is their top of step)
-//   s_res      W ORCA (end of solve)               R f64, R ORCA (candidate), W f64 restart  R ORCA (own, candidate)
-//   s_inv      --                                  W f64 restart lanes                       R ORCA (own, candidate)
-//   s_flag     W f64 (behind its ladder)           R ORCA                                    --
-//   s_hpos/s_hrad  R f64 (pairs); W f64 (head of A: behind hand-off 2 / the third barrier)   --  (its own arrays)
-//   s_lines    W/R the owning ORCA wavefront       --                                        --
-// The candidate's velocity an ORCA wavefront reads in B of a restart step races with the restart lane's write; that value
-// is never used: the slow path overwrites it in C.  In C the ORCA wavefronts wait for
-// their reads before the third barrier, and the first write of s_res behind it is the end of the next solve.
+// RESTART STEPS (some env of the workgroup ends: roughly one workgroup-step in ten) and the launch's first solve take the
+// SLOW PATH.  The float64 wavefront knows the done flags when its ladder ends and stores the workgroup's there: word EW of
+// s_flag[t & 1].  Behind the hand-off of such a step it stores each env's flag (words 0 .. EW - 1) and its restart lanes
+// stage the new human -- float64 position and goal in two slots of the human's ORCA wavefront's line table (dead in that
+// window as well; other slots than the candidate exchange uses), the start velocity over the solve's in s_res[t & 1],
+// (frad, maximum speed) in s_inv -- and all four wavefronts meet at a second barrier, `staged`, behind which the ORCA
+// wavefronts read every operand from LDS: velocities, s_inv, and for the quads of a restarted env (its flag word) position
+// and goal of their human and the position of their candidate; the others keep their copy.  The prologue stages every
+// human the same way, with every flag set, as "step -1" (parity 1), and its barrier, `seed`, stands for both.  No third
+// barrier fences these reads from the next publish as it did while s_res was one buffer: the next publish goes to the
+// other parity.  Which barriers a role executes when is wg4_step_barriers (wg4_barrier_plan.hpp), one function for both
+// loops: all four wavefronts execute the same barriers in the same order on every path, the last step's included.
+// Step t and who touches what (W = writes, R = reads; f64 = the float64 wavefront; p = t & 1):
+//   A  the barrier before (hand-off or staged of step t - 1, or the seed) -> hand-off of step t
+//   B  hand-off of step t -> the next barrier (a normal step: this is the head of step t + 1's A; a restart step: staged)
+//   C  restart steps only: staged -> hand-off of step t + 1 (the head of step t + 1's A)
+//                  A                                  B                                          C
+//   s_res[p]       W ORCA (end of the solve)          R f64 (own slot); then W f64 restart lanes  R ORCA (own, candidate)
+//   s_inv          --                                 W f64 restart lanes                         R ORCA (own, candidate)
+//   s_flag[p]      W f64 word EW (behind its ladder)  R ORCA word EW; W f64 words 0 .. EW - 1     R ORCA (its env's word)
+//   s_lines        W/R its ORCA wavefront: the solve, R its ORCA wavefront (exchange slots);      R its ORCA wavefront
+//                  then W the exchange slots          W f64 restart lanes (staging slots)         (staging slots)
+//   s_hpos/s_hrad  R f64 (pairs)                      W f64 behind its last barrier of the step: its own arrays
+// The slot an ORCA wavefront reads in B is its own wavefront's write of A; the hand-off's fences order them.  A restarted
+// env's quads integrate the old human before the hand-off and exchange its position behind it; the slow path overwrites
+// all of that.
 //
 // The float64 wavefront's ladder, Explorer accounting, finished-episode stores, robot integrate / restart and the epilogue
 // are the TWIN of env_rollout_quad_kernel's (env_rollout_quad.hip): a change to either is made to both.  The text is
 // not shared: with the tail in common functions this kernel's two forms came out at 1791 and 2811 instructions for
 // 1804 and 2840 with another SGPR use, and the older kernel lost registers to scratch (profiles/r19_env_refactor.txt,
 // section 4), on the path the benchmark's headline runs.  The humans' integrate / restart holds the twin's statements
-// (pos + (double)r * dt, the pool fetch, human_times) in another order: the restart before hand-off 1, the integrate
-// between the hand-offs, the velocity register and human_times after hand-off 2.
+// (pos + (double)r * dt, the pool fetch, human_times) in another order: the restart fetch before the hand-off, the
+// integrate behind it, then the velocity register and human_times; and the integrate and the position pack are
+// executed a second time, on the ORCA quads' copy.
 template <int NT>
 struct Wg4 {
     static_assert(NT == 5, "the four-wavefront form is built for 5 humans only");
     static constexpr int EW = 8;                              // envs per workgroup
     static constexpr int NQ = EW * NT;                        // populated quads = populated float64 lanes: 40 of 48 / 64
+    static constexpr int EPW = 3;                             // envs per ORCA wavefront: 3 + 3 + 2, 15 / 15 / 10 of 16 quads
+    static_assert(EPW * NT <= 16 && 3 * EPW >= EW, "an env's quads share a wavefront and three wavefronts hold them all");
+    // A wavefront's line table (64 float4 slots) between two solves: slot q = quad q's (px, py, rx, ry) for the quads
+    // whose candidate it is; slots STAGE + 2 q, + 1 = the float64 position and goal a restart lane stages for quad q
+    static constexpr int STAGE = 16;
+    static_assert(STAGE + 2 * 16 <= 64, "the staging slots lie inside the wavefront's table");
+    static constexpr int FLAGS = 16;                          // words per parity of s_flag: EW env flags, then the workgroup's
+    static_assert(EW < FLAGS, "one word per env and one for the workgroup");
 };
 
 // value of the lane a DPP control selects (all lanes of the wavefront active)
@@ -93,27 +110,56 @@ __device__ __forceinline__ double dpp_d(double v)
 }
 constexpr int DPP_QUAD_XOR1 = 0xB1, DPP_QUAD_XOR2 = 0x4E, DPP_ROW_HALF_MIRROR = 0x141;   // quad_perm [1,0,3,2], [2,3,0,1]
 
+// a double2 as the float4 of the same 16 bytes and back: whole-register moves, for the slots of a line table
+__device__ __forceinline__ float4 d2_as_f4(double2 v)
+{
+    const long long x = __builtin_bit_cast(long long, v.x), y = __builtin_bit_cast(long long, v.y);
+    return make_float4(__builtin_bit_cast(float, (int)x), __builtin_bit_cast(float, (int)(x >> 32)),
+                       __builtin_bit_cast(float, (int)y), __builtin_bit_cast(float, (int)(y >> 32)));
+}
+__device__ __forceinline__ double2 f4_as_d2(float4 v)
+{
+    const long long x = ((long long)__builtin_bit_cast(int, v.y) << 32) | (unsigned int)__builtin_bit_cast(int, v.x);
+    const long long y = ((long long)__builtin_bit_cast(int, v.w) << 32) | (unsigned int)__builtin_bit_cast(int, v.z);
+    return make_double2(__builtin_bit_cast(double, x), __builtin_bit_cast(double, y));
+}
+
+// the staging slots of the human in hand-off slot `hs` = env * NT + human, in the table of the ORCA wavefront that holds it
+template <int NT>
+__device__ __forceinline__ float4 *wg4_stage(float4 *lines, int hs)
+{
+    constexpr int PER = Wg4<NT>::EPW * NT;                      // hand-off slots per ORCA wavefront, in order
+    const int w = hs / PER;
+    return lines + w * 64 + Wg4<NT>::STAGE + 2 * (hs - w * PER);
+}
+
+// `n` workgroup barriers, n from wg4_step_barriers with the flags the caller knows at that point spelt as constants, so that
+// the loop folds (with a run-time count the compiler keeps a counted loop round the s_barrier)
+__device__ __forceinline__ void wg4_sync(int n)
+{
+    for (int i = 0; i < n; ++i) __syncthreads();
+}
+
 template <int NT, int VIS, bool UNI>
 __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
 {
     static_assert(VIS == 0, "the four-wavefront form is built for an invisible robot only");
-    constexpr int EW = Wg4<NT>::EW, NQ = Wg4<NT>::NQ;
-    // hand-off arrays, one slot per (env, human).  Written by the float64 wavefront between the step's two barriers:
-    // s_pack = (px, py, prefx, prefy) of quad_orca_core's operands, every step; s_inv = (frad, maximum speed) and the
-    // start velocity in s_res, restart lanes only.  Written by the ORCA wavefronts outside that window, read by the
-    // float64 one and (their candidate's) by the ORCA ones inside it, and by the ORCA ones' slow path behind it: s_res,
-    // the human's new velocity, one buffer (table above).  s_hpos / s_hrad, the float64 position and radius the overlap
-    // pairs read from partner lanes, are the float64 wavefront's own: written after the second barrier, read in its
-    // next step.
-    __shared__ float4 s_pack[NQ];
-    __shared__ float2 s_res[NQ], s_inv[NQ];
-    // word 0: some human of the workgroup restarts on this step (the float64 wavefront's any_restart).  The other words
-    // are the room the second velocity buffer had: the workgroup's LDS, and with it the CU's, stays what it was
-    __shared__ int s_flag[2 * NQ];
+    constexpr int EW = Wg4<NT>::EW, NQ = Wg4<NT>::NQ, EPW = Wg4<NT>::EPW, STAGE = Wg4<NT>::STAGE, FLAGS = Wg4<NT>::FLAGS;
+    // hand-off arrays, one slot per (env, human), slot = env * NT + human.  s_res: the human's new velocity, two buffers
+    // by step parity, written by the ORCA wavefronts at the end of a solve (and by restart lanes: the start velocity),
+    // read by the float64 wavefront every step and by the slow path.  s_inv = (frad, maximum speed), written in the
+    // prologue and by restart lanes, read by the slow path.  s_hpos / s_hrad, the float64 position and radius the overlap
+    // pairs read from partner lanes, are the float64 wavefront's own.
+    __shared__ float2 s_res[2 * NQ], s_inv[NQ];
+    // per parity: words 0 .. EW - 1, env g restarts on this step; word EW, some env of the workgroup does.  The other
+    // words are room earlier layouts used: the workgroup's LDS, and with it the CU's, stays what it was
+    __shared__ int s_flag[4 * NQ];
+    static_assert(2 * FLAGS <= 4 * NQ, "two parities of flags");
     __shared__ double2 s_hpos[NQ];
     __shared__ double s_hrad[NQ];
     // the ORCA wavefronts' sorted half-planes (quad_common.hpp: QuadTable): 64 slots each, private to the wavefront.  A lane
-    // reads its quad's four slots, its own, and the two operands of its pass-A intersection (lp1_spread): seven reads
+    // reads its quad's four slots, its own, and the two operands of its pass-A intersection (lp1_spread): seven reads.
+    // Between two solves: the candidate exchange and the restart staging (Wg4)
     __shared__ float4 s_lines[3 * 64];
     STAMP(0);
     STAMP_WHERE();
@@ -128,62 +174,84 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
     const mcn_rollout &ro = p.roll;
 
     if (role < 3) {
-        // ---------------- ORCA wavefronts: the float32 solve, nothing else ----------------
-        const int lane = tid & 63, k = tid & 3, q = tid >> 2;
-        const bool pop = q < NQ;                                 // idle quads (and envs >= E) hold no half-plane, write nothing
-        const int ge = q / NT, h = q - ge * NT;
+        // ---------------- ORCA wavefronts: the float32 solve and the integrate of their copy ----------------
+        const int lane = tid & 63, k = tid & 3, q = lane >> 2;  // quad q of this wavefront
+        const int le = q / NT, h = q - le * NT;                  // (env of the wavefront, human)
+        const int ge = role * EPW + le;                          // env of the workgroup
+        const bool pop = le < EPW && ge < EW;                    // idle quads (and envs >= E) hold no half-plane, write nothing
         const bool active = pop && (long)chunk_ * EW + ge < p.E;
-        const int hi = pop ? q : 0;                              // LDS slot of this quad's human (idle quads read slot 0)
+        const int hi = pop ? ge * NT + h : 0;                    // hand-off slot of this quad's human (idle quads read slot 0)
         const bool cand_h = k < NT - 1;                          // candidate is another human
         const int j = cand_h ? k + (k >= h ? 1 : 0) : h;
-        const int ci = pop ? ge * NT + j : 0;
+        const int ci = pop ? ge * NT + j : 0;                    // the candidate's hand-off slot ...
+        const int cq = pop ? le * NT + j : 0;                    // ... and its quad in this wavefront
+        const int fi = pop ? ge : 0;                             // the env's flag word
         const bool publish = pop && k == 0;
         const float inv_th = in_vgpr(1.0f / c.orca_time_horizon), inv_ts = in_vgpr(1.0f / (float)c.time_step);
+        const double dt = in_vgpr(c.time_step);
         float4 *const tab = s_lines + role * 64;
-        // what a normal step keeps in registers: own velocity v, the candidate's cv, (frad, ms) and the candidate's frad
-        float vx = 0, vy = 0, cvx = 0, cvy = 0, frad = 0, ms = 0, orad = 0;
-        bool slow = true;                                        // wave-uniform: step 0 of a launch is a restart step
-        __syncthreads();                                         // the float64 wavefront has seeded the packs
+        const float4 *const stage = tab + STAGE + 2 * (pop ? q : 0), *const cstage = tab + STAGE + 2 * cq;
+        // what a normal step keeps in registers: the float64 copy of position and goal, the position operands formed from
+        // it, own velocity v, the candidate's position and velocity, (frad, ms) and the candidate's frad
+        double2 pos = make_double2(0, 0), goal = make_double2(0, 0);
+        float4 P = make_float4(0, 0, 0, 0);
+        float vx = 0, vy = 0, cpx = 0, cpy = 0, cvx = 0, cvy = 0, frad = 0, ms = 0, orad = 0;
+        // Slow path, behind a seed or staged barrier: every operand from LDS, one round trip for the nine reads (the empty
+        // asm needs them all).  `par`: parity of the step whose hand-off came before (the prologue's: 1).  The velocities
+        // are what the solves or the prologue left with the restart lanes' overwritten, frad / ms as the restart lanes
+        // left them; position and goal are staged for restarted envs only, the other quads keep theirs.
+        auto reload = [&](const int par) {
+            const float2 *res = s_res + par * NQ;
+            float2 v = res[hi], cv = res[ci];
+            float2 fm = s_inv[hi];
+            float od = s_inv[ci].x;                              // the candidate's own frad
+            int mine = s_flag[par * FLAGS + fi];
+            float4 sp = stage[0], sg = stage[1], sc = cstage[0];
+            asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(cv.x), "+v"(cv.y), "+v"(fm.x), "+v"(fm.y), "+v"(od), "+v"(mine));
+            asm volatile("" : "+v"(sp.x), "+v"(sp.y), "+v"(sp.z), "+v"(sp.w), "+v"(sg.x), "+v"(sg.y), "+v"(sg.z), "+v"(sg.w),
+                              "+v"(sc.x), "+v"(sc.y), "+v"(sc.z), "+v"(sc.w));
+            vx = v.x; vy = v.y; cvx = cv.x; cvy = cv.y; frad = fm.x; ms = fm.y; orad = od;
+            if (mine != 0) {
+                pos = f4_as_d2(sp);
+                goal = f4_as_d2(sg);
+                const double2 cpos = f4_as_d2(sc);
+                P = quad_orca_position_pack(pos, goal);
+                cpx = (float)cpos.x; cpy = (float)cpos.y;        // the candidate's own (float)pos
+            }
+        };
+        wg4_sync(wg4_step_barriers(kWg4Orca, true, false, false).seed);      // the float64 wavefront has staged every human
+        reload(1);
         STAMP(1);
 
         for (int t = 0; t < T; ++t) {
-            // behind hand-off 2: the positions, own and candidate's, on every step
-            float4 P = s_pack[hi];
-            float2 cp = *reinterpret_cast<const float2 *>(s_pack + ci);
-            if (slow) {
-                // restart step (and step 0): every other operand from LDS too -- the velocities as the prologue or
-                // the last step's solves left them with restart lanes overwritten, frad / ms as the restart lanes left
-                // them.  Issued behind the two above, one LDS round trip for the six: the empty asm needs the last four,
-                // and LDS answers in order.  (The positions stay out of it: as its operands they would be copied into
-                // the registers the two paths share, six moves on every normal step.)  The barrier behind it keeps the
-                // solves' next write of s_res behind every wavefront's reads.
-                float2 v = s_res[hi], cv = s_res[ci];
-                float2 fm = s_inv[hi];
-                float od = s_inv[ci].x;                          // the candidate's own frad
-                asm volatile("" : "+v"(v.x), "+v"(v.y), "+v"(cv.x), "+v"(cv.y), "+v"(fm.x), "+v"(fm.y), "+v"(od));
-                __syncthreads();                                 // restart steps only: s_res has been read
-                vx = v.x; vy = v.y; cvx = cv.x; cvy = cv.y; frad = fm.x; ms = fm.y; orad = od;
-            }
             float rx, ry;
             quad_orca_core(c, lane, k, cand_h && active, make_float4(P.x, P.y, vx, vy), make_float4(P.z, P.w, frad, ms),
-                           make_float4(cp.x, cp.y, cvx, cvy), orad, inv_th, inv_ts, rx, ry, QuadTable{tab});
-            if (publish) s_res[hi] = make_float2(rx, ry);
+                           make_float4(cpx, cpy, cvx, cvy), orad, inv_th, inv_ts, rx, ry, QuadTable{tab});
+            // the owner's integrate on this quad's copy, and the next step's position operands from it
+            pos = make_double2(pos.x + (double)rx * dt, pos.y + (double)ry * dt);
+            P = quad_orca_position_pack(pos, goal);
+            const int par = t & 1;
+            if (publish) {
+                s_res[par * NQ + hi] = make_float2(rx, ry);
+                tab[q] = make_float4(P.x, P.y, rx, ry);          // for the quads whose candidate this human is
+            }
             if (t < 20) STAMP(40 + t);
-            __syncthreads();                                     // hand-off 1: the humans' new velocities
-            // between the hand-offs, where this wavefront waits for the float64 chain: the workgroup's restart flag and
-            // the candidate's new velocity, one LDS round trip; the own new velocity is (rx, ry), identical on the
-            // quad's lanes.  On a restart step the candidate's read races with the restart lane's overwrite and the quad's
-            // registers hold the old human's: nothing formed here is used then, the slow path re-reads it all.
-            int flag = s_flag[0];
-            float2 cv = s_res[ci];
-            asm volatile("" : "+v"(flag), "+v"(cv.x), "+v"(cv.y));      // waited for before the barrier
-            slow = __builtin_amdgcn_readfirstlane(flag) != 0;
-            vx = rx; vy = ry; cvx = cv.x; cvy = cv.y;
-            __syncthreads();                                     // hand-off 2: the next step's positions
+            const Wg4StepBarriers normal = wg4_step_barriers(kWg4Orca, false, false, t + 1 == T);
+            wg4_sync(normal.handoff);                            // the hand-off: the humans' new velocities, the flags
+            // the workgroup's restart flag and the candidate's slot, one LDS round trip (the hand-off's fences order the
+            // slot's read behind every quad's write); the own new velocity is (rx, ry), identical on the quad's lanes
+            int flag = s_flag[par * FLAGS + EW];
+            float4 x = tab[cq];
+            asm volatile("" : "+v"(flag), "+v"(x.x), "+v"(x.y), "+v"(x.z), "+v"(x.w));
+            const bool slow = __builtin_amdgcn_readfirstlane(flag) != 0;
+            vx = rx; vy = ry; cpx = x.x; cpy = x.y; cvx = x.z; cvy = x.w;
+            const Wg4StepBarriers plan = wg4_step_barriers(kWg4Orca, false, slow, t + 1 == T);
+            if (plan.staged) {
+                wg4_sync(wg4_step_barriers(kWg4Orca, false, true, t + 1 == T).staged);      // the new humans are staged
+                reload(par);
+            }
             if (t < 37) STAMP(2 + t);
         }
-        // the float64 wavefront executes the third barrier of the last step too (no test of the step count in its loop)
-        if (slow) __syncthreads();
     } else {
         // ---------------- float64 wavefront: lane 8 g + h = (env g, human h), h >= NT idle ----------------
         static_assert(EW * 8 == 64, "eight lanes per env fill the wavefront");
@@ -234,18 +302,22 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
         const double k_discomfort = in_vgpr(c.discomfort_dist), k_factor = in_vgpr(c.discomfort_penalty_factor);
         const int k_stride = ro.case_stride, k_pool = ro.pool_size;
         const bool count_hh = c.count_hh != 0;
-        // the first step's operands: the loaded state goes through the hand-off arrays
+        // the first solve's operands: the loaded state is staged as a restart stages a new human, every flag set, in the
+        // buffers of parity 1 ("step -1")
         {
             float4 A, B;
             quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
             if (pop) {
-                s_pack[hs] = make_float4(A.x, A.y, B.x, B.y); s_res[hs] = make_float2(A.z, A.w);
+                float4 *const stage = wg4_stage<NT>(s_lines, hs);
+                stage[0] = d2_as_f4(pos); stage[1] = d2_as_f4(goal);
+                s_res[NQ + hs] = make_float2(A.z, A.w);
                 s_inv[hs] = make_float2(B.z, B.w);
                 s_hpos[hs] = pos; s_hrad[hs] = rad;
             }
+            s_flag[FLAGS + g] = 1;
+            s_flag[FLAGS + EW] = 1;
         }
-        __syncthreads();
-        __syncthreads();                                         // step 0 is a restart step: the ORCA wavefronts have read s_res
+        wg4_sync(wg4_step_barriers(kWg4Float64, true, false, false).seed);
         STAMP(1);
 
         for (int t = 0; t < T; ++t) {
@@ -335,11 +407,12 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
             o_rew = rew; o_dmin = dmin; o_dn = dn; o_inf = inf; o_hh = hh_sum;
             const double t_new = gtime + dt;
             // the workgroup's restart flag as soon as the done flags are known: the store is long complete when this
-            // wavefront reaches hand-off 1 (issued there, the barrier's wait for it sat on the chain of every step on
+            // wavefront reaches the hand-off (issued there, the barrier's wait for it sat on the chain of every step on
             // which this wavefront is the last to arrive: the unicycle robot's)
             const bool restart = do_reset && dn;
             const bool any_restart = __any(restart);             // roughly one workgroup-step in ten
-            s_flag[0] = any_restart ? 1 : 0;                     // (every lane the same word: no exec mask to set up)
+            const int par = t & 1;
+            s_flag[par * FLAGS + EW] = any_restart ? 1 : 0;      // (every lane the same word: no exec mask to set up)
 
             // ---- Explorer accounting: every lane of the env updates its copy; the stores are the lead lane's ----
             const int case_g = rs.next_case;
@@ -391,11 +464,10 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                 gtime = t_new;
             }
 
-            // ---- humans of a finished env restart from the scenario pool NOW, while this wavefront would wait at hand-off 1
+            // ---- humans of a finished env restart from the scenario pool NOW, while this wavefront would wait at the hand-off
             //      for the ORCA ones anyway (it knows the done flag first): the case is fetched straight into the state
             //      registers (nothing below reads the old one: the swept circle, the pairs and the ladder are done) and
-            //      converted; between the hand-offs a restart lane only stores what it holds here ----
-            float4 n_pack = make_float4(0, 0, 0, 0);
+            //      converted; behind the hand-off a restart lane only stores what it holds here ----
             float2 n_fvel = make_float2(0, 0), n_inv = make_float2(0, 0);
             if (restart) {
                 DIAG_COUNT(1);
@@ -411,42 +483,48 @@ __device__ __forceinline__ void rollout_wg4(const StepParams &p, const int T)
                     vpref = kp->roll.pool_hvpref[pa];
                 }
                 htime = 0;
-                // every float converted from the new float64 state, as the prologue does for a loaded one
+                // every float converted from the new float64 state, as the prologue does for a loaded one (position and
+                // goal go to the ORCA quads as float64: they form the position operands themselves)
                 float4 A, B;
                 quad_orca_operands(c, pos, vel, goal, rad, vpref, A, B);
                 // (pinned: not to be sunk behind the barrier)
-                n_pack = make_float4(in_vgpr(A.x), in_vgpr(A.y), in_vgpr(B.x), in_vgpr(B.y));
                 n_fvel = make_float2(in_vgpr(A.z), in_vgpr(A.w));
                 n_inv = make_float2(in_vgpr(B.z), in_vgpr(B.w));
             }
 
             if (t < 20) STAMP(40 + t);
-            __syncthreads();                                     // hand-off 1: the humans' new velocities
-            // ---- the chain every wavefront of the workgroup waits for: velocity -> position -> pack ----
-            float2 *vel_io = s_res;
+            const Wg4StepBarriers plan = wg4_step_barriers(kWg4Float64, false, any_restart, t + 1 == T);
+            wg4_sync(plan.handoff);                              // the hand-off: the humans' new velocities
             {
-                const float2 r = vel_io[hs];
+                const float2 r = s_res[par * NQ + hs];
                 hax = (double)r.x; hay = (double)r.y;            // (restart lanes too: the epilogue's human_act)
             }
-            if (!restart) {
-                pos = make_double2(pos.x + hax * dt, pos.y + hay * dt);
-                if (pop) s_pack[hs] = quad_orca_position_pack(pos, goal);
+            if (plan.staged) {
+                // restart steps only: the new humans for the ORCA quads, who re-read every operand behind the barrier
+                // (stores under their own mask; a restart lane's read of s_res above precedes its write in program order)
+                // Every address of this rare block is formed here, from the one index the step keeps (opaque, so that
+                // nothing of it is hoisted into registers the loop would hold): the env's flag word, read by the slow
+                // path only, and the staging slots.
+                int hs2 = hs;
+                asm volatile("" : "+v"(hs2));
+                s_flag[par * FLAGS + hs2 / NT] = restart ? 1 : 0;   // (an env's eight lanes the same word)
+                if (pop && restart) {
+                    float4 *const stage = wg4_stage<NT>(s_lines, hs2);
+                    stage[0] = d2_as_f4(pos); stage[1] = d2_as_f4(goal);
+                    s_res[par * NQ + hs2] = n_fvel; s_inv[hs2] = n_inv;
+                }
+                wg4_sync(wg4_step_barriers(kWg4Float64, false, true, t + 1 == T).staged);
             }
-            if (any_restart) {                                   // (stores under their own mask: no select on the chain)
-                if (pop && restart) { s_pack[hs] = n_pack; vel_io[hs] = n_fvel; s_inv[hs] = n_inv; }
-            }
-            __syncthreads();                                     // hand-off 2: the next step's positions
-            // restart steps only: the ORCA wavefronts re-read every operand behind hand-off 2 and fence those reads from
-            // their solves' next write of s_res with one more barrier (after the last step: behind their loop); this
-            // wavefront takes part at once, before its own work, on its own copy of the flag they read
-            if (any_restart) __syncthreads();
             if (t < 37) STAMP(2 + t);
 
-            // ---- off the chain: this wavefront's own arrays, the velocity register, the clock of the step just taken ----
-            if (pop) s_hpos[hs] = pos;
+            // ---- this wavefront's own copy and arrays, the velocity register, the clock of the step just taken ----
             if (!restart) {
+                pos = make_double2(pos.x + hax * dt, pos.y + hay * dt);
                 // (the solve's next operand is the ORCA wavefronts' float; (float)vel would give the same bits)
                 vel = make_double2(hax, hay);
+            }
+            if (pop) s_hpos[hs] = pos;
+            if (!restart) {
                 if (track && htime == 0 && norm2(pos.x - goal.x, pos.y - goal.y) < rad) htime = t_new;
             }
             if (any_restart) {
