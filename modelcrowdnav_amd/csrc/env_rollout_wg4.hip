@@ -45,7 +45,11 @@ namespace mcn {
 //   * frad and the maximum speed change only on a restart and live in s_inv, written in the prologue and by restart lanes;
 //     the ORCA wavefronts keep them, and the candidate's frad, in registers from one restart step to the next;
 //   * what a restarted human publishes (start velocity, s_inv) is converted BEFORE the hand-off, where the
-//     float64 wavefront would idle anyway.
+//     float64 wavefront would idle anyway;
+//   * the 2-D LP's four take steps decide from min(fail, code_i), known before the step's test (QuadTable::lean_take,
+//     quad_take_plan.hpp): five instructions in a row per step for eight, ten fewer in the loop.  On the SIMDs that hold
+//     two ORCA wavefronts an instruction costs its issue slot on or off the chain (profiles/r30_rollout_parallel_takes.txt:
+//     the form that evaluated all sixteen tests at once had a shorter chain, thirty instructions more, and lost 4 %).
 // Each value is produced by the operation, on the operands, that the other forms use, so the same bits.
 //
 // RESTART STEPS (some env of the workgroup ends: roughly one workgroup-step in ten) and the launch's first solve take the

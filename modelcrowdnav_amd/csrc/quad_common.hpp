@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include "orca_device.hpp"
 #include "orca_static.hpp"
+#include "quad_take_plan.hpp"
 
 namespace mcn {
 
@@ -36,6 +37,13 @@ __device__ __forceinline__ double qbd(double v)
 }
 template <int I>
 __device__ __forceinline__ float4 qb4(float4 v) { return make_float4(qbf<I>(v.x), qbf<I>(v.y), qbf<I>(v.z), qbf<I>(v.w)); }
+// The same broadcast with bound_ctrl set, which changes no value here either (a quad is active or inactive as a whole): the
+// form the compiler folds into the instruction that reads it where that is a VOP2's first operand (v_min_i32_dpp).  The
+// lean take steps alone use it: the other callers' code stays what it is.
+template <int I>
+__device__ __forceinline__ int qbi_fold(int v) { return __builtin_amdgcn_mov_dpp(v, I * 0x55, 0xf, 0xf, true); }
+template <int I>
+__device__ __forceinline__ float qbf_fold(float v) { return __builtin_bit_cast(float, qbi_fold<I>(__builtin_bit_cast(int, v))); }
 
 __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
 {
@@ -56,11 +64,14 @@ __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
 //              squared distance for rank and half-plane, the 1-D LP's clamp as two selects.
 //              And it spreads the 1-D LP's six (line, earlier line) intersections over the quad as 2 + 2 + 1 + 1
 //              (`spread`, lp1_spread below) where the other callers run 0 + 1 + 2 + 3 as three passes on every lane.
+//              And its four take steps decide from the minimum beside the test instead of from `fail` behind it
+//              (`lean_take`, take_step_lean in quad_take_plan.hpp): per step five instructions in a row where the other
+//              callers have eight, and two instructions fewer.
 struct QuadDpp {
-    static constexpr bool table = false, slim = false, spread = false;
+    static constexpr bool table = false, slim = false, spread = false, lean_take = false;
 };
 struct QuadTable {
-    static constexpr bool table = true, slim = true, spread = true;
+    static constexpr bool table = true, slim = true, spread = true, lean_take = true;
     float4 *tab;                                                 // this wavefront's 64 slots
 };
 
@@ -366,16 +377,32 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     // nothing failed yet" is fail > I; a violation folds the line's code in (min: nl <= 4 keeps a feasible line's 4
     // from changing it), and the candidate is taken where fail is still above I afterwards
     int fail = nl;
+    if constexpr (Path::lean_take) {
+        // the same four steps, each deciding from min(fail, code_i), which is known before the step's test: behind the
+        // compare one mask AND and the selects (take_step_lean: the same `fail` and the same `take` on every input)
+#define MCN_LP2_TAKE_LEAN(I)                                                                   \
+        {                                                                                      \
+            const int code_i = qbi_fold<I>(fcode);                                             \
+            const float cx_i = qbf_fold<I>(cx), cy_i = qbf_fold<I>(cy);                         \
+            const bool out = det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > 0.0f;             \
+            const TakeStep s = take_step_lean(fail, code_i, out, I);                           \
+            fail = s.fail;                                                                     \
+            rx = s.take ? cx_i : rx; ry = s.take ? cy_i : ry;                                   \
+        }
+        MCN_LP2_TAKE_LEAN(0) MCN_LP2_TAKE_LEAN(1) MCN_LP2_TAKE_LEAN(2) MCN_LP2_TAKE_LEAN(3)
+#undef MCN_LP2_TAKE_LEAN
+    } else {
 #define MCN_LP2_TAKE(I)                                                                        \
-    {                                                                                          \
-        const int code_i = qbi<I>(fcode); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy);    \
-        const bool out = det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > 0.0f;                 \
-        fail = ((fail > I) & out) ? min(fail, code_i) : fail;                                   \
-        const bool take = (fail > I) & out;                                                     \
-        rx = take ? cx_i : rx; ry = take ? cy_i : ry;                                           \
-    }
-    MCN_LP2_TAKE(0) MCN_LP2_TAKE(1) MCN_LP2_TAKE(2) MCN_LP2_TAKE(3)
+        {                                                                                      \
+            const int code_i = qbi<I>(fcode); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy); \
+            const bool out = det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > 0.0f;             \
+            fail = ((fail > I) & out) ? min(fail, code_i) : fail;                               \
+            const bool take = (fail > I) & out;                                                 \
+            rx = take ? cx_i : rx; ry = take ? cy_i : ry;                                       \
+        }
+        MCN_LP2_TAKE(0) MCN_LP2_TAKE(1) MCN_LP2_TAKE(2) MCN_LP2_TAKE(3)
 #undef MCN_LP2_TAKE
+    }
     if (fail < nl) {
         // dense crowd: 3-D LP (RVO2 linearProgram3).  fail / nl / the running result are quad-uniform, so the
         // whole region is entered per quad and the quad broadcasts inside see all four lanes.  Per round: find
