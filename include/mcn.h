@@ -247,6 +247,28 @@ int mcn_env_rollout_sf(const mcn_env_cfg *cfg, double strength, double range, do
                        const mcn_env_state *st, const double *actions, int32_t T, const mcn_env_out *out,
                        const mcn_rollout *roll, int32_t E, int32_t N, void *stream);
 
+/*
+ * mcn_env_rollout_orca_sf -- mcn_env_rollout_orca over social-force pedestrians (cfg->human_policy ==
+ * MCN_HUMANS_SOCIALFORCE): T consecutive closed-loop steps with an ORCA-driven holonomic robot in ONE launch (env_step.hip:
+ * env_step_loop_orca_sf_kernel), for any batch and any 1 <= N <= MCN_MAX_HUMANS.  Each step equals, bit for bit, this
+ * per-step sequence:
+ *   1  the robot's action exactly as in mcn_env_rollout_orca's step 1 (the robot's parameters are its policy's own);
+ *   2  mcn_env_step_sf(cfg, strength, range, relaxation_rate, st, that action, out, roll, E, N, update = 1),
+ *      cfg->robot_visible read at run time as that call reads it.
+ * strength / range / relaxation_rate: as mcn_env_step_sf.  The traces, and `st`, `out->rec`, `out->human_act` and `roll`
+ * on return: as mcn_env_rollout_orca.  MCN_EINVAL before any launch: everything mcn_env_rollout_orca refuses (NULL cfg /
+ * st / out, a missing state array, st->rvpref included, T < 1, N outside 1 .. MCN_MAX_HUMANS, max_neighbors outside
+ * 0 .. MCN_MAX_LINES, time_horizon or time_step not positive, a robot_safety_space that is not finite, a robot that is not
+ * holonomic, mcn_rollout's own rules), everything mcn_env_step_sf refuses (strength or relaxation_rate negative or not
+ * finite, range not finite or not > 0), and a cfg->human_policy other than MCN_HUMANS_SOCIALFORCE.
+ */
+int mcn_env_rollout_orca_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
+                            const mcn_env_state *st, double robot_safety_space, float neighbor_dist,
+                            int32_t max_neighbors, float time_horizon, int32_t T, const mcn_env_out *out,
+                            const mcn_rollout *roll, double *tr_robot, double *tr_humans, double *tr_hrad,
+                            double *tr_action, mcn_step_rec *tr_rec, double *tr_human_act, int32_t E, int32_t N,
+                            void *stream);
+
 /* Scenario rules of CrowdSim.reset (crowd_sim.py:120-163). */
 enum { MCN_RULE_CIRCLE = 0, MCN_RULE_SQUARE = 1 };
 

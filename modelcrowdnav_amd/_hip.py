@@ -138,6 +138,11 @@ def _load():
     lib.mcn_env_rollout_orca.argtypes = [C.POINTER(EnvCfg), C.POINTER(EnvState), _d, _f, _i, _f, _i, C.POINTER(EnvOut),
                                          C.POINTER(Rollout), _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]
     lib.mcn_env_rollout_orca.restype = C.c_int
+    # the same over social-force humans: strength / range / relaxation_rate follow cfg, then mcn_env_rollout_orca's own
+    lib.mcn_env_rollout_orca_sf.argtypes = [C.POINTER(EnvCfg), _d, _d, _d, C.POINTER(EnvState), _d, _f, _i, _f, _i,
+                                            C.POINTER(EnvOut), C.POINTER(Rollout), _vp, _vp, _vp, _vp, _vp, _vp, _i, _i,
+                                            _vp]
+    lib.mcn_env_rollout_orca_sf.restype = C.c_int
     lib.mcn_set_tuning.argtypes = [C.POINTER(Tuning)]
     lib.mcn_set_tuning.restype = C.c_int
     lib.mcn_get_tuning.argtypes = [C.POINTER(Tuning)]
@@ -278,7 +283,7 @@ def last_rollout_form():
 lib = _load()
 
 # every symbol include/mcn.h declares; tests/test_abi.py checks the .so exports each one
-EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_last_rollout_form", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_rollout_orca", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_orca_finish", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
+EXPORTED = ["mcn_version", "mcn_abi_version", "mcn_sizeof", "mcn_last_dispatch", "mcn_last_rollout_form", "mcn_pack_x3", "mcn_pack_x3_bytes", "mcn_set_tuning", "mcn_get_tuning", "mcn_env_step", "mcn_env_lp3_queue_bytes", "mcn_env_rollout", "mcn_env_rollout_orca", "mcn_env_step_sf", "mcn_env_rollout_sf", "mcn_env_rollout_orca_sf", "mcn_scenario_pool", "mcn_orca_batch", "mcn_orca_finish", "mcn_pack_linear", "mcn_sarl_workspace_bytes",
             "mcn_sarl_lookahead", "mcn_sarl_lookahead_env", "mcn_sarl_predict", "mcn_sarl_om_prepare", "mcn_sarl_predict_om", "mcn_sgan_workspace_bytes", "mcn_sgan_step", "mcn_sgan_predict", "mcn_mlp_world_step", "mcn_attn_world_workspace_bytes",
             "mcn_attn_world_step", "mcn_lstm_rl_predict", "mcn_lstm_rl_order", "mcn_cadrl_predict",
             "mcn_sarl_train_param_count", "mcn_sarl_train_workspace_bytes", "mcn_sarl_loss_grad", "mcn_sgd_momentum_step",

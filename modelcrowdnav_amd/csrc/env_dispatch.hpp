@@ -19,6 +19,7 @@ enum KernelFamily {
     kStepLoop,          // env_step.hip: env_step_loop_kernel
     kStepLoopSf,        // env_step.hip: env_step_loop_sf_kernel
     kStepLoopOrca,      // env_step.hip: env_step_loop_orca_kernel (mcn_env_rollout_orca: its one path)
+    kStepLoopOrcaSf,    // env_step.hip: env_step_loop_orca_sf_kernel (mcn_env_rollout_orca_sf: its one path)
 };
 
 inline const char *family_name(KernelFamily f)
@@ -31,6 +32,7 @@ inline const char *family_name(KernelFamily f)
         case kStepLoop:     return "env_step_loop_kernel";
         case kStepLoopSf:   return "env_step_loop_sf_kernel";
         case kStepLoopOrca: return "env_step_loop_orca_kernel";
+        case kStepLoopOrcaSf: return "env_step_loop_orca_sf_kernel";
     }
     return "";
 }

@@ -67,8 +67,8 @@ struct GroupCand {
 // One env step for the workgroup's env slots: everything between the state in HBM before the step and after it.  A
 // device function so that two kernels can share it: env_step_kernel (one step per launch) and env_step_loop_kernel
 // (T steps per launch for the one-wavefront form, below).
-// ROB: closed loop (env_step_loop_orca_kernel, run-time N only): the robot's action is not read from p.actions but solved
-// here, by the env's leader lane, as ORCA.predict_batch + mcn_orca_batch would (float32 operands converted where that
+// ROB: closed loop (env_step_loop_orca_kernel / env_step_loop_orca_sf_kernel, run-time N only): the robot's action is not
+// read from p.actions but solved here, by the env's leader lane, as ORCA.predict_batch + mcn_orca_batch would (float32 operands converted where that
 // code converts them, the float32 result widened to float64); `cl` carries the robot policy's parameters and the trace
 // arrays, `t` is the step's row in them.
 template <int BLOCK, int NT, int VIS, int MODE, int HH_T, int ROB = 0>
@@ -176,9 +176,19 @@ __device__ __forceinline__ void env_step_body(const StepParams &p, const ClosedL
             const RobotCand rc{sAgF, sRadD, gbase, cl->safety_space};
             const LdsLines RL{sL + tid, BLOCK};        // this lane's line slots: its human's solve (K1) reuses them afterwards
             float rx = 0, ry = 0;
-            orca_solve(rc, N, (float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y, (float)(rattr.x + 0.01 + cl->safety_space),
-                       (float)rattr.y, (float)(rgoal.x - rpos.x), (float)(rgoal.y - rpos.y),
-                       cl->neighbor_dist, cl->max_neighbors, cl->time_horizon, (float)dt, RL, rx, ry);
+            if constexpr (MODE == MCN_HUMANS_SOCIALFORCE) {
+                // no human's solve shares the line slots here, so the rows behind the robot's own (p.nl_cap holds both,
+                // launch_env_step_loop_orca_sf) take the 3-D LP's projected lines: nothing of the solve is in scratch
+                const int rows = cl->max_neighbors < N ? cl->max_neighbors : N;
+                const LdsLines RP{sL + (size_t)rows * BLOCK + tid, BLOCK};
+                orca_solve_lds(rc, N, (float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y, (float)(rattr.x + 0.01 + cl->safety_space),
+                               (float)rattr.y, (float)(rgoal.x - rpos.x), (float)(rgoal.y - rpos.y),
+                               cl->neighbor_dist, cl->max_neighbors, cl->time_horizon, (float)dt, RL, RP, rx, ry);
+            } else {
+                orca_solve(rc, N, (float)rpos.x, (float)rpos.y, (float)rvel.x, (float)rvel.y, (float)(rattr.x + 0.01 + cl->safety_space),
+                           (float)rattr.y, (float)(rgoal.x - rpos.x), (float)(rgoal.y - rpos.y),
+                           cl->neighbor_dist, cl->max_neighbors, cl->time_horizon, (float)dt, RL, rx, ry);
+            }
             act = make_double2((double)rx, (double)ry);
             sRobAct[slot] = act;                       // holonomic: the swept test (K2) takes the action as it is
             if (cl->tr_robot) {
@@ -543,6 +553,20 @@ __global__ __launch_bounds__(64) void env_step_loop_orca_kernel(const StepParams
     }
 }
 
+// The closed loop over social-force humans (mcn_env_rollout_orca_sf): the same body with the social-force K1.  That K1 has
+// no half-planes, so the line slots (p.nl_cap rows) are the robot's alone: its lines and, behind them, the projected lines
+// of its 3-D LP, which therefore needs no private memory; the humans read the float64 tiles and the robot's position and
+// radius, which the leader lane staged before the body's first barrier.  count_hh is fixed at compile time as in
+// env_step_loop_sf_kernel.
+template <int HH_T>
+__global__ __launch_bounds__(64) void env_step_loop_orca_sf_kernel(const StepParams p, const ClosedLoop cl, const int T)
+{
+    for (int t = 0; t < T; ++t) {
+        env_step_body<64, 0, 0, MCN_HUMANS_SOCIALFORCE, HH_T, 1>(p, &cl, t);
+        __syncthreads();                       // the next step restages the LDS tiles this one still reads
+    }
+}
+
 // The deferred 3-D LPs of one step (lp3_queue.hpp).  Finishes each parked solve exactly as the step kernel would have
 // (same sorted half-planes, same running result) and then does for that human what the step kernel skipped: the
 // exported action, and -- by the flag the step kernel left -- the integration (crowd_sim.py:416-421) or the look-ahead
@@ -723,6 +747,18 @@ void launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T,
         hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_ORCA>), dim3(waves_total), dim3(64), sm, stream, p, cl, T);
     else
         hipLaunchKernelGGL((env_step_loop_orca_kernel<MCN_HUMANS_LINEAR>), dim3(waves_total), dim3(64), sm, stream, p, cl, T);
+}
+
+// mcn_env_rollout_orca_sf: one env_step_loop_orca_sf_kernel launch for any batch and any 1 <= N <= MCN_MAX_HUMANS
+// (social-force humans, holonomic robot: validated by the caller).  The social-force step has no line slots of its own:
+// p.nl_cap is what the robot's solve can fill, R = min(max_neighbors, N) rows of lines and, for R >= 1, R - 1 rows of
+// projected lines (closed_loop_rollout, mcn_api.hip).
+void launch_env_step_loop_orca_sf(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream)
+{
+    const int waves_total = (int)lane_wavefronts(p);
+    const size_t sm = step_smem_bytes(64, p.nl_cap);
+    if (p.cfg.count_hh) hipLaunchKernelGGL((env_step_loop_orca_sf_kernel<1>), dim3(waves_total), dim3(64), sm, stream, p, cl, T);
+    else                hipLaunchKernelGGL((env_step_loop_orca_sf_kernel<0>), dim3(waves_total), dim3(64), sm, stream, p, cl, T);
 }
 
 // One single step as planned (env_dispatch.hpp: plan_env_step); p.lp3_defer already carries plan.lp3_defer.

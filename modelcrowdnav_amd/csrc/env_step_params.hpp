@@ -27,12 +27,14 @@ struct StepParams {
     int unused_2, unused_3;
     int lp3_defer;       // 0 / 1 (StepPlan.lp3_defer): the compile-time-N ORCA kernels park their 3-D LPs in out.lp3_queue
     int unused_4;
-    // MCN_HUMANS_SOCIALFORCE only (mcn_env_step_sf / mcn_env_rollout_sf): A (m/s^2), B (m), k (1/s) of social_force.hpp
+    // MCN_HUMANS_SOCIALFORCE only (mcn_env_step_sf / mcn_env_rollout_sf / mcn_env_rollout_orca_sf): A (m/s^2), B (m),
+    // k (1/s) of social_force.hpp
     double sf_strength, sf_range, sf_relaxation_rate;
 };
 
-// mcn_env_rollout_orca only (env_step.hip: env_step_loop_orca_kernel): the robot's own ORCA parameters and the per-step
-// trace arrays, each of which may be NULL.  A second kernel argument, so that StepParams stays what the other kernels take.
+// mcn_env_rollout_orca / mcn_env_rollout_orca_sf only (env_step.hip: env_step_loop_orca_kernel and its social-force
+// twin): the robot's own ORCA parameters and the per-step trace arrays, each of which may be NULL.  A second kernel
+// argument, so that StepParams stays what the other kernels take.
 struct ClosedLoop {
     double safety_space;               // the robot policy's: a radius goes float32 as (radius + 0.01) + safety_space (orca.py:100,103)
     float neighbor_dist, time_horizon;

@@ -21,6 +21,7 @@ void launch_env_step(const StepParams &p, const StepPlan &plan, hipStream_t stre
 void launch_env_step_loop(const StepParams &p, int T, hipStream_t stream);
 void launch_env_step_loop_sf(const StepParams &p, int T, hipStream_t stream);
 void launch_env_step_loop_orca(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream);
+void launch_env_step_loop_orca_sf(const StepParams &p, const ClosedLoop &cl, int T, hipStream_t stream);
 // env_step_quad.hip, env_pair.hip
 void launch_env_step_quad(const StepParams &p, bool split, hipStream_t stream);
 void launch_env_pair(const StepParams &p, bool nontemporal, hipStream_t stream);

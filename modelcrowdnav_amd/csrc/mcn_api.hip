@@ -208,6 +208,55 @@ static int run_rollout(mcn::StepParams &p, const mcn::RolloutPlan &plan, const d
     return launched();
 }
 
+// the model's parameters (include/mcn.h): A >= 0, B > 0, k >= 0, all finite
+static bool sf_params_ok(double strength, double range, double relaxation_rate)
+{
+    return isfinite(strength) && isfinite(range) && isfinite(relaxation_rate) && strength >= 0 && range > 0 &&
+           relaxation_rate >= 0;
+}
+
+// mcn_env_rollout_orca and its social-force twin: validation, argument blocks and the one launch.  `sf`: NULL for ORCA or
+// linear humans, else {strength, range, relaxation_rate} (checked by the caller) for social-force ones.
+static int closed_loop_rollout(const mcn_env_cfg *cfg, const double *sf, const mcn_env_state *st,
+                               double robot_safety_space, float neighbor_dist, int32_t max_neighbors, float time_horizon,
+                               int32_t T, const mcn_env_out *out, const mcn_rollout *roll, double *tr_robot,
+                               double *tr_humans, double *tr_hrad, double *tr_action, mcn_step_rec *tr_rec,
+                               double *tr_human_act, int32_t E, int32_t N, void *stream)
+{
+    if (!cfg || !st || !out || T < 1) return MCN_EINVAL;
+    if (max_neighbors < 0 || max_neighbors > MCN_MAX_LINES) return MCN_EINVAL;
+    if (!(time_horizon > 0) || !(cfg->time_step > 0) || !((float)cfg->time_step > 0)) return MCN_EINVAL;
+    if (!isfinite(robot_safety_space)) return MCN_EINVAL;
+    if (cfg->robot_kinematics != MCN_KIN_HOLONOMIC) return MCN_EINVAL;          // the ORCA robot is holonomic
+    if (sf ? cfg->human_policy != MCN_HUMANS_SOCIALFORCE
+           : cfg->human_policy != MCN_HUMANS_ORCA && cfg->human_policy != MCN_HUMANS_LINEAR) return MCN_EINVAL;
+    if (!st->rvpref) return MCN_EINVAL;                                         // the robot's max speed
+    mcn::StepParams p;
+    const int rc = fill_step_params(p, tuning(), cfg, st, nullptr, nullptr, out, roll, E, N, 1, sf != nullptr, false);
+    if (rc != MCN_OK) return rc;
+    // line slots per lane: the larger of what a human's solve and the robot's solve (all N humans as candidates) can fill.
+    // Social-force humans fill none: there the robot's 3-D LP keeps its projected lines (one fewer than its lines at most)
+    // in rows behind its own
+    const int rob_nl = max_neighbors < N ? max_neighbors : N;
+    if (sf) p.nl_cap = rob_nl + (rob_nl > 0 ? rob_nl - 1 : 0);
+    else if (rob_nl > p.nl_cap) p.nl_cap = rob_nl;
+    mcn::ClosedLoop cl;
+    memset(&cl, 0, sizeof(cl));
+    cl.safety_space = robot_safety_space;       // added after the 0.01, in the reference's order (orca.py:100,103)
+    cl.neighbor_dist = neighbor_dist; cl.time_horizon = time_horizon; cl.max_neighbors = max_neighbors;
+    cl.tr_robot = tr_robot; cl.tr_humans = tr_humans; cl.tr_hrad = tr_hrad; cl.tr_action = tr_action;
+    cl.tr_rec = tr_rec; cl.tr_human_act = tr_human_act;
+    if (sf) {
+        p.sf_strength = sf[0]; p.sf_range = sf[1]; p.sf_relaxation_rate = sf[2];
+        g_last_dispatch = mcn::family_name(mcn::kStepLoopOrcaSf);
+        mcn::launch_env_step_loop_orca_sf(p, cl, T, (hipStream_t)stream);
+    } else {
+        g_last_dispatch = mcn::family_name(mcn::kStepLoopOrca);
+        mcn::launch_env_step_loop_orca(p, cl, T, (hipStream_t)stream);
+    }
+    return launched();
+}
+
 extern "C" {
 
 #ifdef MCN_DIAG
@@ -276,35 +325,21 @@ int mcn_env_rollout_orca(const mcn_env_cfg *cfg, const mcn_env_state *st, double
                          double *tr_hrad, double *tr_action, mcn_step_rec *tr_rec, double *tr_human_act,
                          int32_t E, int32_t N, void *stream)
 {
-    if (!cfg || !st || !out || T < 1) return MCN_EINVAL;
-    if (max_neighbors < 0 || max_neighbors > MCN_MAX_LINES) return MCN_EINVAL;
-    if (!(time_horizon > 0) || !(cfg->time_step > 0) || !((float)cfg->time_step > 0)) return MCN_EINVAL;
-    if (!isfinite(robot_safety_space)) return MCN_EINVAL;
-    if (cfg->robot_kinematics != MCN_KIN_HOLONOMIC) return MCN_EINVAL;          // the ORCA robot is holonomic
-    if (cfg->human_policy != MCN_HUMANS_ORCA && cfg->human_policy != MCN_HUMANS_LINEAR) return MCN_EINVAL;
-    if (!st->rvpref) return MCN_EINVAL;                                         // the robot's max speed
-    mcn::StepParams p;
-    const int rc = fill_step_params(p, tuning(), cfg, st, nullptr, nullptr, out, roll, E, N, 1, false, false);
-    if (rc != MCN_OK) return rc;
-    // line slots per lane: the larger of what a human's solve and the robot's solve (all N humans as candidates) can fill
-    const int rob_nl = max_neighbors < N ? max_neighbors : N;
-    if (rob_nl > p.nl_cap) p.nl_cap = rob_nl;
-    mcn::ClosedLoop cl;
-    memset(&cl, 0, sizeof(cl));
-    cl.safety_space = robot_safety_space;       // added after the 0.01, in the reference's order (orca.py:100,103)
-    cl.neighbor_dist = neighbor_dist; cl.time_horizon = time_horizon; cl.max_neighbors = max_neighbors;
-    cl.tr_robot = tr_robot; cl.tr_humans = tr_humans; cl.tr_hrad = tr_hrad; cl.tr_action = tr_action;
-    cl.tr_rec = tr_rec; cl.tr_human_act = tr_human_act;
-    g_last_dispatch = mcn::family_name(mcn::kStepLoopOrca);
-    mcn::launch_env_step_loop_orca(p, cl, T, (hipStream_t)stream);
-    return launched();
+    return closed_loop_rollout(cfg, nullptr, st, robot_safety_space, neighbor_dist, max_neighbors, time_horizon, T, out,
+                               roll, tr_robot, tr_humans, tr_hrad, tr_action, tr_rec, tr_human_act, E, N, stream);
 }
 
-// the model's parameters (include/mcn.h): A >= 0, B > 0, k >= 0, all finite
-static bool sf_params_ok(double strength, double range, double relaxation_rate)
+int mcn_env_rollout_orca_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,
+                            const mcn_env_state *st, double robot_safety_space, float neighbor_dist,
+                            int32_t max_neighbors, float time_horizon, int32_t T, const mcn_env_out *out,
+                            const mcn_rollout *roll, double *tr_robot, double *tr_humans, double *tr_hrad,
+                            double *tr_action, mcn_step_rec *tr_rec, double *tr_human_act, int32_t E, int32_t N,
+                            void *stream)
 {
-    return isfinite(strength) && isfinite(range) && isfinite(relaxation_rate) && strength >= 0 && range > 0 &&
-           relaxation_rate >= 0;
+    if (!sf_params_ok(strength, range, relaxation_rate)) return MCN_EINVAL;
+    const double sf[3] = {strength, range, relaxation_rate};
+    return closed_loop_rollout(cfg, sf, st, robot_safety_space, neighbor_dist, max_neighbors, time_horizon, T, out, roll,
+                               tr_robot, tr_humans, tr_hrad, tr_action, tr_rec, tr_human_act, E, N, stream);
 }
 
 int mcn_env_step_sf(const mcn_env_cfg *cfg, double strength, double range, double relaxation_rate,

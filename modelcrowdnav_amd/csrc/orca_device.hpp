@@ -212,4 +212,74 @@ __device__ void orca_solve(const Cand &cand, int ncand, float px, float py, floa
     outx = rx; outy = ry;
 }
 
+// lp3 with its projected lines in LDS rows of the caller's (P: at most n - 1 of them) instead of private memory, inlined
+// into its one caller: a kernel whose only solve goes through here has no scratch.  The same operations in the same
+// order as lp3 above, which stays as it is: its compiled code is shared by kernels whose instructions are pinned.
+template <class Acc>
+__device__ __forceinline__ void lp3_lds(const Acc &L, const LdsLines &P, int n, int begin, float radius, float &rx, float &ry)
+{
+    float dist = 0.0f;
+    for (int i = begin; i < n; ++i) {
+        const float4 li = L.get(i);
+        if (det2(li.z, li.w, li.x - rx, li.y - ry) > dist) {
+            int m = 0;
+            for (int j = 0; j < i; ++j) {
+                const float4 lj = L.get(j);
+                float qx, qy;
+                const float dt = det2(li.z, li.w, lj.z, lj.w);
+                if (fabsf(dt) <= kRvoEps) {
+                    if (dot2(li.z, li.w, lj.z, lj.w) > 0.0f) continue;
+                    qx = 0.5f * (li.x + lj.x); qy = 0.5f * (li.y + lj.y);
+                } else {
+                    const float s = det2(lj.z, lj.w, li.x - lj.x, li.y - lj.y) / dt;
+                    qx = li.x + s * li.z; qy = li.y + s * li.w;
+                }
+                const float ddx = lj.z - li.z, ddy = lj.w - li.w;
+                const float inv = 1.0f / sqrtf(dot2(ddx, ddy, ddx, ddy));
+                P.set(m++, make_float4(qx, qy, ddx * inv, ddy * inv));
+            }
+            const float kx = rx, ky = ry;
+            if (lp2(P, m, radius, -li.w, li.z, true, rx, ry) < m) { rx = kx; ry = ky; }
+            dist = det2(li.z, li.w, li.x - rx, li.y - ry);
+        }
+    }
+}
+
+// orca_solve with lp3_lds: the 3-D LP's projected lines go to the LDS rows P (at most nl - 1 <= min(max_neighbors,
+// ncand) - 1 of them).  Same operations in the same order, same result.
+template <class Cand>
+__device__ void orca_solve_lds(const Cand &cand, int ncand, float px, float py, float vx, float vy, float radius,
+                               float max_speed, float prefx, float prefy, float neighbor_dist, int max_neighbors,
+                               float time_horizon, float time_step, const LdsLines &L, const LdsLines &P, float &outx,
+                               float &outy)
+{
+    const float range_sq = neighbor_dist * neighbor_dist;
+    const float inv_th = 1.0f / time_horizon;
+    const float inv_ts = 1.0f / time_step;
+    int nl = 0;
+    for (int c = 0; c < ncand; ++c) {
+        float4 o; float orad;
+        cand.fetch(c, o, orad);
+        const float ddx = px - o.x, ddy = py - o.y;
+        const float d = dot2(ddx, ddy, ddx, ddy);
+        if (!(d < range_sq)) continue;
+        int rank = 0;
+        for (int k = 0; k < ncand; ++k) {
+            if (k == c) continue;
+            float4 ok; float rk;
+            cand.fetch(k, ok, rk);
+            const float ex = px - ok.x, ey = py - ok.y;
+            const float dk = dot2(ex, ey, ex, ey);
+            rank += (dk < range_sq) && (dk < d || (dk == d && k < c));
+        }
+        if (rank >= max_neighbors) continue;
+        L.set(rank, orca_line(px, py, vx, vy, radius, o, orad, inv_th, inv_ts));
+        ++nl;
+    }
+    float rx, ry;
+    const int fail = lp2(L, nl, max_speed, prefx, prefy, false, rx, ry);
+    if (fail < nl) lp3_lds(L, P, nl, fail, max_speed, rx, ry);
+    outx = rx; outy = ry;
+}
+
 }  // namespace mcn

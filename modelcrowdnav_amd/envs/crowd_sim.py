@@ -338,14 +338,13 @@ class VecCrowdSim(object):
 
     def rollout_orca(self, policy, T, trace=False):
         """T consecutive closed-loop steps with the ORCA robot `policy` (an envs.policy.orca.ORCA: its safety_space,
-        neighbor_dist, max_neighbors and time_horizon) in one mcn_env_rollout_orca call: each step is
-        `policy.predict_batch(env)` followed by `step(that action)`, bit for bit.  ORCA or linear humans, holonomic robot.
+        neighbor_dist, max_neighbors and time_horizon) in one mcn_env_rollout_orca call (social-force humans:
+        mcn_env_rollout_orca_sf): each step is `policy.predict_batch(env)` followed by `step(that action)`, bit for bit.
+        ORCA, linear or social-force humans, holonomic robot.
         With `trace` returns a dict of [T, ...] device tensors -- robot [T,E,5] (px, py, vx, vy, theta before the step),
         humans [T,E,N,4] (px, py, vx, vy before it), hrad [T,E,N], action [T,E,2], human_act [T,E,N,2], rec [T,E,3]
         (mcn_step_rec rows) and its typed views reward / dmin / done / info / hh_count [T,E] -- else None."""
         E, N, dev, T = self.num_envs, self._alloc_N, self.device, int(T)
-        if self.human_policy_name == "socialforce":
-            raise NotImplementedError("rollout_orca: ORCA or linear humans")
         tr = None
         if trace:
             z = lambda *shape: torch.zeros(*shape, dtype=torch.float64, device=dev)
@@ -354,12 +353,10 @@ class VecCrowdSim(object):
             tr.update({k: v.view(T, E) for k, v in _hip.step_rec_views(tr["rec"].view(T * E, 3)).items()})
         names = ("robot", "humans", "hrad", "action", "rec", "human_act")
         out = self._out if self.export_human_actions else self._out_lean
-        rc = _hip.lib.mcn_env_rollout_orca(self._cfg_struct(None), self._st, float(policy.safety_space),
-                                           float(policy.neighbor_dist), int(policy.max_neighbors),
-                                           float(policy.time_horizon), T, out, self._roll,
-                                           *[_hip.ptr(tr[k]) if tr is not None else None for k in names],
-                                           E, N, _hip.stream_ptr(dev))
-        _hip.check(rc, "mcn_env_rollout_orca")
+        self._env_call("mcn_env_rollout_orca", None, self.human_policy_name == "socialforce", self._st,
+                       float(policy.safety_space), float(policy.neighbor_dist), int(policy.max_neighbors),
+                       float(policy.time_horizon), T, out, self._roll,
+                       *[_hip.ptr(tr[k]) if tr is not None else None for k in names], E, N, _hip.stream_ptr(dev))
         return tr
 
     def onestep_lookahead(self, actions):

@@ -230,8 +230,8 @@ class VecExplorer(object):
 
     def _closed_loop_ok(self, transformer, action_fn, action_seq, stay):
         """The automatic rule of run_k_episodes(closed_loop=None): an ORCA robot policy (holonomic) choosing every
-        action, on a VecCrowdSim whose step is the plain mcn_env_step with ORCA or linear humans, and -- when memory rows are
-        wanted -- a transformer whose rows can be made from the trace."""
+        action, on a VecCrowdSim whose step is the plain mcn_env_step (or mcn_env_step_sf) with ORCA, linear or
+        social-force humans, and -- when memory rows are wanted -- a transformer whose rows can be made from the trace."""
         from .envs.crowd_sim import VecCrowdSim
         from .envs.policy.orca import ORCA
         env = self.env
@@ -239,7 +239,7 @@ class VecExplorer(object):
             return False
         if type(self.policy).predict_batch is not ORCA.predict_batch:
             return False
-        if type(env).step is not VecCrowdSim.step or env.human_policy_name not in ("orca", "linear"):
+        if type(env).step is not VecCrowdSim.step or env.human_policy_name not in ("orca", "linear", "socialforce"):
             return False
         if getattr(env.robot, "kinematics", "holonomic") == "unicycle":
             return False
@@ -382,8 +382,9 @@ class VecExplorer(object):
         `test_case` plays that one case k times (explorer.py:54 hands it to every reset; the counter ends one past it).
         `closed_loop`: None = automatic -- with an ORCA robot policy (the imitation-learning demonstrator, `--policy orca`)
         and no action_fn / action_seq / stay, the robot's solve and the env step run up to 128 steps per launch
-        (VecCrowdSim.rollout_orca); memory rows and collected rows then come from that launch's trace, and every result
-        equals the per-step loop's.  False forces the per-step loop; True raises where the closed loop does not apply."""
+        (VecCrowdSim.rollout_orca: ORCA, linear or social-force humans); memory rows and collected rows then come from
+        that launch's trace, and every result equals the per-step loop's.  False forces the per-step loop; True raises
+        where the closed loop does not apply."""
         env = self.env
         rank, ws = mdist.world()
         E_local = env.num_envs
@@ -415,8 +416,8 @@ class VecExplorer(object):
             keep_export, env.export_human_actions = env.export_human_actions, True
         auto = self._closed_loop_ok(transformer, action_fn, action_seq, stay)
         if closed_loop and not auto:
-            raise ValueError("closed_loop=True needs an ORCA robot policy choosing every action, ORCA humans, a holonomic "
-                             "robot and memory rows that can be made from the trace")
+            raise ValueError("closed_loop=True needs an ORCA robot policy choosing every action, ORCA, linear or "
+                             "social-force humans, a holonomic robot and memory rows that can be made from the trace")
         self.last_run_closed_loop = auto if closed_loop is None else bool(closed_loop)
         if self.last_run_closed_loop:
             steps, trace = self._drive_closed_loop(limit, rounds, transformer, collect)

@@ -88,7 +88,8 @@ def main():
     ap.add_argument("--modes", default="orca,given")
     ap.add_argument("--visible", action="store_true")
     ap.add_argument("--human-policy", default="orca", choices=("orca", "socialforce"),
-                    help="the env's own humans in the 'orca' mode of --modes and in --rollout (socialforce: default parameters)")
+                    help="the env's own humans in the 'orca' mode of --modes, in --rollout and in --closed-loop "
+                         "(socialforce: default parameters)")
     ap.add_argument("--unfused", action="store_true", help="with --rollout: mcn_tuning.rollout_fused = 0 (T step launches)")
     ap.add_argument("--no-hh", action="store_true", help="no human-human overlap count (ModelCrowdSim.step does not count)")
     ap.add_argument("--pair-stream", type=int, default=-1, help="mcn_tuning.pair_stream")
@@ -110,7 +111,8 @@ def main():
                          "mcn_orca_batch launch + torch update per simulated step, and the E = 1 CrowdSim method against "
                          "its former host loop")
     ap.add_argument("--closed-loop", action="store_true",
-                    help="time one 128-step mcn_env_rollout_orca launch (with and without traces) at --sizes x --humans "
+                    help="time one 128-step mcn_env_rollout_orca launch (--human-policy socialforce: mcn_env_rollout_orca_sf; "
+                         "with and without traces) at --sizes x --humans "
                          "against 128 x (ORCA.predict_batch + env.step) and against the per-step Explorer loop body")
     ap.add_argument("--trainer", action="store_true",
                     help="time Trainer.optimize_batch(100) at batch 100 x --humans: fused HIP step (fused=True) against "
@@ -134,7 +136,7 @@ def main():
     if a.closed_loop:
         for N in [int(x) for x in str(a.humans).split(",")]:
             for E in [int(x) for x in a.sizes.split(",")]:
-                closed_loop_bench(E, N)
+                closed_loop_bench(E, N, human_policy=a.human_policy)
         return
     if a.finish:
         for N in [int(x) for x in str(a.humans).split(",")]:
@@ -316,12 +318,13 @@ def world_trainer_bench(N, batch=100, epochs=3, rows=25000, reps=5, world="atten
                                                                    (t - k) * 1e3 / steps, steps))
 
 
-def closed_loop_bench(E, N, T=128, reps=5):
+def closed_loop_bench(E, N, T=128, reps=5, human_policy="orca"):
     """us per simulated step of the closed loop with an ORCA robot (safety_space 0.15, the imitation-learning
-    demonstrator): one T-step mcn_env_rollout_orca launch without / with traces, T x (predict_batch + step), and the
+    demonstrator) over ORCA or social-force humans (--human-policy; socialforce: default parameters): one T-step
+    mcn_env_rollout_orca / mcn_env_rollout_orca_sf launch without / with traces, T x (predict_batch + step), and the
     per-step loop body of VecExplorer.run_k_episodes(update_memory=True, imitation_learning=True) with a SARL target
     policy.  The four forms alternate inside every repeat; min / median / max over the repeats."""
-    from modelcrowdnav_amd import configs
+    from modelcrowdnav_amd import _hip, configs
     from modelcrowdnav_amd.envs.policy.policy_factory import policy_factory
     from modelcrowdnav_amd.policy.sarl import SARL
     dev = torch.device("cuda", 0)
@@ -329,6 +332,7 @@ def closed_loop_bench(E, N, T=128, reps=5):
     pol = policy_factory["orca"]()
     pol.multiagent_training, pol.safety_space = True, 0.15
     env.robot.set_policy(pol)
+    env.human_policy_name = human_policy
     sarl = SARL(); sarl.configure(configs.policy_config()); sarl.kinematics = "holonomic"; sarl.set_device(dev)
 
     def per_step():
@@ -347,16 +351,19 @@ def closed_loop_bench(E, N, T=128, reps=5):
     forms = [("closed loop", lambda: env.rollout_orca(pol, T)), ("closed loop + traces", lambda: env.rollout_orca(pol, T, trace=True)),
              ("per step", per_step), ("explorer loop body", explorer_body)]
     times = {k: [] for k, _ in forms}
+    ran = {}
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for rep in range(reps + 1):                       # the first repeat warms up
         for name, fn in forms:
             torch.cuda.synchronize()
             s.record(); fn(); e.record(); torch.cuda.synchronize()
+            ran[name] = _hip.last_dispatch()
             if rep:
                 times[name].append(s.elapsed_time(e) * 1e3 / T)
     for name, _ in forms:
         v = sorted(times[name])
-        print("N=%d E=%6d T=%d %-22s min %8.2f  median %8.2f  max %8.2f us/step" % (N, E, T, name, v[0], v[len(v) // 2], v[-1]))
+        print("N=%d E=%6d T=%d %s humans %-22s min %8.2f  median %8.2f  max %8.2f us/step  (%s)" % (
+            N, E, T, human_policy, name, v[0], v[len(v) // 2], v[-1], ran[name]))
 
 
 def rollout_bench(a):
