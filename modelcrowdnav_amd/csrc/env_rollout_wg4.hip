@@ -50,6 +50,10 @@ namespace mcn {
 //     quad_take_plan.hpp): five instructions in a row per step for eight, ten fewer in the loop.  On the SIMDs that hold
 //     two ORCA wavefronts an instruction costs its issue slot on or off the chain (profiles/r30_rollout_parallel_takes.txt:
 //     the form that evaluated all sixteen tests at once had a shorter chain, thirty instructions more, and lost 4 %).
+//     The 3-D LP candidate's three take steps are the same lean steps (QuadTable::lean_lp3);
+//   * the rank's four quad broadcasts of the key are folded into the subtractions that read them (QuadTable::fold_rank:
+//     four v_sub_u32_dpp).  The take steps' candidate broadcasts folded into v_cndmask_b32_dpp need inline asm, which the
+//     compiler cannot schedule around: eight instructions fewer, 0.8 % slower (profiles/r31_rollout_dpp_fold.txt).
 // Each value is produced by the operation, on the operands, that the other forms use, so the same bits.
 //
 // RESTART STEPS (some env of the workgroup ends: roughly one workgroup-step in ten) and the launch's first solve take the

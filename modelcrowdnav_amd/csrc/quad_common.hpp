@@ -66,12 +66,17 @@ __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
 //              (`spread`, lp1_spread below) where the other callers run 0 + 1 + 2 + 3 as three passes on every lane.
 //              And its four take steps decide from the minimum beside the test instead of from `fail` behind it
 //              (`lean_take`, take_step_lean in quad_take_plan.hpp): per step five instructions in a row where the other
-//              callers have eight, and two instructions fewer.
+//              callers have eight, and two instructions fewer.  The 3-D LP candidate's three take steps are the same
+//              lean steps here (`lean_lp3`; the other callers keep the guarded ones).
+//              And the rank's four quad broadcasts of the key sit inside the subtractions that read them (`fold_rank`:
+//              four v_sub_u32_dpp for four v_mov_b32_dpp and three v_sub_u32).
 struct QuadDpp {
     static constexpr bool table = false, slim = false, spread = false, lean_take = false;
+    static constexpr bool fold_rank = false, lean_lp3 = false;
 };
 struct QuadTable {
     static constexpr bool table = true, slim = true, spread = true, lean_take = true;
+    static constexpr bool fold_rank = true, lean_lp3 = true;
     float4 *tab;                                                 // this wavefront's 64 slots
 };
 
@@ -178,6 +183,20 @@ __device__ __forceinline__ bool lp1_spread(const float4 &ln, const float4 &lnA, 
     return ok;
 }
 
+// One lean take step (take_step_lean in quad_take_plan.hpp) of an incremental LP on the quad: line I is LN on every lane,
+// lane I holds its verdict (fcode) and its candidate (cx, cy); `fail`, rx and ry are the running values.  The verdict's
+// broadcast is the form the compiler folds into the minimum (v_min_i32_dpp).  A file-scope macro because two functions
+// use it (lp3_candidate_quad<true> and quad_orca_core's lean branch); undefined at the end of this header.
+#define MCN_TAKE_LEAN(I, LN)                                                                   \
+        {                                                                                      \
+            const int code_i = qbi_fold<I>(fcode);                                             \
+            const float cx_i = qbf_fold<I>(cx), cy_i = qbf_fold<I>(cy);                         \
+            const bool out = det2(LN.z, LN.w, LN.x - rx, LN.y - ry) > 0.0f;                     \
+            const TakeStep s = take_step_lean(fail, code_i, out, I);                           \
+            fail = s.fail;                                                                     \
+            rx = s.take ? cx_i : rx; ry = s.take ? cy_i : ry;                                   \
+        }
+
 // 3-D LP candidate of line `i` (run-time, quad-uniform), computed by the four lanes of the quad TOGETHER: lane k
 // projects line k on line i (RVO2 linearProgram3's inner loop, one projection per lane instead of three in a row),
 // then solves the direction-optimising 1-D LP of ITS projected line against the earlier kept ones speculatively
@@ -193,6 +212,7 @@ __device__ __forceinline__ bool lp1_spread(const float4 &ln, const float4 &lnA, 
 // a mask: its violation test det2(0, 0, ., .) > 0, and in a kept lane's 1-D LP it is "parallel" with num = +-0 (0 > num
 // false) or, with a NaN den, fminf / fmaxf keep tr / tl and tl > tr repeats the previous step's answer.  So no kept
 // flag is broadcast, and the take steps are the 2-D LP's `fail > I` form (quad_orca_velocity).
+template <bool LEAN = false>
 __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float4 &lj, int i, int k, float radius, float &rx,
                                                    float &ry)
 {
@@ -239,16 +259,21 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float
     rx = radius * ox; ry = radius * oy;
     // as MCN_LP2_TAKE over the lines 0 .. 2: `fail` stays 3 until a violated line's 1-D LP is infeasible
     int fail = 3;
+    if constexpr (LEAN) {
+        // (Path::lean_lp3) the same three steps in the 2-D LP's lean form: take_step_lean, the broadcasts foldable
+        MCN_TAKE_LEAN(0, P0) MCN_TAKE_LEAN(1, P1) MCN_TAKE_LEAN(2, P2)
+    } else {
 #define MCN_LP3_INNER_TAKE(I, PI)                                                              \
-    {                                                                                          \
-        const int code_i = qbi<I>(fcode); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy);    \
-        const bool out = det2(PI.z, PI.w, PI.x - rx, PI.y - ry) > 0.0f;                         \
-        fail = ((fail > I) & out) ? min(fail, code_i) : fail;                                   \
-        const bool take = (fail > I) & out;                                                     \
-        rx = take ? cx_i : rx; ry = take ? cy_i : ry;                                           \
-    }
-    MCN_LP3_INNER_TAKE(0, P0) MCN_LP3_INNER_TAKE(1, P1) MCN_LP3_INNER_TAKE(2, P2)
+        {                                                                                      \
+            const int code_i = qbi<I>(fcode); const float cx_i = qbf<I>(cx), cy_i = qbf<I>(cy); \
+            const bool out = det2(PI.z, PI.w, PI.x - rx, PI.y - ry) > 0.0f;                     \
+            fail = ((fail > I) & out) ? min(fail, code_i) : fail;                               \
+            const bool take = (fail > I) & out;                                                 \
+            rx = take ? cx_i : rx; ry = take ? cy_i : ry;                                       \
+        }
+        MCN_LP3_INNER_TAKE(0, P0) MCN_LP3_INNER_TAKE(1, P1) MCN_LP3_INNER_TAKE(2, P2)
 #undef MCN_LP3_INNER_TAKE
+    }
     return fail == 3;
 }
 
@@ -316,7 +341,17 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     // get +inf's bits, above every in-range key.  Lane q ranks before lane k iff key_q < key_k, or key_q == key_k and
     // q < k, i.e. key_q - key_k < (q < k) (no overflow: keys lie in [0, 0x7f800000]).
     const int key = in ? __builtin_bit_cast(int, d) : 0x7f800000;
-    const int kd0 = qbi<0>(key) - key, kd1 = qbi<1>(key) - key, kd2 = qbi<2>(key) - key, kd3 = qbi<3>(key) - key;
+    int kd0, kd1, kd2, kd3;
+    if constexpr (Path::fold_rank) {
+        // the four broadcasts inside their subtractions (v_sub_u32_dpp).  The DPP combiner works per basic block, and left
+        // alone the subtractions sink behind the half-plane guard's branch, away from their broadcasts: the empty statement
+        // keeps the four differences where they are formed.  (The compiler emits these DPP reads itself, so the two
+        // instructions between the write of `key` and the first of them are its to place.)
+        kd0 = qbi_fold<0>(key) - key; kd1 = qbi_fold<1>(key) - key; kd2 = qbi_fold<2>(key) - key; kd3 = qbi_fold<3>(key) - key;
+        asm volatile("" : "+v"(kd0), "+v"(kd1), "+v"(kd2), "+v"(kd3));
+    } else {
+        kd0 = qbi<0>(key) - key; kd1 = qbi<1>(key) - key; kd2 = qbi<2>(key) - key; kd3 = qbi<3>(key) - key;
+    }
     const int rank = (kd0 < (0 < k ? 1 : 0)) + (kd1 < (1 < k ? 1 : 0)) + (kd2 < (2 < k ? 1 : 0)) + (kd3 < 0);
     // in-range candidates of the quad: the quad's four bits of one ballot
     const int nin = __builtin_popcount((unsigned)(__builtin_amdgcn_ballot_w64(in) >> (lane & ~3)) & 0xfu);
@@ -380,17 +415,7 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     if constexpr (Path::lean_take) {
         // the same four steps, each deciding from min(fail, code_i), which is known before the step's test: behind the
         // compare one mask AND and the selects (take_step_lean: the same `fail` and the same `take` on every input)
-#define MCN_LP2_TAKE_LEAN(I)                                                                   \
-        {                                                                                      \
-            const int code_i = qbi_fold<I>(fcode);                                             \
-            const float cx_i = qbf_fold<I>(cx), cy_i = qbf_fold<I>(cy);                         \
-            const bool out = det2(L[I].z, L[I].w, L[I].x - rx, L[I].y - ry) > 0.0f;             \
-            const TakeStep s = take_step_lean(fail, code_i, out, I);                           \
-            fail = s.fail;                                                                     \
-            rx = s.take ? cx_i : rx; ry = s.take ? cy_i : ry;                                   \
-        }
-        MCN_LP2_TAKE_LEAN(0) MCN_LP2_TAKE_LEAN(1) MCN_LP2_TAKE_LEAN(2) MCN_LP2_TAKE_LEAN(3)
-#undef MCN_LP2_TAKE_LEAN
+        MCN_TAKE_LEAN(0, L[0]) MCN_TAKE_LEAN(1, L[1]) MCN_TAKE_LEAN(2, L[2]) MCN_TAKE_LEAN(3, L[3])
     } else {
 #define MCN_LP2_TAKE(I)                                                                        \
         {                                                                                      \
@@ -426,12 +451,14 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
             if constexpr (Path::table) ln = path.tab[(lane & ~3) | nxt];      // one 16-byte read for sel4's 12 selects
             else ln = sel4(L, nxt);
             float cx3, cy3;
-            const bool ok3 = lp3_candidate_quad(ln, srt, nxt, k, ms, cx3, cy3);
+            const bool ok3 = lp3_candidate_quad<Path::lean_lp3>(ln, srt, nxt, k, ms, cx3, cy3);
             rx = ok3 ? cx3 : rx; ry = ok3 ? cy3 : ry;
             dist = det2(ln.z, ln.w, ln.x - rx, ln.y - ry);
             i = nxt + 1;
         }
     }
 }
+
+#undef MCN_TAKE_LEAN
 
 }  // namespace mcn
