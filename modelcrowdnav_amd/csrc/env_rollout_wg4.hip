@@ -53,7 +53,12 @@ namespace mcn {
 //     The 3-D LP candidate's three take steps are the same lean steps (QuadTable::lean_lp3);
 //   * the rank's four quad broadcasts of the key are folded into the subtractions that read them (QuadTable::fold_rank:
 //     four v_sub_u32_dpp).  The take steps' candidate broadcasts folded into v_cndmask_b32_dpp need inline asm, which the
-//     compiler cannot schedule around: eight instructions fewer, 0.8 % slower (profiles/r31_rollout_dpp_fold.txt).
+//     compiler cannot schedule around: eight instructions fewer, 0.8 % slower (profiles/r31_rollout_dpp_fold.txt);
+//   * the three range guards of a normal step (half-plane, clip, 1-D LP discriminant) compute the fast values first and
+//     replace them under a branch marked unlikely (QuadTable::straight; fast_f32.hpp: FAST_FIRST): each guard is one
+//     not-taken s_cbranch_scc0 where the step went to a block behind the loop's end and back, 98 cycles a round trip for a
+//     wavefront alone on its SIMD (profiles/r32_branch_cost.txt), +2.2 % (profiles/r32_rollout_branch_layout.txt).  The one
+//     taken branch left before the hand-off is the skip over the 3-D LP: moving that loop out of line measured nothing.
 // Each value is produced by the operation, on the operands, that the other forms use, so the same bits.
 //
 // RESTART STEPS (some env of the workgroup ends: roughly one workgroup-step in ten) and the launch's first solve take the

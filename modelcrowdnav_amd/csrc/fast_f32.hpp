@@ -18,6 +18,16 @@
 // expansion: ONE wave-uniform branch per guard, so the float state stays bit-identical to the oracle for every input.
 // `used` = lanes whose result is consumed; the operands of the others (empty neighbour slots, discarded select sides)
 // never force the slow path.
+//
+// FAST_FIRST (the four-wavefront rollout form only: QuadTable::straight in quad_common.hpp).  `if (fast) return fast(x);
+// return ieee(x);` tells the compiler nothing about which side is hot: it laid the IEEE expansion on the fall-through path
+// and reached the fast sequence through a taken s_cbranch_scc0 to a block behind the loop's end and an s_branch back.  A
+// taken scalar branch costs a lone wavefront 29 cycles, that round trip 98 (profiles/r32_branch_cost.txt), on a path with
+// three such guards per step.  With the tag the fast value is computed unconditionally and REPLACED, on every lane as
+// before, inside one wave-uniform branch marked unlikely under the same condition: the guard is one not-taken
+// s_cbranch_scc0 and the IEEE block lies behind the loop.  In-range lanes get the same bits from either arm (the exhaustive
+// result above), so every value is what it was.  The fast value of an out-of-range operand is computed and dropped: rsq /
+// rcp of zero, a denormal, inf or NaN raise nothing on this hardware.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -63,11 +73,17 @@ __device__ __forceinline__ bool wave_fast(unsigned long long used, bool ok) { re
 __device__ __forceinline__ bool wave_fast(bool used, bool ok) { return wave_fast(lanes(used), ok); }
 
 // == sqrtf(x), bit for bit
-template <class U = bool>
+template <bool FAST_FIRST = false, class U = bool>
 __device__ __forceinline__ float sqrt_f32(float x, U used = true)
 {
-    if (wave_fast(used, sqrt5_ok(x))) return sqrt5(x);
-    return sqrtf(x);
+    if constexpr (FAST_FIRST) {
+        float r = sqrt5(x);
+        if (__builtin_expect(!wave_fast(used, sqrt5_ok(x)), 0)) r = sqrtf(x);
+        return r;
+    } else {
+        if (wave_fast(used, sqrt5_ok(x))) return sqrt5(x);
+        return sqrtf(x);
+    }
 }
 
 // == 1.0f / x, bit for bit
@@ -80,11 +96,17 @@ __device__ __forceinline__ float rcp_f32(float x, U used = true)
 
 // == 1.0f / sqrtf(x), bit for bit (two roundings, as written); the root of an x in sqrt5's range lies in [2^-51, 2^64):
 // inside rcp3's range, so one guard covers both
-template <class U = bool>
+template <bool FAST_FIRST = false, class U = bool>
 __device__ __forceinline__ float rcp_sqrt_f32(float x, U used = true)
 {
-    if (wave_fast(used, sqrt5_ok(x))) return rcp3(sqrt5(x));
-    return 1.0f / sqrtf(x);
+    if constexpr (FAST_FIRST) {
+        float r = rcp3(sqrt5(x));
+        if (__builtin_expect(!wave_fast(used, sqrt5_ok(x)), 0)) r = 1.0f / sqrtf(x);
+        return r;
+    } else {
+        if (wave_fast(used, sqrt5_ok(x))) return rcp3(sqrt5(x));
+        return 1.0f / sqrtf(x);
+    }
 }
 
 }  // namespace mcn

@@ -28,6 +28,7 @@ namespace mcn {
 //
 // orca_u_dir_rel is the block itself, on a relative position (rpx, rpy) = o - p and its squared length the caller holds
 // already (quad_orca_core ranks its candidates by that very number); orca_u_dir computes the two first.
+template <bool FAST_FIRST = false>
 __device__ __forceinline__ float4 orca_u_dir_rel(float rpx, float rpy, float dist_sq, float vx, float vy, float radius,
                                                  float4 o, float orad, float inv_th, float inv_ts, bool used = true)
 {
@@ -54,7 +55,14 @@ __device__ __forceinline__ float4 orca_u_dir_rel(float rpx, float rpy, float dis
     const unsigned long long m_used = lanes(used);
     const unsigned long long m_w = __builtin_amdgcn_ballot_w64(sqrt5_ok(wl_sq));
     const unsigned long long m_l = __builtin_amdgcn_ballot_w64(sqrt5_ok(leg_sq)) & __builtin_amdgcn_ballot_w64(dist_sq < 0x1p126f);
-    if ((m_used & ~((m_circle & m_w) | (~m_circle & m_l))) == 0) {
+    if constexpr (FAST_FIRST) {
+        // (fast_f32.hpp, FAST_FIRST) the fast values first, on every lane; the rare wavefront with a used operand outside
+        // the ranges replaces all four on every lane, as the else arm below does
+        wl = sqrt5(wl_sq); iw = rcp3(wl); leg = sqrt5(leg_sq); id = rcp3(dist_sq);
+        if (__builtin_expect((m_used & ~((m_circle & m_w) | (~m_circle & m_l))) != 0, 0)) {
+            wl = sqrtf(wl_sq); iw = 1.0f / wl; leg = sqrtf(leg_sq); id = 1.0f / dist_sq;
+        }
+    } else if ((m_used & ~((m_circle & m_w) | (~m_circle & m_l))) == 0) {
         wl = sqrt5(wl_sq); iw = rcp3(wl); leg = sqrt5(leg_sq); id = rcp3(dist_sq);
     } else {
         wl = sqrtf(wl_sq); iw = 1.0f / wl; leg = sqrtf(leg_sq); id = 1.0f / dist_sq;

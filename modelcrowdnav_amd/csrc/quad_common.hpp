@@ -70,13 +70,16 @@ __device__ __forceinline__ float4 sel4(const float4 (&L)[4], int i)
 //              lean steps here (`lean_lp3`; the other callers keep the guarded ones).
 //              And the rank's four quad broadcasts of the key sit inside the subtractions that read them (`fold_rank`:
 //              four v_sub_u32_dpp for four v_mov_b32_dpp and three v_sub_u32).
+//              And its five range guards (half-plane, clip, lp1_spread's discriminant, the 3-D LP candidate's two) compute
+//              the fast values first and replace them under a branch marked unlikely (`straight`; fast_f32.hpp: FAST_FIRST),
+//              so that the IEEE expansions lie behind the step's text and a guard is one not-taken branch.
 struct QuadDpp {
     static constexpr bool table = false, slim = false, spread = false, lean_take = false;
-    static constexpr bool fold_rank = false, lean_lp3 = false;
+    static constexpr bool fold_rank = false, lean_lp3 = false, straight = false;
 };
 struct QuadTable {
     static constexpr bool table = true, slim = true, spread = true, lean_take = true;
-    static constexpr bool fold_rank = true, lean_lp3 = true;
+    static constexpr bool fold_rank = true, lean_lp3 = true, straight = true;
     float4 *tab;                                                 // this wavefront's 64 slots
 };
 
@@ -152,14 +155,14 @@ __device__ __forceinline__ void lp1_cut(bool live, float t, float den, float num
 // Lane 0 forms den, num and num / den of pair (3, 2) by the expressions, on the operands, that lane 3 forms them with
 // in lp1_rt's pass i = 2 (ln = line 3, li = line 2: the table's slots hold the bits lane 3's `srt` and L[2] are), and a
 // DPP move copies bits, NaN payloads included: every bound, `ok` and the candidate are bit for bit lp1_rt's.
-template <bool SELECT_CLAMP>
+template <bool SELECT_CLAMP, bool STRAIGHT = false>
 __device__ __forceinline__ bool lp1_spread(const float4 &ln, const float4 &lnA, const float4 &liA, const float4 &liB, int k,
                                            float radius, float optx, float opty, float &rx, float &ry)
 {
     const float dp = dot2(ln.x, ln.y, ln.z, ln.w);
     const float disc = dp * dp + radius * radius - dot2(ln.x, ln.y, ln.x, ln.y);
     bool ok = !(disc < 0.0f);
-    const float sq = sqrt_f32(disc, ok);
+    const float sq = sqrt_f32<STRAIGHT>(disc, ok);
     float tl = -dp - sq;
     float tr = -dp + sq;
     const float denA = det2(lnA.z, lnA.w, liA.z, liA.w);
@@ -212,7 +215,7 @@ __device__ __forceinline__ bool lp1_spread(const float4 &ln, const float4 &lnA, 
 // a mask: its violation test det2(0, 0, ., .) > 0, and in a kept lane's 1-D LP it is "parallel" with num = +-0 (0 > num
 // false) or, with a NaN den, fminf / fmaxf keep tr / tl and tl > tr repeats the previous step's answer.  So no kept
 // flag is broadcast, and the take steps are the 2-D LP's `fail > I` form (quad_orca_velocity).
-template <bool LEAN = false>
+template <bool LEAN = false, bool STRAIGHT = false>
 __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float4 &lj, int i, int k, float radius, float &rx,
                                                    float &ry)
 {
@@ -224,7 +227,7 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float
     const unsigned long long m_kept = lanes(k < i) & ~(lanes(par) & lanes(same));
     const float sc = det2(lj.z, lj.w, li.x - lj.x, li.y - lj.y) / dt;
     const float ddx = lj.z - li.z, ddy = lj.w - li.w;
-    const float inv = keptb ? rcp_sqrt_f32(dot2(ddx, ddy, ddx, ddy), m_kept) : 0.0f;
+    const float inv = keptb ? rcp_sqrt_f32<STRAIGHT>(dot2(ddx, ddy, ddx, ddy), m_kept) : 0.0f;
     const float4 q = make_float4(par ? 0.5f * (li.x + lj.x) : li.x + sc * li.z,
                                  par ? 0.5f * (li.y + lj.y) : li.y + sc * li.w, ddx * inv, ddy * inv);
     const float4 P0 = qb4<0>(q), P1 = qb4<1>(q), P2 = qb4<2>(q);
@@ -234,7 +237,7 @@ __device__ __forceinline__ bool lp3_candidate_quad(const float4 &li, const float
     const float dp = dot2(q.x, q.y, q.z, q.w);
     const float disc = dp * dp + radius * radius - dot2(q.x, q.y, q.x, q.y);
     bool ok = !(disc < 0.0f);
-    const float sq = sqrt_f32(disc, lanes(!(disc < 0.0f)) & m_kept);
+    const float sq = sqrt_f32<STRAIGHT>(disc, lanes(!(disc < 0.0f)) & m_kept);
     float tl = -dp - sq;
     float tr = -dp + sq;
 #pragma unroll
@@ -358,7 +361,7 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     const int nl = nin < c.orca_max_neighbors ? nin : c.orca_max_neighbors;
     float4 mine;
     if constexpr (Path::slim) {
-        const float4 ud = orca_u_dir_rel(ddx, ddy, d, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
+        const float4 ud = orca_u_dir_rel<Path::straight>(ddx, ddy, d, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
         mine = make_float4(fvx + 0.5f * ud.x, fvy + 0.5f * ud.y, ud.z, ud.w);          // as orca_line_select
     } else {
         mine = orca_line_select(fpx, fpy, fvx, fvy, frad, o, orad, inv_th, inv_ts, in);
@@ -392,7 +395,7 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     {
         const float pp = dot2(prefx, prefy, prefx, prefy);
         const bool clip = pp > ms * ms;
-        const float inv = rcp_sqrt_f32(pp, clip);
+        const float inv = rcp_sqrt_f32<Path::straight>(pp, clip);
         rx = clip ? ms * (prefx * inv) : prefx;
         ry = clip ? ms * (prefy * inv) : prefy;
     }
@@ -405,7 +408,7 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
     float cx, cy;
     // lane k's code for the take steps below: 4 when its 1-D LP is feasible, else k (the 2-D LP fails at line k)
     bool ok1;
-    if constexpr (Path::spread) ok1 = lp1_spread<Path::slim>(srt, lnA, liA, L[1], k, ms, prefx, prefy, cx, cy);
+    if constexpr (Path::spread) ok1 = lp1_spread<Path::slim, Path::straight>(srt, lnA, liA, L[1], k, ms, prefx, prefy, cx, cy);
     else ok1 = lp1_rt<false, Path::slim>(L, srt, k, ms, prefx, prefy, cx, cy);
     const int fcode = ok1 ? 4 : k;
     // `fail` stays nl until a violated line's 1-D LP is infeasible and then is that line, so "line I is below nl and
@@ -428,6 +431,8 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
         MCN_LP2_TAKE(0) MCN_LP2_TAKE(1) MCN_LP2_TAKE(2) MCN_LP2_TAKE(3)
 #undef MCN_LP2_TAKE
     }
+    // (not marked unlikely: with the round loop behind the step's text the headline measured nothing, and the changed
+    //  block frequencies rearranged the unicycle form's float64 loop, +2 % per step: profiles/r32_rollout_branch_layout.txt)
     if (fail < nl) {
         // dense crowd: 3-D LP (RVO2 linearProgram3).  fail / nl / the running result are quad-uniform, so the
         // whole region is entered per quad and the quad broadcasts inside see all four lanes.  Per round: find
@@ -451,7 +456,7 @@ __device__ __forceinline__ void quad_orca_core(const mcn_env_cfg &c, int lane, i
             if constexpr (Path::table) ln = path.tab[(lane & ~3) | nxt];      // one 16-byte read for sel4's 12 selects
             else ln = sel4(L, nxt);
             float cx3, cy3;
-            const bool ok3 = lp3_candidate_quad<Path::lean_lp3>(ln, srt, nxt, k, ms, cx3, cy3);
+            const bool ok3 = lp3_candidate_quad<Path::lean_lp3, Path::straight>(ln, srt, nxt, k, ms, cx3, cy3);
             rx = ok3 ? cx3 : rx; ry = ok3 ? cy3 : ry;
             dist = det2(ln.z, ln.w, ln.x - rx, ln.y - ry);
             i = nxt + 1;
